@@ -39,6 +39,10 @@ FAILS -- a multi-GPU line is never printed without its collective.
   bound by the links, which is why the product leaves predictions sharded unless asked.
 --mem host (cfg1 / cfg2 / cfg3): the columns are host numpy arrays handed to the C-ABI as POLS_MEM_HOST -- the PCIe-inclusive
   rate ("data": "synthetic, host-resident"); never the headline value.
+--dump-outputs DIR: after the timed steps, the arrays the last timed step handed back (coef, pred, ... as the plan returns them) are
+  written as DIR/<name>.npy, float32 / float64 (integer status codes as float64), at most 64 MB in all (per rank: DIR/<name>_rank<r>.npy
+  when N > 1).  Larger outputs keep a fixed, seeded sample of their rows, the row numbers in DIR/<name>_rows.npy.  The inputs are a
+  function of the arguments alone, so two builds run with the same arguments can be compared output for output.
 """
 from __future__ import annotations
 
@@ -57,7 +61,7 @@ for p in (str(ROOT), str(ROOT / "tests")):
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
-HBM_PEAK_GBS = 8000.0   # MI355X HBM3E spec peak, /opt/skills/guides/MI355X_MICROARCH.md
+HBM_PEAK_GBS = 8000.0   # MI355X HBM3E spec peak
 
 
 # ------------------------------------------------------------------------------------------------ CPU baseline (rank 0, N = 1)
@@ -286,6 +290,44 @@ def build_workload(cfg: str, eng, rank: int, world: int, dtype_flag: str, mem: s
     raise SystemExit(f"unknown --config {cfg}")
 
 
+DUMP_BYTES = 64_000_000     # --dump-outputs: the most one run writes, .npy headers included
+
+
+def dump_outputs(results: dict, out_dir: Path, budget: int, suffix: str = "") -> None:
+    """--dump-outputs: every array of `results` as out_dir/<name><suffix>.npy.  If they add up to more than `budget` bytes, each keeps
+    the same fraction of its rows (axis 0): one row drawn from every stride of the array by a fixed seed, so the sample depends on the
+    shape alone; the row numbers go to <name><suffix>_rows.npy (float64, exact).  Call it after a device synchronise."""
+    arrays = {}
+    for name, v in results.items():
+        if v is None:
+            continue
+        is_float = v.dtype in (torch.float32, torch.float64) if isinstance(v, torch.Tensor) else v.dtype in (np.float32, np.float64)
+        n = int(v.shape[0]) if v.ndim else 1
+        row_bytes = (v.element_size() if isinstance(v, torch.Tensor) else v.itemsize) if is_float else 8
+        row_bytes *= max(1, int(np.prod(v.shape[1:])))
+        arrays[name] = (v, is_float, n, row_bytes)
+    budget -= 256 * 2 * len(arrays)                                                    # .npy headers
+    full = sum(n * rb for _, _, n, rb in arrays.values())
+    with_rows = sum(n * (rb + 8) for _, _, n, rb in arrays.values())                   # + 8 bytes of row number per sampled row
+    out_dir.mkdir(parents=True, exist_ok=True)
+    for name, (v, is_float, n, rb) in arrays.items():
+        idx = None
+        if full > budget and n > 0:
+            m = max(1, n * budget // with_rows)
+            edges = np.arange(m + 1, dtype=np.int64) * n // m                      # m strides of n // m or n // m + 1 rows
+            rng = np.random.default_rng(20240611)
+            idx = edges[:-1] + (rng.random(m) * np.diff(edges)).astype(np.int64)
+        if isinstance(v, torch.Tensor):
+            a = v.index_select(0, torch.from_numpy(idx).to(v.device)) if idx is not None else v
+            a = a.detach().cpu().numpy()
+        else:
+            a = v[idx] if idx is not None else v
+        a = np.ascontiguousarray(a if is_float else a.astype(np.float64))
+        np.save(out_dir / f"{name}{suffix}.npy", a)
+        if idx is not None:
+            np.save(out_dir / f"{name}{suffix}_rows.npy", idx.astype(np.float64))
+
+
 def self_launch_command(n_gpus: int, argv: list) -> list:
     """argv of the launcher `bench.py --gpus N` turns itself into when nothing has launched it (no WORLD_SIZE): the driver's own
     command form, on 127.0.0.1 (the container's hostname may not resolve)."""
@@ -314,7 +356,11 @@ def main() -> None:
     ap.add_argument("--groups", type=int, default=0, help="cfg2 / cfg3 / cfg5: this many groups (per GPU for cfg2 / cfg3, in total for cfg5) "
                                                          "instead of the config's own count -- e.g. 12500 = the 8-GPU shard of cfg5 on one GPU")
     ap.add_argument("--gather", default="coef", choices=["coef", "pred", "none"], help="N > 1: what is re-assembled every step")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (at most 64 MB in all)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -473,6 +519,10 @@ def main() -> None:
         dist.barrier()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:
+        # before anything below runs a plan again (the kernel-sample pass, the stream probe): the frames share their output buffers
+        dump_outputs(plans[(step_no[0] - 1) % len(plans)].results, Path(args.dump_outputs), DUMP_BYTES // world,
+                     f"_rank{rank}" if world > 1 else "")
     # the re-assembled table against its parts, outside the timed region: one more gather of the current step's table, then every rank's
     # checksum of its own rows against the checksum of its slice of what arrived (collective: all ranks take part, rank 0 asserts)
     if gather:

@@ -1,4 +1,5 @@
-import sys, time; sys.path.insert(0, "/root/repo")
+import os, sys; _ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))   # the checkout this script lives in
+import sys, time; sys.path.insert(0, _ROOT)
 import numpy as np, torch
 from polars_ols_amd import Engine
 eng = Engine(0)

@@ -1,5 +1,6 @@
+import os, sys; _ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))   # the checkout this script lives in
 import os, sys, numpy as np, torch
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, _ROOT)
 from polars_ols_amd.engine import Engine
 eng = Engine(0)
 G, n, k = 10_000, 1_000, 6

@@ -141,3 +141,24 @@ def test_native_cabi_harness(tmp_path):
     d = json.loads(out.stdout.strip().splitlines()[-1])
     assert d["kernel"].startswith("k1_gram_chol_f32_k8") and d["groups_not_ok"] == 0
     assert d["max_abs_dcoef_group0"] < 1e-4 and d["max_abs_dpred_group0"] < 1e-4 and d["regressions_per_s"] > 1e6
+
+
+def test_bench_dump_outputs(tmp_path):
+    """--dump-outputs: the last timed step's coefficients and predictions, checked against the frame that step read (regenerated on the
+    host from its seed: the steps rotate over frames 1234 + 1000 f, the last timed one is (warmup + steps - 1) mod frames)."""
+    import numpy as np
+
+    import synth
+
+    d = _run({}, "--no-cpu-baseline", "--dump-outputs", str(tmp_path))
+    assert d["steps"] == 12 and d["warmup"] == 3
+    assert sorted(p.name for p in tmp_path.iterdir()) == ["coef.npy", "pred.npy"]
+    assert sum(p.stat().st_size for p in tmp_path.iterdir()) <= 64_000_000
+    coef, pred = np.load(tmp_path / "coef.npy"), np.load(tmp_path / "pred.npy")
+    assert coef.shape == (10_000, 8) and coef.dtype == np.float32 and pred.shape == (10_000_000,) and pred.dtype == np.float32
+    assert np.abs(coef - 1.0).max() < 0.05                                     # beta = 1, noise 0.1, 1 000 rows per group
+    frame = (3 + 12 - 1) % d["config"]["frames_rotated"]
+    for g in (0, 4_321, 9_999):
+        _, cols, _ = synth.frame_columns(1234 + 1000 * frame, 8, 1000 * g, 1000 * (g + 1), dtype=np.float32)
+        want = np.stack(cols, 1).astype(np.float64) @ coef[g].astype(np.float64)
+        assert np.allclose(pred[1000 * g: 1000 * (g + 1)], want, rtol=1e-4, atol=1e-4), g
