@@ -54,19 +54,24 @@ int fail(int code, const char *fmt, ...) {
 }
 
 // ------------------------------------------------------------------ scratch / offsets / timing
-int ensure_scratch(pols_ctx *ctx, int slot, size_t bytes, void **out) {
-    Scratch &s = ctx->scratch[slot];
-    if (bytes > s.cap) {
-        if (s.ptr) POLS_HIP(hipFree(s.ptr));
-        s.ptr = nullptr;
-        s.cap = 0;
+int grow(DeviceBuffer &b, size_t bytes, void **out, bool *fresh) {
+    if (fresh) *fresh = bytes > b.cap;
+    if (bytes > b.cap) {
+        if (b.ptr) POLS_HIP(hipFree(b.ptr));
+        b.ptr = nullptr;
+        b.cap = 0;
         const size_t want = std::max(bytes, (size_t)1 << 16);
-        POLS_HIP(hipMalloc(&s.ptr, want));
-        s.cap = want;
+        POLS_HIP(hipMalloc(&b.ptr, want));
+        b.cap = want;
     }
-    *out = s.ptr;
+    *out = b.ptr;
     return POLS_OK;
 }
+int grow(CachedTable &t, size_t bytes, void **out) {
+    if (bytes > t.buf.cap) t.valid = false;
+    return grow(t.buf, bytes, out);
+}
+int ensure_scratch(pols_ctx *ctx, Work w, size_t bytes, void **out) { return grow(ctx->work[(int)w], bytes, out); }
 
 int upload_small(pols_ctx *ctx, void *dst_device, const void *src, size_t bytes) {
     if (bytes == 0) return POLS_OK;
@@ -101,9 +106,9 @@ int upload_offsets(pols_ctx *ctx, const int64_t *offs, int64_t n_groups, const i
     const size_t bytes = sizeof(int64_t) * (size_t)cnt;
     // Promised hit: the caller vouches that (pointer, count, generation) names the same content as last time -- O(1), what a
     // marshalled Plan passes.  The statistics of the offsets (largest group, alignment, overflow rows) are cached with them.
-    if (generation != 0 && ctx->scratch[0].ptr && ctx->offs_host == offs && ctx->offs_n == n_groups &&
+    if (generation != 0 && ctx->offsets.valid && ctx->offs_host == offs && ctx->offs_n == n_groups &&
         ctx->offs_generation == generation) {
-        *d_offs = static_cast<const int64_t *>(ctx->scratch[0].ptr);
+        *d_offs = static_cast<const int64_t *>(ctx->offsets.buf.ptr);
         *max_rows = ctx->offs_max_rows;
         return POLS_OK;
     }
@@ -133,13 +138,15 @@ int upload_offsets(pols_ctx *ctx, const int64_t *offs, int64_t n_groups, const i
     }
     if (mn < 0) return fail(POLS_ERR_INVALID, "group_offsets must be ascending");
     const uint64_t sum = ((h0 * 31 + h1) * 31 + h2) * 31 + h3;
-    const bool hit = ctx->scratch[0].ptr && ctx->offs_n == n_groups && ctx->offs_sum == sum &&
+    const bool hit = ctx->offsets.valid && ctx->offs_n == n_groups && ctx->offs_sum == sum &&
                      ctx->offs_copy.size() == (size_t)cnt && std::memcmp(ctx->offs_copy.data(), offs, bytes) == 0;
     if (!hit) {
         void *dptr = nullptr;
-        int rc = ensure_scratch(ctx, 0, bytes, &dptr);
+        ctx->offsets.valid = false;
+        int rc = grow(ctx->offsets, bytes, &dptr);
         if (rc) return rc;
         if ((rc = upload_small(ctx, dptr, offs, bytes))) return rc;   // pinned ring: no stream synchronisation
+        ctx->offsets.valid = true;
         ctx->offs_copy.assign(offs, offs + cnt);
         ctx->offs_n = n_groups;
         ctx->offs_sum = sum;
@@ -161,7 +168,7 @@ int upload_offsets(pols_ctx *ctx, const int64_t *offs, int64_t n_groups, const i
     }
     ctx->offs_aligned[0] = (ored & 1) == 0;
     ctx->offs_aligned[1] = (ored & 3) == 0;
-    *d_offs = static_cast<const int64_t *>(ctx->scratch[0].ptr);
+    *d_offs = static_cast<const int64_t *>(ctx->offsets.buf.ptr);
     *max_rows = mx;
     return POLS_OK;
 }
@@ -307,7 +314,7 @@ static int fill_null_weights(pols_ctx *ctx, const pols_batch *b, Staged *st) {
     if (!st->w || b->null_free || b->n_rows <= 0) return POLS_OK;
     void *dst = const_cast<void *>(st->w);                     // HOST batch: the staged copy is ours -- in place
     if (b->mem == POLS_MEM_DEVICE) {                           // DEVICE batch: the caller's column stays untouched
-        int rc = ensure_scratch(ctx, 17, round256(dtype_size(b->dtype) * (size_t)b->n_rows), &dst);
+        int rc = ensure_scratch(ctx, Work::NullWeights, round256(dtype_size(b->dtype) * (size_t)b->n_rows), &dst);
         if (rc) return rc;
     }
     const int vn = b->dtype == POLS_F32 ? 4 : 2;
@@ -334,7 +341,7 @@ static int stage_inputs(pols_ctx *ctx, const pols_batch *b, int64_t coef_rows, i
     }
     const int ncols = b->n_features + 1 + (b->weights ? 1 : 0);
     void *in = nullptr, *out = nullptr;
-    int rc = ensure_scratch(ctx, 1, colb * ncols + round256((size_t)b->n_rows), &in);
+    int rc = ensure_scratch(ctx, Work::HostInputs, colb * ncols + round256((size_t)b->n_rows), &in);
     if (rc) return rc;
     char *p = static_cast<char *>(in);
     auto put = [&](const void *src, size_t bytes, const void **dst) -> int {
@@ -355,7 +362,7 @@ static int stage_inputs(pols_ctx *ctx, const pols_batch *b, int64_t coef_rows, i
     if (o) {
         const size_t coefb = round256(sz * (size_t)coef_rows * kt);
         const size_t statb = round256(sizeof(int32_t) * (size_t)b->n_groups);
-        rc = ensure_scratch(ctx, 2, coefb + 2 * colb + statb, &out);
+        rc = ensure_scratch(ctx, Work::HostOutputs, coefb + 2 * colb + statb, &out);
         if (rc) return rc;
         char *q = static_cast<char *>(out);
         if (o->coef) st->coef = q;
@@ -463,7 +470,7 @@ static int compact_nulls(pols_ctx *ctx, const pols_batch *b, int policy, Compact
                  gfb = round256(sizeof(int64_t) * std::max<size_t>(n_slabs, 1));
     void *d = nullptr;
     const bool stage_targets = n_targets > 0 && b->mem == POLS_MEM_HOST;      // host targets: uploaded behind the compacted columns
-    if ((rc = ensure_scratch(ctx, 14, cntb + baseb + gfb + vb + 2 * tabb + offb + colb * (size_t)(ncols + (stage_targets ? m : 0)), &d))) return rc;
+    if ((rc = ensure_scratch(ctx, Work::DynPrep, cntb + baseb + gfb + vb + 2 * tabb + offb + colb * (size_t)(ncols + (stage_targets ? m : 0)), &d))) return rc;
     char *base = static_cast<char *>(d);
     char *q_valid = base + cntb + baseb + gfb, *q_tab = q_valid + vb, *q_offs = q_tab + 2 * tabb;
     char *cols = q_offs + offb;
@@ -579,8 +586,11 @@ void pols_destroy(pols_ctx *ctx) {
     if (!ctx) return;
     hipSetDevice(ctx->device);
     hipStreamSynchronize(ctx->stream);
-    for (auto &s : ctx->scratch)
-        if (s.ptr) hipFree(s.ptr);
+    for (DeviceBuffer *d : {&ctx->offsets.buf, &ctx->chunk_cache.buf, &ctx->k3c.buf, &ctx->k3h.buf, &ctx->class_cache.buf, &ctx->seg_cache[0].buf,
+                            &ctx->seg_cache[1].buf, &ctx->start_flags.buf, &ctx->k3c_gran, &ctx->k4c_fix})
+        if (d->ptr) hipFree(d->ptr);
+    for (auto &d : ctx->work)
+        if (d.ptr) hipFree(d.ptr);
     if (ctx->fb_flag) hipFree(ctx->fb_flag);
     for (auto &t : ctx->timed) { hipEventDestroy(t.start); hipEventDestroy(t.stop); }
     for (auto &ps : ctx->pinned) {
@@ -702,7 +712,7 @@ static int wide_static(pols_ctx *ctx, const pols_batch *b, const pols_ols_params
     if ((rc = fill_null_weights(ctx, b, &st))) return rc;
     const size_t G = (size_t)b->n_groups;
     const int NZ = kt + m, nt = (NZ + 63) / 64, npairs = nt * (nt + 1) / 2;
-    // multi-target: device pointers of the m target and m prediction columns (host batches are staged in slot 4)
+    // multi-target: device pointers of the m target and m prediction columns (host batches are staged in Work::HostStaged)
     std::vector<const void *> yptr;
     std::vector<void *> pptr;
     const bool host = b->mem == POLS_MEM_HOST;
@@ -712,7 +722,7 @@ static int wide_static(pols_ctx *ctx, const pols_batch *b, const pols_ols_params
         if (pred_cols) pptr.assign(pred_cols, pred_cols + m);
         if (host) {
             void *mt = nullptr;
-            if ((rc = ensure_scratch(ctx, 4, colb_mt * (size_t)m * (pred_cols ? 2 : 1), &mt))) return rc;
+            if ((rc = ensure_scratch(ctx, Work::HostStaged, colb_mt * (size_t)m * (pred_cols ? 2 : 1), &mt))) return rc;
             char *q = static_cast<char *>(mt);
             for (int t = 0; t < m; ++t) {
                 POLS_HIP(hipMemcpyAsync(q, y_cols[t], dtype_size(b->dtype) * (size_t)b->n_rows, hipMemcpyHostToDevice, ctx->stream));
@@ -734,15 +744,15 @@ static int wide_static(pols_ctx *ctx, const pols_batch *b, const pols_ols_params
     std::vector<const void *> table(st.x.begin(), st.x.end());         // [features][targets][predictions]
     table.insert(table.end(), yptr.begin(), yptr.end());
     table.insert(table.end(), pptr.begin(), pptr.end());
-    if ((rc = ensure_scratch(ctx, 6, sizeof(void *) * table.size(), &tab))) return rc;
+    if ((rc = ensure_scratch(ctx, Work::Tables, sizeof(void *) * table.size(), &tab))) return rc;
     if ((rc = upload_small(ctx, tab, table.data(), sizeof(void *) * table.size()))) return rc;   // `table` is a local: pinned ring
     const size_t gram_b = round256(mat * G), part_b = round256(mat * G * (size_t)splits), c64_b = round256(sizeof(double) * G * kt * m);
     const bool nulls = p->null_policy != POLS_NULL_IGNORE;
     const size_t mask_b = nulls ? round256((size_t)b->n_rows) + round256(sizeof(double) * G) : 0;
-    if ((rc = ensure_scratch(ctx, 5, gram_b + part_b + c64_b + mask_b, &scr))) return rc;
+    if ((rc = ensure_scratch(ctx, Work::Gram, gram_b + part_b + c64_b + mask_b, &scr))) return rc;
     if (!st.status) {
         void *sp = nullptr;
-        if ((rc = ensure_scratch(ctx, 7, sizeof(int32_t) * G, &sp))) return rc;
+        if ((rc = ensure_scratch(ctx, Work::Status, sizeof(int32_t) * G, &sp))) return rc;
         st.status = static_cast<int32_t *>(sp);
     }
     if (!ctx->fb_flag) {
@@ -809,7 +819,7 @@ static int wide_static(pols_ctx *ctx, const pols_batch *b, const pols_ols_params
         a.work_w_elems = (int64_t)(kt + m) * std::max<int64_t>(1, max_rows);
         a.work_stride = a.work_w_elems + ncmax * ncmax + 2 * ncmax + (lu ? (int64_t)kt * m : 0);
         while (workers > 1 && (double)workers * (double)a.work_stride * 8.0 > 1e9) workers /= 2;
-        if ((rc = ensure_scratch(ctx, 3, sizeof(double) * (size_t)workers * (size_t)a.work_stride, &wk))) return rc;
+        if ((rc = ensure_scratch(ctx, Work::Fixup, sizeof(double) * (size_t)workers * (size_t)a.work_stride, &wk))) return rc;
         a.work = static_cast<double *>(wk);
         if ((rc = wide_minnorm_launch(ctx, b->dtype, a, workers))) return rc;
     }
@@ -824,7 +834,7 @@ static int wide_static(pols_ctx *ctx, const pols_batch *b, const pols_ols_params
 
 // Long groups cut into segments (the streamed static path, the statistics of long groups): a group is one workgroup in those
 // kernels, so ONE regression over a 10M-row frame used to be one CU's work.  Groups longer than two segments are cut into pieces
-// of about N / (8 x CUs) rows (256-row multiples), the others are one segment each; tables in scratch slot 23 -- segment offsets,
+// of about N / (8 x CUs) rows (256-row multiples), the others are one segment each; tables in ctx->seg_cache -- segment offsets,
 // segment -> group, group -> first segment -- followed by `extra_per_seg` bytes per segment for the caller's partial results.
 // n_seg = 0: nothing is longer than two segments (or POLS_NO_SPLIT).  Cached per frame.
 struct SegTables {
@@ -842,13 +852,12 @@ static int ensure_segments(pols_ctx *ctx, const pols_batch *b, int64_t max_rows,
                                                       : std::max<int64_t>(4096, ((b->n_rows / std::max<int64_t>(1, 8 * (int64_t)ctx->num_cus) + 1023) / 1024) * 1024);
     if (!ids && (!(max_rows > 2 * seg_target) || ctx->opt.no_split)) return POLS_OK;
     const int64_t n_items = ids ? (int64_t)ids->size() : b->n_groups;
-    auto &sc = ctx->seg_cache[ids ? 1 : 0];               // (class tables have their own slot: they no longer evict the whole-frame tables)
-    const int slot = ids ? 26 : 23;
+    auto &sc = ctx->seg_cache[ids ? 1 : 0];               // (class tables have their own: they do not evict the whole-frame tables)
     int rc;
     // (the key is the frame; the per-segment extra area only has to be large enough -- its users differ in what they keep there: the Gram
     // partials of ls_core, the moments of the statistics entry, nothing for pols_predict -- and it is kept at the largest size asked for,
     // so that alternating users of one frame stop rebuilding and re-uploading the tables)
-    const bool same_frame = sc.ptr && sc.ptr == ctx->scratch[slot].ptr && sc.offs_id == ctx->offs_id && sc.n_groups == b->n_groups && sc.n_rows == b->n_rows &&
+    const bool same_frame = sc.valid && sc.offs_id == ctx->offs_id && sc.n_groups == b->n_groups && sc.n_rows == b->n_rows &&
                             sc.seg_target == seg_target && sc.class_key == class_key && sc.n_items == n_items;
     const bool hit = same_frame && sc.nz2 >= extra_per_seg;
     auto lay = [&](char *sb, int64_t n_seg) {
@@ -861,9 +870,9 @@ static int ensure_segments(pols_ctx *ctx, const pols_batch *b, int64_t max_rows,
         t->n_seg = n_seg;
         return b_so + b_sm + b_sf;
     };
-    if (hit) { lay(static_cast<char *>(ctx->scratch[slot].ptr), sc.n_seg); t->max_len = sc.max_len; t->max_seg = sc.max_seg; return POLS_OK; }
+    if (hit) { lay(static_cast<char *>(sc.buf.ptr), sc.n_seg); t->max_len = sc.max_len; t->max_seg = sc.max_seg; return POLS_OK; }
     if (same_frame) extra_per_seg = std::max<size_t>(extra_per_seg, sc.nz2);
-    sc.ptr = nullptr;
+    sc.valid = false;
     std::vector<int64_t> so;
     std::vector<int32_t> sm, sf((size_t)n_items + 1);
     if (!ids) so.push_back(0);
@@ -888,13 +897,13 @@ static int ensure_segments(pols_ctx *ctx, const pols_batch *b, int64_t max_rows,
     const int64_t n_seg = (int64_t)sm.size();
     const size_t tabs = round256(sizeof(int64_t) * so.size()) + round256(sizeof(int32_t) * sm.size()) + round256(sizeof(int32_t) * sf.size());
     void *ds = nullptr;
-    if ((rc = ensure_scratch(ctx, slot, tabs + round256(extra_per_seg * (size_t)n_seg), &ds))) return rc;
+    if ((rc = grow(sc, tabs + round256(extra_per_seg * (size_t)n_seg), &ds))) return rc;
     char *sb = static_cast<char *>(ds);
     lay(sb, n_seg);
     if ((rc = upload_small(ctx, const_cast<int64_t *>(t->offs), so.data(), sizeof(int64_t) * so.size()))) return rc;
     if ((rc = upload_small(ctx, const_cast<int32_t *>(t->map), sm.data(), sizeof(int32_t) * sm.size()))) return rc;
     if ((rc = upload_small(ctx, const_cast<int32_t *>(t->first), sf.data(), sizeof(int32_t) * sf.size()))) return rc;
-    sc.ptr = ds; sc.offs_id = ctx->offs_id; sc.n_groups = b->n_groups; sc.n_rows = b->n_rows; sc.seg_target = seg_target;
+    sc.valid = true; sc.offs_id = ctx->offs_id; sc.n_groups = b->n_groups; sc.n_rows = b->n_rows; sc.seg_target = seg_target;
     sc.class_key = class_key; sc.n_items = n_items;
     sc.n_seg = n_seg; sc.nz2 = extra_per_seg; sc.nulls = false; sc.max_len = max_len; sc.max_seg = max_seg;
     t->max_len = max_len; t->max_seg = max_seg;
@@ -1006,7 +1015,7 @@ static int ls_core(pols_ctx *ctx, const pols_batch *b, const pols_ols_params *p,
     // Every static solve is followed by the SVD fix-up pass over the groups it flags, so a status buffer always exists.
     if (!enet && !st.status) {
         void *sp = nullptr;
-        if ((rc = ensure_scratch(ctx, 7, sizeof(int32_t) * (size_t)b->n_groups, &sp))) return rc;
+        if ((rc = ensure_scratch(ctx, Work::Status, sizeof(int32_t) * (size_t)b->n_groups, &sp))) return rc;
         st.status = static_cast<int32_t *>(sp);
     }
     // OLS branch (the reference solves it with a backward-stable pivoted QR / dgelsd): flag groups whose Cholesky
@@ -1038,8 +1047,8 @@ static int ls_core(pols_ctx *ctx, const pols_batch *b, const pols_ols_params *p,
         void *wk = nullptr;
         int w_use = workers;
         while (w_use > 1 && (double)w_use * (double)stride * 8.0 > 4e9) w_use /= 2;
-        int r2;   // slot 5 holds the Gram matrices / coef64 of the streamed path: the work area gets its own slot
-        if ((r2 = ensure_scratch(ctx, 3, sizeof(double) * (size_t)w_use * (size_t)stride, &wk))) return r2;
+        int r2;   // Work::Gram holds the Gram matrices / coef64 of the streamed path: the work area gets its own buffer
+        if ((r2 = ensure_scratch(ctx, Work::Fixup, sizeof(double) * (size_t)w_use * (size_t)stride, &wk))) return r2;
         std::memset(&ka, 0, sizeof(ka));
         ka.y = st.y; ka.w = st.w;
         for (int j = 0; j < b->n_features; ++j) ka.x[j] = st.x[j];
@@ -1229,7 +1238,7 @@ static int ls_core(pols_ctx *ctx, const pols_batch *b, const pols_ols_params *p,
         // few groups of hundreds of segments: the segment sums go through 16 slices per group (gram_reduce_launch)
         const int n_slices = (split && sg.max_seg >= 256 && ng <= 256) ? 16 : 1;
         const size_t slice_bytes = n_slices > 1 ? round256(sizeof(double) * nz * nz * (size_t)n_slices * (size_t)ng) : 0;
-        if ((rc = ensure_scratch(ctx, 5, gram_bytes + c64_bytes + nv_bytes + slice_bytes, &scr))) return rc;
+        if ((rc = ensure_scratch(ctx, Work::Gram, gram_bytes + c64_bytes + nv_bytes + slice_bytes, &scr))) return rc;
         double *nvalid = nulls ? reinterpret_cast<double *>(static_cast<char *>(scr) + gram_bytes + c64_bytes) : nullptr;
         const int64_t *seg_offs = split ? sg.offs : d_offs;
         const int32_t *seg_map = sg.map, *seg_first = sg.first;
@@ -1316,10 +1325,10 @@ static int ls_core(pols_ctx *ctx, const pols_batch *b, const pols_ols_params *p,
     // the lists of the classes cut[0] < cut[1] < ... (rows): class c holds the groups of cut[c - 1] < rows <= cut[c], the last one the rest
     auto build_lists = [&](const int64_t *cut, int n_cut) -> int {
         auto &cc = ctx->class_cache;
-        bool same = cc.ptr && cc.ptr == ctx->scratch[24].ptr && cc.offs_id == ctx->offs_id && cc.n_cut == n_cut;
+        bool same = cc.valid && cc.offs_id == ctx->offs_id && cc.n_cut == n_cut;
         for (int c = 0; c < n_cut && same; ++c) same = cc.cut[c] == cut[c];
         if (same) return POLS_OK;
-        cc.ptr = nullptr;
+        cc.valid = false;
         std::vector<int32_t> lists[4];
         for (int64_t g = 0; g < b->n_groups; ++g) {
             const int64_t n = b->group_offsets[g + 1] - b->group_offsets[g];
@@ -1328,7 +1337,7 @@ static int ls_core(pols_ctx *ctx, const pols_batch *b, const pols_ols_params *p,
             lists[c].push_back((int32_t)g);
         }
         void *d = nullptr;
-        int r2 = ensure_scratch(ctx, 24, sizeof(int32_t) * (size_t)b->n_groups, &d);
+        int r2 = grow(cc, sizeof(int32_t) * (size_t)b->n_groups, &d);
         if (r2) return r2;
         size_t at = 0;
         for (int c = 0; c <= n_cut; ++c) {
@@ -1338,7 +1347,7 @@ static int ls_core(pols_ctx *ctx, const pols_batch *b, const pols_ols_params *p,
         }
         for (int c = n_cut + 1; c < 4; ++c) cc.n[c] = 0;
         cc.host_last.swap(lists[n_cut]);
-        cc.ptr = d; cc.offs_id = ctx->offs_id; cc.n_cut = n_cut;
+        cc.valid = true; cc.offs_id = ctx->offs_id; cc.n_cut = n_cut;
         for (int c = 0; c < n_cut; ++c) cc.cut[c] = cut[c];
         return POLS_OK;
     };
@@ -1352,7 +1361,7 @@ static int ls_core(pols_ctx *ctx, const pols_batch *b, const pols_ols_params *p,
         for (int c = c_hi; c >= c_lo; --c) {
             if (cc.n[c] == 0) continue;
             K1Args ac = a;
-            ac.glist = static_cast<const int32_t *>(cc.ptr) + first[c];
+            ac.glist = static_cast<const int32_t *>(cc.buf.ptr) + first[c];
             ac.n_groups = cc.n[c];
             ac.class_max_rows = c < n_cut ? cut[c] : max_rows;
             int r2 = k1_launch(ctx, b->dtype, kt, ac, ac.class_max_rows, true);
@@ -1386,7 +1395,7 @@ static int ls_core(pols_ctx *ctx, const pols_batch *b, const pols_ols_params *p,
             std::string names;
             const auto &cc = ctx->class_cache;
             if (cc.n[n_cut] > 0) {
-                const int32_t *d_top = static_cast<const int32_t *>(cc.ptr) + (b->n_groups - cc.n[n_cut]);
+                const int32_t *d_top = static_cast<const int32_t *>(cc.buf.ptr) + (b->n_groups - cc.n[n_cut]);
                 if ((rc = run_stream(&cc.host_last, d_top, k1_top, max_rows))) return rc;
                 names = ctx->last_kernel;
             }
@@ -1461,7 +1470,7 @@ int pols_multi_target_least_squares(pols_ctx *ctx, const pols_batch *b, const vo
         const size_t coefb = round256(sz * G * n_targets * kt), statb = round256(sizeof(int32_t) * G), colb = round256(sz * std::max<size_t>(N, 1));
         const size_t tabb = round256(sizeof(void *) * (size_t)std::max(b->n_features, n_targets));
         void *d = nullptr;
-        if ((rc = ensure_scratch(ctx, 15, coefb + statb + 2 * tabb + (host && pred_cols ? colb * (size_t)n_targets : 0), &d))) return rc;
+        if ((rc = ensure_scratch(ctx, Work::CompactOut, coefb + statb + 2 * tabb + (host && pred_cols ? colb * (size_t)n_targets : 0), &d))) return rc;
         char *q = static_cast<char *>(d);
         void *dcoef = (!host && coef) ? coef : static_cast<void *>(q);
         int32_t *dstat = (!host && status) ? status : reinterpret_cast<int32_t *>(q + coefb);
@@ -1470,7 +1479,7 @@ int pols_multi_target_least_squares(pols_ctx *ctx, const pols_batch *b, const vo
         pp.null_policy = POLS_NULL_IGNORE;
         if ((rc = pols_multi_target_least_squares(ctx, &c.bb, c.ycols.data(), n_targets, &pp, nullptr, dcoef, dstat))) return rc;
         if (pred_cols) {
-            // (the inner call uploaded the COMPACTED offsets into the slot c.d_offs points to: the original ones again)
+            // (the inner call uploaded the COMPACTED offsets in place of the frame's: the original ones again)
             const int64_t *d_offs = nullptr;
             int64_t mr = 0;
             if ((rc = upload_offsets(ctx, b->group_offsets, b->n_groups, &d_offs, &mr, b->offsets_generation))) return rc;
@@ -1527,7 +1536,7 @@ int pols_least_squares_statistics(pols_ctx *ctx, const pols_batch *b, const pols
         const size_t coefb = round256(sz * G * kt), statb = round256(sizeof(int32_t) * G), vecb = round256(sizeof(double) * G),
                      matb = round256(sizeof(double) * G * kt);
         void *d = nullptr;
-        if ((rc = ensure_scratch(ctx, 15, coefb + statb + 3 * vecb + 3 * matb, &d))) return rc;
+        if ((rc = ensure_scratch(ctx, Work::CompactOut, coefb + statb + 3 * vecb + 3 * matb, &d))) return rc;
         char *q = static_cast<char *>(d);
         pols_out od;
         std::memset(&od, 0, sizeof(od));
@@ -1564,7 +1573,7 @@ int pols_least_squares_statistics(pols_ctx *ctx, const pols_batch *b, const pols
         else { enet = true; enet_l1 = p->has_l1_ratio ? p->l1_ratio : 0.5; }
         const size_t vecb = round256(sizeof(double) * G), matb = round256(sizeof(double) * G * kt);
         void *scr4 = nullptr;
-        if (host && (rc = ensure_scratch(ctx, 4, 3 * vecb + 3 * matb, &scr4))) return rc;
+        if (host && (rc = ensure_scratch(ctx, Work::HostStaged, 3 * vecb + 3 * matb, &scr4))) return rc;
         WideInfo wi;
         pols_out oo = *o;
         char coef_sentinel;
@@ -1590,10 +1599,10 @@ int pols_least_squares_statistics(pols_ctx *ctx, const pols_batch *b, const pols
         if (!o->coef) oo.coef = nullptr;
         return unstage_outputs(ctx, b, b->n_groups, kt, &oo, wi.st);
     }
-    // slot 6: [coefficients when the caller did not ask for them (device batches)] [statistic arrays of a host batch]
+    // Work::Tables: [coefficients when the caller did not ask for them (device batches)] [statistic arrays of a host batch]
     const size_t coefb = round256(sz * G * kt), vecb = round256(sizeof(double) * G), matb = round256(sizeof(double) * G * kt);
     void *scr = nullptr;
-    if ((rc = ensure_scratch(ctx, 6, coefb + 3 * vecb + 3 * matb, &scr))) return rc;
+    if ((rc = ensure_scratch(ctx, Work::Tables, coefb + 3 * vecb + 3 * matb, &scr))) return rc;
     char *q = static_cast<char *>(scr);
     pols_out oo = *o;
     char coef_sentinel;   // host batches stage every non-NULL output: ask for the coefficients, throw the copy away below
@@ -1606,7 +1615,7 @@ int pols_least_squares_statistics(pols_ctx *ctx, const pols_batch *b, const pols
     if (!gram) {
         void *gs = nullptr;
         const size_t nz = (size_t)kt + 1;
-        if ((rc = ensure_scratch(ctx, 5, round256(sizeof(double) * nz * nz * G), &gs))) return rc;
+        if ((rc = ensure_scratch(ctx, Work::Gram, round256(sizeof(double) * nz * nz * G), &gs))) return rc;
         GramArgs ga;
         std::memset(&ga, 0, sizeof(ga));
         ga.y = info.st.y; ga.w = info.st.w;
@@ -1621,7 +1630,7 @@ int pols_least_squares_statistics(pols_ctx *ctx, const pols_batch *b, const pols
         if (sgg.n_seg > 0) {
             const int n_slices = (sgg.max_seg >= 256 && G <= 256) ? 16 : 1;
             void *sl = nullptr;
-            if (n_slices > 1 && (rc = ensure_scratch(ctx, 3, round256(sizeof(double) * nz * nz * (size_t)n_slices * G), &sl))) return rc;   // (slot 3: the fix-up work area, idle here)
+            if (n_slices > 1 && (rc = ensure_scratch(ctx, Work::Fixup, round256(sizeof(double) * nz * nz * (size_t)n_slices * G), &sl))) return rc;   // (the fix-up work area, idle here)
             ga.offs = sgg.offs; ga.n_groups = sgg.n_seg; ga.gram = reinterpret_cast<double *>(sgg.extra);
             if ((rc = gram_stream_launch(ctx, b->dtype, ga))) return rc;
             GramReduceArgs ra;
@@ -1648,7 +1657,7 @@ int pols_least_squares_statistics(pols_ctx *ctx, const pols_batch *b, const pols
         if ((rc = ensure_segments(ctx, b, mr, per_seg, &sg))) return rc;
         if (sg.n_seg > 0) {
             void *pp = nullptr;
-            if ((rc = ensure_scratch(ctx, 19, round256(sizeof(double) * G * (3 * (size_t)kt + 1)), &pp))) return rc;   // (slot 19: the rolling entry's, never live here)
+            if ((rc = ensure_scratch(ctx, Work::RowCompact, round256(sizeof(double) * G * (3 * (size_t)kt + 1)), &pp))) return rc;   // (Work::RowCompact: the rolling entry's, never live here)
             sa.seg_offs = sg.offs; sa.seg_map = sg.map; sa.seg_first = sg.first; sa.n_seg = sg.n_seg;
             sa.seg_part = reinterpret_cast<double *>(sg.extra);
             sa.prep = static_cast<double *>(pp);
@@ -1706,10 +1715,10 @@ static int dynamic_prologue(pols_ctx *ctx, const pols_batch *b, int null_policy,
     // (a caller's validity bytes without weights / intercept: the columns may still hold NaNs on the masked rows -- they are
     //  zero-filled like everywhere else, so that no prefix sum ever meets a NaN; null_free says there is nothing to fill)
     if (scan || has_w || icpt || (st->valid != nullptr && !b->null_free)) {
-        // slot 14: [flags][validity bytes][feature pointers in][column pointers out][sqrt(w)][target][k columns]
+        // Work::DynPrep: [flags][validity bytes][feature pointers in][column pointers out][sqrt(w)][target][k columns]
         void *d = nullptr;
         const size_t tabb = round256(sizeof(void *) * (size_t)std::max(k, 1));
-        if ((rc = ensure_scratch(ctx, 14, 256 + vb + 2 * tabb + colb * (size_t)(k + 2), &d))) return rc;
+        if ((rc = ensure_scratch(ctx, Work::DynPrep, 256 + vb + 2 * tabb + colb * (size_t)(k + 2), &d))) return rc;
         base = static_cast<char *>(d);
         char *cols = base + 256 + vb + 2 * tabb;
         std::vector<void *> outp((size_t)k);
@@ -1772,15 +1781,15 @@ static int build_chunk_tables(pols_ctx *ctx, const pols_batch *b, int64_t mp, in
 // inversion: a few hundred long chunks instead of thousands of 64-row ones
 static int64_t hbm_state_chunk(int64_t n_rows) { return std::max<int64_t>(64, (n_rows + 383) / 384); }
 
-// Scratch slot 6 of the dynamic entries: [128 doubles: RLS prior mean][column pointer table for more than 32 features]
-static int dynamic_slot6(pols_ctx *ctx, void **base) {
-    return ensure_scratch(ctx, 6, sizeof(double) * K4Y_KMAX + sizeof(void *) * K4Y_KMAX, base);
+// Work::Tables of the dynamic entries: [128 doubles: RLS prior mean][column pointer table for more than 32 features]
+static int dynamic_tables(pols_ctx *ctx, void **base) {
+    return ensure_scratch(ctx, Work::Tables, sizeof(double) * K4Y_KMAX + sizeof(void *) * K4Y_KMAX, base);
 }
 static int upload_column_table(pols_ctx *ctx, const Staged &st, int k, K4Args *a) {
     for (int j = 0; j < std::min(k, (int)POLS_MAX_FEATURES); ++j) a->x[j] = st.x[j];
     if (k <= POLS_MAX_FEATURES) return POLS_OK;
     void *d = nullptr;
-    int rc = dynamic_slot6(ctx, &d);
+    int rc = dynamic_tables(ctx, &d);
     if (rc) return rc;
     char *tab = static_cast<char *>(d) + sizeof(double) * K4Y_KMAX;
     if ((rc = upload_small(ctx, tab, st.x.data(), sizeof(void *) * (size_t)k))) return rc;
@@ -1788,16 +1797,16 @@ static int upload_column_table(pols_ctx *ctx, const Staged &st, int k, K4Args *a
     return POLS_OK;
 }
 
-// Sequence-start bytes of the row-parallel dynamic kernels (scratch slot 16), cached per uploaded offsets.
+// Sequence-start bytes of the row-parallel dynamic kernels, cached per uploaded offsets.
 static int ensure_start_flags(pols_ctx *ctx, const int64_t *d_offs, int64_t n_groups, int64_t n_rows, const uint8_t **flags) {
-    void *d = nullptr;
-    int rc = ensure_scratch(ctx, 16, round256((size_t)n_rows + 4), &d);
-    if (rc) return rc;
     auto &fc = ctx->start_flags;
-    if (fc.ptr != d || fc.offs_id != ctx->offs_id || fc.n_groups != n_groups || fc.n_rows != n_rows) {
-        fc.ptr = nullptr;
+    void *d = nullptr;
+    int rc = grow(fc, round256((size_t)n_rows + 4), &d);
+    if (rc) return rc;
+    if (!fc.valid || fc.offs_id != ctx->offs_id || fc.n_groups != n_groups || fc.n_rows != n_rows) {
+        fc.valid = false;
         if ((rc = k3c_start_flags(ctx, d_offs, n_groups, n_rows, static_cast<uint8_t *>(d)))) return rc;
-        fc.ptr = d; fc.offs_id = ctx->offs_id; fc.n_groups = n_groups; fc.n_rows = n_rows;
+        fc.valid = true; fc.offs_id = ctx->offs_id; fc.n_groups = n_groups; fc.n_rows = n_rows;
     }
     *flags = static_cast<const uint8_t *>(d);
     return POLS_OK;
@@ -1816,23 +1825,23 @@ static void packed_tile_starts(const int64_t *offs, int64_t n_groups, int64_t N,
 
 // Packed tiles of the row-parallel dynamic kernels (K3c / K4c): no sequence longer than a tile (less the three rows a tile may start
 // before its first sequence) -> tiles are cut at sequence starts, whole sequences, first fit in frame order; tile t owns rows
-// [map[t], map[t + 1]).  Taken when the tiles come out at least 70 % full; *n_tiles = 0 otherwise.  Scratch slot 18, cached per frame.
+// [map[t], map[t + 1]).  Taken when the tiles come out at least 70 % full; *n_tiles = 0 otherwise.  Cached per frame (ctx->k3c).
 static int ensure_packed_tiles(pols_ctx *ctx, const pols_batch *b, int64_t tile_rows, int64_t max_rows, const int64_t **map, int64_t *n_tiles) {
     *map = nullptr; *n_tiles = 0;
     if (max_rows > tile_rows - 3) return POLS_OK;
     const int64_t N = b->n_rows;
     auto &tc = ctx->k3c;
     void *dmap = nullptr;
-    int rc = ensure_scratch(ctx, 18, round256(sizeof(int64_t) * (size_t)(b->n_groups + 2)), &dmap);
+    int rc = grow(tc, round256(sizeof(int64_t) * (size_t)(b->n_groups + 2)), &dmap);
     if (rc) return rc;
-    if (tc.ptr != dmap || tc.offs_id != ctx->offs_id || tc.n_groups != b->n_groups || tc.n_rows != N || tc.tile_rows != tile_rows) {
-        tc.ptr = nullptr;
+    if (!tc.valid || tc.offs_id != ctx->offs_id || tc.n_groups != b->n_groups || tc.n_rows != N || tc.tile_rows != tile_rows) {
+        tc.valid = false;
         std::vector<int64_t> first;
         packed_tile_starts(b->group_offsets, b->n_groups, N, tile_rows, &first);
         const int64_t nt = (int64_t)first.size() - 1;
         tc.n_tiles = nt * tile_rows * 7 <= N * 10 ? nt : 0;
         if (tc.n_tiles && (rc = upload_small(ctx, dmap, first.data(), sizeof(int64_t) * first.size()))) return rc;
-        tc.ptr = dmap; tc.offs_id = ctx->offs_id; tc.n_groups = b->n_groups; tc.n_rows = N; tc.tile_rows = tile_rows;
+        tc.valid = true; tc.offs_id = ctx->offs_id; tc.n_groups = b->n_groups; tc.n_rows = N; tc.tile_rows = tile_rows;
     }
     *n_tiles = tc.n_tiles;
     if (tc.n_tiles) *map = static_cast<const int64_t *>(dmap);
@@ -1840,16 +1849,16 @@ static int ensure_packed_tiles(pols_ctx *ctx, const pols_batch *b, int64_t tile_
 }
 
 // K3c's halo form: per tile of tile_rows rows the first row of the sequence that holds the row in front of the tile (tile 0: 0) -- the
-// prior's decay up to the tile is then exact.  Scratch slot 25, cached per frame.
+// prior's decay up to the tile is then exact.  Cached per frame (ctx->k3h).
 static int ensure_tile_seq0(pols_ctx *ctx, const pols_batch *b, int64_t tile_rows, int64_t n_tiles, const int64_t **map) {
     *map = nullptr;
     const int64_t N = b->n_rows;
     auto &tc = ctx->k3h;
     void *dmap = nullptr;
-    int rc = ensure_scratch(ctx, 25, round256(sizeof(int64_t) * (size_t)(n_tiles + 1)), &dmap);
+    int rc = grow(tc, round256(sizeof(int64_t) * (size_t)(n_tiles + 1)), &dmap);
     if (rc) return rc;
-    if (tc.ptr != dmap || tc.offs_id != ctx->offs_id || tc.n_groups != b->n_groups || tc.n_rows != N || tc.tile_rows != tile_rows) {
-        tc.ptr = nullptr;
+    if (!tc.valid || tc.offs_id != ctx->offs_id || tc.n_groups != b->n_groups || tc.n_rows != N || tc.tile_rows != tile_rows) {
+        tc.valid = false;
         std::vector<int64_t> first((size_t)n_tiles, 0);
         const int64_t *offs = b->group_offsets;
         int64_t g = 0;
@@ -1859,7 +1868,7 @@ static int ensure_tile_seq0(pols_ctx *ctx, const pols_batch *b, int64_t tile_row
             first[(size_t)t] = offs[g];
         }
         if ((rc = upload_small(ctx, dmap, first.data(), sizeof(int64_t) * first.size()))) return rc;
-        tc.ptr = dmap; tc.offs_id = ctx->offs_id; tc.n_groups = b->n_groups; tc.n_rows = N; tc.tile_rows = tile_rows;
+        tc.valid = true; tc.offs_id = ctx->offs_id; tc.n_groups = b->n_groups; tc.n_rows = N; tc.tile_rows = tile_rows;
     }
     *map = static_cast<const int64_t *>(dmap);
     return POLS_OK;
@@ -1904,7 +1913,7 @@ int pols_recursive_least_squares(pols_ctx *ctx, const pols_batch *b, const pols_
     a.initial_state_covariance = p->initial_state_covariance;
     if (p->initial_state_mean) {
         void *d = nullptr;
-        if ((rc = dynamic_slot6(ctx, &d))) return rc;
+        if ((rc = dynamic_tables(ctx, &d))) return rc;
         if ((rc = upload_small(ctx, d, p->initial_state_mean, sizeof(double) * kf))) return rc;   // the host array belongs to the caller (kf values)
         a.mean0 = static_cast<const double *>(d);
     }
@@ -1923,7 +1932,7 @@ int pols_recursive_least_squares(pols_ctx *ctx, const pols_batch *b, const pols_
                      b_brec = round256(sizeof(double) * K3C_NCP * (size_t)n_blocks), b_bint = round256(sizeof(int32_t) * (size_t)n_blocks),
                      total = 2 * b_rec + 2 * b_int + 2 * b_brec + b_bint;
         void *d = nullptr;
-        if ((rc = ensure_scratch(ctx, 8, total, &d))) return rc;
+        if ((rc = ensure_scratch(ctx, Work::K3cRecords, total, &d))) return rc;
         char *base = static_cast<char *>(d);
         const uint8_t *flags = nullptr;
         if ((rc = ensure_start_flags(ctx, d_offs, b->n_groups, N, &flags))) return rc;
@@ -1958,11 +1967,9 @@ int pols_recursive_least_squares(pols_ctx *ctx, const pols_batch *b, const pols_
             const size_t gbytes = (size_t)n_tiles * 32 * 16;
             if (kf <= 6 && halo <= 4 && tile_rows == 1024 && n_tiles > 1 && gbytes < ((size_t)1 << 31) && ctx->opt.rls_engine != 4) {
                 void *g = nullptr;
-                if ((rc = ensure_scratch(ctx, 28, gbytes, &g))) return rc;
-                if (ctx->k3c_gran_ptr != g || ctx->scratch[28].cap != ctx->k3c_gran_cap) {       // fresh or grown: no stale tag may survive
-                    POLS_HIP(hipMemsetAsync(g, 0, ctx->scratch[28].cap, ctx->stream));
-                    ctx->k3c_gran_ptr = g; ctx->k3c_gran_cap = ctx->scratch[28].cap;
-                }
+                bool fresh = false;
+                if ((rc = grow(ctx->k3c_gran, gbytes, &g, &fresh))) return rc;
+                if (fresh) POLS_HIP(hipMemsetAsync(g, 0, ctx->k3c_gran.cap, ctx->stream));       // no stale tag may survive
                 c.gran = g; c.gran_bytes = (int64_t)gbytes; c.epoch = ++ctx->k3c_epoch;
                 c.spin_limit = ctx->opt.rls_spin_limit >= 0 ? ctx->opt.rls_spin_limit : 64;
                 c.early_publish = ctx->opt.rls_early;
@@ -2000,7 +2007,8 @@ int pols_recursive_least_squares(pols_ctx *ctx, const pols_batch *b, const pols_
 
 // Host-side tables shared by the chunk-parallel dynamic kernels (K4 rolling, K3s RLS scan): validity prefix
 // (cnt / vidx), per-group warm-up constants of solve_rolling_ols (ls.rs:881-900) and the chunk list; uploaded to
-// scratch slot 4, the per-chunk totals live in slot 5 (`slots` doubles per chunk).
+// ctx->chunk_cache's table, the per-chunk totals live in Work::Gram (`slots` doubles per chunk).  Only the tables of a mask-free batch on
+// the uploaded offsets are kept for the next call: other offsets (a compacted frame) can share every key the cache compares.
 static int build_chunk_tables(pols_ctx *ctx, const pols_batch *b, int64_t mp, int slots, K4Args *a, int64_t min_chunk, int64_t max_chunk) {
     int rc;
     const int64_t N = b->n_rows;
@@ -2008,7 +2016,8 @@ static int build_chunk_tables(pols_ctx *ctx, const pols_batch *b, int64_t mp, in
     const uint8_t *hv = nullptr;
     // validity bytes that live on the device: the prefix tables are built there too (dyn_prep.hip valid_tables_launch) -- copying the
     // bytes home, walking every row and uploading two int32 tables was 40+ ms of a 10 M-row call whose kernels take 3-5
-    const bool dev_tables = b->valid && b->mem == POLS_MEM_DEVICE && ctx->scratch[0].ptr && b->n_groups > 0 && N > 0;
+    const bool uploaded = ctx->offsets.valid && b->group_offsets == ctx->offs_host;
+    const bool dev_tables = b->valid && b->mem == POLS_MEM_DEVICE && uploaded && b->n_groups > 0 && N > 0;
     if (b->valid && !dev_tables) {
         if (b->mem == POLS_MEM_DEVICE) {
             hvalid.resize((size_t)N);
@@ -2024,11 +2033,12 @@ static int build_chunk_tables(pols_ctx *ctx, const pols_batch *b, int64_t mp, in
     // uncoalesced and more concurrent lanes cost more in the memory system than they win in parallelism)
     const int64_t chunk_len = std::min<int64_t>(std::max(max_chunk, min_chunk), std::max<int64_t>(min_chunk, N / 16384));
     auto &cc = ctx->chunk_cache;
-    if (!hv && !dev_tables && cc.tab && cc.tab == ctx->scratch[10].ptr && cc.offs_id == ctx->offs_id && cc.n_groups == b->n_groups &&
+    const bool cacheable = !hv && !dev_tables && uploaded;
+    if (cacheable && cc.valid && cc.offs_id == ctx->offs_id && cc.n_groups == b->n_groups &&
         cc.n_rows == N && cc.mp == mp && cc.chunk_len == (int32_t)chunk_len) {      // same frame as the last call
         void *tot = nullptr;
-        if ((rc = ensure_scratch(ctx, 5, sizeof(double) * (size_t)slots * std::max<size_t>(1, (size_t)cc.n_chunks), &tot))) return rc;
-        const char *tp = static_cast<const char *>(cc.tab);
+        if ((rc = ensure_scratch(ctx, Work::Gram, sizeof(double) * (size_t)slots * std::max<size_t>(1, (size_t)cc.n_chunks), &tot))) return rc;
+        const char *tp = static_cast<const char *>(cc.buf.ptr);
         a->groups = reinterpret_cast<const K4Group *>(tp);
         a->chunks = reinterpret_cast<const K4Chunk *>(tp + cc.b_groups);
         a->order = reinterpret_cast<const int32_t *>(tp + cc.b_groups + round256(sizeof(K4Chunk) * (size_t)cc.n_chunks));
@@ -2085,9 +2095,9 @@ static int build_chunk_tables(pols_ctx *ctx, const pols_batch *b, int64_t mp, in
         std::stable_sort(order.begin(), order.end(), [&](int32_t x, int32_t y) { return chunks[(size_t)x].t1 - chunks[(size_t)x].t0 > chunks[(size_t)y].t1 - chunks[(size_t)y].t0; });
     const size_t b_order = round256(sizeof(int32_t) * order.size());
     void *tab = nullptr, *tot = nullptr;
-    cc.tab = nullptr;                                  // the slot is about to be rewritten (and possibly re-allocated)
-    if ((rc = ensure_scratch(ctx, 10, b_groups + b_chunks + b_order + 2 * b_cnt + b_sc + b_sb + b_co + 256, &tab))) return rc;   // slot 10 belongs to these tables alone
-    if ((rc = ensure_scratch(ctx, 5, sizeof(double) * (size_t)slots * std::max<size_t>(1, chunks.size()), &tot))) return rc;
+    cc.valid = false;                                  // the table is about to be rewritten
+    if ((rc = grow(cc, b_groups + b_chunks + b_order + 2 * b_cnt + b_sc + b_sb + b_co + 256, &tab))) return rc;
+    if ((rc = ensure_scratch(ctx, Work::Gram, sizeof(double) * (size_t)slots * std::max<size_t>(1, chunks.size()), &tot))) return rc;
     char *tp = static_cast<char *>(tab);
     if ((rc = upload_small(ctx, tp, groups.data(), sizeof(K4Group) * groups.size()))) return rc;   // locals: through the pinned ring
     if ((rc = upload_small(ctx, tp + b_groups, chunks.data(), sizeof(K4Chunk) * chunks.size()))) return rc;
@@ -2107,7 +2117,7 @@ static int build_chunk_tables(pols_ctx *ctx, const pols_batch *b, int64_t mp, in
         char *xb = tp + b_groups + b_chunks + b_order + 2 * b_cnt;
         RowCompactArgs ra;
         std::memset(&ra, 0, sizeof(ra));
-        ra.valid = b->valid; ra.offs = static_cast<const int64_t *>(ctx->scratch[0].ptr);
+        ra.valid = b->valid; ra.offs = static_cast<const int64_t *>(ctx->offsets.buf.ptr);
         ra.n_rows = N; ra.n_groups = b->n_groups; ra.n_slabs = n_slabs;
         ra.slab_cnt = reinterpret_cast<uint32_t *>(xb);
         ra.slab_base = reinterpret_cast<int64_t *>(xb + b_sc);
@@ -2127,10 +2137,9 @@ static int build_chunk_tables(pols_ctx *ctx, const pols_batch *b, int64_t mp, in
     a->n_groups = (int32_t)b->n_groups;
     a->totals = static_cast<double *>(tot);
     a->chunk_len = (int32_t)chunk_len;
-    cc.tab = nullptr;
-    if (!hv && !dev_tables) {
+    if (cacheable) {
         cc.offs_id = ctx->offs_id; cc.n_groups = b->n_groups; cc.n_rows = N; cc.mp = mp; cc.n_chunks = a->n_chunks;
-        cc.chunk_len = (int32_t)chunk_len; cc.tab = tab; cc.b_groups = b_groups;
+        cc.chunk_len = (int32_t)chunk_len; cc.valid = true; cc.b_groups = b_groups;
     }
     return POLS_OK;
 }
@@ -2192,7 +2201,7 @@ int pols_rolling_least_squares(pols_ctx *ctx, const pols_batch *b, const pols_ro
         // K4p, 11..32 features, still runs on compacted columns).
         const bool gather = c_tiles_ok && N < ((int64_t)1 << 31) && ctx->opt.rolling_engine != 5;
         void *d = nullptr;
-        if ((rc = ensure_scratch(ctx, 19, b_cnt + b_base + b_offs + b_gf + 2 * b_tab + (gather ? 0 : colb * (size_t)(k + 1)), &d))) return rc;
+        if ((rc = ensure_scratch(ctx, Work::RowCompact, b_cnt + b_base + b_offs + b_gf + 2 * b_tab + (gather ? 0 : colb * (size_t)(k + 1)), &d))) return rc;
         char *base = static_cast<char *>(d);
         char *cols = base + b_cnt + b_base + b_offs + b_gf + 2 * b_tab;
         std::vector<const void *> inp((size_t)k + 1);
@@ -2230,24 +2239,21 @@ int pols_rolling_least_squares(pols_ctx *ctx, const pols_batch *b, const pols_ro
             void *dc = nullptr, *df = nullptr, *dm = nullptr;
             if (gather) {
                 void *dsrc = nullptr;
-                if ((rc = ensure_scratch(ctx, 23, round256(sizeof(int32_t) * (size_t)(Nc + 4)), &dsrc))) return rc;
+                if ((rc = ensure_scratch(ctx, Work::GatherMap, round256(sizeof(int32_t) * (size_t)(Nc + 4)), &dsrc))) return rc;
                 ra.src = static_cast<int32_t *>(dsrc);
                 if ((rc = row_compact_srcmap_launch(ctx, ra))) return rc;
             } else {
                 if ((rc = row_compact_scatter_launch(ctx, b->dtype, ra))) return rc;
-                if ((rc = ensure_scratch(ctx, 20, round256(sz * (size_t)Nc * (size_t)k), &dc))) return rc;
+                if ((rc = ensure_scratch(ctx, Work::CompactCoef, round256(sz * (size_t)Nc * (size_t)k), &dc))) return rc;
             }
             if (!c_tiles_ok) {
-                // the compacted frame through K4p: chunk tables of the COMPACTED offsets (never cached: two null patterns of one frame can
-                // share every key the cache compares)
+                // the compacted frame through K4p: chunk tables of the COMPACTED offsets (build_chunk_tables does not cache them)
                 pols_batch cb = *b;
                 cb.group_offsets = c_offs.data(); cb.n_rows = Nc; cb.valid = nullptr;
                 const int64_t pchunk = max_c <= 1024 ? 1024 : std::min<int64_t>(1024, std::max<int64_t>(256, Nc / 16384));
                 K4Args a;
                 std::memset(&a, 0, sizeof(a));
-                ctx->chunk_cache.tab = nullptr;
                 if ((rc = build_chunk_tables(ctx, &cb, mp, k * k + k, &a, pchunk, pchunk))) return rc;
-                ctx->chunk_cache.tab = nullptr;
                 a.y = outp[0];
                 for (int j = 0; j < k; ++j) a.x[j] = outp[(size_t)j + 1];
                 a.coef = dc; a.pred = nullptr;
@@ -2262,7 +2268,7 @@ int pols_rolling_least_squares(pols_ctx *ctx, const pols_batch *b, const pols_ro
                 if (ds.post && (rc = dyn_post_launch(ctx, b->dtype, ds.pa))) return rc;
                 return unstage_outputs(ctx, b, b->n_rows, k, o, st);
             }
-            if ((rc = ensure_scratch(ctx, 21, round256((size_t)Nc + 4), &df))) return rc;
+            if ((rc = ensure_scratch(ctx, Work::CompactStarts, round256((size_t)Nc + 4), &df))) return rc;
             if ((rc = k3c_start_flags(ctx, ra.c_offs, G, Nc, static_cast<uint8_t *>(df)))) return rc;
             K4cArgs c;
             std::memset(&c, 0, sizeof(c));
@@ -2285,7 +2291,7 @@ int pols_rolling_least_squares(pols_ctx *ctx, const pols_batch *b, const pols_ro
                 if (nt * K4C_PACKED_ROWS * 7 <= Nc * 10 || w > k4c_max_window(k)) {    // (a window beyond the halo forms: packed whatever the fill)
                     c.window = std::min<int64_t>(w, 2 * K4C_PACKED_ROWS);
                     c.min_periods = std::min<int64_t>(mp, c.window);     // (see the null-free route below)
-                    if ((rc = ensure_scratch(ctx, 22, round256(sizeof(int64_t) * first.size()), &dm))) return rc;
+                    if ((rc = ensure_scratch(ctx, Work::CompactTiles, round256(sizeof(int64_t) * first.size()), &dm))) return rc;
                     if ((rc = upload_small(ctx, dm, first.data(), sizeof(int64_t) * first.size()))) return rc;
                     c.tile_row0 = static_cast<const int64_t *>(dm); c.n_packed = nt;
                 }
@@ -2342,7 +2348,7 @@ int pols_rolling_least_squares(pols_ctx *ctx, const pols_batch *b, const pols_ro
             void *d = nullptr;
             const int64_t n_blk = (n_slabs + 1023) / 1024;
             const size_t b_blk = round256(sizeof(unsigned long long) * 2 * (size_t)n_blk);
-            if ((rc = ensure_scratch(ctx, 19, 256 + b_blk + 2 * b_r2 + b_sol + b_sc + 3 * b_s8 + 2 * b_g8 + b_g4, &d))) return rc;   // (slot 19: the compaction's, never live here)
+            if ((rc = ensure_scratch(ctx, Work::RowCompact, 256 + b_blk + 2 * b_r2 + b_sol + b_sc + 3 * b_s8 + 2 * b_g8 + b_g4, &d))) return rc;   // (Work::RowCompact: the compaction's, never live here)
             char *q = static_cast<char *>(d);
             RollMaskArgs ma;
             std::memset(&ma, 0, sizeof(ma));
@@ -2447,13 +2453,13 @@ int pols_predict_policy(pols_ctx *ctx, const pols_batch *b, const void *coef, in
     if (b->mem == POLS_MEM_HOST) {
         void *d = nullptr;
         const size_t bytes = dtype_size(b->dtype) * (size_t)coef_rows * kt;
-        if ((rc = ensure_scratch(ctx, 5, bytes, &d))) return rc;
+        if ((rc = ensure_scratch(ctx, Work::Gram, bytes, &d))) return rc;
         POLS_HIP(hipMemcpyAsync(d, coef, bytes, hipMemcpyHostToDevice, ctx->stream));
         d_coef = d;
     }
     if (kt > POLS_MAX_FEATURES) {                                  // wide frames: column pointers through a device table
         void *tab = nullptr;
-        if ((rc = ensure_scratch(ctx, 6, sizeof(void *) * (size_t)b->n_features, &tab))) return rc;
+        if ((rc = ensure_scratch(ctx, Work::Tables, sizeof(void *) * (size_t)b->n_features, &tab))) return rc;
         if ((rc = upload_small(ctx, tab, st.x.data(), sizeof(void *) * (size_t)b->n_features))) return rc;
         WideArgs wa;
         std::memset(&wa, 0, sizeof(wa));
@@ -2557,7 +2563,7 @@ int pols_least_squares_sharded(pols_ctx *const *ctxs, pols_comm *const *comms, i
             if (sb.n_groups == 0) return done(POLS_OK);
             return done(pols_least_squares(ctx, &sb, p, &so));
         }
-        // device-side assembly: stage the shard on this device (scratch slot 13), solve it there with the outputs next to it, then
+        // device-side assembly: stage the shard on this device (Work::Collective), solve it there with the outputs next to it, then
         // the collectives on this device's stream.  Every rank takes part in every collective, shard or no shard.
         int rc2 = check_ctx(ctx);
         if (rc2) return done(rc2);
@@ -2566,7 +2572,7 @@ int pols_least_squares_sharded(pols_ctx *const *ctxs, pols_comm *const *comms, i
         const size_t statb = round256(sizeof(int32_t) * (size_t)std::max<int64_t>(sb.n_groups, 1));
         const int n_in = 1 + b->n_features + (b->weights ? 1 : 0);
         void *base = nullptr;
-        if ((rc2 = ensure_scratch(ctx, 13, colb * (size_t)(n_in + 2) + vb + coefb + allb + statb, &base))) return done(rc2);
+        if ((rc2 = ensure_scratch(ctx, Work::Collective, colb * (size_t)(n_in + 2) + vb + coefb + allb + statb, &base))) return done(rc2);
         char *q = static_cast<char *>(base);
         auto put = [&](const void *src, size_t bytes, size_t slot) -> const void * {
             char *d = q; q += slot;

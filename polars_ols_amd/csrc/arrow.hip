@@ -359,12 +359,12 @@ struct Ingested {
     T *y = nullptr, *w = nullptr;
     std::vector<const void *> x;
     std::vector<T *> targets;     // multi-target: the fields of the target struct
-    char *free_area = nullptr;    // what is left of the scratch slot behind the columns (outputs, export scratch)
+    char *free_area = nullptr;    // what is left of Work::Arrow behind the columns (outputs, export scratch)
     size_t free_bytes = 0;
     bool null_free = false;
 };
 
-// Stages target (or the fields of a target struct), features and weights as contiguous device columns of T in scratch slot 12,
+// Stages target (or the fields of a target struct), features and weights as contiguous device columns of T in Work::Arrow,
 // leaving `extra` bytes behind them.  Null -> NaN; a null weight acts as the weight 1e-24 (sqrt_w.fill_null(1e-12),
 // least_squares.py:193).
 template <typename T>
@@ -377,7 +377,7 @@ static int ingest_all(pols_ctx *ctx, const std::vector<ColView> &targets, const 
     if (weights) raw_cap = std::max(raw_cap, weights->raw_bytes());
     const size_t n_in = targets.size() + feat.size() + (weights ? 1 : 0);
     void *base = nullptr;
-    int rc = ensure_scratch(ctx, 12, colb * n_in + raw_cap + extra, &base);
+    int rc = ensure_scratch(ctx, Work::Arrow, colb * n_in + raw_cap + extra, &base);
     if (rc) return rc;
     char *q = static_cast<char *>(base);
     char *raw = q + colb * n_in;

@@ -29,9 +29,43 @@ int fail(int code, const char *fmt, ...);
     } while (0)
 
 // ---------------------------------------------------------------- context
-struct Scratch {
+// grow-only device buffer
+struct DeviceBuffer {
     void *ptr = nullptr;
     size_t cap = 0;
+};
+
+// a device table cached across calls, owned by one cache of pols_ctx: it holds what the cache's key fields describe while `valid` is set
+struct CachedTable {
+    DeviceBuffer buf;
+    bool valid = false;
+};
+
+// the context's transient work buffers: each call asks for what it needs and holds nothing across calls.  Uses that share a buffer
+// are never live at the same time.
+enum class Work : int {
+    HostInputs,     // inputs of HOST batches; K9 (k9_layout.hip): key / column staging
+    HostOutputs,    // outputs of HOST batches
+    Fixup,          // fix-up work area; per-chunk states of K4y, work of K8, Gram slices of the statistics entry
+    HostStaged,     // staged targets / statistics of HOST batches
+    Gram,           // Gram matrices / chunk totals / staged coefficients
+    Tables,         // RLS prior mean, column pointer tables, coefficients of the statistics entry, K9's key probes
+    Status,         // status words
+    K3cRecords,     // K3c tile / block records
+    K9Keys,         // group-key ingestion (K9)
+    Timeline,       // timeline stamps (POLS_TIMELINE) and debug records of K3c / K4c
+    Arrow,          // Arrow ingestion
+    Collective,     // collective staging
+    DynPrep,        // dynamic-path prep / null-policy compaction (dyn_prep.hip)
+    CompactOut,     // host-batch outputs of the compacted static entries
+    NullWeights,    // null-weight-filled copy of a DEVICE batch's weights column (static entries)
+    RowCompact,     // row compaction of the rolling entry (tables, columns); per-group moments of the statistics entry
+    CompactCoef,    // coefficients of the compacted rolling frame
+    CompactStarts,  // sequence-start bytes of the compacted rolling frame
+    CompactTiles,   // first rows of the compacted frame's packed tiles
+    CompactTotals,  // row compaction: totals of every 1 024 slabs (row_compact_offsets_launch)
+    GatherMap,      // rolling GATHER tiles: source row of every compacted row
+    Count
 };
 
 struct TimedLaunch {
@@ -89,14 +123,7 @@ struct pols_ctx {
     hipStream_t stream = nullptr;
     hipEvent_t switch_event = nullptr;       // pols_set_stream: the new stream waits for what the old one still has in flight
     int num_cus = 0;
-    // device scratch (grow-only): [0] group offsets, [1] inputs for HOST batches, [2] outputs, [3] fix-up work area,
-    // [4] staged targets / statistics of HOST batches, [5] Gram matrices / chunk totals / staged coefficients, [6] RLS prior mean,
-    // [7] status words, [8] K3c tile / block records, [9] group-key ingestion (K9), [10] chunk / group tables of the dynamic kernels
-    // (nothing else may take this slot: the tables are cached across calls), [11] timeline stamps, [12] Arrow ingestion,
-    // [13] collective staging, [14] dynamic-path prep / null-policy compaction (dyn_prep.hip), [15] their host-batch outputs
-    // [16] sequence-start bytes of the row-parallel dynamic kernels (K3c / K4c), [17] null-weight-filled copy of a DEVICE batch's weights column (static entries), [18] first rows of K3c's packed tiles, [19..22] row compaction of the rolling entry (columns, coefficients, start bytes, tile map), [23] segment tables + partial Gram matrices of the streamed static path,
-    // [24] group lists of the size classes, [25] K3c halo form: first row of the sequence in front of every tile, [26] segment tables of the last size class, [27] K4c: rows without a factorisation (the LU list), [28] K3c look-back form: the tiles' record granules
-    pols::Scratch scratch[29];
+    pols::DeviceBuffer work[(int)pols::Work::Count];
     pols::Options opt;
     bool timing = false;
     int timing_stride = 1;                   // time every n-th eligible launch (pols_timing_enable(ctx, n))
@@ -108,6 +135,7 @@ struct pols_ctx {
     // cache of the last uploaded group_offsets so steady-state calls on the same frame do not re-upload metadata.  A hit is
     // either PROMISED by the caller (same host pointer, count and non-zero pols_batch.offsets_generation) or VERIFIED: same
     // count, same content hash AND a memcmp against the host copy kept here -- a hash collision cannot alias two frames.
+    pols::CachedTable offsets;               // the uploaded offsets on the device
     const int64_t *offs_host = nullptr;
     uint64_t offs_generation = 0;
     std::vector<int64_t> offs_copy;
@@ -128,31 +156,36 @@ struct pols_ctx {
     int32_t *fb_flag = nullptr;              // device word, see K1Args::fb_flag
     int32_t epoch = 0;
     bool offs_aligned[2] = {false, false};   // every group start AND size a multiple of 2 / of 4 rows
-    // cache of the chunk tables of the dynamic kernels (scratch slot 4) for mask-free batches: rebuilt only when the
-    // offsets, min_periods or the chunk length change
-    struct { uint64_t offs_id = 0; int64_t n_groups = -1, n_rows = -1, mp = -1, n_chunks = 0; int32_t chunk_len = 0;
-             const void *tab = nullptr; size_t b_groups = 0; } chunk_cache;
-    // K3c (k3c_scan.hip), scratch slot 18: first row of every PACKED tile (tiles cut at sequence starts, single-pass mode); n_tiles 0 =
+    // The caches below each own their device table (pols::CachedTable): a hit needs the table's `valid` flag and a matching key.
+    // chunk tables of the dynamic kernels for mask-free batches of the uploaded offsets: rebuilt only when the offsets,
+    // min_periods or the chunk length change
+    struct : pols::CachedTable { uint64_t offs_id = 0; int64_t n_groups = -1, n_rows = -1, mp = -1, n_chunks = 0; int32_t chunk_len = 0;
+                                 size_t b_groups = 0; } chunk_cache;
+    // K3c (k3c_scan.hip): first row of every PACKED tile (tiles cut at sequence starts, single-pass mode); n_tiles 0 =
     // this frame does not pack (a sequence longer than a tile, or tiles too empty)
-    struct { const void *ptr = nullptr; uint64_t offs_id = 0; int64_t n_groups = -1, n_rows = -1, tile_rows = 0, n_tiles = 0; } k3c;
-    // K3c halo form, scratch slot 25: per tile the first row of the sequence that holds the row in front of it
-    struct { const void *ptr = nullptr; uint64_t offs_id = 0; int64_t n_groups = -1, n_rows = -1, tile_rows = 0; } k3h;
-    // segment tables of the streamed static path (scratch slot 23: long groups cut into segments): rebuilt when other offsets arrive
-    struct { const void *ptr = nullptr; uint64_t offs_id = 0; int64_t cut[3] = {0, 0, 0}, n[4] = {0, 0, 0, 0}; int n_cut = 0;
-             std::vector<int32_t> host_last; } class_cache;   // group lists of the size classes (slot 24; host_last: the last class' ids, for its segment tables)
-    struct { const void *ptr = nullptr; uint64_t offs_id = 0; int64_t n_groups = -1, n_rows = -1, seg_target = 0, n_seg = 0, max_len = 0, max_seg = 0, class_key = 0, n_items = 0; size_t nz2 = 0; bool nulls = false; } seg_cache[2];   // [0] whole-frame tables (slot 23), [1] the last size class' tables (slot 26)
-    const void *k3c_gran_ptr = nullptr;      // K3c look-back form (scratch slot 28): the slot's address when it was last zeroed; the launches' running tag
-    unsigned long long k3c_epoch = 0;
-    size_t k3c_gran_cap = 0;
-    const void *k4c_fix_ptr = nullptr;       // K4c's LU list (scratch slot 27): the slot's address when its counters were last zeroed, and whose turn it is
-    uint64_t k4c_fix_turn = 0;
-    // sequence-start bytes (scratch slot 16): rebuilt when other offsets arrive
-    struct { const void *ptr = nullptr; uint64_t offs_id = 0; int64_t n_groups = -1, n_rows = -1; } start_flags;
+    struct : pols::CachedTable { uint64_t offs_id = 0; int64_t n_groups = -1, n_rows = -1, tile_rows = 0, n_tiles = 0; } k3c;
+    // K3c halo form: per tile the first row of the sequence that holds the row in front of it
+    struct : pols::CachedTable { uint64_t offs_id = 0; int64_t n_groups = -1, n_rows = -1, tile_rows = 0; } k3h;
+    // group lists of the size classes (host_last: the last class' ids, for its segment tables)
+    struct : pols::CachedTable { uint64_t offs_id = 0; int64_t cut[3] = {0, 0, 0}, n[4] = {0, 0, 0, 0}; int n_cut = 0;
+                                 std::vector<int32_t> host_last; } class_cache;
+    // segment tables of the streamed static path (long groups cut into segments): [0] the whole frame's, [1] the last size class'
+    struct : pols::CachedTable { uint64_t offs_id = 0; int64_t n_groups = -1, n_rows = -1, seg_target = 0, n_seg = 0, max_len = 0, max_seg = 0, class_key = 0, n_items = 0; size_t nz2 = 0; bool nulls = false; } seg_cache[2];
+    // sequence-start bytes of the row-parallel dynamic kernels (K3c / K4c): rebuilt when other offsets arrive
+    struct : pols::CachedTable { uint64_t offs_id = 0; int64_t n_groups = -1, n_rows = -1; } start_flags;
+    pols::DeviceBuffer k3c_gran;             // K3c look-back form: the tiles' record granules, zeroed when (re)allocated
+    unsigned long long k3c_epoch = 0;        // ... and the launches' running tag
+    pols::DeviceBuffer k4c_fix;              // K4c / K4p: rows without a factorisation (the LU list), counters zeroed when (re)allocated
+    uint64_t k4c_fix_turn = 0;               // ... and which of its two counters is this launch's
 };
 
 namespace pols {
 
-int ensure_scratch(pols_ctx *ctx, int slot, size_t bytes, void **out);
+// grows `b` to at least `bytes` (64 KB at the least; a (re)allocation drops the contents); fresh: it was (re)allocated just now
+int grow(DeviceBuffer &b, size_t bytes, void **out, bool *fresh = nullptr);
+// ... a cached table: a (re)allocation clears its `valid`
+int grow(CachedTable &t, size_t bytes, void **out);
+int ensure_scratch(pols_ctx *ctx, Work w, size_t bytes, void **out);
 // uploads group offsets (cached), returns device pointer and max group size; generation: pols_batch.offsets_generation
 int upload_offsets(pols_ctx *ctx, const int64_t *offs, int64_t n_groups, const int64_t **d_offs, int64_t *max_rows,
                    uint64_t generation = 0);

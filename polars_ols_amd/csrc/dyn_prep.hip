@@ -603,7 +603,7 @@ int row_compact_offsets_launch(pols_ctx *ctx, const RowCompactArgs &a0) {
     RowCompactArgs a = a0;
     const unsigned n_blk = (unsigned)((a.n_slabs + 1023) / 1024);
     void *bc = nullptr;
-    int rc = ensure_scratch(ctx, 26, sizeof(unsigned long long) * (size_t)n_blk, &bc);    // totals of every 1 024 slabs
+    int rc = ensure_scratch(ctx, Work::CompactTotals, sizeof(unsigned long long) * (size_t)n_blk, &bc);    // totals of every 1 024 slabs
     if (rc) return rc;
     a.blk_cnt = static_cast<unsigned long long *>(bc);
     hipLaunchKernelGGL(rc_count_kernel, dim3((unsigned)a.n_slabs), dim3(RC_SLAB), 0, ctx->stream, a);

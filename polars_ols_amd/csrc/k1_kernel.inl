@@ -1377,7 +1377,7 @@ static int k1p_launch(pols_ctx *ctx, const K1Args &a) {
     if constexpr (KT == 8 && !HAS_W) {
         if (ctx->opt.timeline) {                             // phase cycles summed per persistent wave (debug): 7 "stamps" = 6 phases
             void *d = nullptr;
-            int rc = ensure_scratch(ctx, 11, sizeof(unsigned long long) * 8 * (size_t)blocks * 4, &d);
+            int rc = ensure_scratch(ctx, Work::Timeline, sizeof(unsigned long long) * 8 * (size_t)blocks * 4, &d);
             if (rc) return rc;
             aa.dbg = static_cast<unsigned long long *>(d);
             hipLaunchKernelGGL((k1p_kernel<T, KT, HAS_W, SUB, RC, true>), dim3((unsigned)blocks), dim3(256), 0, ctx->stream, aa);
@@ -1420,7 +1420,7 @@ static int k1_launch_fast(pols_ctx *ctx, const K1Args &a) {
     const bool timeline = ctx->opt.timeline;
     if (timeline) {
         void *d = nullptr;
-        int rc = ensure_scratch(ctx, 11, sizeof(unsigned long long) * 8 * (size_t)a.n_groups, &d);   // slot 3 holds the fix-up work area
+        int rc = ensure_scratch(ctx, Work::Timeline, sizeof(unsigned long long) * 8 * (size_t)a.n_groups, &d);   // (Work::Fixup holds the fix-up work area)
         if (rc) return rc;
         aa.dbg = static_cast<unsigned long long *>(d);
     }

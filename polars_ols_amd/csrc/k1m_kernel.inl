@@ -339,7 +339,7 @@ static int k1m_launch_kw(pols_ctx *ctx, const K1Args &a, int64_t max_rows) {
     const bool timeline = ctx->opt.timeline;
     if (timeline) {
         void *d = nullptr;
-        int rc = ensure_scratch(ctx, 11, sizeof(unsigned long long) * 8 * (size_t)a.n_groups, &d);
+        int rc = ensure_scratch(ctx, Work::Timeline, sizeof(unsigned long long) * 8 * (size_t)a.n_groups, &d);
         if (rc) return rc;
         aa.dbg = static_cast<unsigned long long *>(d);
     }

@@ -414,7 +414,7 @@ static int k2w_launch_v(pols_ctx *ctx, const K2wArgs &a) {
     K2wArgs aa = a;
     if (ctx->opt.timeline) {
         void *d = nullptr;
-        int rc = ensure_scratch(ctx, 11, sizeof(unsigned long long) * 8 * (size_t)a.n_groups, &d);
+        int rc = ensure_scratch(ctx, Work::Timeline, sizeof(unsigned long long) * 8 * (size_t)a.n_groups, &d);
         if (rc) return rc;
         aa.dbg = static_cast<unsigned long long *>(d);
     }

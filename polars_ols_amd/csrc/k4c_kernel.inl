@@ -611,7 +611,7 @@ static int k4c_launch_h(pols_ctx *ctx, const K4cArgs &a0) {
     }
     if (ctx->opt.timeline) {
         void *dbg = nullptr;
-        int rc = ensure_scratch(ctx, 11, sizeof(unsigned long long) * 8 * (size_t)a.n_tiles, &dbg);
+        int rc = ensure_scratch(ctx, Work::Timeline, sizeof(unsigned long long) * 8 * (size_t)a.n_tiles, &dbg);
         if (rc) return rc;
         a.dbg = static_cast<unsigned long long *>(dbg);
     }

@@ -726,13 +726,14 @@ int k4p_launch(pols_ctx *ctx, int dtype, const K4Args &a, bool rls, bool single_
     ctx->last_kernel = std::string(rls ? "k3p_rls_inverse_wave" : "k4p_rolling_inverse_wave") + (dtype == POLS_F32 ? "_f32" : "_f64");
     K4Args aa = a;
     if (!rls && !ctx->opt.debug_skip_fixup) {          // (POLS_DEBUG_SKIP_FIXUP: the walk's own answer, NaN on such rows -- the test's A/B)
-        // the list of rows whose sums could not be inverted (scratch slot 27, shared with K4c: [two counters that take turns][rows])
+        // the list of rows whose sums could not be inverted (ctx->k4c_fix: [two counters that take turns][rows])
         const int64_t n_rows = a.groups_end_row;
         void *fx = nullptr;
         const int64_t cap = std::min<int64_t>(std::max<int64_t>(n_rows, 1), (int64_t)1 << 22);
-        int rc = ensure_scratch(ctx, 27, 256 + sizeof(int64_t) * (size_t)cap, &fx);
+        bool fresh = false;
+        int rc = grow(ctx->k4c_fix, 256 + sizeof(int64_t) * (size_t)cap, &fx, &fresh);
         if (rc) return rc;
-        if (ctx->k4c_fix_ptr != fx) { POLS_HIP(hipMemsetAsync(fx, 0, 256, ctx->stream)); ctx->k4c_fix_ptr = fx; ctx->k4c_fix_turn = 0; }
+        if (fresh) { POLS_HIP(hipMemsetAsync(fx, 0, 256, ctx->stream)); ctx->k4c_fix_turn = 0; }
         aa.fix_count = static_cast<int32_t *>(fx) + 32 * (ctx->k4c_fix_turn & 1);
         aa.fix_next = static_cast<int32_t *>(fx) + 32 * ((ctx->k4c_fix_turn + 1) & 1);
         ++ctx->k4c_fix_turn;

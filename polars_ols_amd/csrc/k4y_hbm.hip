@@ -335,9 +335,9 @@ static int ky_launch_t(pols_ctx *ctx, const K4Args &a_in, bool rls) {
     K4Args a = a_in;
     const size_t lds = sizeof(double) * YCtx<T, NT, GLOBAL>::lds_doubles(a.k);
     const int ns = a.k * a.k + a.k;
-    if (GLOBAL) {                                              // one K x K state per chunk (scratch slot 3)
+    if (GLOBAL) {                                              // one K x K state per chunk (Work::Fixup)
         void *st = nullptr;
-        int rc = ensure_scratch(ctx, 3, sizeof(double) * (size_t)a.n_chunks * a.k * (a.k | 1), &st);
+        int rc = ensure_scratch(ctx, Work::Fixup, sizeof(double) * (size_t)a.n_chunks * a.k * (a.k | 1), &st);
         if (rc) return rc;
         a.state = static_cast<double *>(st);
     } else {

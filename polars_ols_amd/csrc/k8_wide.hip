@@ -630,9 +630,9 @@ int wide_stats_launch(pols_ctx *ctx, int dtype, const WideArgs &a, const WideSta
         if (dtype == POLS_F32) hipLaunchKernelGGL((wide_stats_kernel<float, 256, true>), dim3((unsigned)a.n_groups), dim3(256), lds, ctx->stream, a, o);
         else hipLaunchKernelGGL((wide_stats_kernel<double, 256, true>), dim3((unsigned)a.n_groups), dim3(256), lds, ctx->stream, a, o);
     } else {
-        // the solve is over: its work area (slot 3) is free to hold one kt x kt matrix per group
+        // the solve is over: its work area (Work::Fixup) is free to hold one kt x kt matrix per group
         void *w = nullptr;
-        int rc = ensure_scratch(ctx, 3, sizeof(double) * (size_t)a.n_groups * a.kt * (a.kt | 1), &w);
+        int rc = ensure_scratch(ctx, Work::Fixup, sizeof(double) * (size_t)a.n_groups * a.kt * (a.kt | 1), &w);
         if (rc) return rc;
         o.work = static_cast<double *>(w);
         const size_t lds = sizeof(double) * 4 * (size_t)a.kt;

@@ -213,7 +213,7 @@ template <typename U>
 static int sort_and_segment(pols_ctx *ctx, pols_layout *L, const int64_t *d_keys, int64_t mn, int bits, bool sorted) {
     const int64_t n = L->n;
     const size_t nb = round256(sizeof(U) * (size_t)n), ib = round256(sizeof(uint32_t) * (size_t)n);
-    // slot 9: [u_in | u_out | iota | unique keys (U) | counts (u32) | run count | rocprim temp]
+    // Work::K9Keys: [u_in | u_out | iota | unique keys (U) | counts (u32) | run count | rocprim temp]
     size_t t_sort = 0, t_rle = 0, t_scan = 0;
     U *np_u = nullptr;
     uint32_t *np_i = nullptr;
@@ -225,7 +225,7 @@ static int sort_and_segment(pols_ctx *ctx, pols_layout *L, const int64_t *d_keys
     // (the tail of the region also carries the unique keys home as int64: up to n of them)
     const size_t tmpb = round256(std::max(std::max(t_sort, sizeof(int64_t) * (size_t)n), std::max(t_rle, t_scan)));
     void *base = nullptr;
-    int rc = ensure_scratch(ctx, 9, 3 * nb + 2 * ib + 256 + tmpb, &base);
+    int rc = ensure_scratch(ctx, Work::K9Keys, 3 * nb + 2 * ib + 256 + tmpb, &base);
     if (rc) return rc;
     char *p = static_cast<char *>(base);
     U *u_in = reinterpret_cast<U *>(p);            p += nb;
@@ -332,7 +332,7 @@ static int move_columns(pols_ctx *ctx, pols_layout *L, int dtype_bytes, const vo
         char *stage = nullptr;
         if (mem == POLS_MEM_HOST) {                          // PCIe-inclusive convenience path: stage in, move, stage out
             void *s = nullptr;
-            if ((rc = ensure_scratch(ctx, 1, 2 * round256(colb) * (size_t)nc, &s))) return rc;
+            if ((rc = ensure_scratch(ctx, Work::HostInputs, 2 * round256(colb) * (size_t)nc, &s))) return rc;
             stage = static_cast<char *>(s);
             for (int c = 0; c < nc; ++c) {
                 POLS_HIP(hipMemcpyAsync(stage + round256(colb) * c, src[c0 + c], colb, hipMemcpyHostToDevice, ctx->stream));
@@ -404,14 +404,14 @@ int pols_layout_create(pols_ctx *ctx, const int64_t *keys, int64_t n_rows, int m
     int rc;
     if (mem == POLS_MEM_HOST) {
         void *d = nullptr;
-        if ((rc = ensure_scratch(ctx, 1, sizeof(int64_t) * (size_t)n_rows, &d))) return bail(rc);
+        if ((rc = ensure_scratch(ctx, Work::HostInputs, sizeof(int64_t) * (size_t)n_rows, &d))) return bail(rc);
         if (hipMemcpyAsync(d, keys, sizeof(int64_t) * (size_t)n_rows, hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
             return bail(fail(POLS_ERR_HIP, "group_layout: key upload failed"));
         d_keys = static_cast<const int64_t *>(d);
     }
     const unsigned nblk = std::min<unsigned>(blocks_for(n_rows, 512), (unsigned)std::max(ctx->num_cus, 1) * PROBE_BLOCKS_PER_CU);
     void *pr = nullptr;
-    if ((rc = ensure_scratch(ctx, 6, sizeof(KeyProbe) * nblk, &pr))) return bail(rc);
+    if ((rc = ensure_scratch(ctx, Work::Tables, sizeof(KeyProbe) * nblk, &pr))) return bail(rc);
     std::vector<KeyProbe> part(nblk);
     hipLaunchKernelGGL(key_probe_kernel, dim3(nblk), dim3(256), 0, ctx->stream, d_keys, n_rows, static_cast<KeyProbe *>(pr));
     if (hipMemcpyAsync(part.data(), pr, sizeof(KeyProbe) * nblk, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
@@ -469,7 +469,7 @@ int pols_layout_row_groups(pols_ctx *ctx, pols_layout *L, int64_t *out, int mem)
     int64_t *d_out = out;
     if (mem == POLS_MEM_HOST) {
         void *d = nullptr;
-        int rc = ensure_scratch(ctx, 1, sizeof(int64_t) * (size_t)L->n, &d);
+        int rc = ensure_scratch(ctx, Work::HostInputs, sizeof(int64_t) * (size_t)L->n, &d);
         if (rc) return rc;
         d_out = static_cast<int64_t *>(d);
     }

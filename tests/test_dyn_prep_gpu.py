@@ -146,6 +146,55 @@ def test_no_nulls_keeps_the_callers_columns_and_cached_tables(eng):
     assert _close(a["coef"].cpu().numpy(), ref["coef"], 1e-6)
 
 
+def _static_rolling_static(eng, offs, k, seed, full):
+    """least_squares -> rolling "drop" on a frame with NaN targets (row compaction) -> least_squares, on one engine and one set of
+    offsets: the rolling call's work buffers must leave the streamed path's cached segment tables alone.  Returns the rolling call's kernel."""
+    import torch
+
+    rng = np.random.default_rng(seed)
+    n = int(offs[-1])
+    cols = [rng.standard_normal(n) for _ in range(k)]
+    y = sum((j + 1) * 0.3 * c for j, c in enumerate(cols)) + 0.7 + 0.1 * rng.standard_normal(n)
+    y_nan = y.copy()
+    y_nan[rng.random(n) < 0.03] = np.nan
+    t = lambda a: torch.from_numpy(a).cuda()  # noqa: E731
+    yy, yn, cc = t(y), t(y_nan), [t(c) for c in cols]
+    a = eng.least_squares(yy, cc, offs, want=("coef", "pred"))
+    assert eng.last_kernel.startswith("k5_gram_stream"), eng.last_kernel
+    eng.rolling_least_squares(yn, cc, offs, window_size=252, null_policy="drop")
+    rolling = eng.last_kernel
+    b = eng.least_squares(yy, cc, offs, want=("coef", "pred"))
+    assert eng.last_kernel.startswith("k5_gram_stream"), eng.last_kernel
+    eng.synchronize()
+    assert torch.equal(a["coef"].nan_to_num(7.0), b["coef"].nan_to_num(7.0)) and torch.equal(a["pred"].nan_to_num(7.0), b["pred"].nan_to_num(7.0))
+    ref = orc.batched_least_squares(y, cols, offs)
+    assert _close(a["coef"].cpu().numpy().reshape(-1, k)[full], np.asarray(ref["coef"]).reshape(-1, k)[full], 1e-6)
+    return rolling
+
+
+def test_gather_source_map_keeps_the_whole_frame_segment_tables(eng):
+    """One group longer than two segments (the streamed static path cuts it: whole-frame segment tables cached on the engine) and a few short
+    ones, small enough that the rolling GATHER route's source map fits the smallest device buffer."""
+    rng = np.random.default_rng(31)
+    sizes = np.concatenate([[9_500], rng.integers(300, 500, size=8)])
+    offs = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+    assert offs[-1] < 15_000
+    rolling = _static_rolling_static(eng, offs, 6, 32, np.ones(len(sizes), bool))
+    assert rolling in ("k4_rolling_tiles_f64_gathered", "k4_rolling_tiles_f32_gathered"), rolling
+
+
+def test_row_compaction_keeps_the_size_class_segment_tables(eng):
+    """The frame of test_k1_gpu.py::test_size_classes_with_a_streamed_top_class: 9 000 groups, the 25 long ones a streamed class of their
+    own (its segment tables cached on the engine); the rolling call's row compaction writes its block totals in between."""
+    k = 8
+    rng = np.random.default_rng(1000 + k)
+    sizes = np.clip(rng.lognormal(np.log(250), 0.9, size=9000).astype(np.int64), 0, 5000)
+    sizes[rng.integers(0, 9000, size=25)] = rng.integers(5000 // 2 + 200, 5000, size=25)
+    sizes[11] = 0
+    offs = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+    _static_rolling_static(eng, offs, k, 33, sizes > 3 * k)
+
+
 def test_initial_state_mean_covers_the_intercept(eng):
     """initial_state_mean has kt = n_features + 1 entries when the entry appends the ones column itself."""
     y, cols, offs, w = _frame(9, np.float64, 2, nulls=False)
