@@ -256,6 +256,38 @@ typedef struct pols_stats_out {
 int pols_least_squares_statistics(pols_ctx *ctx, const pols_batch *b, const pols_ols_params *p, pols_out *out,
                                   const pols_stats_out *stats);
 
+/* Robust standard errors for mode="statistics" (extends pols_least_squares_statistics above; the reference's
+ * compute_feature_metrics, src/statistics.rs:79-156, has only the constant-variance form).  Per group, on the same rows,
+ * sqrt(w) scaling and ones column as pols_least_squares_statistics, with A = X'X + alpha I, b = A^-1 X'y its side-car
+ * coefficients, e_i = y_i - x_i'b and the leverage h_i = x_i' A^-1 x_i:
+ *   u_i = c_i e_i x_i,  c_i = 1 (HC0, HC1, HAC), (1 - h_i)^-1/2 (HC2), (1 - h_i)^-1 (HC3),
+ *   S   = sum_i u_i u_i', plus for HAC sum_{l=1..L} (1 - l / (L + 1)) sum_i (u_i u_{i-l}' + u_{i-l} u_i') with
+ *         L = min(maxlags, n - 1), lags over the group's rows in their order (no small-sample factor: HAC, maxlags 0 == HC0),
+ *   V   = A^-1 S A^-1 (times n / df for HC1),  std_err_j = sqrt(V_jj),  t_j = b_j / std_err_j,  p_j as the non-robust entry.
+ * df, r2 / mae / mse, the coefficients, status and the failure rules are those of pols_least_squares_statistics; HC2 / HC3
+ * also give NaN standard errors / t / p to a group with a row of 1 - h_i < 1e-10.  POLS_COV_NONROBUST calls
+ * pols_least_squares_statistics.  Up to 31 columns (incl. the intercept) and maxlags 0..255; wider calls and longer lags
+ * return POLS_ERR_UNSUPPORTED, a negative maxlags (HAC) or an unknown cov_type POLS_ERR_INVALID. */
+enum {
+    POLS_COV_NONROBUST = 0,
+    POLS_COV_HC0 = 1,
+    POLS_COV_HC1 = 2,
+    POLS_COV_HC2 = 3,
+    POLS_COV_HC3 = 4,
+    POLS_COV_HAC = 5          /* Newey-West: Bartlett weights over maxlags lags */
+};
+
+typedef struct pols_cov_params {
+    int32_t cov_type;         /* POLS_COV_* */
+    int32_t maxlags;          /* HAC only */
+} pols_cov_params;
+
+/* cov_type = POLS_COV_NONROBUST, maxlags = 0 */
+void pols_cov_params_default(pols_cov_params *c);
+
+int pols_least_squares_statistics_robust(pols_ctx *ctx, const pols_batch *b, const pols_ols_params *p, const pols_cov_params *cov,
+                                         pols_out *out, const pols_stats_out *stats);
+
 /* ---- group-key ingestion: `.over(key)` / `group_by(key)` ------------------------------------------------------------
  * The reference's plugin functions never see a key column: Polars partitions the frame on the host and calls them once per
  * group (README.md:19, README.md:57 and :91 `.over("group")`, tests/test_ols.py:110, :384, :860).  The batched entries
@@ -355,6 +387,12 @@ int pols_least_squares_statistics_arrow(pols_ctx *ctx, const pols_arrow_column *
                                         int32_t n_features, const pols_arrow_column *weights, const int64_t *group_offsets,
                                         int64_t n_groups, int32_t add_intercept, const pols_ols_params *p, struct ArrowArray *out,
                                         struct ArrowSchema *out_schema);
+/* pols_least_squares_statistics_arrow with robust standard errors (pols_least_squares_statistics_robust): the same struct schema,
+ * `cov` after `p`. */
+int pols_least_squares_statistics_robust_arrow(pols_ctx *ctx, const pols_arrow_column *target, const pols_arrow_column *features,
+                                               int32_t n_features, const pols_arrow_column *weights, const int64_t *group_offsets,
+                                               int64_t n_groups, int32_t add_intercept, const pols_ols_params *p,
+                                               const pols_cov_params *cov, struct ArrowArray *out, struct ArrowSchema *out_schema);
 /* multi_target_least_squares (ex.rs:511-591): `targets` is the STRUCT Series of inputs[0] (format "+s", one numeric field per
  * target; a null struct row is a null in every field); out: a struct array "predictions" of n_rows rows with the targets' field
  * names (multi_target_struct_dtype, :511-519), NaN -> null.  Residuals are the caller's `target - predictions`

@@ -17,6 +17,7 @@
 #include "k5_enet.hpp"
 #include "k6_svd.hpp"
 #include "k7_stats.hpp"
+#include "k7r_robust.hpp"
 #include "k8_wide.hpp"
 #include "dyn_prep.hpp"
 
@@ -1513,8 +1514,11 @@ int pols_multi_target_least_squares(pols_ctx *ctx, const pols_batch *b, const vo
 }
 
 // ------------------------------------------------------------------ mode = "statistics"
-int pols_least_squares_statistics(pols_ctx *ctx, const pols_batch *b, const pols_ols_params *p, pols_out *o,
-                                  const pols_stats_out *s) {
+// The body of pols_least_squares_statistics and of its robust twin: cov == nullptr is the non-robust entry; otherwise (HC0 .. HAC,
+// validated by pols_least_squares_statistics_robust, at most K7_KMAX columns) K7 still writes r2 / mae / mse and the status words and
+// K7r (k7r_robust.hip) the standard errors, t- and p-values.
+static int statistics_body(pols_ctx *ctx, const pols_batch *b, const pols_ols_params *p, const pols_cov_params *cov, pols_out *o,
+                           const pols_stats_out *s) {
     int rc = check_ctx(ctx);
     if (rc) return rc;
     if ((rc = check_batch(b, o, K8_KMAX))) return rc;
@@ -1530,7 +1534,7 @@ int pols_least_squares_statistics(pols_ctx *ctx, const pols_batch *b, const pols
         if ((rc = compact_nulls(ctx, b, p->null_policy, &c))) return rc;
         pols_ols_params pp = *p;
         pp.null_policy = POLS_NULL_IGNORE;
-        if (b->mem == POLS_MEM_DEVICE) return pols_least_squares_statistics(ctx, &c.bb, &pp, o, s);
+        if (b->mem == POLS_MEM_DEVICE) return statistics_body(ctx, &c.bb, &pp, cov, o, s);
         const int kt = b->n_features + (b->add_intercept ? 1 : 0);
         const size_t G = (size_t)b->n_groups, sz = dtype_size(b->dtype);
         const size_t coefb = round256(sz * G * kt), statb = round256(sizeof(int32_t) * G), vecb = round256(sizeof(double) * G),
@@ -1548,7 +1552,7 @@ int pols_least_squares_statistics(pols_ctx *ctx, const pols_batch *b, const pols
         for (int i = 0; i < 6; ++i) { dev[i] = user[i] ? reinterpret_cast<double *>(q) : nullptr; q += i < 3 ? vecb : matb; }
         pols_stats_out sd;
         sd.r2 = dev[0]; sd.mae = dev[1]; sd.mse = dev[2]; sd.std_err = dev[3]; sd.t_values = dev[4]; sd.p_values = dev[5];
-        if ((rc = pols_least_squares_statistics(ctx, &c.bb, &pp, &od, &sd))) return rc;
+        if ((rc = statistics_body(ctx, &c.bb, &pp, cov, &od, &sd))) return rc;
         if (o->coef) POLS_HIP(hipMemcpyAsync(o->coef, od.coef, sz * G * kt, hipMemcpyDeviceToHost, ctx->stream));
         if (o->status) POLS_HIP(hipMemcpyAsync(o->status, od.status, sizeof(int32_t) * G, hipMemcpyDeviceToHost, ctx->stream));
         for (int i = 0; i < 6; ++i)
@@ -1670,13 +1674,57 @@ int pols_least_squares_statistics(pols_ctx *ctx, const pols_batch *b, const pols
         q += (i < 3) ? vecb : matb;
     }
     sa.r2 = dev[0]; sa.mae = dev[1]; sa.mse = dev[2]; sa.se = dev[3]; sa.tv = dev[4]; sa.pv = dev[5];
-    if ((rc = k7_stats_launch(ctx, b->dtype, sa))) return rc;
+    if (cov) {
+        // robust: K7 keeps r2 / mae / mse / status, K7r writes the standard errors, t- and p-values (its own buffers: sa's segment
+        // tables are the frame's cached ones, the partial sums of K7 and K7r live apart)
+        RobustArgs ra;
+        std::memset(&ra, 0, sizeof(ra));
+        ra.s = sa;
+        sa.se = sa.tv = sa.pv = nullptr;
+        ra.cov_type = cov->cov_type;
+        ra.maxlags = cov->cov_type == POLS_COV_HAC ? cov->maxlags : 0;
+        const int64_t n_items = sa.seg_offs ? sa.n_seg : (int64_t)G;
+        void *rp = nullptr, *rm = nullptr;
+        if ((rc = ensure_scratch(ctx, Work::RobustPrep, round256(sizeof(double) * G * k7r_prep_stride(kt)), &rp))) return rc;
+        if ((rc = ensure_scratch(ctx, Work::RobustMeat, round256(sizeof(double) * (size_t)n_items * k7r_part_stride(kt)), &rm))) return rc;
+        ra.prep = static_cast<double *>(rp);
+        ra.part = static_cast<double *>(rm);
+        if ((rc = k7_stats_launch(ctx, b->dtype, sa))) return rc;
+        if ((rc = k7r_robust_launch(ctx, b->dtype, ra))) return rc;
+    } else if ((rc = k7_stats_launch(ctx, b->dtype, sa))) return rc;
     if (!host) return POLS_OK;
     for (int i = 0; i < 6; ++i)
         if (user[i])
             POLS_HIP(hipMemcpyAsync(user[i], dev[i], sizeof(double) * G * (i < 3 ? 1 : kt), hipMemcpyDeviceToHost, ctx->stream));
     if (!o->coef) oo.coef = nullptr;
     return unstage_outputs(ctx, b, b->n_groups, kt, &oo, info.st);
+}
+
+int pols_least_squares_statistics(pols_ctx *ctx, const pols_batch *b, const pols_ols_params *p, pols_out *o,
+                                  const pols_stats_out *s) {
+    return statistics_body(ctx, b, p, nullptr, o, s);
+}
+
+void pols_cov_params_default(pols_cov_params *c) {
+    if (!c) return;
+    c->cov_type = POLS_COV_NONROBUST;
+    c->maxlags = 0;
+}
+
+int pols_least_squares_statistics_robust(pols_ctx *ctx, const pols_batch *b, const pols_ols_params *p, const pols_cov_params *cov,
+                                         pols_out *o, const pols_stats_out *s) {
+    if (!cov) return fail(POLS_ERR_INVALID, "cov is NULL");
+    if (cov->cov_type < POLS_COV_NONROBUST || cov->cov_type > POLS_COV_HAC) return fail(POLS_ERR_INVALID, "unknown cov_type %d", cov->cov_type);
+    if (cov->cov_type == POLS_COV_NONROBUST) return pols_least_squares_statistics(ctx, b, p, o, s);
+    if (cov->cov_type == POLS_COV_HAC) {
+        if (cov->maxlags < 0) return fail(POLS_ERR_INVALID, "HAC: maxlags %d < 0", cov->maxlags);
+        if (cov->maxlags > K7R_MAXLAGS) return fail(POLS_ERR_UNSUPPORTED, "HAC: maxlags %d > %d", cov->maxlags, K7R_MAXLAGS);
+    }
+    if (!b) return fail(POLS_ERR_INVALID, "batch is NULL");
+    const int kt = b->n_features + (b->add_intercept ? 1 : 0);
+    if (kt > K7_KMAX)
+        return fail(POLS_ERR_UNSUPPORTED, "robust statistics: %d features (incl. intercept) > %d; wider frames have only the non-robust form", kt, K7_KMAX);
+    return statistics_body(ctx, b, p, cov, o, s);
 }
 
 // Dynamic models share the staging of a batch whose coefficient output has one row per input row, and the pre-processing the

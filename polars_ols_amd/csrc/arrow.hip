@@ -2,6 +2,7 @@
 // plugin body of src/expressions.rs (pols_*_arrow, include/pols_mi355x.h):
 //   least_squares / least_squares_coefficients (:390-446)                  pols_least_squares_arrow
 //   least_squares_statistics (:448-509)                                     pols_least_squares_statistics_arrow
+//     ... with robust standard errors                                       pols_least_squares_statistics_robust_arrow
 //   multi_target_least_squares (:511-591; inputs[0] is a STRUCT Series)     pols_multi_target_least_squares_arrow
 //   recursive_least_squares[_coefficients] (:593-646)                       pols_recursive_least_squares_arrow
 //   rolling_least_squares[_coefficients] (:648-701)                         pols_rolling_least_squares_arrow
@@ -620,7 +621,7 @@ static int list_names(ArrowArray *a, ArrowSchema *s, const char *name, const std
 template <typename T>
 static int arrow_statistics(pols_ctx *ctx, const ColView &target, const std::vector<ColView> &feat, const ColView *weights,
                             const int64_t *group_offsets, int64_t n_groups, int32_t add_intercept, const pols_ols_params *p,
-                            ArrowArray *out, ArrowSchema *out_schema) {
+                            const pols_cov_params *cov, ArrowArray *out, ArrowSchema *out_schema) {
     const int64_t n_rows = target.rows(), G = std::max<int64_t>(n_groups, 1);
     const int kt = (int)feat.size() + (add_intercept ? 1 : 0);
     const size_t coefb = round256(sizeof(T) * (size_t)G * kt), sb = round256(sizeof(double) * (size_t)G), tb = round256(sizeof(double) * (size_t)G * kt);
@@ -639,7 +640,7 @@ static int arrow_statistics(pols_ctx *ctx, const ColView &target, const std::vec
     pols_out o;
     std::memset(&o, 0, sizeof(o));
     o.coef = dcoef; o.status = dstat;
-    if ((rc = pols_least_squares_statistics(ctx, &b, p, &o, &so))) return rc;
+    if ((rc = cov ? pols_least_squares_statistics_robust(ctx, &b, p, cov, &o, &so) : pols_least_squares_statistics(ctx, &b, p, &o, &so))) return rc;
     // everything is small (per group): home in one go
     std::vector<T> hcoef((size_t)n_groups * kt);
     std::vector<double> h3((size_t)n_groups * 3), ht((size_t)n_groups * kt * 3), hc64((size_t)n_groups * kt);
@@ -733,8 +734,21 @@ int pols_least_squares_statistics_arrow(pols_ctx *ctx, const pols_arrow_column *
     int rc = common_views(ctx, target, features, n_features, weights, &group_offsets, &n_groups, add_intercept, POLS_MAX_FEATURES_STATISTICS, p, out, out_schema, &cv);
     if (rc) return rc;
     const ColView *w = weights ? &cv.wv : nullptr;
-    if (cv.all_f32) return arrow_statistics<float>(ctx, cv.target, cv.feat, w, group_offsets, n_groups, add_intercept, p, out, out_schema);
-    return arrow_statistics<double>(ctx, cv.target, cv.feat, w, group_offsets, n_groups, add_intercept, p, out, out_schema);
+    if (cv.all_f32) return arrow_statistics<float>(ctx, cv.target, cv.feat, w, group_offsets, n_groups, add_intercept, p, nullptr, out, out_schema);
+    return arrow_statistics<double>(ctx, cv.target, cv.feat, w, group_offsets, n_groups, add_intercept, p, nullptr, out, out_schema);
+}
+
+int pols_least_squares_statistics_robust_arrow(pols_ctx *ctx, const pols_arrow_column *target, const pols_arrow_column *features,
+                                               int32_t n_features, const pols_arrow_column *weights, const int64_t *group_offsets,
+                                               int64_t n_groups, int32_t add_intercept, const pols_ols_params *p,
+                                               const pols_cov_params *cov, struct ArrowArray *out, struct ArrowSchema *out_schema) {
+    if (!cov) return fail(POLS_ERR_INVALID, "cov is NULL");
+    CommonViews cv;
+    int rc = common_views(ctx, target, features, n_features, weights, &group_offsets, &n_groups, add_intercept, POLS_MAX_FEATURES_STATISTICS, p, out, out_schema, &cv);
+    if (rc) return rc;
+    const ColView *w = weights ? &cv.wv : nullptr;
+    if (cv.all_f32) return arrow_statistics<float>(ctx, cv.target, cv.feat, w, group_offsets, n_groups, add_intercept, p, cov, out, out_schema);
+    return arrow_statistics<double>(ctx, cv.target, cv.feat, w, group_offsets, n_groups, add_intercept, p, cov, out, out_schema);
 }
 
 int pols_recursive_least_squares_arrow(pols_ctx *ctx, const pols_arrow_column *target, const pols_arrow_column *features, int32_t n_features,

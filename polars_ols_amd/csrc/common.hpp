@@ -65,6 +65,8 @@ enum class Work : int {
     CompactTiles,   // first rows of the compacted frame's packed tiles
     CompactTotals,  // row compaction: totals of every 1 024 slabs (row_compact_offsets_launch)
     GatherMap,      // rolling GATHER tiles: source row of every compacted row
+    RobustPrep,     // robust statistics (K7r): A^-1, coefficients, trace, ok per group
+    RobustMeat,     // robust statistics (K7r): U'W partial sums per segment / group
     Count
 };
 

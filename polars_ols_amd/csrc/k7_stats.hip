@@ -15,8 +15,6 @@
 
 namespace pols {
 
-constexpr int K7_KMAX = 31;
-
 template <int NV>
 __device__ __forceinline__ void k7_block_sum(double (&v)[NV], double (*red)[4]) {   // red: NV x 4 doubles of LDS
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -29,65 +27,6 @@ __device__ __forceinline__ void k7_block_sum(double (&v)[NV], double (*red)[4]) 
     __syncthreads();
 #pragma unroll
     for (int i = 0; i < NV; ++i) v[i] = red[i][0] + red[i][1] + red[i][2] + red[i][3];
-}
-
-// wave 0 of the group: A = X'X + lambda I factored, A^-1 X'y and diag(A^-1) (src/statistics.rs:100-121), the dispatcher's coefficients
-template <typename T>
-__device__ __forceinline__ void k7_small_solve(const StatsArgs &a, int64_t g, int lane, double *L, double *M, double *rinv, double *bvec,
-                                               double *tvec, double *binv, double *cdis, double *dg, int *okflag_p) {
-    const int kt = a.kt, NZ = kt + 1;
-    const double *G = a.gram + (size_t)g * NZ * NZ;
-    int &okflag = *okflag_p;
-    {
-        for (int q = lane; q < kt * kt; q += 64) {
-            const int i = q / kt, j = q - i * kt;
-            L[q] = G[i * NZ + j] + (i == j ? a.lambda : 0.0);
-        }
-        if (lane < kt) {
-            bvec[lane] = G[lane * NZ + kt];
-            cdis[lane] = (double)static_cast<const T *>(a.coef)[g * kt + lane];
-        }
-        __builtin_amdgcn_wave_barrier();
-        bool ok = true;
-        for (int j = 0; j < kt; ++j) {
-            double d = L[j * kt + j];
-            for (int p = 0; p < j; ++p) d -= L[j * kt + p] * L[j * kt + p];
-            ok = ok && (d > 0.0);                                   // also false for NaN
-            const double ri = 1.0 / sqrt(d);
-            if (lane == 0) rinv[j] = ri;
-            if (lane > j && lane < kt) {
-                double acc = L[lane * kt + j];
-                for (int p = 0; p < j; ++p) acc -= L[lane * kt + p] * L[j * kt + p];
-                L[lane * kt + j] = acc * ri;
-            }
-            __builtin_amdgcn_wave_barrier();
-        }
-        // M = L^-1, column c on lane c (forward substitution against e_c)
-        if (lane < kt) {
-            const int c = lane;
-            for (int i = 0; i < c; ++i) M[i * kt + c] = 0.0;
-            M[c * kt + c] = rinv[c];
-            for (int i = c + 1; i < kt; ++i) {
-                double acc = 0.0;
-                for (int p = c; p < i; ++p) acc += L[i * kt + p] * M[p * kt + c];
-                M[i * kt + c] = -acc * rinv[i];
-            }
-        }
-        __builtin_amdgcn_wave_barrier();
-        if (lane < kt) {
-            double t = 0.0;
-            for (int j = 0; j <= lane; ++j) t += M[lane * kt + j] * bvec[j];
-            tvec[lane] = t;
-        }
-        __builtin_amdgcn_wave_barrier();
-        if (lane < kt) {
-            double bi = 0.0, dd = 0.0;
-            for (int p = lane; p < kt; ++p) { const double m = M[p * kt + lane]; bi += m * tvec[p]; dd += m * m; }
-            binv[lane] = bi;                                        // A^-1 X'y          (:116)
-            dg[lane] = dd;                                          // diag(A^-1)
-        }
-        if (lane == 0) okflag = ok ? 1 : 0;
-    }
 }
 
 template <typename T>

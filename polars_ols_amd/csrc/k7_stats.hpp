@@ -28,6 +28,8 @@ struct StatsArgs {
 
 int k7_stats_launch(pols_ctx *ctx, int dtype, const StatsArgs &a);
 
+constexpr int K7_KMAX = 31;   // columns (incl. the intercept) of the K7 kernels; wider statistics run on K8
+
 #if defined(__HIPCC__)
 // Two-sided Student-t p-value 2 (1 - cdf(|t|)) == I_{df/(df+t^2)}(df/2, 1/2): regularised incomplete beta by Lentz' continued
 // fraction (what statrs 0.17.1 evaluates for src/statistics.rs:45-49).  Shared by K7 and the wide statistics kernel (K8).
@@ -62,6 +64,66 @@ __device__ inline double k7_betai(double a, double b, double x) {
     const double bt = exp(lgamma(a + b) - lgamma(a) - lgamma(b) + a * log(x) + b * log1p(-x));
     if (x < (a + 1.0) / (a + b + 2.0)) return bt * k7_betacf(a, b, x) / a;
     return 1.0 - bt * k7_betacf(b, a, 1.0 - x) / b;
+}
+
+// wave 0 of the group: A = X'X + lambda I factored, A^-1 X'y and diag(A^-1) (src/statistics.rs:100-121), the dispatcher's coefficients.
+// Shared by K7 and the robust covariance kernels (K7r), which keep all of M = L^-1 to form the whole A^-1 = M'M.
+template <typename T>
+__device__ __forceinline__ void k7_small_solve(const StatsArgs &a, int64_t g, int lane, double *L, double *M, double *rinv, double *bvec,
+                                               double *tvec, double *binv, double *cdis, double *dg, int *okflag_p) {
+    const int kt = a.kt, NZ = kt + 1;
+    const double *G = a.gram + (size_t)g * NZ * NZ;
+    int &okflag = *okflag_p;
+    {
+        for (int q = lane; q < kt * kt; q += 64) {
+            const int i = q / kt, j = q - i * kt;
+            L[q] = G[i * NZ + j] + (i == j ? a.lambda : 0.0);
+        }
+        if (lane < kt) {
+            bvec[lane] = G[lane * NZ + kt];
+            cdis[lane] = (double)static_cast<const T *>(a.coef)[g * kt + lane];
+        }
+        __builtin_amdgcn_wave_barrier();
+        bool ok = true;
+        for (int j = 0; j < kt; ++j) {
+            double d = L[j * kt + j];
+            for (int p = 0; p < j; ++p) d -= L[j * kt + p] * L[j * kt + p];
+            ok = ok && (d > 0.0);                                   // also false for NaN
+            const double ri = 1.0 / sqrt(d);
+            if (lane == 0) rinv[j] = ri;
+            if (lane > j && lane < kt) {
+                double acc = L[lane * kt + j];
+                for (int p = 0; p < j; ++p) acc -= L[lane * kt + p] * L[j * kt + p];
+                L[lane * kt + j] = acc * ri;
+            }
+            __builtin_amdgcn_wave_barrier();
+        }
+        // M = L^-1, column c on lane c (forward substitution against e_c)
+        if (lane < kt) {
+            const int c = lane;
+            for (int i = 0; i < c; ++i) M[i * kt + c] = 0.0;
+            M[c * kt + c] = rinv[c];
+            for (int i = c + 1; i < kt; ++i) {
+                double acc = 0.0;
+                for (int p = c; p < i; ++p) acc += L[i * kt + p] * M[p * kt + c];
+                M[i * kt + c] = -acc * rinv[i];
+            }
+        }
+        __builtin_amdgcn_wave_barrier();
+        if (lane < kt) {
+            double t = 0.0;
+            for (int j = 0; j <= lane; ++j) t += M[lane * kt + j] * bvec[j];
+            tvec[lane] = t;
+        }
+        __builtin_amdgcn_wave_barrier();
+        if (lane < kt) {
+            double bi = 0.0, dd = 0.0;
+            for (int p = lane; p < kt; ++p) { const double m = M[p * kt + lane]; bi += m * tvec[p]; dd += m * m; }
+            binv[lane] = bi;                                        // A^-1 X'y          (:116)
+            dg[lane] = dd;                                          // diag(A^-1)
+        }
+        if (lane == 0) okflag = ok ? 1 : 0;
+    }
 }
 
 #endif

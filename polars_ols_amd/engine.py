@@ -208,9 +208,13 @@ class Engine:
             res["pred"] = preds
         return res
 
-    def least_squares_statistics(self, y, x_cols: Sequence, offsets, **kwargs) -> Dict:
+    def least_squares_statistics(self, y, x_cols: Sequence, offsets, cov_type: str = "nonrobust", maxlags: Optional[int] = None,
+                                 **kwargs) -> Dict:
         """mode="statistics" (src/expressions.rs:468-509) for every group: returns ``coef`` (batch dtype), ``status`` and
-        the f64 arrays ``r2 mae mse`` [n_groups] and ``std_err t_values p_values`` [n_groups, k]."""
+        the f64 arrays ``r2 mae mse`` [n_groups] and ``std_err t_values p_values`` [n_groups, k].  ``cov_type`` "HC0" .. "HC3"
+        or "HAC" (with ``maxlags``) makes the last three robust (pols_least_squares_statistics_robust); "nonrobust" is the
+        reference's constant-variance form."""
+        cov = _cov_params(self._lib, cov_type, maxlags)
         kwargs.setdefault("want", ("coef", "status"))
         plan = self.plan_least_squares(y, x_cols, offsets, **kwargs)
         b = plan._b
@@ -224,8 +228,12 @@ class Engine:
         for key in ("std_err", "t_values", "p_values"):
             res[key] = self._alloc(dev, f64, (b.n_groups, kt), like)
         so = L.StatsOut(**{k: self._ptr(res[k]) for k in ("r2", "mae", "mse", "std_err", "t_values", "p_values")})
-        L.check(self._lib.pols_least_squares_statistics(self._h, C.byref(plan._b), C.byref(plan._p), C.byref(plan._o),
-                                                        C.byref(so)))
+        if cov is None:
+            L.check(self._lib.pols_least_squares_statistics(self._h, C.byref(plan._b), C.byref(plan._p), C.byref(plan._o),
+                                                            C.byref(so)))
+        else:
+            L.check(self._lib.pols_least_squares_statistics_robust(self._h, C.byref(plan._b), C.byref(plan._p), C.byref(cov),
+                                                                   C.byref(plan._o), C.byref(so)))
         return res
 
     def least_squares(self, y, x_cols: Sequence, offsets, **kwargs) -> Dict:
@@ -454,6 +462,25 @@ def _least_squares_arrow(self, target, features, *, target_name: str = "y", weig
 Engine.least_squares_arrow = _least_squares_arrow
 
 
+def _cov_params(lib, cov_type: str = "nonrobust", maxlags: Optional[int] = None) -> Optional[L.CovParams]:
+    """pols_cov_params of a ``cov_type`` / ``maxlags`` pair, None for "nonrobust" (the non-robust entry).  ValueError: an unknown
+    cov_type, HAC without maxlags (or a negative one), maxlags with another cov_type."""
+    if cov_type not in L.COV_TYPES:
+        raise ValueError(f"cov_type must be one of {sorted(L.COV_TYPES)}, got {cov_type!r}")
+    if cov_type == "HAC":
+        if maxlags is None or isinstance(maxlags, bool) or int(maxlags) != maxlags or maxlags < 0:
+            raise ValueError(f"cov_type='HAC' needs maxlags, a non-negative integer (got {maxlags!r})")
+    elif maxlags is not None:
+        raise ValueError(f"maxlags applies to cov_type='HAC' only (got cov_type={cov_type!r})")
+    if cov_type == "nonrobust":
+        return None
+    c = L.CovParams()
+    lib.pols_cov_params_default(C.byref(c))
+    c.cov_type = L.COV_TYPES[cov_type]
+    c.maxlags = int(maxlags) if maxlags is not None else 0
+    return c
+
+
 def _ols_params(lib, alpha=0.0, l1_ratio=None, max_iter=1000, tol=1e-5, positive=False, solve_method=None, rcond=None,
                 null_policy="ignore"):
     p = L.OlsParams()
@@ -490,12 +517,17 @@ def _arrow_call(self, fn, first, first_name: str, features, weights, offsets, ad
             e.close()
 
 
-def _statistics_arrow(self, target, features, *, target_name: str = "y", weights=None, offsets=None, add_intercept: bool = False, **kw):
+def _statistics_arrow(self, target, features, *, target_name: str = "y", weights=None, offsets=None, add_intercept: bool = False,
+                      cov_type: str = "nonrobust", maxlags: Optional[int] = None, **kw):
     """``pols_least_squares_statistics_arrow`` (plugin least_squares_statistics, src/expressions.rs:448-509): the ``statistics``
-    struct, one row per group."""
+    struct, one row per group.  A robust ``cov_type`` calls ``pols_least_squares_statistics_robust_arrow`` (same struct)."""
+    cov = _cov_params(self._lib, cov_type, maxlags)
     p = _ols_params(self._lib, **kw)
-    return _arrow_call(self, self._lib.pols_least_squares_statistics_arrow, target, target_name, features, weights, offsets, add_intercept,
-                       (C.byref(p),))
+    if cov is None:
+        return _arrow_call(self, self._lib.pols_least_squares_statistics_arrow, target, target_name, features, weights, offsets,
+                           add_intercept, (C.byref(p),))
+    return _arrow_call(self, self._lib.pols_least_squares_statistics_robust_arrow, target, target_name, features, weights, offsets,
+                       add_intercept, (C.byref(p), C.byref(cov)))
 
 
 def _multi_target_arrow(self, targets, features, *, weights=None, offsets=None, add_intercept: bool = False, **kw):

@@ -317,8 +317,10 @@ class Statistics(dict):
         self.keys_ = keys
 
 
-def _static_statistics(eng: Engine, y, xs, offs, w, icpt: bool, kw: OLSKwargs, names, keys) -> Statistics:
+def _static_statistics(eng: Engine, y, xs, offs, w, icpt: bool, kw: OLSKwargs, names, keys, cov=None) -> Statistics:
     d = kw.to_dict()
+    if cov is not None:                                        # (cov_type, maxlags): robust standard errors / t / p
+        d["cov_type"], d["maxlags"] = cov
     out = eng.least_squares_statistics(y, xs, offs, weights=w, add_intercept=icpt, **d)
     st = out["status"]
     bad = bool((st == 4).any())
@@ -328,7 +330,7 @@ def _static_statistics(eng: Engine, y, xs, offs, w, icpt: bool, kw: OLSKwargs, n
 
 
 def _apply_static(frame: Frame, over, eng: Optional[Engine], target: Expr, features: Sequence[Expr], sample_weights,
-                  add_intercept: bool, mode: str, kw: OLSKwargs):
+                  add_intercept: bool, mode: str, kw: OLSKwargs, cov=None):
     """compute_least_squares body: least_squares.py:199-239 + src/expressions.rs:390-446 (null policies :201-296)."""
     y, xs, names, icpt, w = _pre_process_data(frame, target, features, sample_weights, add_intercept)
     n = y.shape[0]
@@ -349,7 +351,7 @@ def _apply_static(frame: Frame, over, eng: Optional[Engine], target: Expr, featu
         coef, pred = out.get("coef"), out.get("pred") if mode == "predictions" else out.get("resid")
     else:
         # handle_nulls ahead of the statistics code (ex.rs:469-471): the entry filters / zero-fills on the device itself
-        return "statistics", _static_statistics(eng, y_s, xs_s, offs, w_s, icpt, kw, names, keys)
+        return "statistics", _static_statistics(eng, y_s, xs_s, offs, w_s, icpt, kw, names, keys, cov)
     if mode == "coefficients":
         # without .over the single struct broadcasts to every row of the frame, like a Polars scalar (gid is all zeros)
         return "coefficients", Coefficients(names, coef, keys, grp.gid_frame(coef))
@@ -387,12 +389,44 @@ def _apply_dynamic(frame: Frame, over, eng: Optional[Engine], target: Expr, feat
 
 # ---- the reference's module-level functions (least_squares.py:242-491) -------------------------------------------
 
+_VALID_COV_TYPES = ("nonrobust", "HC0", "HC1", "HC2", "HC3", "HAC")
+
+
+def _robust_cov(cov_type: str, cov_kwds: Optional[Dict[str, Any]], mode: str, kind: str = "ols"):
+    """(cov_type, maxlags) of a robust request, None for the default "nonrobust"; ValueError for what has no robust form: an unknown
+    cov_type, a mode other than "statistics", multi-target / RLS / rolling models, HAC without cov_kwds={"maxlags": L}."""
+    if cov_type not in _VALID_COV_TYPES:
+        raise ValueError(f"'cov_type' must be one of {_VALID_COV_TYPES}, got {cov_type!r}")
+    if cov_type == "nonrobust" and not cov_kwds:
+        return None
+    if kind != "ols":
+        raise ValueError(f"cov_type / cov_kwds apply to single-target least squares in mode='statistics', not to {kind} models")
+    if mode != "statistics":
+        raise ValueError(f"cov_type={cov_type!r} needs mode='statistics' (got mode={mode!r})")
+    kwds = dict(cov_kwds or {})
+    unknown = set(kwds) - {"maxlags"}
+    if unknown:
+        raise ValueError(f"unknown cov_kwds {sorted(unknown)}")
+    if cov_type == "HAC":
+        lags = kwds.get("maxlags")
+        if lags is None or isinstance(lags, bool) or int(lags) != lags or lags < 0:
+            raise ValueError(f"cov_type='HAC' needs cov_kwds={{'maxlags': L}} with an integer L >= 0 (got {cov_kwds!r})")
+        return cov_type, int(lags)
+    if kwds:
+        raise ValueError(f"cov_kwds {kwds} apply to cov_type='HAC' only")
+    return cov_type, None
+
+
 def compute_least_squares(target, *features, sample_weights=None, add_intercept: bool = False,
-                          mode: str = "predictions", ols_kwargs: Optional[OLSKwargs] = None) -> Expr:
+                          mode: str = "predictions", ols_kwargs: Optional[OLSKwargs] = None, cov_type: str = "nonrobust",
+                          cov_kwds: Optional[Dict[str, Any]] = None) -> Expr:
+    """``cov_type`` ("HC0" .. "HC3", "HAC" with ``cov_kwds={"maxlags": L}``) makes the standard errors, t- and p-values of
+    mode="statistics" robust; the other fields do not depend on it."""
     assert mode in _VALID_OUTPUT_MODES, f"'mode' must be one of {_VALID_OUTPUT_MODES}"
+    cov = _robust_cov(cov_type, cov_kwds, mode)
     kw = ols_kwargs or OLSKwargs()
     t, fs = parse_into_expr(target), [parse_into_expr(f) for f in features]
-    return Expr(t._name, fn=lambda frame, over, eng: _apply_static(frame, over, eng, t, fs, sample_weights, add_intercept, mode, kw))
+    return Expr(t._name, fn=lambda frame, over, eng: _apply_static(frame, over, eng, t, fs, sample_weights, add_intercept, mode, kw, cov))
 
 
 def compute_multi_target_least_squares(targets, *features, sample_weights=None, add_intercept: bool = False,
@@ -568,8 +602,11 @@ def _parse_formula(formula: str, include_dependent_variable: bool) -> Tuple[List
     return [_term_expr(t) for t in lhs_terms + rhs_terms], add_intercept
 
 
-def compute_least_squares_from_formula(formula: str, sample_weights=None, mode: str = "predictions", **kwargs) -> Expr:
+def compute_least_squares_from_formula(formula: str, sample_weights=None, mode: str = "predictions", cov_type: str = "nonrobust",
+                                       cov_kwds: Optional[Dict[str, Any]] = None, **kwargs) -> Expr:
     exprs, add_intercept = _parse_formula(formula, include_dependent_variable=True)   # ls.py:432-452
+    kind = "rls" if kwargs.get("half_life") else ("rolling" if kwargs.get("window_size") else "ols")
+    _robust_cov(cov_type, cov_kwds, mode, kind)
     if kwargs.get("half_life"):
         return compute_recursive_least_squares(exprs[0], *exprs[1:], add_intercept=add_intercept, sample_weights=sample_weights,
                                                mode=mode, rls_kwargs=RLSKwargs(**kwargs))
@@ -577,7 +614,7 @@ def compute_least_squares_from_formula(formula: str, sample_weights=None, mode: 
         return compute_rolling_least_squares(exprs[0], *exprs[1:], add_intercept=add_intercept, sample_weights=sample_weights,
                                              mode=mode, rolling_kwargs=RollingKwargs(**kwargs))
     return compute_least_squares(exprs[0], *exprs[1:], add_intercept=add_intercept, sample_weights=sample_weights, mode=mode,
-                                 ols_kwargs=OLSKwargs(**kwargs))
+                                 ols_kwargs=OLSKwargs(**kwargs), cov_type=cov_type, cov_kwds=cov_kwds)
 
 
 def predict(coefficients: Coefficients, *features, frame: Frame, null_policy: str = "zero", add_intercept: bool = False,
@@ -604,10 +641,14 @@ class LeastSquares:
 
     def least_squares(self, *features, sample_weights=None, add_intercept: bool = False, mode: str = "predictions",
                       null_policy: str = "ignore", solve_method: Optional[str] = None, multi_target: bool = False,
-                      **ols_kwargs) -> Expr:
-        fn = compute_least_squares if not multi_target else compute_multi_target_least_squares
-        return fn(self._expr, *features, sample_weights=sample_weights, add_intercept=add_intercept, mode=mode,
-                  ols_kwargs=OLSKwargs(null_policy=null_policy, solve_method=solve_method, **ols_kwargs))
+                      cov_type: str = "nonrobust", cov_kwds: Optional[Dict[str, Any]] = None, **ols_kwargs) -> Expr:
+        kw = OLSKwargs(null_policy=null_policy, solve_method=solve_method, **ols_kwargs)
+        if multi_target:
+            _robust_cov(cov_type, cov_kwds, mode, "multi-target")
+            return compute_multi_target_least_squares(self._expr, *features, sample_weights=sample_weights, add_intercept=add_intercept,
+                                                      mode=mode, ols_kwargs=kw)
+        return compute_least_squares(self._expr, *features, sample_weights=sample_weights, add_intercept=add_intercept, mode=mode,
+                                     ols_kwargs=kw, cov_type=cov_type, cov_kwds=cov_kwds)
 
     def ols(self, *features, **kwargs) -> Expr:
         return self.least_squares(*features, **kwargs)
@@ -648,6 +689,9 @@ class LeastSquares:
 
     def from_formula(self, formula: str, **kwargs) -> Expr:
         features, add_intercept = _parse_formula(formula, include_dependent_variable=False)
+        if kwargs.get("half_life") or kwargs.get("window_size"):
+            _robust_cov(kwargs.pop("cov_type", "nonrobust"), kwargs.pop("cov_kwds", None), kwargs.get("mode", "predictions"),
+                        "rls" if kwargs.get("half_life") else "rolling")
         if kwargs.get("half_life"):
             return self.rls(*features, add_intercept=add_intercept, **kwargs)
         if kwargs.get("window_size"):
