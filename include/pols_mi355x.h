@@ -274,7 +274,9 @@ enum {
     POLS_COV_HC1 = 2,
     POLS_COV_HC2 = 3,
     POLS_COV_HC3 = 4,
-    POLS_COV_HAC = 5          /* Newey-West: Bartlett weights over maxlags lags */
+    POLS_COV_HAC = 5,         /* Newey-West: Bartlett weights over maxlags lags */
+    POLS_COV_CLUSTER = 6,     /* one-way cluster-robust: pols_least_squares_statistics_cluster only */
+    POLS_COV_CLUSTER2 = 7     /* two-way cluster-robust: pols_least_squares_statistics_cluster only */
 };
 
 typedef struct pols_cov_params {
@@ -287,6 +289,37 @@ void pols_cov_params_default(pols_cov_params *c);
 
 int pols_least_squares_statistics_robust(pols_ctx *ctx, const pols_batch *b, const pols_ols_params *p, const pols_cov_params *cov,
                                          pols_out *out, const pols_stats_out *stats);
+
+/* Cluster-robust standard errors for mode="statistics" (no reference counterpart; statsmodels' cov_type="cluster", Stata's
+ * vce(cluster ...)).  Per group, on exactly the rows, sqrt(w) scaling, ones column, A = X'X + alpha I, b and df of
+ * pols_least_squares_statistics_robust, with e_i = y_i - x_i'b and u_i = e_i x_i:
+ *   one-way  the clusters are the distinct ids among the group's kept rows, G their number;  s_c = sum_{i in c} u_i,
+ *            z_c = A^-1 s_c,  V_jj = q sum_c z_cj^2  with q = G / (G - 1) (N - 1) / df when use_correction (Stata's CR1),
+ *            1 otherwise (N: the group's kept rows);
+ *   two-way  ids A and B, AB = the distinct (a, b) pairs:  V_jj = q_A sum z_A^2 + q_B sum z_B^2 - q_AB sum z_AB^2, each q with
+ *            its own G (Cameron-Gelbach-Miller);
+ *   se_j = sqrt(V_jj), t_j = b_j / se_j, p_j two-sided Student-t with G - 1 degrees of freedom (two-way: min(G_A, G_B) - 1) --
+ *   the Stata / statsmodels convention, deliberately not K7's df.
+ * NaN se / t / p for a group with G < 2 (two-way: min(G_A, G_B) < 2), with df <= 0 under the correction, or whose factorisation
+ * failed; two-way, a coefficient with V_jj < 0 alone.  r2 / mae / mse, the coefficients and status are those of
+ * pols_least_squares_statistics, bit for bit.  Sums run in a fixed order (clusters by ascending id, rows in frame order inside a
+ * cluster), so results are bit-identical from run to run.  ids[w] hold one int64 per row in the batch's row order, where b->mem says;
+ * they follow their rows through the null policy (a cluster whose rows all dropped does not count).  n_clusters (optional, where
+ * b->mem says): n_groups x 1 (G) or n_groups x 2 (G_A, G_B) int64.  Up to 31 columns (incl. the intercept) and fewer than 2^31 rows;
+ * larger calls return POLS_ERR_UNSUPPORTED; a NULL id column or a cov_type other than CLUSTER / CLUSTER2 POLS_ERR_INVALID.  The robust entry above
+ * rejects POLS_COV_CLUSTER / CLUSTER2 with POLS_ERR_INVALID. */
+typedef struct pols_cluster_params {
+    int32_t cov_type;         /* POLS_COV_CLUSTER (ids[0]) or POLS_COV_CLUSTER2 (ids[0], ids[1]) */
+    int32_t use_correction;   /* 1: G / (G - 1) (N - 1) / df per way (default); 0: none */
+    const int64_t *ids[2];    /* cluster id per row */
+    int64_t *n_clusters;      /* optional output */
+} pols_cluster_params;
+
+/* cov_type = POLS_COV_CLUSTER, use_correction = 1, ids = n_clusters = NULL */
+void pols_cluster_params_default(pols_cluster_params *c);
+
+int pols_least_squares_statistics_cluster(pols_ctx *ctx, const pols_batch *b, const pols_ols_params *p, const pols_cluster_params *cl,
+                                          pols_out *out, const pols_stats_out *stats);
 
 /* ---- group-key ingestion: `.over(key)` / `group_by(key)` ------------------------------------------------------------
  * The reference's plugin functions never see a key column: Polars partitions the frame on the host and calls them once per
@@ -393,6 +426,14 @@ int pols_least_squares_statistics_robust_arrow(pols_ctx *ctx, const pols_arrow_c
                                                int32_t n_features, const pols_arrow_column *weights, const int64_t *group_offsets,
                                                int64_t n_groups, int32_t add_intercept, const pols_ols_params *p,
                                                const pols_cov_params *cov, struct ArrowArray *out, struct ArrowSchema *out_schema);
+/* pols_least_squares_statistics_arrow with cluster-robust standard errors (pols_least_squares_statistics_cluster): the same struct
+ * schema.  ids[0] (and ids[1] for POLS_COV_CLUSTER2) are integer columns (formats l L i I s S c C), one row per target row; a null
+ * id is POLS_ERR_INVALID.  cl->ids and cl->n_clusters are ignored. */
+int pols_least_squares_statistics_cluster_arrow(pols_ctx *ctx, const pols_arrow_column *target, const pols_arrow_column *features,
+                                                int32_t n_features, const pols_arrow_column *weights, const int64_t *group_offsets,
+                                                int64_t n_groups, int32_t add_intercept, const pols_ols_params *p,
+                                                const pols_cluster_params *cl, const pols_arrow_column *ids, int32_t n_ids,
+                                                struct ArrowArray *out, struct ArrowSchema *out_schema);
 /* multi_target_least_squares (ex.rs:511-591): `targets` is the STRUCT Series of inputs[0] (format "+s", one numeric field per
  * target; a null struct row is a null in every field); out: a struct array "predictions" of n_rows rows with the targets' field
  * names (multi_target_struct_dtype, :511-519), NaN -> null.  Residuals are the caller's `target - predictions`

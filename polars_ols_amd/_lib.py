@@ -83,8 +83,13 @@ class CovParams(C.Structure):         # pols_cov_params
     _fields_ = [("cov_type", C.c_int32), ("maxlags", C.c_int32)]
 
 
-# cov_type of the robust statistics entries (POLS_COV_*), under the names statsmodels uses
-COV_TYPES = {"nonrobust": 0, "HC0": 1, "HC1": 2, "HC2": 3, "HC3": 4, "HAC": 5}
+# cov_type of the robust statistics entries (POLS_COV_*), under the names statsmodels uses; "cluster" / "cluster2" (one- / two-way)
+# belong to the cluster entries (ClusterParams)
+COV_TYPES = {"nonrobust": 0, "HC0": 1, "HC1": 2, "HC2": 3, "HC3": 4, "HAC": 5, "cluster": 6, "cluster2": 7}
+
+
+class ClusterParams(C.Structure):     # pols_cluster_params
+    _fields_ = [("cov_type", C.c_int32), ("use_correction", C.c_int32), ("ids", C.c_void_p * 2), ("n_clusters", C.c_void_p)]
 
 
 EXPORTS = [
@@ -102,6 +107,7 @@ EXPORTS = [
     "pols_multi_target_least_squares_arrow", "pols_recursive_least_squares_arrow", "pols_rolling_least_squares_arrow",
     "pols_predict_arrow", "pols_least_squares_sharded",
     "pols_cov_params_default", "pols_least_squares_statistics_robust", "pols_least_squares_statistics_robust_arrow",
+    "pols_cluster_params_default", "pols_least_squares_statistics_cluster", "pols_least_squares_statistics_cluster_arrow",
 ]
 # measurement aids (include/pols_mi355x_debug.h): not part of the reference interface
 DEBUG_EXPORTS = ["pols_timing_enable", "pols_timing_collect", "pols_last_kernel_name", "pols_stream_probe", "pols_stream_probe_ex"]
@@ -159,6 +165,9 @@ def lib() -> C.CDLL:
         L.pols_cov_params_default.argtypes, L.pols_cov_params_default.restype = [C.POINTER(CovParams)], None
         L.pols_least_squares_statistics_robust.argtypes = [C.c_void_p, C.POINTER(Batch), C.POINTER(OlsParams), C.POINTER(CovParams),
                                                            C.POINTER(Out), C.POINTER(StatsOut)]
+        L.pols_cluster_params_default.argtypes, L.pols_cluster_params_default.restype = [C.POINTER(ClusterParams)], None
+        L.pols_least_squares_statistics_cluster.argtypes = [C.c_void_p, C.POINTER(Batch), C.POINTER(OlsParams), C.POINTER(ClusterParams),
+                                                            C.POINTER(Out), C.POINTER(StatsOut)]
         L.pols_layout_create.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.POINTER(C.c_void_p)]
         L.pols_layout_destroy.argtypes = [C.c_void_p]
         L.pols_layout_destroy.restype = None
@@ -176,6 +185,8 @@ def lib() -> C.CDLL:
         _common = [C.c_void_p, _ac, _ac, C.c_int32, _ac, C.POINTER(C.c_int64), C.c_int64, C.c_int32]
         L.pols_least_squares_statistics_arrow.argtypes = _common + [C.POINTER(OlsParams), C.c_void_p, C.c_void_p]
         L.pols_least_squares_statistics_robust_arrow.argtypes = _common + [C.POINTER(OlsParams), C.POINTER(CovParams), C.c_void_p, C.c_void_p]
+        L.pols_least_squares_statistics_cluster_arrow.argtypes = _common + [C.POINTER(OlsParams), C.POINTER(ClusterParams), _ac, C.c_int32,
+                                                                            C.c_void_p, C.c_void_p]
         L.pols_multi_target_least_squares_arrow.argtypes = _common + [C.POINTER(OlsParams), C.c_void_p, C.c_void_p]
         L.pols_recursive_least_squares_arrow.argtypes = _common + [C.POINTER(RlsParams), C.c_int32, C.c_void_p, C.c_void_p]
         L.pols_rolling_least_squares_arrow.argtypes = _common + [C.POINTER(RollingParams), C.c_int32, C.c_void_p, C.c_void_p]

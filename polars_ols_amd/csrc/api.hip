@@ -18,6 +18,7 @@
 #include "k6_svd.hpp"
 #include "k7_stats.hpp"
 #include "k7r_robust.hpp"
+#include "k7c_cluster.hpp"
 #include "k8_wide.hpp"
 #include "dyn_prep.hpp"
 
@@ -449,6 +450,7 @@ struct Compacted {
     Staged st;                                  // the ORIGINAL rows on the device (for predictions over every row)
     const int64_t *d_offs = nullptr;            // ... and their offsets
     const uint8_t *vbytes = nullptr;            // row validity (device)
+    RowCompactArgs ra;                          // the compaction's tables (slab bases: valid until the next compaction)
 };
 
 // `targets` (n_targets >= 1 pointers living where b->mem says) replace b->y as the leading columns: the multi-target mask of
@@ -519,6 +521,7 @@ static int compact_nulls(pols_ctx *ctx, const pols_batch *b, int policy, Compact
         if ((rc = row_compact_scatter_launch(ctx, b->dtype, ra))) return rc;
     }
     struct { uint8_t *vbytes; } ca{ra.valid_out};
+    c->ra = ra;
     c->xcols.assign(outp.begin() + m, outp.begin() + m + k);
     c->ycols.assign(outp.begin(), outp.begin() + m);
     c->d_offs = d_offs;
@@ -1514,11 +1517,30 @@ int pols_multi_target_least_squares(pols_ctx *ctx, const pols_batch *b, const vo
 }
 
 // ------------------------------------------------------------------ mode = "statistics"
-// The body of pols_least_squares_statistics and of its robust twin: cov == nullptr is the non-robust entry; otherwise (HC0 .. HAC,
-// validated by pols_least_squares_statistics_robust, at most K7_KMAX columns) K7 still writes r2 / mae / mse and the status words and
-// K7r (k7r_robust.hip) the standard errors, t- and p-values.
-static int statistics_body(pols_ctx *ctx, const pols_batch *b, const pols_ols_params *p, const pols_cov_params *cov, pols_out *o,
-                           const pols_stats_out *s) {
+// The ids of a batch's rows on the device: the caller's own for a device batch, staged into Work::ClusterIds for a host batch.
+static int cluster_device_ids(pols_ctx *ctx, const pols_batch *b, const pols_cluster_params *cl, int ways, const int64_t **dev) {
+    if (b->mem == POLS_MEM_DEVICE) {
+        for (int w = 0; w < ways; ++w) dev[w] = cl->ids[w];
+        return POLS_OK;
+    }
+    const size_t colb = round256(sizeof(int64_t) * (size_t)std::max<int64_t>(b->n_rows, 1));
+    void *d = nullptr;
+    int rc = ensure_scratch(ctx, Work::ClusterIds, colb * (size_t)ways, &d);
+    if (rc) return rc;
+    for (int w = 0; w < ways; ++w) {
+        char *dst = static_cast<char *>(d) + colb * (size_t)w;
+        if (b->n_rows) POLS_HIP(hipMemcpyAsync(dst, cl->ids[w], sizeof(int64_t) * (size_t)b->n_rows, hipMemcpyHostToDevice, ctx->stream));
+        dev[w] = reinterpret_cast<const int64_t *>(dst);
+    }
+    return POLS_OK;
+}
+
+// The body of pols_least_squares_statistics and of its robust and cluster twins: cov == cl == nullptr is the non-robust entry; with
+// cov (HC0 .. HAC, validated by pols_least_squares_statistics_robust, at most K7_KMAX columns) K7 still writes r2 / mae / mse and the
+// status words and K7r (k7r_robust.hip) the standard errors, t- and p-values; with cl (validated by
+// pols_least_squares_statistics_cluster) K7c (k7c_cluster.hip) writes them.
+static int statistics_body(pols_ctx *ctx, const pols_batch *b, const pols_ols_params *p, const pols_cov_params *cov,
+                           const pols_cluster_params *cl, pols_out *o, const pols_stats_out *s) {
     int rc = check_ctx(ctx);
     if (rc) return rc;
     if ((rc = check_batch(b, o, K8_KMAX))) return rc;
@@ -1534,9 +1556,36 @@ static int statistics_body(pols_ctx *ctx, const pols_batch *b, const pols_ols_pa
         if ((rc = compact_nulls(ctx, b, p->null_policy, &c))) return rc;
         pols_ols_params pp = *p;
         pp.null_policy = POLS_NULL_IGNORE;
-        if (b->mem == POLS_MEM_DEVICE) return statistics_body(ctx, &c.bb, &pp, cov, o, s);
-        const int kt = b->n_features + (b->add_intercept ? 1 : 0);
         const size_t G = (size_t)b->n_groups, sz = dtype_size(b->dtype);
+        pols_cluster_params cc;
+        if (cl) {
+            // the ids follow their rows: the source row of every kept row (the compaction's own slab bases), then a gather
+            cc = *cl;
+            const int ways = cl->cov_type == POLS_COV_CLUSTER2 ? 2 : 1;
+            const int64_t *src[2] = {nullptr, nullptr};
+            if ((rc = cluster_device_ids(ctx, b, cl, ways, src))) return rc;
+            const int64_t nv = c.offs[G];
+            const size_t mapb = round256(sizeof(int32_t) * (size_t)std::max<int64_t>(nv, 1)), colb = round256(sizeof(int64_t) * (size_t)std::max<int64_t>(nv, 1));
+            void *d = nullptr;
+            if ((rc = ensure_scratch(ctx, Work::ClusterCompact, mapb + colb * (size_t)ways, &d))) return rc;
+            int64_t *dst[2] = {nullptr, nullptr};
+            for (int w = 0; w < ways; ++w) dst[w] = reinterpret_cast<int64_t *>(static_cast<char *>(d) + mapb + colb * (size_t)w);
+            if (nv > 0) {
+                RowCompactArgs ra = c.ra;
+                ra.src = static_cast<int32_t *>(d);
+                if ((rc = row_compact_srcmap_launch(ctx, ra))) return rc;
+                if ((rc = k7c_gather_ids_launch(ctx, ra.src, nv, src, dst, ways))) return rc;
+            }
+            for (int w = 0; w < ways; ++w) cc.ids[w] = dst[w];
+            if (b->mem == POLS_MEM_HOST && cl->n_clusters) {
+                void *nc = nullptr;
+                if ((rc = ensure_scratch(ctx, Work::ClusterCounts, round256(sizeof(int64_t) * G * (size_t)ways), &nc))) return rc;
+                cc.n_clusters = static_cast<int64_t *>(nc);
+            }
+        }
+        const pols_cluster_params *clc = cl ? &cc : nullptr;
+        if (b->mem == POLS_MEM_DEVICE) return statistics_body(ctx, &c.bb, &pp, cov, clc, o, s);
+        const int kt = b->n_features + (b->add_intercept ? 1 : 0);
         const size_t coefb = round256(sz * G * kt), statb = round256(sizeof(int32_t) * G), vecb = round256(sizeof(double) * G),
                      matb = round256(sizeof(double) * G * kt);
         void *d = nullptr;
@@ -1552,7 +1601,10 @@ static int statistics_body(pols_ctx *ctx, const pols_batch *b, const pols_ols_pa
         for (int i = 0; i < 6; ++i) { dev[i] = user[i] ? reinterpret_cast<double *>(q) : nullptr; q += i < 3 ? vecb : matb; }
         pols_stats_out sd;
         sd.r2 = dev[0]; sd.mae = dev[1]; sd.mse = dev[2]; sd.std_err = dev[3]; sd.t_values = dev[4]; sd.p_values = dev[5];
-        if ((rc = statistics_body(ctx, &c.bb, &pp, cov, &od, &sd))) return rc;
+        if ((rc = statistics_body(ctx, &c.bb, &pp, cov, clc, &od, &sd))) return rc;
+        if (cl && cl->n_clusters)
+            POLS_HIP(hipMemcpyAsync(cl->n_clusters, cc.n_clusters, sizeof(int64_t) * G * (cl->cov_type == POLS_COV_CLUSTER2 ? 2 : 1),
+                                    hipMemcpyDeviceToHost, ctx->stream));
         if (o->coef) POLS_HIP(hipMemcpyAsync(o->coef, od.coef, sz * G * kt, hipMemcpyDeviceToHost, ctx->stream));
         if (o->status) POLS_HIP(hipMemcpyAsync(o->status, od.status, sizeof(int32_t) * G, hipMemcpyDeviceToHost, ctx->stream));
         for (int i = 0; i < 6; ++i)
@@ -1691,6 +1743,29 @@ static int statistics_body(pols_ctx *ctx, const pols_batch *b, const pols_ols_pa
         ra.part = static_cast<double *>(rm);
         if ((rc = k7_stats_launch(ctx, b->dtype, sa))) return rc;
         if ((rc = k7r_robust_launch(ctx, b->dtype, ra))) return rc;
+    } else if (cl) {
+        // cluster-robust: K7 keeps r2 / mae / mse / status, K7c writes the standard errors, t- and p-values and the cluster counts
+        ClusterArgs ca;
+        std::memset(&ca, 0, sizeof(ca));
+        ca.s = sa;
+        sa.se = sa.tv = sa.pv = nullptr;
+        ca.n_rows = b->n_rows;
+        ca.ways = cl->cov_type == POLS_COV_CLUSTER2 ? 2 : 1;
+        ca.use_correction = cl->use_correction ? 1 : 0;
+        if ((rc = cluster_device_ids(ctx, b, cl, ca.ways, ca.ids))) return rc;
+        const int64_t n_items = sa.seg_offs ? sa.n_seg : (int64_t)G;
+        void *cp = nullptr, *cq = nullptr, *nc = nullptr;
+        if ((rc = ensure_scratch(ctx, Work::ClusterPrep, round256(sizeof(double) * G * k7r_prep_stride(kt)), &cp))) return rc;
+        if ((rc = ensure_scratch(ctx, Work::ClusterPart, round256(sizeof(double) * ((size_t)n_items * k7c_part_stride(kt) + 3 * G * ((size_t)kt + 1))), &cq)))
+            return rc;
+        if (cl->n_clusters && host && (rc = ensure_scratch(ctx, Work::ClusterCounts, round256(sizeof(int64_t) * G * (size_t)ca.ways), &nc))) return rc;
+        ca.n_clusters = host ? static_cast<int64_t *>(nc) : cl->n_clusters;
+        ca.prep = static_cast<double *>(cp);
+        ca.part = static_cast<double *>(cq);
+        if ((rc = k7_stats_launch(ctx, b->dtype, sa))) return rc;
+        if ((rc = k7c_cluster_launch(ctx, b->dtype, ca))) return rc;
+        if (host && cl->n_clusters)
+            POLS_HIP(hipMemcpyAsync(cl->n_clusters, ca.n_clusters, sizeof(int64_t) * G * (size_t)ca.ways, hipMemcpyDeviceToHost, ctx->stream));
     } else if ((rc = k7_stats_launch(ctx, b->dtype, sa))) return rc;
     if (!host) return POLS_OK;
     for (int i = 0; i < 6; ++i)
@@ -1702,7 +1777,7 @@ static int statistics_body(pols_ctx *ctx, const pols_batch *b, const pols_ols_pa
 
 int pols_least_squares_statistics(pols_ctx *ctx, const pols_batch *b, const pols_ols_params *p, pols_out *o,
                                   const pols_stats_out *s) {
-    return statistics_body(ctx, b, p, nullptr, o, s);
+    return statistics_body(ctx, b, p, nullptr, nullptr, o, s);
 }
 
 void pols_cov_params_default(pols_cov_params *c) {
@@ -1714,6 +1789,8 @@ void pols_cov_params_default(pols_cov_params *c) {
 int pols_least_squares_statistics_robust(pols_ctx *ctx, const pols_batch *b, const pols_ols_params *p, const pols_cov_params *cov,
                                          pols_out *o, const pols_stats_out *s) {
     if (!cov) return fail(POLS_ERR_INVALID, "cov is NULL");
+    if (cov->cov_type == POLS_COV_CLUSTER || cov->cov_type == POLS_COV_CLUSTER2)
+        return fail(POLS_ERR_INVALID, "cov_type %d: cluster-robust standard errors go through pols_least_squares_statistics_cluster", cov->cov_type);
     if (cov->cov_type < POLS_COV_NONROBUST || cov->cov_type > POLS_COV_HAC) return fail(POLS_ERR_INVALID, "unknown cov_type %d", cov->cov_type);
     if (cov->cov_type == POLS_COV_NONROBUST) return pols_least_squares_statistics(ctx, b, p, o, s);
     if (cov->cov_type == POLS_COV_HAC) {
@@ -1724,7 +1801,31 @@ int pols_least_squares_statistics_robust(pols_ctx *ctx, const pols_batch *b, con
     const int kt = b->n_features + (b->add_intercept ? 1 : 0);
     if (kt > K7_KMAX)
         return fail(POLS_ERR_UNSUPPORTED, "robust statistics: %d features (incl. intercept) > %d; wider frames have only the non-robust form", kt, K7_KMAX);
-    return statistics_body(ctx, b, p, cov, o, s);
+    return statistics_body(ctx, b, p, cov, nullptr, o, s);
+}
+
+void pols_cluster_params_default(pols_cluster_params *c) {
+    if (!c) return;
+    c->cov_type = POLS_COV_CLUSTER;
+    c->use_correction = 1;
+    c->ids[0] = c->ids[1] = nullptr;
+    c->n_clusters = nullptr;
+}
+
+int pols_least_squares_statistics_cluster(pols_ctx *ctx, const pols_batch *b, const pols_ols_params *p, const pols_cluster_params *cl,
+                                          pols_out *o, const pols_stats_out *s) {
+    if (!cl) return fail(POLS_ERR_INVALID, "cluster params are NULL");
+    if (cl->cov_type != POLS_COV_CLUSTER && cl->cov_type != POLS_COV_CLUSTER2)
+        return fail(POLS_ERR_INVALID, "cluster statistics: cov_type %d is neither POLS_COV_CLUSTER nor POLS_COV_CLUSTER2", cl->cov_type);
+    if (!b) return fail(POLS_ERR_INVALID, "batch is NULL");
+    const int kt = b->n_features + (b->add_intercept ? 1 : 0);
+    if (kt > K7_KMAX)
+        return fail(POLS_ERR_UNSUPPORTED, "cluster statistics: %d features (incl. intercept) > %d; wider frames have only the non-robust form", kt, K7_KMAX);
+    const int ways = cl->cov_type == POLS_COV_CLUSTER2 ? 2 : 1;
+    for (int w = 0; w < ways; ++w)
+        if (!cl->ids[w] && b->n_rows > 0) return fail(POLS_ERR_INVALID, "cluster statistics: ids[%d] is NULL", w);
+    if (b->n_rows >= ((int64_t)1 << 31)) return fail(POLS_ERR_UNSUPPORTED, "cluster statistics: %lld rows (row indices are 31-bit)", (long long)b->n_rows);
+    return statistics_body(ctx, b, p, nullptr, cl, o, s);
 }
 
 // Dynamic models share the staging of a batch whose coefficient output has one row per input row, and the pre-processing the

@@ -3,6 +3,7 @@
 //   least_squares / least_squares_coefficients (:390-446)                  pols_least_squares_arrow
 //   least_squares_statistics (:448-509)                                     pols_least_squares_statistics_arrow
 //     ... with robust standard errors                                       pols_least_squares_statistics_robust_arrow
+//     ... with cluster-robust standard errors                               pols_least_squares_statistics_cluster_arrow
 //   multi_target_least_squares (:511-591; inputs[0] is a STRUCT Series)     pols_multi_target_least_squares_arrow
 //   recursive_least_squares[_coefficients] (:593-646)                       pols_recursive_least_squares_arrow
 //   rolling_least_squares[_coefficients] (:648-701)                         pols_rolling_least_squares_arrow
@@ -621,7 +622,7 @@ static int list_names(ArrowArray *a, ArrowSchema *s, const char *name, const std
 template <typename T>
 static int arrow_statistics(pols_ctx *ctx, const ColView &target, const std::vector<ColView> &feat, const ColView *weights,
                             const int64_t *group_offsets, int64_t n_groups, int32_t add_intercept, const pols_ols_params *p,
-                            const pols_cov_params *cov, ArrowArray *out, ArrowSchema *out_schema) {
+                            const pols_cov_params *cov, const pols_cluster_params *cl, ArrowArray *out, ArrowSchema *out_schema) {
     const int64_t n_rows = target.rows(), G = std::max<int64_t>(n_groups, 1);
     const int kt = (int)feat.size() + (add_intercept ? 1 : 0);
     const size_t coefb = round256(sizeof(T) * (size_t)G * kt), sb = round256(sizeof(double) * (size_t)G), tb = round256(sizeof(double) * (size_t)G * kt);
@@ -640,7 +641,9 @@ static int arrow_statistics(pols_ctx *ctx, const ColView &target, const std::vec
     pols_out o;
     std::memset(&o, 0, sizeof(o));
     o.coef = dcoef; o.status = dstat;
-    if ((rc = cov ? pols_least_squares_statistics_robust(ctx, &b, p, cov, &o, &so) : pols_least_squares_statistics(ctx, &b, p, &o, &so))) return rc;
+    if ((rc = cov  ? pols_least_squares_statistics_robust(ctx, &b, p, cov, &o, &so)
+              : cl ? pols_least_squares_statistics_cluster(ctx, &b, p, cl, &o, &so)
+                   : pols_least_squares_statistics(ctx, &b, p, &o, &so))) return rc;
     // everything is small (per group): home in one go
     std::vector<T> hcoef((size_t)n_groups * kt);
     std::vector<double> h3((size_t)n_groups * 3), ht((size_t)n_groups * kt * 3), hc64((size_t)n_groups * kt);
@@ -734,8 +737,8 @@ int pols_least_squares_statistics_arrow(pols_ctx *ctx, const pols_arrow_column *
     int rc = common_views(ctx, target, features, n_features, weights, &group_offsets, &n_groups, add_intercept, POLS_MAX_FEATURES_STATISTICS, p, out, out_schema, &cv);
     if (rc) return rc;
     const ColView *w = weights ? &cv.wv : nullptr;
-    if (cv.all_f32) return arrow_statistics<float>(ctx, cv.target, cv.feat, w, group_offsets, n_groups, add_intercept, p, nullptr, out, out_schema);
-    return arrow_statistics<double>(ctx, cv.target, cv.feat, w, group_offsets, n_groups, add_intercept, p, nullptr, out, out_schema);
+    if (cv.all_f32) return arrow_statistics<float>(ctx, cv.target, cv.feat, w, group_offsets, n_groups, add_intercept, p, nullptr, nullptr, out, out_schema);
+    return arrow_statistics<double>(ctx, cv.target, cv.feat, w, group_offsets, n_groups, add_intercept, p, nullptr, nullptr, out, out_schema);
 }
 
 int pols_least_squares_statistics_robust_arrow(pols_ctx *ctx, const pols_arrow_column *target, const pols_arrow_column *features,
@@ -747,8 +750,70 @@ int pols_least_squares_statistics_robust_arrow(pols_ctx *ctx, const pols_arrow_c
     int rc = common_views(ctx, target, features, n_features, weights, &group_offsets, &n_groups, add_intercept, POLS_MAX_FEATURES_STATISTICS, p, out, out_schema, &cv);
     if (rc) return rc;
     const ColView *w = weights ? &cv.wv : nullptr;
-    if (cv.all_f32) return arrow_statistics<float>(ctx, cv.target, cv.feat, w, group_offsets, n_groups, add_intercept, p, cov, out, out_schema);
-    return arrow_statistics<double>(ctx, cv.target, cv.feat, w, group_offsets, n_groups, add_intercept, p, cov, out, out_schema);
+    if (cv.all_f32) return arrow_statistics<float>(ctx, cv.target, cv.feat, w, group_offsets, n_groups, add_intercept, p, cov, nullptr, out, out_schema);
+    return arrow_statistics<double>(ctx, cv.target, cv.feat, w, group_offsets, n_groups, add_intercept, p, cov, nullptr, out, out_schema);
+}
+
+// an integer id column (any of l L i I s S c C) as int64 on the host; a null id is an error (nulls are rejected, not dropped)
+static int host_ids(const ColView &v, int64_t *dst) {
+    int64_t r = 0;
+    for (const auto &ch : v.chunks) {
+        const ArrowArray *a = ch.a;
+        const uint8_t *bits = (a->null_count != 0 && a->n_buffers >= 1 && a->buffers[0]) ? static_cast<const uint8_t *>(a->buffers[0]) : nullptr;
+        const void *vals = a->buffers[1];
+        for (int64_t i = 0; i < ch.length; ++i, ++r) {
+            const int64_t k = ch.offset + i;
+            if (bits && !((bits[k >> 3] >> (k & 7)) & 1)) return fail(POLS_ERR_INVALID, "cluster ids: null at row %lld", (long long)r);
+            switch (v.type.code) {
+                case 'l': dst[r] = static_cast<const int64_t *>(vals)[k]; break;
+                case 'L': dst[r] = (int64_t)static_cast<const uint64_t *>(vals)[k]; break;
+                case 'i': dst[r] = static_cast<const int32_t *>(vals)[k]; break;
+                case 'I': dst[r] = static_cast<const uint32_t *>(vals)[k]; break;
+                case 's': dst[r] = static_cast<const int16_t *>(vals)[k]; break;
+                case 'S': dst[r] = static_cast<const uint16_t *>(vals)[k]; break;
+                case 'c': dst[r] = static_cast<const int8_t *>(vals)[k]; break;
+                default: dst[r] = static_cast<const uint8_t *>(vals)[k]; break;
+            }
+        }
+    }
+    return POLS_OK;
+}
+
+int pols_least_squares_statistics_cluster_arrow(pols_ctx *ctx, const pols_arrow_column *target, const pols_arrow_column *features,
+                                                int32_t n_features, const pols_arrow_column *weights, const int64_t *group_offsets,
+                                                int64_t n_groups, int32_t add_intercept, const pols_ols_params *p,
+                                                const pols_cluster_params *cl, const pols_arrow_column *ids, int32_t n_ids,
+                                                struct ArrowArray *out, struct ArrowSchema *out_schema) {
+    if (!cl) return fail(POLS_ERR_INVALID, "cluster params are NULL");
+    if (cl->cov_type != POLS_COV_CLUSTER && cl->cov_type != POLS_COV_CLUSTER2)
+        return fail(POLS_ERR_INVALID, "cluster statistics: cov_type %d is neither POLS_COV_CLUSTER nor POLS_COV_CLUSTER2", cl->cov_type);
+    const int ways = cl->cov_type == POLS_COV_CLUSTER2 ? 2 : 1;
+    if (!ids || n_ids != ways) return fail(POLS_ERR_INVALID, "cluster statistics: %d id columns for %d-way clustering", (int)n_ids, ways);
+    CommonViews cv;
+    int rc = common_views(ctx, target, features, n_features, weights, &group_offsets, &n_groups, add_intercept, POLS_MAX_FEATURES_STATISTICS, p, out, out_schema, &cv);
+    if (rc) return rc;
+    const int64_t n = cv.n_rows;
+    std::vector<int64_t> hid((size_t)std::max<int64_t>(n, 1) * ways);
+    for (int w = 0; w < ways; ++w) {
+        ColView iv;
+        if ((rc = view_primitive(&ids[w], "cluster ids", &iv))) return rc;
+        if (iv.type.code == 'f' || iv.type.code == 'g') return fail(POLS_ERR_INVALID, "cluster ids: integer columns only (format '%c')", iv.type.code);
+        if (iv.rows() != n) return fail(POLS_ERR_INVALID, "cluster ids: %lld rows, the target %lld", (long long)iv.rows(), (long long)n);
+        if ((rc = host_ids(iv, hid.data() + (size_t)w * n))) return rc;
+    }
+    const size_t colb = round256(sizeof(int64_t) * (size_t)std::max<int64_t>(n, 1));
+    void *d = nullptr;
+    if ((rc = ensure_scratch(ctx, Work::ClusterIds, colb * (size_t)ways, &d))) return rc;
+    pols_cluster_params c2 = *cl;
+    c2.n_clusters = nullptr;
+    for (int w = 0; w < ways; ++w) {
+        char *dst = static_cast<char *>(d) + colb * (size_t)w;
+        if (n) POLS_HIP(hipMemcpyAsync(dst, hid.data() + (size_t)w * n, sizeof(int64_t) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+        c2.ids[w] = reinterpret_cast<const int64_t *>(dst);
+    }
+    const ColView *w = weights ? &cv.wv : nullptr;
+    if (cv.all_f32) return arrow_statistics<float>(ctx, cv.target, cv.feat, w, group_offsets, n_groups, add_intercept, p, nullptr, &c2, out, out_schema);
+    return arrow_statistics<double>(ctx, cv.target, cv.feat, w, group_offsets, n_groups, add_intercept, p, nullptr, &c2, out, out_schema);
 }
 
 int pols_recursive_least_squares_arrow(pols_ctx *ctx, const pols_arrow_column *target, const pols_arrow_column *features, int32_t n_features,

@@ -67,6 +67,13 @@ enum class Work : int {
     GatherMap,      // rolling GATHER tiles: source row of every compacted row
     RobustPrep,     // robust statistics (K7r): A^-1, coefficients, trace, ok per group
     RobustMeat,     // robust statistics (K7r): U'W partial sums per segment / group
+    ClusterIds,     // cluster statistics (K7c): id columns staged from the host (host batches, Arrow columns)
+    ClusterCompact, // cluster statistics (K7c): the ids of the rows a null policy keeps, and their source rows
+    ClusterPrep,    // cluster statistics (K7c): A^-1, coefficients, trace, ok per group
+    ClusterPart,    // cluster statistics (K7c): run partials per segment / group, per-group sums of the three clusterings
+    ClusterSort,    // cluster statistics (K7c): radix keys and values, row -> group, key probes, rocPRIM temporary storage
+    ClusterOrder,   // cluster statistics (K7c): position -> row of the clustering being scored
+    ClusterCounts,  // cluster statistics (K7c): cluster counts of a host batch before they go home
     Count
 };
 

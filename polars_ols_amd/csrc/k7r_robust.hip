@@ -258,6 +258,15 @@ static int k7r_launch_t(pols_ctx *ctx, const RobustArgs &r0) {
     return POLS_OK;
 }
 
+int k7r_prepare_launch(pols_ctx *ctx, int dtype, const RobustArgs &r) {
+    if (r.s.kt > K7_KMAX) return fail(POLS_ERR_UNSUPPORTED, "robust statistics: %d features (incl. intercept) > %d", r.s.kt, K7_KMAX);
+    if (r.s.n_groups == 0) return POLS_OK;
+    if (dtype == POLS_F32) hipLaunchKernelGGL(k7r_prepare_kernel<float>, dim3((unsigned)r.s.n_groups), dim3(64), 0, ctx->stream, r);
+    else hipLaunchKernelGGL(k7r_prepare_kernel<double>, dim3((unsigned)r.s.n_groups), dim3(64), 0, ctx->stream, r);
+    POLS_HIP(hipGetLastError());
+    return POLS_OK;
+}
+
 int k7r_robust_launch(pols_ctx *ctx, int dtype, const RobustArgs &r) {
     if (r.s.kt > K7_KMAX) return fail(POLS_ERR_UNSUPPORTED, "robust statistics: %d features (incl. intercept) > %d", r.s.kt, K7_KMAX);
     if (r.maxlags < 0 || r.maxlags > K7R_MAXLAGS) return fail(POLS_ERR_UNSUPPORTED, "robust statistics: maxlags %d outside 0..%d", r.maxlags, K7R_MAXLAGS);

@@ -22,4 +22,7 @@ __host__ __device__ inline size_t k7r_part_stride(int kt) { return (size_t)kt * 
 // prepare / meat / finish on the stream; the r2 / mae / mse of the call come from K7 (k7_stats_launch) unchanged
 int k7r_robust_launch(pols_ctx *ctx, int dtype, const RobustArgs &r);
 
+// the prepare launch alone (r.s, r.prep): A^-1, b, trace(A^-1) and ok per group -- what the cluster-robust statistics (K7c) start from
+int k7r_prepare_launch(pols_ctx *ctx, int dtype, const RobustArgs &r);
+
 }  // namespace pols

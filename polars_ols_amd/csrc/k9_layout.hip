@@ -16,6 +16,7 @@
 //   row_groups     the group id of every frame row (what broadcasts a per-group coefficient struct back over the frame).
 // All of it is HBM-bound integer / byte work: no LDS tricks, just coalesced streams and as few passes as the key range allows.
 #include "common.hpp"
+#include "k9_sort.hpp"
 
 #include <rocprim/rocprim.hpp>
 
@@ -210,6 +211,15 @@ __global__ void __launch_bounds__(256) row_groups_kernel(const int64_t *__restri
 static inline unsigned blocks_for(int64_t n, int per_block) { return (unsigned)((n + per_block - 1) / per_block); }
 
 template <typename U>
+int k9_radix_sort_pairs(pols_ctx *ctx, void *tmp, size_t *tmp_bytes, const U *keys_in, U *keys_out, const uint32_t *vals_in,
+                        uint32_t *vals_out, int64_t n, int bits) {
+    POLS_HIP((rocprim::radix_sort_pairs(tmp, *tmp_bytes, keys_in, keys_out, vals_in, vals_out, (size_t)n, 0u, (unsigned)bits, ctx->stream)));
+    return POLS_OK;
+}
+template int k9_radix_sort_pairs<uint32_t>(pols_ctx *, void *, size_t *, const uint32_t *, uint32_t *, const uint32_t *, uint32_t *, int64_t, int);
+template int k9_radix_sort_pairs<uint64_t>(pols_ctx *, void *, size_t *, const uint64_t *, uint64_t *, const uint32_t *, uint32_t *, int64_t, int);
+
+template <typename U>
 static int sort_and_segment(pols_ctx *ctx, pols_layout *L, const int64_t *d_keys, int64_t mn, int bits, bool sorted) {
     const int64_t n = L->n;
     const size_t nb = round256(sizeof(U) * (size_t)n), ib = round256(sizeof(uint32_t) * (size_t)n);
@@ -218,14 +228,14 @@ static int sort_and_segment(pols_ctx *ctx, pols_layout *L, const int64_t *d_keys
     U *np_u = nullptr;
     uint32_t *np_i = nullptr;
     int64_t *np_o = nullptr;
-    POLS_HIP((rocprim::radix_sort_pairs(nullptr, t_sort, (const U *)np_u, np_u, (const uint32_t *)np_i, np_i, (size_t)n, 0u, (unsigned)bits,
-                                         ctx->stream)));
+    int rc = k9_radix_sort_pairs<U>(ctx, nullptr, &t_sort, np_u, np_u, np_i, np_i, n, bits);
+    if (rc) return rc;
     POLS_HIP((rocprim::run_length_encode(nullptr, t_rle, (const U *)np_u, (unsigned int)n, np_u, np_i, np_i, ctx->stream)));
     POLS_HIP((rocprim::exclusive_scan(nullptr, t_scan, (const uint32_t *)np_i, np_o, (int64_t)0, (size_t)n + 1, rocprim::plus<int64_t>(), ctx->stream)));
     // (the tail of the region also carries the unique keys home as int64: up to n of them)
     const size_t tmpb = round256(std::max(std::max(t_sort, sizeof(int64_t) * (size_t)n), std::max(t_rle, t_scan)));
     void *base = nullptr;
-    int rc = ensure_scratch(ctx, Work::K9Keys, 3 * nb + 2 * ib + 256 + tmpb, &base);
+    rc = ensure_scratch(ctx, Work::K9Keys, 3 * nb + 2 * ib + 256 + tmpb, &base);
     if (rc) return rc;
     char *p = static_cast<char *>(base);
     U *u_in = reinterpret_cast<U *>(p);            p += nb;
@@ -243,8 +253,7 @@ static int sort_and_segment(pols_ctx *ctx, pols_layout *L, const int64_t *d_keys
         L->order = static_cast<uint32_t *>(L->arena);
         L->inverse_slot = reinterpret_cast<uint32_t *>(static_cast<char *>(L->arena) + ib);
         size_t t = tmpb;
-        POLS_HIP((rocprim::radix_sort_pairs(tmp, t, (const U *)u_in, u_out, (const uint32_t *)iota, L->order, (size_t)n, 0u,
-                                             (unsigned)bits, ctx->stream)));
+        if ((rc = k9_radix_sort_pairs<U>(ctx, tmp, &t, u_in, u_out, iota, L->order, n, bits))) return rc;
         sorted_keys = u_out;
         L->identity = false;
     }

@@ -209,12 +209,23 @@ class Engine:
         return res
 
     def least_squares_statistics(self, y, x_cols: Sequence, offsets, cov_type: str = "nonrobust", maxlags: Optional[int] = None,
-                                 **kwargs) -> Dict:
+                                 clusters=None, use_correction: bool = True, **kwargs) -> Dict:
         """mode="statistics" (src/expressions.rs:468-509) for every group: returns ``coef`` (batch dtype), ``status`` and
         the f64 arrays ``r2 mae mse`` [n_groups] and ``std_err t_values p_values`` [n_groups, k].  ``cov_type`` "HC0" .. "HC3"
         or "HAC" (with ``maxlags``) makes the last three robust (pols_least_squares_statistics_robust); "nonrobust" is the
-        reference's constant-variance form."""
-        cov = _cov_params(self._lib, cov_type, maxlags)
+        reference's constant-variance form.  ``cov_type="cluster"`` with ``clusters`` = one integer id column (one-way) or a pair
+        (two-way), in the rows' order and where ``y`` lives, makes them cluster-robust (pols_least_squares_statistics_cluster,
+        ``use_correction``: Stata's G / (G - 1) (N - 1) / df) and adds ``n_clusters`` [n_groups] or [n_groups, 2] (int64)."""
+        if cov_type == "cluster":
+            if maxlags is not None:
+                raise ValueError("maxlags applies to cov_type='HAC' only (got cov_type='cluster')")
+            ids = _cluster_columns(clusters)
+            cov = None
+        else:
+            if clusters is not None:
+                raise ValueError(f"clusters applies to cov_type='cluster' only (got cov_type={cov_type!r})")
+            cov = _cov_params(self._lib, cov_type, maxlags)
+            ids = None
         kwargs.setdefault("want", ("coef", "status"))
         plan = self.plan_least_squares(y, x_cols, offsets, **kwargs)
         b = plan._b
@@ -228,7 +239,25 @@ class Engine:
         for key in ("std_err", "t_values", "p_values"):
             res[key] = self._alloc(dev, f64, (b.n_groups, kt), like)
         so = L.StatsOut(**{k: self._ptr(res[k]) for k in ("r2", "mae", "mse", "std_err", "t_values", "p_values")})
-        if cov is None:
+        if ids is not None:
+            keep = []
+            for a in ids:
+                if a.shape[0] != b.n_rows:
+                    raise ValueError(f"clusters: {a.shape[0]} ids for {b.n_rows} rows")
+                if dev:
+                    keep.append(torch.as_tensor(a, device=like.device).to(torch.int64).contiguous())
+                elif _is_torch(a):
+                    keep.append(np.ascontiguousarray(a.cpu().numpy(), dtype=np.int64))
+                else:
+                    keep.append(np.ascontiguousarray(a, dtype=np.int64))
+            res["n_clusters"] = self._alloc(dev, torch.int64 if dev else np.int64, (b.n_groups,) if len(ids) == 1 else (b.n_groups, 2), like)
+            cl = _cluster_params(self._lib, len(ids), use_correction)
+            for i, a in enumerate(keep):
+                cl.ids[i] = self._ptr(a)
+            cl.n_clusters = self._ptr(res["n_clusters"])
+            L.check(self._lib.pols_least_squares_statistics_cluster(self._h, C.byref(plan._b), C.byref(plan._p), C.byref(cl),
+                                                                    C.byref(plan._o), C.byref(so)))
+        elif cov is None:
             L.check(self._lib.pols_least_squares_statistics(self._h, C.byref(plan._b), C.byref(plan._p), C.byref(plan._o),
                                                             C.byref(so)))
         else:
@@ -467,6 +496,8 @@ def _cov_params(lib, cov_type: str = "nonrobust", maxlags: Optional[int] = None)
     cov_type, HAC without maxlags (or a negative one), maxlags with another cov_type."""
     if cov_type not in L.COV_TYPES:
         raise ValueError(f"cov_type must be one of {sorted(L.COV_TYPES)}, got {cov_type!r}")
+    if cov_type in ("cluster", "cluster2"):
+        raise ValueError("cluster-robust standard errors need their ids: least_squares_statistics(cov_type='cluster', clusters=...)")
     if cov_type == "HAC":
         if maxlags is None or isinstance(maxlags, bool) or int(maxlags) != maxlags or maxlags < 0:
             raise ValueError(f"cov_type='HAC' needs maxlags, a non-negative integer (got {maxlags!r})")
@@ -478,6 +509,29 @@ def _cov_params(lib, cov_type: str = "nonrobust", maxlags: Optional[int] = None)
     lib.pols_cov_params_default(C.byref(c))
     c.cov_type = L.COV_TYPES[cov_type]
     c.maxlags = int(maxlags) if maxlags is not None else 0
+    return c
+
+
+def _cluster_columns(clusters) -> list:
+    """The id columns of ``clusters``: one column (one-way) or a pair / list of two (two-way).  ValueError otherwise."""
+    if clusters is None:
+        raise ValueError("cov_type='cluster' needs clusters: one id column, or two for two-way clustering")
+    cols = list(clusters) if isinstance(clusters, (tuple, list)) else [clusters]
+    if not 1 <= len(cols) <= 2:
+        raise ValueError(f"clusters: one or two id columns (got {len(cols)}); three or more ways are not supported")
+    for a in cols:
+        dt = a.dtype
+        if (_is_torch(a) and (dt.is_floating_point or dt.is_complex or dt == torch.bool)) or \
+                (not _is_torch(a) and np.asarray(a).dtype.kind not in "iu"):
+            raise ValueError(f"clusters: integer id columns only (got {dt})")
+    return cols
+
+
+def _cluster_params(lib, ways: int, use_correction: bool = True) -> L.ClusterParams:
+    c = L.ClusterParams()
+    lib.pols_cluster_params_default(C.byref(c))
+    c.cov_type = L.COV_TYPES["cluster2" if ways == 2 else "cluster"]
+    c.use_correction = 1 if use_correction else 0
     return c
 
 
@@ -518,9 +572,28 @@ def _arrow_call(self, fn, first, first_name: str, features, weights, offsets, ad
 
 
 def _statistics_arrow(self, target, features, *, target_name: str = "y", weights=None, offsets=None, add_intercept: bool = False,
-                      cov_type: str = "nonrobust", maxlags: Optional[int] = None, **kw):
+                      cov_type: str = "nonrobust", maxlags: Optional[int] = None, clusters=None, use_correction: bool = True, **kw):
     """``pols_least_squares_statistics_arrow`` (plugin least_squares_statistics, src/expressions.rs:448-509): the ``statistics``
-    struct, one row per group.  A robust ``cov_type`` calls ``pols_least_squares_statistics_robust_arrow`` (same struct)."""
+    struct, one row per group.  A robust ``cov_type`` calls ``pols_least_squares_statistics_robust_arrow`` (same struct);
+    ``cov_type="cluster"`` with ``clusters`` (one or two pyarrow integer columns) ``pols_least_squares_statistics_cluster_arrow``."""
+    if cov_type == "cluster":
+        if maxlags is not None:
+            raise ValueError("maxlags applies to cov_type='HAC' only (got cov_type='cluster')")
+        if clusters is None:
+            raise ValueError("cov_type='cluster' needs clusters: one id column, or two for two-way clustering")
+        cols = list(clusters) if isinstance(clusters, (tuple, list)) else [clusters]
+        if not 1 <= len(cols) <= 2:
+            raise ValueError(f"clusters: one or two id columns (got {len(cols)})")
+        p = _ols_params(self._lib, **kw)
+        cl = _cluster_params(self._lib, len(cols), use_correction)
+        ex = [_ArrowExport(f"cluster_{i}", c) for i, c in enumerate(cols)]
+        try:
+            arr = (L.ArrowColumn * len(ex))(*[e.column for e in ex])
+            return _arrow_call(self, self._lib.pols_least_squares_statistics_cluster_arrow, target, target_name, features, weights,
+                               offsets, add_intercept, (C.byref(p), C.byref(cl), arr, len(ex)))
+        finally:
+            for e in ex:
+                e.close()
     cov = _cov_params(self._lib, cov_type, maxlags)
     p = _ols_params(self._lib, **kw)
     if cov is None:

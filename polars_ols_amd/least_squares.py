@@ -315,11 +315,17 @@ class Statistics(dict):
                          coefficients=out["coef"], standard_errors=out["std_err"], t_values=out["t_values"],
                          p_values=out["p_values"])
         self.keys_ = keys
+        # cov_type="cluster": the clusters G per group ([G] one-way, [G, 2] two-way: G_A, G_B); None otherwise
+        self.n_clusters = out.get("n_clusters")
+        if self.n_clusters is not None:
+            self["n_clusters"] = self.n_clusters
 
 
 def _static_statistics(eng: Engine, y, xs, offs, w, icpt: bool, kw: OLSKwargs, names, keys, cov=None) -> Statistics:
     d = kw.to_dict()
-    if cov is not None:                                        # (cov_type, maxlags): robust standard errors / t / p
+    if cov is not None and cov[0] == "cluster":               # ("cluster", id columns in group order, use_correction)
+        d["cov_type"], d["clusters"], d["use_correction"] = cov
+    elif cov is not None:                                      # (cov_type, maxlags): robust standard errors / t / p
         d["cov_type"], d["maxlags"] = cov
     out = eng.least_squares_statistics(y, xs, offs, weights=w, add_intercept=icpt, **d)
     st = out["status"]
@@ -338,8 +344,11 @@ def _apply_static(frame: Frame, over, eng: Optional[Engine], target: Expr, featu
     # ---- group layout (.over)
     grp = _Groups(eng, None if over is None else (frame[over] if isinstance(over, str) else over), n)
     offs, keys = grp.offsets, grp.keys
-    moved = grp.take([y, w] + list(xs))
-    y_s, w_s, xs_s = moved[0], moved[1], moved[2:]
+    ids = _cluster_ids(frame, cov[1], y) if cov is not None and cov[0] == "cluster" else []
+    moved = grp.take([y, w] + list(xs) + ids)                 # (cluster ids move with their rows, 8 bytes each)
+    y_s, w_s, xs_s = moved[0], moved[1], moved[2:2 + len(xs)]
+    if ids:
+        cov = ("cluster", moved[2 + len(xs):], cov[2])
 
     policy = kw.null_policy
     if mode != "statistics":
@@ -389,12 +398,35 @@ def _apply_dynamic(frame: Frame, over, eng: Optional[Engine], target: Expr, feat
 
 # ---- the reference's module-level functions (least_squares.py:242-491) -------------------------------------------
 
-_VALID_COV_TYPES = ("nonrobust", "HC0", "HC1", "HC2", "HC3", "HAC")
+_VALID_COV_TYPES = ("nonrobust", "HC0", "HC1", "HC2", "HC3", "HAC", "cluster")
+
+
+def _cluster_ids(frame: Frame, groups, like) -> list:
+    """The cluster id columns of cov_kwds["groups"] as int64 where ``like`` lives: names / expressions are read from the frame,
+    arrays taken as they are; ids that are not integers are dictionary-encoded (their order is that of np.unique / torch.unique)."""
+    out = []
+    for g in groups:
+        a = g if (_is_torch(g) or isinstance(g, np.ndarray)) else parse_into_expr(g)._column(frame)
+        if a.shape[0] != like.shape[0]:
+            raise ValueError(f"cov_kwds['groups']: {a.shape[0]} ids for {like.shape[0]} rows")
+        if _is_torch(a):
+            if a.dtype.is_floating_point or a.dtype.is_complex:
+                a = torch.unique(a, return_inverse=True)[1]
+            a = a.to(torch.int64)
+            a = a.to(like.device) if _is_torch(like) else a.cpu().numpy()
+        else:
+            a = np.asarray(a)
+            a = a.astype(np.int64) if a.dtype.kind in "iub" else np.unique(a, return_inverse=True)[1].astype(np.int64)
+            if _is_torch(like):
+                a = torch.as_tensor(a, device=like.device)
+        out.append(a)
+    return out
 
 
 def _robust_cov(cov_type: str, cov_kwds: Optional[Dict[str, Any]], mode: str, kind: str = "ols"):
-    """(cov_type, maxlags) of a robust request, None for the default "nonrobust"; ValueError for what has no robust form: an unknown
-    cov_type, a mode other than "statistics", multi-target / RLS / rolling models, HAC without cov_kwds={"maxlags": L}."""
+    """(cov_type, maxlags) of a robust request, ("cluster", id columns, use_correction) of a cluster-robust one, None for the default
+    "nonrobust"; ValueError for what has no robust form: an unknown cov_type, a mode other than "statistics", multi-target / RLS /
+    rolling models, HAC without cov_kwds={"maxlags": L}, "cluster" without cov_kwds={"groups": ...} or with other keys."""
     if cov_type not in _VALID_COV_TYPES:
         raise ValueError(f"'cov_type' must be one of {_VALID_COV_TYPES}, got {cov_type!r}")
     if cov_type == "nonrobust" and not cov_kwds:
@@ -404,6 +436,20 @@ def _robust_cov(cov_type: str, cov_kwds: Optional[Dict[str, Any]], mode: str, ki
     if mode != "statistics":
         raise ValueError(f"cov_type={cov_type!r} needs mode='statistics' (got mode={mode!r})")
     kwds = dict(cov_kwds or {})
+    if cov_type == "cluster":
+        # statsmodels' spelling: cov_kwds={"groups": one id column or two (two-way), "use_correction": bool}
+        if "maxlags" in kwds:
+            raise ValueError("cov_kwds 'maxlags' applies to cov_type='HAC' only, not to 'cluster'")
+        unknown = set(kwds) - {"groups", "use_correction"}
+        if unknown:
+            raise ValueError(f"unknown cov_kwds {sorted(unknown)} for cov_type='cluster' (groups, use_correction)")
+        groups = kwds.get("groups")
+        if groups is None:
+            raise ValueError("cov_type='cluster' needs cov_kwds={'groups': <column name | Expr | array | [a, b]>}")
+        groups = list(groups) if isinstance(groups, (list, tuple)) else [groups]
+        if not 1 <= len(groups) <= 2:
+            raise ValueError(f"cov_kwds['groups']: one or two id columns (got {len(groups)})")
+        return "cluster", groups, bool(kwds.get("use_correction", True))
     unknown = set(kwds) - {"maxlags"}
     if unknown:
         raise ValueError(f"unknown cov_kwds {sorted(unknown)}")
