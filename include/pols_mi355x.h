@@ -198,7 +198,12 @@ int pols_least_squares(pols_ctx *ctx, const pols_batch *b, const pols_ols_params
  * column appended LAST, compute_is_valid_mask for p->null_policy from the NaNs (= nulls) of the scaled columns
  * (src/expressions.rs:201-228; skipped when b->valid is given or b->null_free is set), nulls -> 0 (ex.rs:603, 629, 656, 683),
  * predictions masked by the validity (ex.rs:640-645, 695-700) and un-scaled by 1 / sqrt(w) (ls.py:234-235).  coef has
- * kt = n_features + add_intercept columns; p->initial_state_mean has kt values. */
+ * kt = n_features + add_intercept columns; p->initial_state_mean has kt values.
+ * A column that is exactly zero for a stretch keeps its decayed information, as in the exact recursion, on every route: the
+ * row-parallel forms that truncate a finite half-life's memory extend a tile's carry-in past the stretch ("Silent
+ * columns").  Not handled: near-silent columns (a scale drop by more than ~1e3 within the halo) and collinear stretches (no f64
+ * method matches those).  After a stretch ends, the P-form routes (> 9 features, POLS_RLS_ENGINE=seq) and the reference itself lose
+ * digits for ~25 half-lives of rows (P / ff - k k' r cancels terms of size ff^-stretch). */
 int pols_recursive_least_squares(pols_ctx *ctx, const pols_batch *b, const pols_rls_params *p, pols_out *o);
 
 /* Replaces solve_rolling_ols (src/least_squares.rs:848-1032) + dynamic make_predictions.

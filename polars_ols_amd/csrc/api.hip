@@ -2110,6 +2110,7 @@ int pols_recursive_least_squares(pols_ctx *ctx, const pols_batch *b, const pols_
         if (halo) {
             if ((rc = ensure_tile_seq0(ctx, b, tile_rows, n_tiles, &c.tile_seq0))) return rc;
             c.halo_batches = halo; c.log2ff = std::log2(c.ff); c.ffstep = std::pow(c.ff, (double)(tile_rows - 4));
+            c.fresh_need = (int32_t)std::min<double>(std::ceil(-32.0 / c.log2ff), 256.0 * halo - 4.0);
             // ... and when the rows that matter all lie in the ONE tile in front (H <= 1 024 = a four-wave tile, up to 6 features), that tile's own
             // aggregate is all the carry-in needs: the look-back-one form (k3c_scan.hip MODE 3) -- every tile publishes its aggregate early, picks up
             // its predecessor's behind its own scan, and re-reads nothing.  POLS_RLS_ENGINE=halo keeps the halo form.

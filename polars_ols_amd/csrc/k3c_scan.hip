@@ -206,10 +206,11 @@ __global__ void __launch_bounds__(64) k3c_top_scan_kernel(const K3cArgs a) {
     }
 }
 
-// LOOK-BACK form, fallback: components [Q0, Q1) of the decayed sums over the a.halo_batches 256-row batches in front of the tile that starts at
-// row tbase, re-accumulated by ONE wave; rows before s0 (the sequence's first row) are left out; component q lands in lane q's cv.
+// DEEP carry-in, one wave: components [Q0, Q1) of the decayed sums over the nb 256-row batches in front of the tile that starts at row tbase,
+// re-accumulated row by row; rows before s0 (the sequence's first row) are left out; component q lands in lane q's cv.
 template <typename T, int K, int R, int Q0, int Q1>
-__device__ __forceinline__ void k3c_slow_halo_piece(const K3cArgs &a, const int64_t tbase, const int64_t s0, const int lane, const double ff, double &cv) {
+__device__ __forceinline__ void k3c_slow_halo_piece(const K3cArgs &a, const int64_t tbase, const int64_t s0, const int lane, const double ff, double &cv,
+                                                    const int nb) {
     constexpr int NX = K4N<K>::NX, NP = Q1 - Q0;
     if constexpr (NP > 0) {
         double hacc[NP];
@@ -217,7 +218,7 @@ __device__ __forceinline__ void k3c_slow_halo_piece(const K3cArgs &a, const int6
         for (int q = 0; q < NP; ++q) hacc[q] = 0.0;
         const double f252 = exp2(252.0 * a.log2ff);
 #pragma unroll 1
-        for (int j = a.halo_batches - 1; j >= 0; --j) {
+        for (int j = nb - 1; j >= 0; --j) {
             const int64_t base = tbase - 256 * (int64_t)(j + 1) + lane * R;
 #pragma unroll
             for (int q = 0; q < NP; ++q) hacc[q] *= f252;
@@ -254,6 +255,79 @@ __device__ __forceinline__ void k3c_slow_halo_piece(const K3cArgs &a, const int6
     }
 }
 
+// Lane q of a wave holds state component q: the column whose diagonal entry that is (-1: an off-diagonal entry or a cross product).
+template <int K>
+__device__ __forceinline__ int k3c_diag_col(const int lane) {
+    int c = -1;
+#pragma unroll
+    for (int p = 0; p < K; ++p) c = lane == tri_index<K>(p, p) ? p : c;
+    return c;
+}
+
+// DEEP carry-in, one wave (a column was stale in the truncated window): the 256-row batches in front of the tile at tbase that the carry-in
+// needs -- newest batch first, each column until its first non-zero value (its newest row lies in that batch or after it), then a.fresh_need
+// rows beyond the oldest such batch, so that every column keeps ff^fresh_need <= 2^-32 of its own history.  A column with no non-zero value
+// takes the batches to the sequence's first row s0, or to where ff^rows underflows (1 075 half-lives): its part of the carry-in is the prior's,
+// which the caller adds in closed form.  Wave-uniform.
+template <typename T, int K, int R>
+__device__ int k3c_deep_batches(const K3cArgs &a, const int64_t tbase, const int64_t s0, const int lane) {
+    const int64_t span = (tbase - s0 + 255) / 256;
+    const int64_t ub = (int64_t)ceil(-1075.0 / (256.0 * a.log2ff)) + 1;
+    const int maxb = (int)(span < ub ? span : ub);
+    const int needb = (a.fresh_need + 255) / 256;
+    unsigned found = 0;
+#pragma unroll 1
+    for (int b = 0; b < maxb; ++b) {
+        const int64_t base = tbase - 256 * (int64_t)(b + 1) + lane * R;
+        const int64_t lb = base < 0 ? 0 : base;                                   // (rows before s0 >= 0 are masked below)
+#pragma unroll 1
+        for (int j = 0; j < K; ++j) {
+            if ((found >> j) & 1u) continue;
+            double v[R];
+            k3c_load_run<T, R>(a.x[j], lb, v);
+            bool nz = false;
+#pragma unroll
+            for (int r = 0; r < R; ++r) nz = nz || (base + r >= s0 && v[r] != 0.0);
+            if (__any(nz)) found |= 1u << j;
+        }
+        if (found == (1u << K) - 1u) return b + 1 + needb < maxb ? b + 1 + needb : maxb;
+    }
+    return maxb;
+}
+
+// HALO form: the columns with a non-zero value in rows [fresh0, tbase) (fresh0 >= the sequence's first row), one wave, newest batch first.
+template <typename T, int K, int R>
+__device__ unsigned k3c_fresh_cols(const K3cArgs &a, const int64_t tbase, const int64_t fresh0, const int lane) {
+    unsigned found = 0;
+#pragma unroll 1
+    for (int64_t top = tbase; top > fresh0 && found != (1u << K) - 1u; top -= 256) {
+        const int64_t base = top - 256 + lane * R;
+        const int64_t lb = base < 0 ? 0 : base;
+#pragma unroll 1
+        for (int j = 0; j < K; ++j) {
+            if ((found >> j) & 1u) continue;
+            double v[R];
+            k3c_load_run<T, R>(a.x[j], lb, v);
+            bool nz = false;
+#pragma unroll
+            for (int r = 0; r < R; ++r) nz = nz || (base + r >= fresh0 && v[r] != 0.0);
+            if (__any(nz)) found |= 1u << j;
+        }
+    }
+    return found;
+}
+
+// The prior-free carry-in of the tile at tbase from the batches k3c_deep_batches picks, one wave, a third of the components per sweep.
+template <typename T, int K, int R>
+__device__ __forceinline__ void k3c_deep_halo(const K3cArgs &a, const int64_t tbase, const int64_t s0, const int lane, const double ff, double &cv) {
+    constexpr int NT = K4N<K>::N, P3 = (NT + 2) / 3;
+    const int nb = k3c_deep_batches<T, K, R>(a, tbase, s0, lane);
+    cv = 0.0;
+    k3c_slow_halo_piece<T, K, R, 0, P3>(a, tbase, s0, lane, ff, cv, nb);
+    k3c_slow_halo_piece<T, K, R, P3, 2 * P3>(a, tbase, s0, lane, ff, cv, nb);
+    k3c_slow_halo_piece<T, K, R, 2 * P3, NT>(a, tbase, s0, lane, ff, cv, nb);
+}
+
 // MODE 0 / 1: the two passes of the scan form; 2: the HALO form (step H); 3: the LOOK-BACK-ONE form -- a finite half-life makes tile t's
 // carry-in a function of tile t - 1's LOCAL aggregate alone (no chain), so every tile publishes that aggregate early (step E, before its
 // scan) as self-validating granules and picks its predecessor's up after its own scan; a wave whose predecessor has not published within the
@@ -272,6 +346,7 @@ __global__ void __launch_bounds__(64 * WAVES, WAVES == 4 ? 3 : (K <= 8 ? 2 : 1))
     __shared__ T s_x[MODE >= 1 ? WAVES : 1][R * K][DYN_STAGE_STRIDE];   // (targets and predictions stay in registers)
     __shared__ double s_hagg[MODE >= 2 ? WAVES : 1][NT + 1];   // HALO form: every wave's share of the decayed sums over the rows in front of the tile; LOOK-BACK: every wave's share of the tile's own aggregate
     __shared__ int s_eclosed[MODE == 3 ? WAVES : 1];          // LOOK-BACK: the wave holds a sequence start
+    __shared__ unsigned s_fresh[MODE >= 2 ? WAVES : 1];       // bit j: column j is fresh -- HALO: in the tile's halo (slot 0); LOOK-BACK: in the wave's own rows
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
 #define K3C_STAMP(i) do { if (a.dbg && threadIdx.x == 64 * (WAVES - 1)) a.dbg[t * 8 + (i)] = __builtin_amdgcn_s_memtime(); } while (0)
     int64_t t = blockIdx.x;
@@ -363,6 +438,13 @@ __global__ void __launch_bounds__(64 * WAVES, WAVES == 4 ? 3 : (K <= 8 ? 2 : 1))
 #pragma unroll
             for (int i = 0; i < 16; ++i) hs += tr[lane * 17 + i];
             s_hagg[wv][lane] = hs;
+        }
+        if (wv == WAVES - 1) {
+            // the columns' freshness, when the halo is cut inside the sequence: a non-zero value at or after row t0 - H + fresh_need (one wave,
+            // newest rows first, a column until its first non-zero value -- on a frame without zeros that is one 16-byte load per column and lane)
+            const int64_t fresh0 = tbase - 256 * (int64_t)nbt + a.fresh_need;
+            const unsigned fm = s0 < tbase - 256 * (int64_t)nbt ? k3c_fresh_cols<T, K, R>(a, tbase, fresh0, lane) : (1u << K) - 1u;
+            if (lane == 0) s_fresh[0] = fm;
         }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
         __builtin_amdgcn_wave_barrier();
@@ -460,6 +542,19 @@ __global__ void __launch_bounds__(64 * WAVES, WAVES == 4 ? 3 : (K <= 8 ? 2 : 1))
         }
     }
     const unsigned long long hmask = __ballot(head);
+    if constexpr (MODE == 3) {
+        // the freshness of every column in this tile's rows, for the successor's carry-in: a non-zero value at least a.fresh_need rows into the tile
+        unsigned wfresh = 0;
+        const int lr0 = (wv * 64 + lane) * R;
+#pragma unroll
+        for (int j = 0; j < K; ++j) {
+            bool nz = false;
+#pragma unroll
+            for (int r = 0; r < R; ++r) nz = nz || (lr0 + r >= a.fresh_need && x[r][j] != 0.0);
+            wfresh |= __any(nz) ? 1u << j : 0u;
+        }
+        if (lane == 0) s_fresh[wv] = wfresh;
+    }
     using U4 = __attribute__((ext_vector_type(4))) unsigned;
     [[maybe_unused]] U4 pg = {0u, 0u, 0u, 0u};               // LOOK-BACK: this lane's granule of the predecessor's record
     if constexpr (MODE == 3) if (a.early_publish) {
@@ -511,7 +606,7 @@ __global__ void __launch_bounds__(64 * WAVES, WAVES == 4 ? 3 : (K <= 8 ? 2 : 1))
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
         if (lane == 0) s_eclosed[wv] = hmask != 0;
         __syncthreads();
-        // the record: NT granules {value, tag = epoch << 1 | "holds a sequence start"} of 16 bytes, each written by ONE write-through store and
+        // the record: NT granules {value, tag = epoch << 2 | "the diagonal's column is fresh" << 1 | "holds a sequence start"} of 16 bytes, each written by ONE write-through store and
         // validated by its own tag (no flag, no fence: MI355X_MICROARCH.md, hand-off granules); tile t's granule q at (32 t + q) 16
         const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(a.gran, 0, (int)a.gran_bytes, 0x00020000);
         if (wv == WAVES - 1 && lane < NT) {
@@ -521,7 +616,11 @@ __global__ void __launch_bounds__(64 * WAVES, WAVES == 4 ? 3 : (K <= 8 ? 2 : 1))
                 rec += s_hagg[w2][lane];
                 if (s_eclosed[w2]) { closed = 1; break; }
             }
-            const unsigned long long vb = (unsigned long long)__double_as_longlong(rec), tg = (a.epoch << 1) | closed;
+            unsigned fm = 0;
+            for (int w2 = 0; w2 < WAVES; ++w2) fm |= s_fresh[w2];
+            const int dc = k3c_diag_col<K>(lane);
+            const unsigned long long fb = dc >= 0 && ((fm >> dc) & 1u) ? 2ull : 0ull;
+            const unsigned long long vb = (unsigned long long)__double_as_longlong(rec), tg = (a.epoch << 2) | fb | closed;
             const U4 g = {(unsigned)vb, (unsigned)(vb >> 32), (unsigned)tg, (unsigned)(tg >> 32)};
             __builtin_amdgcn_raw_buffer_store_b128(g, rsrc, (int)((t * 32 + lane) * 16), 0, /*sc1*/ 16);
         }
@@ -588,10 +687,16 @@ __global__ void __launch_bounds__(64 * WAVES, WAVES == 4 ? 3 : (K <= 8 ? 2 : 1))
                 cv = lane == tri_index<K>(p, p) ? pw : cv;
                 if (a.mean0) cv = lane == NX + p ? pw * a.mean0[p] : cv;
             }
+            double hv = 0.0;
             if (lane < NT) {
 #pragma unroll
-                for (int w2 = 0; w2 < WAVES; ++w2) cv += s_hagg[w2][lane];
+                for (int w2 = 0; w2 < WAVES; ++w2) hv += s_hagg[w2][lane];
             }
+            // DEEP carry-in: the halo was cut inside the sequence and left some column stale (no non-zero value in its newest 256 halo_batches -
+            // fresh_need rows): that column's information lies further back -- this wave re-reads the rows as deep as the columns need
+            const int64_t s0 = a.tile_seq0[t];
+            if (s_fresh[0] != (1u << K) - 1u) k3c_deep_halo<T, K, R>(a, tbase, s0, lane, ff, hv);
+            cv += hv;
             cq.v[0] = lane == NT ? 1.0 : cv;
         } else if constexpr (MODE == 3) {
             if (!a.early_publish) {
@@ -605,7 +710,11 @@ __global__ void __launch_bounds__(64 * WAVES, WAVES == 4 ? 3 : (K <= 8 ? 2 : 1))
                     if (s_closed[wv]) { full = eq; tclosed = true; }
                     else full.then(eq, s_agg[wv][NT], lane);
                     if (lane < NT) {
-                        const unsigned long long vb = (unsigned long long)__double_as_longlong(full.v[0]), tg = (a.epoch << 1) | (tclosed ? 1ull : 0ull);
+                        unsigned fm = 0;
+                        for (int w2 = 0; w2 < WAVES; ++w2) fm |= s_fresh[w2];
+                        const int dc = k3c_diag_col<K>(lane);
+                        const unsigned long long fb = dc >= 0 && ((fm >> dc) & 1u) ? 2ull : 0ull;
+                        const unsigned long long vb = (unsigned long long)__double_as_longlong(full.v[0]), tg = (a.epoch << 2) | fb | (tclosed ? 1ull : 0ull);
                         const U4 g = {(unsigned)vb, (unsigned)(vb >> 32), (unsigned)tg, (unsigned)(tg >> 32)};
                         __builtin_amdgcn_raw_buffer_store_b128(g, rsrc, (int)((t * 32 + lane) * 16), 0, /*sc1*/ 16);
                     }
@@ -629,7 +738,7 @@ __global__ void __launch_bounds__(64 * WAVES, WAVES == 4 ? 3 : (K <= 8 ? 2 : 1))
                 const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(a.gran, 0, (int)a.gran_bytes, 0x00020000);
                 for (int spins = 0;; ++spins) {
                     const unsigned long long tg = ((unsigned long long)pg[3] << 32) | pg[2];
-                    if (__all(lane >= NT || (tg >> 1) == a.epoch)) { got = true; break; }
+                    if (__all(lane >= NT || (tg >> 2) == a.epoch)) { got = true; break; }
                     if (spins >= a.spin_limit) break;
                     __builtin_amdgcn_s_sleep(16);
                     if (lane < NT) pg = __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)(((t - 1) * 32 + lane) * 16), 0, /*sc1*/ 16);
@@ -639,14 +748,42 @@ __global__ void __launch_bounds__(64 * WAVES, WAVES == 4 ? 3 : (K <= 8 ? 2 : 1))
                     pclosed = (__builtin_amdgcn_readfirstlane((int)pg[2]) & 1) != 0;
                 }
             }
+            if (t > 0 && got && !pclosed) {
+                // DEEP carry-in: a column that is stale in tile t - 1 (no non-zero value a.fresh_need rows into it) has its information further back.
+                // Walk the predecessors' records, tile t - m weighted ff^(1 024 (m - 1)), until every column has been fresh in a walked tile, a
+                // record holds a sequence start, or the weight underflows; a record not published within the spin limit: re-read the rows.
+                const int dc = k3c_diag_col<K>(lane);
+                const unsigned long long dmask = __ballot(dc >= 0);
+                unsigned long long sat = __ballot(dc >= 0 && ((pg[2] >> 1) & 1u));
+                if (sat != dmask) {
+                    const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(a.gran, 0, (int)a.gran_bytes, 0x00020000);
+#pragma unroll 1
+                    for (int64_t m = 2; m <= t; ++m) {
+                        const double w = exp2((double)(1024 * (m - 1)) * a.log2ff);
+                        if (w == 0.0) break;
+                        U4 g = {0u, 0u, 0u, 0u};
+                        bool pub = false;
+                        for (int spins = 0;; ++spins) {
+                            if (lane < NT) g = __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)(((t - m) * 32 + lane) * 16), 0, /*sc1*/ 16);
+                            const unsigned long long tg = ((unsigned long long)g[3] << 32) | g[2];
+                            if (__all(lane >= NT || (tg >> 2) == a.epoch)) { pub = true; break; }
+                            if (spins >= a.spin_limit) break;
+                            __builtin_amdgcn_s_sleep(16);
+                        }
+                        if (!pub) { got = false; break; }
+                        if (lane < NT) cv = fma(w, __longlong_as_double((long long)(((unsigned long long)g[1] << 32) | g[0])), cv);
+                        if ((__builtin_amdgcn_readfirstlane((int)g[2]) & 1) != 0) { pclosed = true; break; }
+                        sat |= __ballot(dc >= 0 && ((g[2] >> 1) & 1u));
+                        if (sat == dmask) break;
+                    }
+                    if (!got) pclosed = false;
+                }
+            }
             if (!got) {
-                // the predecessor has not published (not dispatched yet?): this wave re-accumulates the halo itself -- a row at a time (8-byte
-                // loads) and a third of the components per sweep over the rows, because the registers hold the scan's results.  The slow way,
-                // taken under no dispatch order seen so far.
-                constexpr int P3 = (NT + 2) / 3;
-                k3c_slow_halo_piece<T, K, R, 0, P3>(a, tbase, s0, lane, ff, cv);
-                k3c_slow_halo_piece<T, K, R, P3, 2 * P3>(a, tbase, s0, lane, ff, cv);
-                k3c_slow_halo_piece<T, K, R, 2 * P3, NT>(a, tbase, s0, lane, ff, cv);
+                // the predecessor has not published (not dispatched yet?): this wave re-accumulates the carry-in itself from the rows -- as deep as its
+                // columns need (k3c_deep_batches), a row at a time (8-byte loads) and a third of the components per sweep over the rows, because the
+                // registers hold the scan's results.  The slow way, taken under no dispatch order seen so far.
+                k3c_deep_halo<T, K, R>(a, tbase, s0, lane, ff, cv);
             }
             cq.v[0] = lane == NT ? 1.0 : (pclosed ? cv : cv + pv);
         } else if (a.tile_row0) cq.identity(lane);                               // packed: the tile starts (within a run) at a sequence start

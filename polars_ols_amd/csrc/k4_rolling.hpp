@@ -128,6 +128,10 @@ struct K3cArgs {
     unsigned long long epoch;          // this launch's tag (never 0, never reused on this area)
     int32_t spin_limit;                // polls before a wave gives up on its predecessor and re-accumulates the halo itself
     int32_t early_publish;             // 1: the record is computed and published before the tile's scan (step E); 0: it falls out of the scan (A/B)
+    // SILENT columns (both truncated forms): a column is "fresh" when it has a non-zero value in the newest rows of the carry window, at least
+    // fresh_need rows after its oldest row -- its dropped part is then at most ff^fresh_need <= 2^-32 of what the window keeps.  A tile whose
+    // window leaves a column stale extends its carry-in further back (k3c_scan.hip, DEEP carry-in).
+    int32_t fresh_need;                // ceil(32 half_life), at most 256 halo_batches - 4
 };
 constexpr int K3C_HALO_KMAX = 9;      // (one state component per lane in the cross-wave steps)
 constexpr int K3C_HALO_MAX_BATCHES = 8;
