@@ -326,6 +326,60 @@ void pols_cluster_params_default(pols_cluster_params *c);
 int pols_least_squares_statistics_cluster(pols_ctx *ctx, const pols_batch *b, const pols_ols_params *p, const pols_cluster_params *cl,
                                           pols_out *out, const pols_stats_out *stats);
 
+/* Per-row influence diagnostics and prediction intervals (no reference counterpart; statsmodels' OLSInfluence and
+ * get_prediction().summary_frame()).  Per group g, on the rows F_g that pols_least_squares_statistics_robust fits -- the same null-policy
+ * filtering / zero-filling, sqrt(w) scaling (a null weight acting as 1e-24) and ones column last -- with x~_i = sqrt(w_i) x_i,
+ * y~_i = sqrt(w_i) y_i, p = n_features + intercept, A = X~'X~ + alpha I over F_g, b = A^-1 X~'y~ (the side-car coefficients of the
+ * statistics entries), n = |F_g| and their df (n - p, or n - trace A^-1 when alpha > 0):
+ *   sigma2 (group)     sum_{i in F_g} e~_i^2 / df  with  e~_i = y~_i - x~_i'b
+ *   df, t_crit (group) df as above; t_crit = the (1 - (1 - level) / 2) quantile of Student-t with df degrees of freedom
+ *   leverage           h_i = x~_i' A^-1 x~_i
+ *   student_internal   r_i = e~_i / sqrt(sigma2 (1 - h_i))
+ *   student_external   t_i = r_i sqrt((df - 1) / (df - r_i^2)); NaN when df - 1 <= 0 or df - r_i^2 <= 0
+ *   cooks_d            r_i^2 h_i / (p (1 - h_i))
+ *   dffits             t_i sqrt(h_i / (1 - h_i))
+ *   se_mean            sqrt(sigma2 h_i / w_i): the standard error of x_i'b in the target's units
+ *   se_obs             sqrt(sigma2 (1 + h_i) / w_i): statsmodels' WLS convention, var_resid = scale / weights
+ *   mean_lo / mean_hi  x_i'b -+ t_crit se_mean          obs_lo / obs_hi   x_i'b -+ t_crit se_obs      (x_i'b un-scaled)
+ * High leverage: a fitted row with 1 - h_i < 1e-10 has NaN in student_internal, student_external, cooks_d and dffits; its leverage,
+ * standard errors and intervals are written, the rest of its group is unaffected.
+ * Rows outside the fit (the forecasting idiom: a null target under a drop-family policy): a row of the group that the policy left out
+ * of F_g is scored as a NEW OBSERVATION when every feature is non-null after the policy's own fill and its weight is non-null --
+ * leverage (the same quadratic form, not bounded by 1), se_mean, se_obs and the four interval ends; its four influence measures are
+ * NaN.  With a null feature or weight left it is NaN everywhere.  Under "ignore" nothing is masked: NaNs propagate arithmetically.
+ * Penalised / constrained fits: like the statistics entries everything rests on the side-car b whatever the dispatcher solved;
+ * l1_ratio / positive / solve_method affect only out->coef / pred / resid.
+ * A group whose factorisation failed or whose df <= 0 has NaN in every per-row output and in sigma2 / t_crit; out->status is what
+ * pols_least_squares_statistics writes (POLS_GROUP_BAD_DOF included), as are out->coef / pred / resid, bit for bit.
+ * f32 batches: the side-car b takes one step of iterative refinement in f64 first (the Gram matrix of an f32 frame is summed in f32
+ * pieces; a row's residual is a difference that keeps no digits of such a b where it nearly vanishes); f64 batches use it as it is.
+ * Everything is computed in f64; per-row arrays are stored in the batch dtype, per-group arrays as f64; all live where b->mem says and
+ * any may be NULL.  Sums run in a fixed order without atomics: two runs are bit-identical.  Parameter validation as the robust entry
+ * (null policy range, a validity mask only under a drop-family policy, up to 31 columns incl. the intercept, else
+ * POLS_ERR_UNSUPPORTED); a level outside (0, 1) is POLS_ERR_INVALID. */
+typedef struct pols_influence_params {
+    double level;             /* 0 < level < 1, default 0.95 */
+} pols_influence_params;
+
+/* level = 0.95 */
+void pols_influence_params_default(pols_influence_params *q);
+
+typedef struct pols_influence_out {
+    void *leverage, *student_internal, *student_external, *cooks_d, *dffits,
+         *se_mean, *se_obs, *mean_lo, *mean_hi, *obs_lo, *obs_hi;   /* n_rows, batch dtype */
+    double *sigma2, *df, *t_crit;                                   /* n_groups, f64 */
+} pols_influence_out;
+
+int pols_least_squares_influence(pols_ctx *ctx, const pols_batch *b, const pols_ols_params *p, const pols_influence_params *q,
+                                 pols_out *out, const pols_influence_out *infl);
+
+/* the per-row fields of pols_influence_out, in its order: bit i of a field mask names the i-th pointer */
+enum {
+    POLS_INFL_LEVERAGE = 1 << 0, POLS_INFL_STUDENT_INTERNAL = 1 << 1, POLS_INFL_STUDENT_EXTERNAL = 1 << 2, POLS_INFL_COOKS_D = 1 << 3,
+    POLS_INFL_DFFITS = 1 << 4, POLS_INFL_SE_MEAN = 1 << 5, POLS_INFL_SE_OBS = 1 << 6, POLS_INFL_MEAN_LO = 1 << 7,
+    POLS_INFL_MEAN_HI = 1 << 8, POLS_INFL_OBS_LO = 1 << 9, POLS_INFL_OBS_HI = 1 << 10, POLS_INFL_ALL = (1 << 11) - 1
+};
+
 /* ---- group-key ingestion: `.over(key)` / `group_by(key)` ------------------------------------------------------------
  * The reference's plugin functions never see a key column: Polars partitions the frame on the host and calls them once per
  * group (README.md:19, README.md:57 and :91 `.over("group")`, tests/test_ols.py:110, :384, :860).  The batched entries
@@ -439,6 +493,14 @@ int pols_least_squares_statistics_cluster_arrow(pols_ctx *ctx, const pols_arrow_
                                                 int64_t n_groups, int32_t add_intercept, const pols_ols_params *p,
                                                 const pols_cluster_params *cl, const pols_arrow_column *ids, int32_t n_ids,
                                                 struct ArrowArray *out, struct ArrowSchema *out_schema);
+/* pols_least_squares_influence over Arrow columns: a struct array "influence" of n_rows rows whose fields are the per-row arrays named
+ * in `fields` (a mask of POLS_INFL_* bits; 0 = all), in pols_influence_out's order and under its names, Float32 when every input is
+ * Float32, else Float64; a null stands where the plain entry writes NaN for "not defined". */
+int pols_least_squares_influence_arrow(pols_ctx *ctx, const pols_arrow_column *target, const pols_arrow_column *features,
+                                       int32_t n_features, const pols_arrow_column *weights, const int64_t *group_offsets,
+                                       int64_t n_groups, int32_t add_intercept, const pols_ols_params *p,
+                                       const pols_influence_params *q, uint32_t fields, struct ArrowArray *out,
+                                       struct ArrowSchema *out_schema);
 /* multi_target_least_squares (ex.rs:511-591): `targets` is the STRUCT Series of inputs[0] (format "+s", one numeric field per
  * target; a null struct row is a null in every field); out: a struct array "predictions" of n_rows rows with the targets' field
  * names (multi_target_struct_dtype, :511-519), NaN -> null.  Residuals are the caller's `target - predictions`

@@ -92,6 +92,20 @@ class ClusterParams(C.Structure):     # pols_cluster_params
     _fields_ = [("cov_type", C.c_int32), ("use_correction", C.c_int32), ("ids", C.c_void_p * 2), ("n_clusters", C.c_void_p)]
 
 
+class InfluenceParams(C.Structure):   # pols_influence_params
+    _fields_ = [("level", C.c_double)]
+
+
+# per-row outputs of pols_influence_out, in the struct's order (bit i of the Arrow entry's field mask), then its per-group outputs
+INFLUENCE_FIELDS = ("leverage", "student_internal", "student_external", "cooks_d", "dffits", "se_mean", "se_obs",
+                    "mean_lo", "mean_hi", "obs_lo", "obs_hi")
+INFLUENCE_GROUP_FIELDS = ("sigma2", "df", "t_crit")
+
+
+class InfluenceOut(C.Structure):      # pols_influence_out
+    _fields_ = [(n, C.c_void_p) for n in INFLUENCE_FIELDS + INFLUENCE_GROUP_FIELDS]
+
+
 EXPORTS = [
     "pols_device_count", "pols_version", "pols_last_error", "pols_create", "pols_destroy", "pols_set_stream",
     "pols_use_private_stream",
@@ -108,6 +122,7 @@ EXPORTS = [
     "pols_predict_arrow", "pols_least_squares_sharded",
     "pols_cov_params_default", "pols_least_squares_statistics_robust", "pols_least_squares_statistics_robust_arrow",
     "pols_cluster_params_default", "pols_least_squares_statistics_cluster", "pols_least_squares_statistics_cluster_arrow",
+    "pols_influence_params_default", "pols_least_squares_influence", "pols_least_squares_influence_arrow",
 ]
 # measurement aids (include/pols_mi355x_debug.h): not part of the reference interface
 DEBUG_EXPORTS = ["pols_timing_enable", "pols_timing_collect", "pols_last_kernel_name", "pols_stream_probe", "pols_stream_probe_ex"]
@@ -168,6 +183,9 @@ def lib() -> C.CDLL:
         L.pols_cluster_params_default.argtypes, L.pols_cluster_params_default.restype = [C.POINTER(ClusterParams)], None
         L.pols_least_squares_statistics_cluster.argtypes = [C.c_void_p, C.POINTER(Batch), C.POINTER(OlsParams), C.POINTER(ClusterParams),
                                                             C.POINTER(Out), C.POINTER(StatsOut)]
+        L.pols_influence_params_default.argtypes, L.pols_influence_params_default.restype = [C.POINTER(InfluenceParams)], None
+        L.pols_least_squares_influence.argtypes = [C.c_void_p, C.POINTER(Batch), C.POINTER(OlsParams), C.POINTER(InfluenceParams),
+                                                   C.POINTER(Out), C.POINTER(InfluenceOut)]
         L.pols_layout_create.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.POINTER(C.c_void_p)]
         L.pols_layout_destroy.argtypes = [C.c_void_p]
         L.pols_layout_destroy.restype = None
@@ -187,6 +205,8 @@ def lib() -> C.CDLL:
         L.pols_least_squares_statistics_robust_arrow.argtypes = _common + [C.POINTER(OlsParams), C.POINTER(CovParams), C.c_void_p, C.c_void_p]
         L.pols_least_squares_statistics_cluster_arrow.argtypes = _common + [C.POINTER(OlsParams), C.POINTER(ClusterParams), _ac, C.c_int32,
                                                                             C.c_void_p, C.c_void_p]
+        L.pols_least_squares_influence_arrow.argtypes = _common + [C.POINTER(OlsParams), C.POINTER(InfluenceParams), C.c_uint32,
+                                                                   C.c_void_p, C.c_void_p]
         L.pols_multi_target_least_squares_arrow.argtypes = _common + [C.POINTER(OlsParams), C.c_void_p, C.c_void_p]
         L.pols_recursive_least_squares_arrow.argtypes = _common + [C.POINTER(RlsParams), C.c_int32, C.c_void_p, C.c_void_p]
         L.pols_rolling_least_squares_arrow.argtypes = _common + [C.POINTER(RollingParams), C.c_int32, C.c_void_p, C.c_void_p]

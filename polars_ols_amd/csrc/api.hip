@@ -19,6 +19,7 @@
 #include "k7_stats.hpp"
 #include "k7r_robust.hpp"
 #include "k7c_cluster.hpp"
+#include "k7i_influence.hpp"
 #include "k8_wide.hpp"
 #include "dyn_prep.hpp"
 
@@ -1535,12 +1536,60 @@ static int cluster_device_ids(pols_ctx *ctx, const pols_batch *b, const pols_clu
     return POLS_OK;
 }
 
+// What pols_least_squares_influence adds to a statistics call (K7i, k7i_influence.hip).  The group stage runs where the fit runs (on the
+// compacted frame under a null policy), the row pass where the ORIGINAL rows are: the level of statistics_body that compacted them.
+struct InflCall {
+    const pols_influence_params *q;
+    const pols_influence_out *io;
+    bool rows_by_caller = false;            // set by the compaction level: it runs the row pass itself, with the validity bytes
+    double *prep = nullptr, *grp = nullptr; // the group stage's tables (Work::InflPrep; Work::InflGroup behind the RSS)
+};
+
+// The row pass of K7i over the rows of `b` as staged in `st`, then the per-group outputs; valid == nullptr: every row was fitted.
+static int influence_rows(pols_ctx *ctx, const pols_batch *b, const Staged &st, const int64_t *d_offs, const SegTables &sg, const uint8_t *valid,
+                          int zero_fill, const InflCall &ic) {
+    const bool host = b->mem == POLS_MEM_HOST;
+    const size_t G = (size_t)b->n_groups, N = (size_t)b->n_rows, sz = dtype_size(b->dtype), colb = round256(sz * std::max<size_t>(N, 1));
+    const pols_influence_out *io = ic.io;
+    void *const user[K7I_NOUT] = {io->leverage, io->student_internal, io->student_external, io->cooks_d, io->dffits, io->se_mean,
+                                  io->se_obs, io->mean_lo, io->mean_hi, io->obs_lo, io->obs_hi};
+    int rc, n_out = 0;
+    for (int i = 0; i < K7I_NOUT; ++i) n_out += user[i] ? 1 : 0;
+    InflArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.y = st.y; a.w = st.w;
+    for (int j = 0; j < b->n_features; ++j) a.x[j] = st.x[(size_t)j];
+    a.offs = d_offs; a.n_groups = b->n_groups; a.n_rows = b->n_rows;
+    if (sg.n_seg > 0) { a.seg_offs = sg.offs; a.seg_map = sg.map; a.n_seg = sg.n_seg; }
+    a.valid = valid; a.zero_fill = zero_fill;
+    a.k_user = b->n_features; a.kt = b->n_features + (b->add_intercept ? 1 : 0);
+    a.prep = ic.prep; a.grp = ic.grp;
+    void *rows = nullptr;
+    if (host && n_out && (rc = ensure_scratch(ctx, Work::InflRows, colb * (size_t)n_out, &rows))) return rc;
+    char *q = static_cast<char *>(rows);
+    for (int i = 0; i < K7I_NOUT; ++i) {
+        if (!user[i]) continue;
+        if (!host && !aligned16(user[i])) return fail(POLS_ERR_INVALID, "device columns must be 16-byte aligned");
+        a.out[i] = host ? static_cast<void *>(q) : user[i];
+        q += host ? colb : 0;
+    }
+    if ((rc = k7i_rows_launch(ctx, b->dtype, a))) return rc;
+    if (host && N)
+        for (int i = 0; i < K7I_NOUT; ++i)
+            if (user[i]) POLS_HIP(hipMemcpyAsync(user[i], a.out[i], sz * N, hipMemcpyDeviceToHost, ctx->stream));
+    double *const gu[3] = {io->sigma2, io->df, io->t_crit};
+    for (int i = 0; i < 3; ++i)
+        if (gu[i]) POLS_HIP(hipMemcpyAsync(gu[i], ic.grp + (size_t)i * G, sizeof(double) * G, host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, ctx->stream));
+    return POLS_OK;
+}
+
 // The body of pols_least_squares_statistics and of its robust and cluster twins: cov == cl == nullptr is the non-robust entry; with
 // cov (HC0 .. HAC, validated by pols_least_squares_statistics_robust, at most K7_KMAX columns) K7 still writes r2 / mae / mse and the
 // status words and K7r (k7r_robust.hip) the standard errors, t- and p-values; with cl (validated by
-// pols_least_squares_statistics_cluster) K7c (k7c_cluster.hip) writes them.
+// pols_least_squares_statistics_cluster) K7c (k7c_cluster.hip) writes them.  With infl (pols_least_squares_influence: cov == cl == nullptr,
+// at most K7_KMAX columns) K7 also leaves the side-car RSS, and K7i (k7i_influence.hip) writes the per-row diagnostics.
 static int statistics_body(pols_ctx *ctx, const pols_batch *b, const pols_ols_params *p, const pols_cov_params *cov,
-                           const pols_cluster_params *cl, pols_out *o, const pols_stats_out *s) {
+                           const pols_cluster_params *cl, pols_out *o, const pols_stats_out *s, InflCall *infl = nullptr) {
     int rc = check_ctx(ctx);
     if (rc) return rc;
     if ((rc = check_batch(b, o, K8_KMAX))) return rc;
@@ -1584,7 +1633,21 @@ static int statistics_body(pols_ctx *ctx, const pols_batch *b, const pols_ols_pa
             }
         }
         const pols_cluster_params *clc = cl ? &cc : nullptr;
-        if (b->mem == POLS_MEM_DEVICE) return statistics_body(ctx, &c.bb, &pp, cov, clc, o, s);
+        if (infl) infl->rows_by_caller = true;
+        // the influence row pass: over the ORIGINAL rows (c.st), the compaction's validity bytes telling the fitted rows from the others
+        auto rows_of_frame = [&]() -> int {
+            const int64_t *d_offs = nullptr;
+            int64_t mr = 0;
+            int rc2 = upload_offsets(ctx, b->group_offsets, b->n_groups, &d_offs, &mr, b->offsets_generation);   // (the fit uploaded the compacted ones)
+            if (rc2) return rc2;
+            SegTables sgf;
+            if ((rc2 = ensure_segments(ctx, b, mr, 0, &sgf))) return rc2;
+            return influence_rows(ctx, b, c.st, d_offs, sgf, c.vbytes, c.ra.zero_fill, *infl);
+        };
+        if (b->mem == POLS_MEM_DEVICE) {
+            if ((rc = statistics_body(ctx, &c.bb, &pp, cov, clc, o, s, infl))) return rc;
+            return infl ? rows_of_frame() : POLS_OK;
+        }
         const int kt = b->n_features + (b->add_intercept ? 1 : 0);
         const size_t coefb = round256(sz * G * kt), statb = round256(sizeof(int32_t) * G), vecb = round256(sizeof(double) * G),
                      matb = round256(sizeof(double) * G * kt);
@@ -1601,7 +1664,8 @@ static int statistics_body(pols_ctx *ctx, const pols_batch *b, const pols_ols_pa
         for (int i = 0; i < 6; ++i) { dev[i] = user[i] ? reinterpret_cast<double *>(q) : nullptr; q += i < 3 ? vecb : matb; }
         pols_stats_out sd;
         sd.r2 = dev[0]; sd.mae = dev[1]; sd.mse = dev[2]; sd.std_err = dev[3]; sd.t_values = dev[4]; sd.p_values = dev[5];
-        if ((rc = statistics_body(ctx, &c.bb, &pp, cov, clc, &od, &sd))) return rc;
+        if ((rc = statistics_body(ctx, &c.bb, &pp, cov, clc, &od, &sd, infl))) return rc;
+        if (infl && (rc = rows_of_frame())) return rc;
         if (cl && cl->n_clusters)
             POLS_HIP(hipMemcpyAsync(cl->n_clusters, cc.n_clusters, sizeof(int64_t) * G * (cl->cov_type == POLS_COV_CLUSTER2 ? 2 : 1),
                                     hipMemcpyDeviceToHost, ctx->stream));
@@ -1726,6 +1790,16 @@ static int statistics_body(pols_ctx *ctx, const pols_batch *b, const pols_ols_pa
         q += (i < 3) ? vecb : matb;
     }
     sa.r2 = dev[0]; sa.mae = dev[1]; sa.mse = dev[2]; sa.se = dev[3]; sa.tv = dev[4]; sa.pv = dev[5];
+    if (infl) {
+        // K7 leaves the side-car RSS of every group (StatsArgs::rss), K7r's prepare launch A^-1 / b / trace / ok in K7i's own table
+        void *ip = nullptr, *ig = nullptr;
+        if ((rc = ensure_scratch(ctx, Work::InflPrep, round256(sizeof(double) * G * k7r_prep_stride(kt)), &ip))) return rc;
+        const size_t n_items = sa.seg_offs ? (size_t)sa.n_seg : G;   // (f32 batches: the refinement's X~'e~ per segment / group behind the rest)
+        if ((rc = ensure_scratch(ctx, Work::InflGroup, round256(sizeof(double) * (G * 5 + (b->dtype == POLS_F32 ? n_items * (size_t)kt : 0))), &ig))) return rc;
+        sa.rss = static_cast<double *>(ig);
+        infl->prep = static_cast<double *>(ip);
+        infl->grp = static_cast<double *>(ig) + G;
+    }
     if (cov) {
         // robust: K7 keeps r2 / mae / mse / status, K7r writes the standard errors, t- and p-values (its own buffers: sa's segment
         // tables are the frame's cached ones, the partial sums of K7 and K7r live apart)
@@ -1767,6 +1841,31 @@ static int statistics_body(pols_ctx *ctx, const pols_batch *b, const pols_ols_pa
         if (host && cl->n_clusters)
             POLS_HIP(hipMemcpyAsync(cl->n_clusters, ca.n_clusters, sizeof(int64_t) * G * (size_t)ca.ways, hipMemcpyDeviceToHost, ctx->stream));
     } else if ((rc = k7_stats_launch(ctx, b->dtype, sa))) return rc;
+    if (infl) {
+        RobustArgs ra;
+        std::memset(&ra, 0, sizeof(ra));
+        ra.s = sa;
+        ra.prep = infl->prep;
+        if ((rc = k7r_prepare_launch(ctx, b->dtype, ra))) return rc;
+        InflGroupArgs ga;
+        std::memset(&ga, 0, sizeof(ga));
+        if (b->dtype == POLS_F32) {
+            // the Gram matrix of an f32 batch carries f32-sized errors: one step of iterative refinement of b in f64 (k7i_influence.hip)
+            ra.part = infl->grp + 4 * G;
+            if ((rc = k7i_refine_launch(ctx, b->dtype, ra))) return rc;
+            ga.xe = ra.part;
+            ga.seg_first = sa.seg_offs ? sa.seg_first : nullptr;
+        }
+        ga.offs = info.d_offs; ga.n_groups = b->n_groups; ga.kt = kt;
+        ga.lambda = p->alpha; ga.level = infl->q->level;
+        ga.prep = infl->prep; ga.rss = sa.rss; ga.grp = infl->grp;
+        if ((rc = k7i_group_launch(ctx, ga))) return rc;
+        if (!infl->rows_by_caller) {
+            SegTables sgi;
+            sgi.offs = sa.seg_offs; sgi.map = sa.seg_map; sgi.first = sa.seg_first; sgi.n_seg = sa.n_seg;
+            if ((rc = influence_rows(ctx, b, info.st, info.d_offs, sgi, nullptr, 0, *infl))) return rc;
+        }
+    }
     if (!host) return POLS_OK;
     for (int i = 0; i < 6; ++i)
         if (user[i])
@@ -1802,6 +1901,25 @@ int pols_least_squares_statistics_robust(pols_ctx *ctx, const pols_batch *b, con
     if (kt > K7_KMAX)
         return fail(POLS_ERR_UNSUPPORTED, "robust statistics: %d features (incl. intercept) > %d; wider frames have only the non-robust form", kt, K7_KMAX);
     return statistics_body(ctx, b, p, cov, nullptr, o, s);
+}
+
+void pols_influence_params_default(pols_influence_params *q) {
+    if (!q) return;
+    q->level = 0.95;
+}
+
+int pols_least_squares_influence(pols_ctx *ctx, const pols_batch *b, const pols_ols_params *p, const pols_influence_params *q,
+                                 pols_out *o, const pols_influence_out *infl) {
+    if (!q || !infl) return fail(POLS_ERR_INVALID, "influence params / outputs are NULL");
+    if (!(q->level > 0.0 && q->level < 1.0)) return fail(POLS_ERR_INVALID, "influence: level %g outside (0, 1)", q->level);
+    if (!b) return fail(POLS_ERR_INVALID, "batch is NULL");
+    const int kt = b->n_features + (b->add_intercept ? 1 : 0);
+    if (kt > K7_KMAX)
+        return fail(POLS_ERR_UNSUPPORTED, "influence: %d features (incl. intercept) > %d; wider frames have only the statistics", kt, K7_KMAX);
+    pols_stats_out none;
+    std::memset(&none, 0, sizeof(none));
+    InflCall ic{q, infl};
+    return statistics_body(ctx, b, p, nullptr, nullptr, o, &none, &ic);
 }
 
 void pols_cluster_params_default(pols_cluster_params *c) {

@@ -684,6 +684,44 @@ static int arrow_statistics(pols_ctx *ctx, const ColView &target, const std::vec
     return POLS_OK;
 }
 
+// ---- pols_least_squares_influence: a struct of the requested per-row arrays, NaN -> null
+template <typename T>
+static int arrow_influence(pols_ctx *ctx, const ColView &target, const std::vector<ColView> &feat, const ColView *weights,
+                           const int64_t *group_offsets, int64_t n_groups, int32_t add_intercept, const pols_ols_params *p,
+                           const pols_influence_params *iq, uint32_t fields, ArrowArray *out, ArrowSchema *out_schema) {
+    static const char *const field_names[11] = {"leverage", "student_internal", "student_external", "cooks_d", "dffits", "se_mean",
+                                                "se_obs", "mean_lo", "mean_hi", "obs_lo", "obs_hi"};
+    const int64_t n_rows = target.rows();
+    const size_t colb = round256(sizeof(T) * (size_t)std::max<int64_t>(n_rows, 1));
+    int n_out = 0;
+    for (int i = 0; i < 11; ++i) n_out += (fields >> i) & 1u;
+    Ingested<T> in;
+    int rc = ingest_all<T>(ctx, {target}, feat, weights, n_rows, colb * (size_t)n_out + export_scratch_bytes(n_rows, sizeof(T)), &in);
+    if (rc) return rc;
+    char *q = in.free_area;
+    void *cols_out[11];
+    std::vector<std::pair<const T *, int64_t>> cols;
+    std::vector<std::string> names;
+    for (int i = 0; i < 11; ++i) {
+        cols_out[i] = nullptr;
+        if (!((fields >> i) & 1u)) continue;
+        cols_out[i] = q; q += colb;
+        cols.push_back({reinterpret_cast<const T *>(cols_out[i]), (int64_t)1});
+        names.push_back(field_names[i]);
+    }
+    pols_influence_out io;
+    std::memset(&io, 0, sizeof(io));
+    io.leverage = cols_out[0]; io.student_internal = cols_out[1]; io.student_external = cols_out[2]; io.cooks_d = cols_out[3];
+    io.dffits = cols_out[4]; io.se_mean = cols_out[5]; io.se_obs = cols_out[6]; io.mean_lo = cols_out[7]; io.mean_hi = cols_out[8];
+    io.obs_lo = cols_out[9]; io.obs_hi = cols_out[10];
+    pols_batch b;
+    fill_batch(&b, in, n_rows, group_offsets, n_groups, add_intercept);
+    pols_out o;
+    std::memset(&o, 0, sizeof(o));
+    if ((rc = pols_least_squares_influence(ctx, &b, p, iq, &o, &io))) return rc;
+    return export_struct<T>(ctx, cols, names, n_rows, true, "influence", q, out, out_schema);
+}
+
 }  // namespace pols
 
 using namespace pols;
@@ -752,6 +790,22 @@ int pols_least_squares_statistics_robust_arrow(pols_ctx *ctx, const pols_arrow_c
     const ColView *w = weights ? &cv.wv : nullptr;
     if (cv.all_f32) return arrow_statistics<float>(ctx, cv.target, cv.feat, w, group_offsets, n_groups, add_intercept, p, cov, nullptr, out, out_schema);
     return arrow_statistics<double>(ctx, cv.target, cv.feat, w, group_offsets, n_groups, add_intercept, p, cov, nullptr, out, out_schema);
+}
+
+int pols_least_squares_influence_arrow(pols_ctx *ctx, const pols_arrow_column *target, const pols_arrow_column *features,
+                                       int32_t n_features, const pols_arrow_column *weights, const int64_t *group_offsets,
+                                       int64_t n_groups, int32_t add_intercept, const pols_ols_params *p,
+                                       const pols_influence_params *q, uint32_t fields, struct ArrowArray *out,
+                                       struct ArrowSchema *out_schema) {
+    if (!q) return fail(POLS_ERR_INVALID, "influence params are NULL");
+    if (fields & ~(uint32_t)POLS_INFL_ALL) return fail(POLS_ERR_INVALID, "influence: unknown field bits 0x%x", fields);
+    if (fields == 0) fields = POLS_INFL_ALL;
+    CommonViews cv;
+    int rc = common_views(ctx, target, features, n_features, weights, &group_offsets, &n_groups, add_intercept, POLS_MAX_FEATURES_STATISTICS, p, out, out_schema, &cv);
+    if (rc) return rc;
+    const ColView *w = weights ? &cv.wv : nullptr;
+    if (cv.all_f32) return arrow_influence<float>(ctx, cv.target, cv.feat, w, group_offsets, n_groups, add_intercept, p, q, fields, out, out_schema);
+    return arrow_influence<double>(ctx, cv.target, cv.feat, w, group_offsets, n_groups, add_intercept, p, q, fields, out, out_schema);
 }
 
 // an integer id column (any of l L i I s S c C) as int64 on the host; a null id is an error (nulls are rejected, not dropped)

@@ -74,6 +74,9 @@ enum class Work : int {
     ClusterSort,    // cluster statistics (K7c): radix keys and values, row -> group, key probes, rocPRIM temporary storage
     ClusterOrder,   // cluster statistics (K7c): position -> row of the clustering being scored
     ClusterCounts,  // cluster statistics (K7c): cluster counts of a host batch before they go home
+    InflPrep,       // influence diagnostics (K7i): A^-1, coefficients, trace, ok per group (k7r_prepare_launch's layout)
+    InflGroup,      // influence diagnostics (K7i): side-car RSS, then sigma2 / df / t_crit / usable per group, then (f32) X'e per segment / group
+    InflRows,       // influence diagnostics (K7i): per-row outputs of a HOST batch before they go home
     Count
 };
 

@@ -77,6 +77,7 @@ __global__ void __launch_bounds__(256) k7_stats_kernel(const StatsArgs a) {
         if (a.mae) a.mae[g] = acc[1] / nn;
         if (a.r2) a.r2[g] = 1.0 - acc[0] / acc[2];
         if (a.status && ok && !(df > 0.0)) a.status[g] = POLS_GROUP_BAD_DOF;
+        if (a.rss) a.rss[g] = acc[3];
     }
     if (tid < kt) {
         const double nanv = __longlong_as_double(0x7ff8000000000000LL);
@@ -162,6 +163,7 @@ __global__ void __launch_bounds__(64) k7_finish_kernel(const StatsArgs a) {
         if (a.mae) a.mae[g] = acc[3] / nn;
         if (a.r2) a.r2[g] = 1.0 - acc[2] / sst;
         if (a.status && ok && !(df > 0.0)) a.status[g] = POLS_GROUP_BAD_DOF;
+        if (a.rss) a.rss[g] = acc[4];
     }
     if (tid < kt) {
         const double nanv = __longlong_as_double(0x7ff8000000000000LL);

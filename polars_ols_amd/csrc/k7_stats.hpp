@@ -24,6 +24,8 @@ struct StatsArgs {
     int64_t n_seg;
     double *seg_part;          // n_seg x 5 partial sums
     double *prep;              // n_groups x (3 kt + 1): dispatcher coefficients, A^-1 X'y, diag(A^-1), factorisation ok
+    double *rss;               // optional, n_groups: the side-car's residual sum of squares (what sigma^2 = rss / df divides); nullptr for
+                               // every caller but the influence entry (K7i)
 };
 
 int k7_stats_launch(pols_ctx *ctx, int dtype, const StatsArgs &a);

@@ -265,6 +265,39 @@ class Engine:
                                                                    C.byref(plan._o), C.byref(so)))
         return res
 
+    def least_squares_influence(self, y, x_cols: Sequence, offsets, want: Sequence[str] = L.INFLUENCE_FIELDS + L.INFLUENCE_GROUP_FIELDS,
+                                interval_level: float = 0.95, **kwargs) -> Dict:
+        """Per-row influence diagnostics and prediction intervals (pols_least_squares_influence; the definitions are in
+        include/pols_mi355x.h).  ``want``: any of the per-row arrays ``leverage student_internal student_external cooks_d dffits
+        se_mean se_obs mean_lo mean_hi obs_lo obs_hi`` [n_rows, batch dtype], the per-group f64 arrays ``sigma2 df t_crit``
+        [n_groups], and ``coef pred resid status`` as ``least_squares_statistics`` returns them.  Arrays are numpy or torch and live
+        where the inputs live.  A group with df <= 0 has NaN rows and status POLS_GROUP_BAD_DOF; nothing is raised."""
+        level = _influence_level(interval_level)
+        want = tuple(want)
+        known = L.INFLUENCE_FIELDS + L.INFLUENCE_GROUP_FIELDS + ("coef", "pred", "resid", "status")
+        unknown = [w for w in want if w not in known]
+        if unknown:
+            raise ValueError(f"unknown influence fields {unknown}; known: {list(known)}")
+        kwargs["want"] = tuple(w for w in want if w in ("coef", "pred", "resid", "status"))
+        plan = self.plan_least_squares(y, x_cols, offsets, **kwargs)
+        b = plan._b
+        dev = b.mem == L.POLS_MEM_DEVICE
+        like = plan._keep[0][0]
+        res = plan.results
+        for key in L.INFLUENCE_FIELDS:
+            if key in want:
+                res[key] = self._alloc(dev, like.dtype, (b.n_rows,), like)
+        for key in L.INFLUENCE_GROUP_FIELDS:
+            if key in want:
+                res[key] = self._alloc(dev, torch.float64 if dev else np.float64, (b.n_groups,), like)
+        io = L.InfluenceOut(**{k: self._ptr(res.get(k)) for k in L.INFLUENCE_FIELDS + L.INFLUENCE_GROUP_FIELDS})
+        q = L.InfluenceParams()
+        self._lib.pols_influence_params_default(C.byref(q))
+        q.level = level
+        L.check(self._lib.pols_least_squares_influence(self._h, C.byref(plan._b), C.byref(plan._p), C.byref(q), C.byref(plan._o),
+                                                       C.byref(io)))
+        return res
+
     def least_squares(self, y, x_cols: Sequence, offsets, **kwargs) -> Dict:
         """All groups of a (group-sorted) frame in one launch.  ``want`` subset of {"coef","pred","resid","status"};
         ``out`` may carry pre-allocated buffers under the same keys."""
@@ -548,6 +581,13 @@ def _ols_params(lib, alpha=0.0, l1_ratio=None, max_iter=1000, tol=1e-5, positive
     return p
 
 
+def _influence_level(level) -> float:
+    level = float(level)
+    if not 0.0 < level < 1.0:
+        raise ValueError(f"interval level {level} outside (0, 1)")
+    return level
+
+
 def _arrow_call(self, fn, first, first_name: str, features, weights, offsets, add_intercept: bool, tail_args):
     """Shared marshalling of the pols_*_arrow entries: (ctx, first column, features, n, weights, offsets, n_groups, intercept,
     *tail_args, out array, out schema) -> pyarrow Array."""
@@ -601,6 +641,24 @@ def _statistics_arrow(self, target, features, *, target_name: str = "y", weights
                            add_intercept, (C.byref(p),))
     return _arrow_call(self, self._lib.pols_least_squares_statistics_robust_arrow, target, target_name, features, weights, offsets,
                        add_intercept, (C.byref(p), C.byref(cov)))
+
+
+def _influence_arrow(self, target, features, *, target_name: str = "y", weights=None, offsets=None, add_intercept: bool = False,
+                     fields: Optional[Sequence[str]] = None, interval_level: float = 0.95, **kw):
+    """``pols_least_squares_influence_arrow``: the ``influence`` struct, one row per input row, one field per requested per-row
+    array (all of them by default), null where the quantity is not defined."""
+    q = L.InfluenceParams()
+    q.level = _influence_level(interval_level)
+    names = list(L.INFLUENCE_FIELDS if fields is None else fields)
+    unknown = [n for n in names if n not in L.INFLUENCE_FIELDS]
+    if unknown or not names:
+        raise ValueError(f"unknown influence fields {unknown}; known: {list(L.INFLUENCE_FIELDS)}")
+    mask = 0
+    for n in names:
+        mask |= 1 << L.INFLUENCE_FIELDS.index(n)
+    p = _ols_params(self._lib, **kw)
+    return _arrow_call(self, self._lib.pols_least_squares_influence_arrow, target, target_name, features, weights, offsets,
+                       add_intercept, (C.byref(p), C.byref(q), mask))
 
 
 def _multi_target_arrow(self, targets, features, *, weights=None, offsets=None, add_intercept: bool = False, **kw):
@@ -665,6 +723,7 @@ def _predict_arrow(self, coefficients, features, *, add_intercept: bool = False,
 
 
 Engine.least_squares_statistics_arrow = _statistics_arrow
+Engine.least_squares_influence_arrow = _influence_arrow
 Engine.multi_target_least_squares_arrow = _multi_target_arrow
 Engine.recursive_least_squares_arrow = _rls_arrow
 Engine.rolling_least_squares_arrow = _rolling_arrow

@@ -24,6 +24,7 @@ from typing import Any, Dict, List, Literal, Optional, Sequence, Set, Tuple, Uni
 
 import numpy as np
 
+from . import _lib
 from ._lib import PolsPanic
 from .engine import Engine, Layout, _is_torch, default_engine
 
@@ -38,12 +39,12 @@ __all__ = [
     "compute_least_squares", "compute_recursive_least_squares", "compute_rolling_least_squares",
     "compute_least_squares_from_formula", "compute_multi_target_least_squares", "predict",
     "OLSKwargs", "RLSKwargs", "RollingKwargs", "NullPolicy", "OutputMode", "SolveMethod",
-    "Frame", "Expr", "col", "struct", "Coefficients", "Statistics", "LeastSquares",
+    "Frame", "Expr", "col", "struct", "Coefficients", "Statistics", "Influence", "LeastSquares",
 ]
 
 # ---- polars_ols/least_squares.py:47-63 --------------------------------------------------------------------------
 NullPolicy = Literal["zero", "drop", "ignore", "drop_zero", "drop_y_zero_x", "drop_window"]
-OutputMode = Literal["predictions", "residuals", "coefficients", "statistics"]
+OutputMode = Literal["predictions", "residuals", "coefficients", "statistics", "influence"]
 SolveMethod = Literal["qr", "svd", "chol", "lu", "cd", "cd_active_set"]
 
 _VALID_NULL_POLICIES: Set[str] = set(get_args(NullPolicy))
@@ -335,8 +336,56 @@ def _static_statistics(eng: Engine, y, xs, offs, w, icpt: bool, kw: OLSKwargs, n
     return Statistics(names, out, keys)
 
 
+class Influence(dict):
+    """mode="influence": per-row influence diagnostics and prediction intervals (pols_least_squares_influence; the definitions are
+    in include/pols_mi355x.h).  The requested per-row columns -- any of ``leverage student_internal student_external cooks_d dffits
+    se_mean se_obs mean_lo mean_hi obs_lo obs_hi`` -- are in the FRAME's row order (un-taken through ``.over`` like predictions);
+    ``sigma2 df t_crit`` [G] are per group and ``keys`` holds the group keys of an ``.over`` (None for a whole-frame fit).
+
+    A group with df <= 0 has NaN rows and raises nothing: one short group should not fail a per-row result for a whole panel
+    (mode="statistics" raises there, like the reference)."""
+
+    def __init__(self, fields, out, keys, untake):
+        super().__init__({f: untake(out[f]) for f in fields})
+        for g in _lib.INFLUENCE_GROUP_FIELDS:
+            self[g] = out[g]
+        self["keys"] = keys
+        self.fields = list(fields)
+        self.keys_ = keys
+
+
+def _influence_request(mode: str, influence_kwds: Optional[Dict[str, Any]], kind: str = "ols", kw: Optional[OLSKwargs] = None,
+                       cov_type: str = "nonrobust", cov_kwds: Optional[Dict[str, Any]] = None):
+    """(level, fields) of a mode="influence" request, None for every other mode; ValueError for what has no influence form: RLS /
+    rolling / expanding / multi-target models, influence_kwds with another mode, unknown keys or fields, a level outside (0, 1), a
+    non-default cov_type, and l1 (lasso, elastic net) or positive fits, where no hat matrix is defined."""
+    if mode != "influence":
+        if influence_kwds:
+            raise ValueError(f"influence_kwds apply to mode='influence' only (got mode={mode!r})")
+        return None
+    if kind != "ols":
+        raise ValueError(f"mode='influence' applies to single-target least squares, not to {kind} models")
+    if cov_type != "nonrobust" or cov_kwds:
+        raise ValueError(f"mode='influence' has only the constant-variance form: cov_type={cov_type!r} / cov_kwds do not apply")
+    kwds = dict(influence_kwds or {})
+    unknown = set(kwds) - {"level", "fields"}
+    if unknown:
+        raise ValueError(f"unknown influence_kwds {sorted(unknown)} (level, fields)")
+    level = kwds.get("level", 0.95)
+    if isinstance(level, bool) or not isinstance(level, (int, float)) or not 0.0 < float(level) < 1.0:
+        raise ValueError(f"influence_kwds['level'] must lie in (0, 1), got {level!r}")
+    fields = kwds.get("fields")
+    fields = list(_lib.INFLUENCE_FIELDS) if fields is None else ([fields] if isinstance(fields, str) else list(fields))
+    bad = [f for f in fields if f not in _lib.INFLUENCE_FIELDS]
+    if bad or not fields:
+        raise ValueError(f"unknown influence fields {bad}; known: {list(_lib.INFLUENCE_FIELDS)}")
+    if kw is not None and (kw.positive or (kw.l1_ratio is not None and kw.l1_ratio > 0.0)):
+        raise ValueError("mode='influence' needs a hat matrix: not defined for l1-penalised (lasso, elastic net) or positive fits")
+    return float(level), fields
+
+
 def _apply_static(frame: Frame, over, eng: Optional[Engine], target: Expr, features: Sequence[Expr], sample_weights,
-                  add_intercept: bool, mode: str, kw: OLSKwargs, cov=None):
+                  add_intercept: bool, mode: str, kw: OLSKwargs, cov=None, infl=None):
     """compute_least_squares body: least_squares.py:199-239 + src/expressions.rs:390-446 (null policies :201-296)."""
     y, xs, names, icpt, w = _pre_process_data(frame, target, features, sample_weights, add_intercept)
     n = y.shape[0]
@@ -351,6 +400,11 @@ def _apply_static(frame: Frame, over, eng: Optional[Engine], target: Expr, featu
         cov = ("cluster", moved[2 + len(xs):], cov[2])
 
     policy = kw.null_policy
+    if mode == "influence":
+        level, fields = infl
+        out = eng.least_squares_influence(y_s, xs_s, offs, weights=w_s, add_intercept=icpt, interval_level=level,
+                                          want=tuple(fields) + _lib.INFLUENCE_GROUP_FIELDS, **kw.to_dict())
+        return "influence", Influence(fields, out, keys, grp.untake)
     if mode != "statistics":
         # Null policies are fused into the kernels (staging pass: dropped rows get weight 0, surviving nulls become 0;
         # prediction pass: zero-filled features, "drop" masks the rows that were not fitted) -- ex.rs:201-296, 398-427.
@@ -465,14 +519,17 @@ def _robust_cov(cov_type: str, cov_kwds: Optional[Dict[str, Any]], mode: str, ki
 
 def compute_least_squares(target, *features, sample_weights=None, add_intercept: bool = False,
                           mode: str = "predictions", ols_kwargs: Optional[OLSKwargs] = None, cov_type: str = "nonrobust",
-                          cov_kwds: Optional[Dict[str, Any]] = None) -> Expr:
+                          cov_kwds: Optional[Dict[str, Any]] = None, influence_kwds: Optional[Dict[str, Any]] = None) -> Expr:
     """``cov_type`` ("HC0" .. "HC3", "HAC" with ``cov_kwds={"maxlags": L}``) makes the standard errors, t- and p-values of
-    mode="statistics" robust; the other fields do not depend on it."""
+    mode="statistics" robust; the other fields do not depend on it.  mode="influence" (``influence_kwds={"level": 0.95,
+    "fields": [...]}``) returns an ``Influence``: per-row diagnostics and prediction intervals in the frame's row order.  A group
+    with df <= 0 has NaN rows there and does not raise, where mode="statistics" raises."""
     assert mode in _VALID_OUTPUT_MODES, f"'mode' must be one of {_VALID_OUTPUT_MODES}"
-    cov = _robust_cov(cov_type, cov_kwds, mode)
     kw = ols_kwargs or OLSKwargs()
+    infl = _influence_request(mode, influence_kwds, "ols", kw, cov_type, cov_kwds)
+    cov = None if infl is not None else _robust_cov(cov_type, cov_kwds, mode)
     t, fs = parse_into_expr(target), [parse_into_expr(f) for f in features]
-    return Expr(t._name, fn=lambda frame, over, eng: _apply_static(frame, over, eng, t, fs, sample_weights, add_intercept, mode, kw, cov))
+    return Expr(t._name, fn=lambda frame, over, eng: _apply_static(frame, over, eng, t, fs, sample_weights, add_intercept, mode, kw, cov, infl))
 
 
 def compute_multi_target_least_squares(targets, *features, sample_weights=None, add_intercept: bool = False,
@@ -485,6 +542,7 @@ def compute_multi_target_least_squares(targets, *features, sample_weights=None, 
     engine's multi-target entry: one Gram pass over [X | targets] and one factorisation shared by all targets -- what
     solve_multi_target (ls.rs:243-260) does with one SVD."""
     kw = ols_kwargs or OLSKwargs()
+    _influence_request(mode, None, "multi-target")
     msg = "Consider running multiple independent regressions on a multi-expression target!"
     assert not kw.positive and (kw.l1_ratio is None or kw.l1_ratio == 0.0), (
         "Multi-target regression is only supported for unconstrained OLS & Ridge problems." + msg)
@@ -525,7 +583,8 @@ def compute_multi_target_least_squares(targets, *features, sample_weights=None, 
 
 def compute_recursive_least_squares(target, *features, sample_weights=None, add_intercept: bool = False,
                                     mode: str = "predictions", rls_kwargs: Optional[RLSKwargs] = None) -> Expr:
-    valid_output_modes = _VALID_OUTPUT_MODES - {"statistics"}
+    _influence_request(mode, None, "rls")
+    valid_output_modes = _VALID_OUTPUT_MODES - {"statistics", "influence"}
     assert mode in valid_output_modes, f"'mode' must be one of {valid_output_modes}"
     kw = rls_kwargs or RLSKwargs()
     t, fs = parse_into_expr(target), [parse_into_expr(f) for f in features]
@@ -534,7 +593,8 @@ def compute_recursive_least_squares(target, *features, sample_weights=None, add_
 
 def compute_rolling_least_squares(target, *features, sample_weights=None, add_intercept: bool = False,
                                   mode: str = "predictions", rolling_kwargs: Optional[RollingKwargs] = None) -> Expr:
-    valid_output_modes = _VALID_OUTPUT_MODES - {"statistics"}
+    _influence_request(mode, None, "rolling")
+    valid_output_modes = _VALID_OUTPUT_MODES - {"statistics", "influence"}
     assert mode in valid_output_modes, f"'mode' must be one of {valid_output_modes}"
     kw = rolling_kwargs or RollingKwargs()
     t, fs = parse_into_expr(target), [parse_into_expr(f) for f in features]
@@ -649,10 +709,12 @@ def _parse_formula(formula: str, include_dependent_variable: bool) -> Tuple[List
 
 
 def compute_least_squares_from_formula(formula: str, sample_weights=None, mode: str = "predictions", cov_type: str = "nonrobust",
-                                       cov_kwds: Optional[Dict[str, Any]] = None, **kwargs) -> Expr:
+                                       cov_kwds: Optional[Dict[str, Any]] = None, influence_kwds: Optional[Dict[str, Any]] = None,
+                                       **kwargs) -> Expr:
     exprs, add_intercept = _parse_formula(formula, include_dependent_variable=True)   # ls.py:432-452
     kind = "rls" if kwargs.get("half_life") else ("rolling" if kwargs.get("window_size") else "ols")
-    _robust_cov(cov_type, cov_kwds, mode, kind)
+    if _influence_request(mode, influence_kwds, kind, None, cov_type, cov_kwds) is None:
+        _robust_cov(cov_type, cov_kwds, mode, kind)
     if kwargs.get("half_life"):
         return compute_recursive_least_squares(exprs[0], *exprs[1:], add_intercept=add_intercept, sample_weights=sample_weights,
                                                mode=mode, rls_kwargs=RLSKwargs(**kwargs))
@@ -660,7 +722,7 @@ def compute_least_squares_from_formula(formula: str, sample_weights=None, mode: 
         return compute_rolling_least_squares(exprs[0], *exprs[1:], add_intercept=add_intercept, sample_weights=sample_weights,
                                              mode=mode, rolling_kwargs=RollingKwargs(**kwargs))
     return compute_least_squares(exprs[0], *exprs[1:], add_intercept=add_intercept, sample_weights=sample_weights, mode=mode,
-                                 ols_kwargs=OLSKwargs(**kwargs), cov_type=cov_type, cov_kwds=cov_kwds)
+                                 ols_kwargs=OLSKwargs(**kwargs), cov_type=cov_type, cov_kwds=cov_kwds, influence_kwds=influence_kwds)
 
 
 def predict(coefficients: Coefficients, *features, frame: Frame, null_policy: str = "zero", add_intercept: bool = False,
@@ -687,14 +749,16 @@ class LeastSquares:
 
     def least_squares(self, *features, sample_weights=None, add_intercept: bool = False, mode: str = "predictions",
                       null_policy: str = "ignore", solve_method: Optional[str] = None, multi_target: bool = False,
-                      cov_type: str = "nonrobust", cov_kwds: Optional[Dict[str, Any]] = None, **ols_kwargs) -> Expr:
+                      cov_type: str = "nonrobust", cov_kwds: Optional[Dict[str, Any]] = None,
+                      influence_kwds: Optional[Dict[str, Any]] = None, **ols_kwargs) -> Expr:
         kw = OLSKwargs(null_policy=null_policy, solve_method=solve_method, **ols_kwargs)
         if multi_target:
+            _influence_request(mode, influence_kwds, "multi-target")
             _robust_cov(cov_type, cov_kwds, mode, "multi-target")
             return compute_multi_target_least_squares(self._expr, *features, sample_weights=sample_weights, add_intercept=add_intercept,
                                                       mode=mode, ols_kwargs=kw)
         return compute_least_squares(self._expr, *features, sample_weights=sample_weights, add_intercept=add_intercept, mode=mode,
-                                     ols_kwargs=kw, cov_type=cov_type, cov_kwds=cov_kwds)
+                                     ols_kwargs=kw, cov_type=cov_type, cov_kwds=cov_kwds, influence_kwds=influence_kwds)
 
     def ols(self, *features, **kwargs) -> Expr:
         return self.least_squares(*features, **kwargs)
@@ -736,6 +800,8 @@ class LeastSquares:
     def from_formula(self, formula: str, **kwargs) -> Expr:
         features, add_intercept = _parse_formula(formula, include_dependent_variable=False)
         if kwargs.get("half_life") or kwargs.get("window_size"):
+            _influence_request(kwargs.get("mode", "predictions"), kwargs.pop("influence_kwds", None),
+                               "rls" if kwargs.get("half_life") else "rolling")
             _robust_cov(kwargs.pop("cov_type", "nonrobust"), kwargs.pop("cov_kwds", None), kwargs.get("mode", "predictions"),
                         "rls" if kwargs.get("half_life") else "rolling")
         if kwargs.get("half_life"):
