@@ -380,6 +380,51 @@ enum {
     POLS_INFL_MEAN_HI = 1 << 8, POLS_INFL_OBS_LO = 1 << 9, POLS_INFL_OBS_HI = 1 << 10, POLS_INFL_ALL = (1 << 11) - 1
 };
 
+/* Ridge regularisation path with leave-one-out selection of alpha, per group (no reference counterpart; the job of scikit-learn's
+ * RidgeCV).  Per group g, the rows F_g are those pols_least_squares fits -- the same null-policy filtering / zero-filling and validity
+ * mask rules, sqrt(w) scaling with a null weight acting as 1e-24, the ones column last and PENALISED like any other (the reference
+ * adds alpha I to every column, src/least_squares.rs:342-364) -- with x~_i = sqrt(w_i) x_i, y~_i = sqrt(w_i) y_i, n = |F_g|,
+ * kt = n_features + intercept.  For every candidate a_j = params.alphas[j]:
+ *   A_j = X~'X~ + a_j I,   b_j = A_j^-1 X~'y~,   h_ij = x~_i' A_j^-1 x~_i,
+ *   cv_scores[g][j] = (1 / n) sum_{i in F_g} ((y~_i - x~_i'b_j) / (1 - h_ij))^2
+ * which is the exact leave-one-out mean squared error of that ridge on the scaled rows (the leverage identity holds because the
+ * penalty covers every column: no refit).  Unweighted and without an intercept it is scikit-learn's
+ * RidgeCV(fit_intercept=False).cv_results_.mean(0); with sample weights scikit-learn weights the squared errors differently and does
+ * not match -- this definition is the project's own.
+ * A candidate is UNUSABLE for a group -- its score and its coef_path row are NaN -- when
+ *   - A_j has no Cholesky factorisation.  The rule applied, on the computed spectrum s of X~'X~ (Jacobi rotations in f64):
+ *     min(s) + a_j <= 16 kt eps (max(s) + a_j), the noise floor the f64 Cholesky of the static entries puts on a pivot; or
+ *   - some fitted row has 1 - h_ij < 1e-10 (the HC2 / HC3 rule of the robust statistics), or the score is not a number.
+ *   An exact in-sample fit with alpha = 0 is therefore unusable, never "score 0".
+ * The chosen candidate is the usable one with the smallest score, the lowest index on an exact tie.  out->coef / pred / resid are
+ * those of the chosen candidate, with the shape and null-policy masking of pols_least_squares(alpha = chosen) on that group
+ * (predictions un-scaled by 1 / sqrt(w), every row predicted or masked as that entry does).  out->status per group: POLS_GROUP_OK;
+ * POLS_GROUP_EMPTY for n = 0 (coefficients zeros, scores / alpha / score NaN, index -1); POLS_GROUP_FALLBACK when NO candidate is
+ * usable (index -1; alpha, score, coef, pred, resid NaN).  Groups with n <= kt are legal whenever alpha > 0.
+ * The Gram matrix, the decomposition and all scoring run in f64 on the inputs' values, for f32 batches too; coef / coef_path / pred /
+ * resid are stored in the batch dtype.  Sums run in a fixed order without atomics: two runs are bit-identical.
+ * From pols_ols_params only null_policy is consulted; positive, or has_l1_ratio with l1_ratio > 0, is POLS_ERR_INVALID (no hat
+ * matrix).  POLS_ERR_INVALID: alphas == NULL, n_alphas < 1, a negative or non-finite candidate, an unknown null policy, a mask
+ * without a drop-family policy.  POLS_ERR_UNSUPPORTED: more than 31 columns incl. the intercept, more than 64 candidates. */
+typedef struct pols_ridge_cv_params {
+    const double *alphas;     /* HOST array, any order, each >= 0 and finite */
+    int32_t n_alphas;
+} pols_ridge_cv_params;
+
+/* alphas = NULL, n_alphas = 0 */
+void pols_ridge_cv_params_default(pols_ridge_cv_params *q);
+
+typedef struct pols_ridge_cv_out {
+    double  *alpha;           /* n_groups: the chosen alpha                              */
+    int32_t *alpha_index;     /* n_groups: its index in params.alphas, -1 if none usable */
+    double  *score;           /* n_groups: its leave-one-out mean squared error          */
+    double  *cv_scores;       /* n_groups x n_alphas, row-major                          */
+    void    *coef_path;       /* n_groups x n_alphas x kt, batch dtype                   */
+} pols_ridge_cv_out;          /* all live where b->mem says; any may be NULL */
+
+int pols_ridge_cv(pols_ctx *ctx, const pols_batch *b, const pols_ols_params *p, const pols_ridge_cv_params *q, pols_out *out,
+                  const pols_ridge_cv_out *cv);
+
 /* ---- group-key ingestion: `.over(key)` / `group_by(key)` ------------------------------------------------------------
  * The reference's plugin functions never see a key column: Polars partitions the frame on the host and calls them once per
  * group (README.md:19, README.md:57 and :91 `.over("group")`, tests/test_ols.py:110, :384, :860).  The batched entries

@@ -11,6 +11,7 @@ from .least_squares import (  # noqa: F401
     Coefficients, Statistics, Influence, Expr, Frame, LeastSquares, OLSKwargs, RLSKwargs, RollingKwargs, col, struct, compute_least_squares,
     compute_multi_target_least_squares,
     compute_least_squares_from_formula, compute_recursive_least_squares, compute_rolling_least_squares, predict,
+    compute_ridge_cv, RidgeCV,
 )
 
 __version__ = "0.1.0"

@@ -106,6 +106,19 @@ class InfluenceOut(C.Structure):      # pols_influence_out
     _fields_ = [(n, C.c_void_p) for n in INFLUENCE_FIELDS + INFLUENCE_GROUP_FIELDS]
 
 
+class RidgeCvParams(C.Structure):     # pols_ridge_cv_params
+    _fields_ = [("alphas", C.POINTER(C.c_double)), ("n_alphas", C.c_int32)]
+
+
+# pols_ridge_cv_out, in the struct's order
+RIDGE_CV_FIELDS = ("alpha", "alpha_index", "score", "cv_scores", "coef_path")
+RIDGE_CV_MAX_ALPHAS = 64
+
+
+class RidgeCvOut(C.Structure):        # pols_ridge_cv_out
+    _fields_ = [(n, C.c_void_p) for n in RIDGE_CV_FIELDS]
+
+
 EXPORTS = [
     "pols_device_count", "pols_version", "pols_last_error", "pols_create", "pols_destroy", "pols_set_stream",
     "pols_use_private_stream",
@@ -123,6 +136,7 @@ EXPORTS = [
     "pols_cov_params_default", "pols_least_squares_statistics_robust", "pols_least_squares_statistics_robust_arrow",
     "pols_cluster_params_default", "pols_least_squares_statistics_cluster", "pols_least_squares_statistics_cluster_arrow",
     "pols_influence_params_default", "pols_least_squares_influence", "pols_least_squares_influence_arrow",
+    "pols_ridge_cv_params_default", "pols_ridge_cv",
 ]
 # measurement aids (include/pols_mi355x_debug.h): not part of the reference interface
 DEBUG_EXPORTS = ["pols_timing_enable", "pols_timing_collect", "pols_last_kernel_name", "pols_stream_probe", "pols_stream_probe_ex"]
@@ -186,6 +200,9 @@ def lib() -> C.CDLL:
         L.pols_influence_params_default.argtypes, L.pols_influence_params_default.restype = [C.POINTER(InfluenceParams)], None
         L.pols_least_squares_influence.argtypes = [C.c_void_p, C.POINTER(Batch), C.POINTER(OlsParams), C.POINTER(InfluenceParams),
                                                    C.POINTER(Out), C.POINTER(InfluenceOut)]
+        L.pols_ridge_cv_params_default.argtypes, L.pols_ridge_cv_params_default.restype = [C.POINTER(RidgeCvParams)], None
+        L.pols_ridge_cv.argtypes = [C.c_void_p, C.POINTER(Batch), C.POINTER(OlsParams), C.POINTER(RidgeCvParams), C.POINTER(Out),
+                                    C.POINTER(RidgeCvOut)]
         L.pols_layout_create.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.POINTER(C.c_void_p)]
         L.pols_layout_destroy.argtypes = [C.c_void_p]
         L.pols_layout_destroy.restype = None

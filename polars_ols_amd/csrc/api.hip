@@ -21,6 +21,7 @@
 #include "k7c_cluster.hpp"
 #include "k7i_influence.hpp"
 #include "k8_wide.hpp"
+#include "k10_ridge_path.hpp"
 #include "dyn_prep.hpp"
 
 namespace pols {
@@ -1920,6 +1921,98 @@ int pols_least_squares_influence(pols_ctx *ctx, const pols_batch *b, const pols_
     std::memset(&none, 0, sizeof(none));
     InflCall ic{q, infl};
     return statistics_body(ctx, b, p, nullptr, nullptr, o, &none, &ic);
+}
+
+void pols_ridge_cv_params_default(pols_ridge_cv_params *q) {
+    if (!q) return;
+    q->alphas = nullptr;
+    q->n_alphas = 0;
+}
+
+// K10 (k10_ridge_path.hip): Gram pass, eigendecomposition, row pass over the candidates, pick, prediction pass with the winner's
+// coefficients.  Null policies are fused into the tile staging and into the prediction pass, as in ls_core's streamed path.
+int pols_ridge_cv(pols_ctx *ctx, const pols_batch *b, const pols_ols_params *p, const pols_ridge_cv_params *q, pols_out *o,
+                  const pols_ridge_cv_out *ro) {
+    int rc = check_ctx(ctx);
+    if (rc) return rc;
+    if (b && o && b->n_features + (b->add_intercept ? 1 : 0) > K10_KMAX)
+        return fail(POLS_ERR_UNSUPPORTED, "ridge_cv: %d features (incl. intercept) > %d", b->n_features + (b->add_intercept ? 1 : 0), K10_KMAX);
+    if ((rc = check_batch(b, o, K10_KMAX))) return rc;
+    if (!p || !q) return fail(POLS_ERR_INVALID, "params / ridge_cv params is NULL");
+    if (!q->alphas || q->n_alphas < 1) return fail(POLS_ERR_INVALID, "ridge_cv: the grid of candidates is empty");
+    if (q->n_alphas > K10_MAX_ALPHAS) return fail(POLS_ERR_UNSUPPORTED, "ridge_cv: %d candidates > %d", q->n_alphas, K10_MAX_ALPHAS);
+    for (int j = 0; j < q->n_alphas; ++j)
+        if (!(q->alphas[j] >= 0.0) || !std::isfinite(q->alphas[j])) return fail(POLS_ERR_INVALID, "ridge_cv: candidate %d is negative or not finite", j);
+    if (p->positive || (p->has_l1_ratio && p->l1_ratio > 0.0))
+        return fail(POLS_ERR_INVALID, "ridge_cv: positive / l1_ratio fits have no hat matrix");
+    if (p->null_policy < POLS_NULL_IGNORE || p->null_policy > POLS_NULL_DROP_WINDOW) return fail(POLS_ERR_INVALID, "unknown null_policy %d", p->null_policy);
+    const int pol = (b->null_free && !b->valid) ? POLS_NULL_IGNORE : p->null_policy;
+    if (b->valid && (pol == POLS_NULL_IGNORE || pol == POLS_NULL_ZERO))
+        return fail(POLS_ERR_INVALID, "a validity mask needs a drop-family null_policy");
+    if (b->n_groups == 0) return POLS_OK;
+    pols_ridge_cv_out none;
+    std::memset(&none, 0, sizeof(none));
+    if (!ro) ro = &none;
+    const int kt = b->n_features + (b->add_intercept ? 1 : 0), na = q->n_alphas;
+    const bool host = b->mem == POLS_MEM_HOST;
+    const size_t G = (size_t)b->n_groups, sz = dtype_size(b->dtype);
+    const int64_t *d_offs = nullptr;
+    int64_t max_rows = 0;
+    if ((rc = upload_offsets(ctx, b->group_offsets, b->n_groups, &d_offs, &max_rows, b->offsets_generation))) return rc;
+    Staged st;
+    if ((rc = stage_inputs(ctx, b, b->n_groups, kt, o, &st))) return rc;
+    if ((rc = fill_null_weights(ctx, b, &st))) return rc;
+    SegTables sg;
+    if ((rc = ensure_segments(ctx, b, max_rows, 0, &sg))) return rc;
+    const size_t items = sg.n_seg > 0 ? (size_t)sg.n_seg : G;
+    const size_t gramb = round256(sizeof(double) * items * k10_gram_stride(kt)), eigb = round256(sizeof(double) * G * k10_eig_stride(kt));
+    const size_t alb = round256(sizeof(double) * (size_t)na), partb = round256(sizeof(double) * items * (size_t)na), c64b = round256(sizeof(double) * G * kt);
+    void *wg = nullptr, *ws = nullptr, *wo = nullptr;
+    if ((rc = ensure_scratch(ctx, Work::RidgeCvGram, gramb + eigb, &wg))) return rc;
+    if ((rc = ensure_scratch(ctx, Work::RidgeCvScores, alb + partb + c64b, &ws))) return rc;
+    if ((rc = upload_small(ctx, ws, q->alphas, sizeof(double) * (size_t)na))) return rc;
+    RidgeCvArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.y = st.y; a.w = st.w;
+    for (int j = 0; j < b->n_features; ++j) a.x[j] = st.x[(size_t)j];
+    a.offs = d_offs; a.n_groups = b->n_groups; a.n_rows = b->n_rows;
+    if (sg.n_seg > 0) { a.seg_offs = sg.offs; a.seg_map = sg.map; a.seg_first = sg.first; a.n_seg = sg.n_seg; }
+    a.valid = st.valid; a.null_policy = pol;
+    a.k_user = b->n_features; a.kt = kt; a.f32 = b->dtype == POLS_F32 ? 1 : 0;
+    a.alphas = static_cast<const double *>(ws); a.n_alphas = na;
+    a.gram_part = static_cast<double *>(wg);
+    a.eig = reinterpret_cast<double *>(static_cast<char *>(wg) + gramb);
+    a.score_part = reinterpret_cast<double *>(static_cast<char *>(ws) + alb);
+    a.coef64 = reinterpret_cast<double *>(static_cast<char *>(ws) + alb + partb);
+    a.coef = st.coef; a.status = st.status;
+    // the entry's own outputs: where the caller wants them (DEVICE batches) or staged (HOST batches)
+    const size_t vecb = round256(sizeof(double) * G), idxb = round256(sizeof(int32_t) * G), cvb = round256(sizeof(double) * G * (size_t)na),
+                 pathb = round256(sz * G * (size_t)na * kt);
+    if (host) {
+        if ((rc = ensure_scratch(ctx, Work::RidgeCvOut, 2 * vecb + idxb + cvb + pathb, &wo))) return rc;
+        char *c = static_cast<char *>(wo);
+        if (ro->alpha) a.alpha = reinterpret_cast<double *>(c);
+        if (ro->score) a.score = reinterpret_cast<double *>(c + vecb);
+        if (ro->alpha_index) a.alpha_index = reinterpret_cast<int32_t *>(c + 2 * vecb);
+        if (ro->cv_scores) a.cv_scores = reinterpret_cast<double *>(c + 2 * vecb + idxb);
+        if (ro->coef_path) a.coef_path = c + 2 * vecb + idxb + cvb;
+    } else {
+        a.alpha = ro->alpha; a.score = ro->score; a.alpha_index = ro->alpha_index; a.cv_scores = ro->cv_scores; a.coef_path = ro->coef_path;
+    }
+    ctx->last_kernel = sg.n_seg > 0 ? "k10_ridge_path_split" : "k10_ridge_path";
+    if ((rc = k10_gram_launch(ctx, b->dtype, a))) return rc;
+    if ((rc = k10_eig_launch(ctx, a))) return rc;
+    if ((rc = k10_rows_launch(ctx, b->dtype, a))) return rc;
+    if ((rc = k10_pick_launch(ctx, a))) return rc;
+    a.pred = st.pred; a.resid = st.resid;
+    if ((rc = k10_predict_launch(ctx, b->dtype, a))) return rc;
+    if (!host) return POLS_OK;
+    if (ro->alpha) POLS_HIP(hipMemcpyAsync(ro->alpha, a.alpha, sizeof(double) * G, hipMemcpyDeviceToHost, ctx->stream));
+    if (ro->score) POLS_HIP(hipMemcpyAsync(ro->score, a.score, sizeof(double) * G, hipMemcpyDeviceToHost, ctx->stream));
+    if (ro->alpha_index) POLS_HIP(hipMemcpyAsync(ro->alpha_index, a.alpha_index, sizeof(int32_t) * G, hipMemcpyDeviceToHost, ctx->stream));
+    if (ro->cv_scores) POLS_HIP(hipMemcpyAsync(ro->cv_scores, a.cv_scores, sizeof(double) * G * (size_t)na, hipMemcpyDeviceToHost, ctx->stream));
+    if (ro->coef_path) POLS_HIP(hipMemcpyAsync(ro->coef_path, a.coef_path, sz * G * (size_t)na * kt, hipMemcpyDeviceToHost, ctx->stream));
+    return unstage_outputs(ctx, b, b->n_groups, kt, o, st);
 }
 
 void pols_cluster_params_default(pols_cluster_params *c) {

@@ -77,6 +77,9 @@ enum class Work : int {
     InflPrep,       // influence diagnostics (K7i): A^-1, coefficients, trace, ok per group (k7r_prepare_launch's layout)
     InflGroup,      // influence diagnostics (K7i): side-car RSS, then sigma2 / df / t_crit / usable per group, then (f32) X'e per segment / group
     InflRows,       // influence diagnostics (K7i): per-row outputs of a HOST batch before they go home
+    RidgeCvGram,    // ridge path (K10): Gram partials per segment / group, then V, s, V'X~'y~ and the fitted rows per group
+    RidgeCvScores,  // ridge path (K10): the candidates, score partials per segment / group, the winners' coefficients in f64
+    RidgeCvOut,     // ridge path (K10): alpha / score / alpha_index / cv_scores / coef_path of a HOST batch before they go home
     Count
 };
 

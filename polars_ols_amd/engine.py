@@ -298,6 +298,42 @@ class Engine:
                                                        C.byref(io)))
         return res
 
+    def ridge_cv(self, y, x_cols: Sequence, offsets, alphas, *, want: Sequence[str] = ("coef", "alpha", "alpha_index", "score"),
+                 weights=None, valid=None, add_intercept: bool = False, null_policy: str = "ignore", null_free: bool = False) -> Dict:
+        """Ridge regularisation path with leave-one-out selection of alpha for every group in one call (pols_ridge_cv; the
+        definitions are in include/pols_mi355x.h).  ``alphas``: the candidates (any order, each >= 0 and finite, at most 64).
+        ``want``: any of ``coef pred resid status`` (those of the chosen candidate, as ``least_squares(alpha=chosen)`` returns
+        them), ``alpha score`` [n_groups, f64], ``alpha_index`` [n_groups, int32, -1 where no candidate is usable], ``cv_scores``
+        [n_groups, n_alphas, f64] and ``coef_path`` [n_groups, n_alphas, k, batch dtype].  Arrays are numpy or torch and live
+        where the inputs live."""
+        grid = _ridge_cv_grid(alphas)
+        want = tuple(want)
+        known = ("coef", "pred", "resid", "status") + L.RIDGE_CV_FIELDS
+        unknown = [w for w in want if w not in known]
+        if unknown:
+            raise ValueError(f"unknown ridge_cv fields {unknown}; known: {list(known)}")
+        plan = self.plan_least_squares(y, x_cols, offsets, weights=weights, valid=valid, add_intercept=add_intercept,
+                                       null_policy=null_policy, null_free=null_free,
+                                       want=tuple(w for w in want if w in ("coef", "pred", "resid", "status")))
+        b = plan._b
+        kt = b.n_features + b.add_intercept
+        dev = b.mem == L.POLS_MEM_DEVICE
+        like = plan._keep[0][0]
+        res = plan.results
+        f64, i32 = (torch.float64, torch.int32) if dev else (np.float64, np.int32)
+        shapes = {"alpha": ((b.n_groups,), f64), "alpha_index": ((b.n_groups,), i32), "score": ((b.n_groups,), f64),
+                  "cv_scores": ((b.n_groups, len(grid)), f64), "coef_path": ((b.n_groups, len(grid), kt), like.dtype)}
+        for key in L.RIDGE_CV_FIELDS:
+            if key in want:
+                res[key] = self._alloc(dev, shapes[key][1], shapes[key][0], like)
+        ro = L.RidgeCvOut(**{k: self._ptr(res.get(k)) for k in L.RIDGE_CV_FIELDS})
+        q = L.RidgeCvParams()
+        self._lib.pols_ridge_cv_params_default(C.byref(q))
+        q.alphas = grid.ctypes.data_as(C.POINTER(C.c_double))
+        q.n_alphas = len(grid)
+        L.check(self._lib.pols_ridge_cv(self._h, C.byref(plan._b), C.byref(plan._p), C.byref(q), C.byref(plan._o), C.byref(ro)))
+        return res
+
     def least_squares(self, y, x_cols: Sequence, offsets, **kwargs) -> Dict:
         """All groups of a (group-sorted) frame in one launch.  ``want`` subset of {"coef","pred","resid","status"};
         ``out`` may carry pre-allocated buffers under the same keys."""
@@ -579,6 +615,18 @@ def _ols_params(lib, alpha=0.0, l1_ratio=None, max_iter=1000, tol=1e-5, positive
     p.has_rcond, p.rcond = int(rcond is not None), float(rcond) if rcond is not None else 0.0
     p.null_policy = L.NULL_POLICIES[null_policy]
     return p
+
+
+def _ridge_cv_grid(alphas) -> np.ndarray:
+    """the candidates of a ridge path as a contiguous f64 array; ValueError for an empty grid or a negative / non-finite candidate"""
+    if _is_torch(alphas):
+        alphas = alphas.detach().cpu().numpy()
+    grid = np.ascontiguousarray(np.atleast_1d(np.asarray(alphas, dtype=np.float64)).ravel())
+    if grid.size == 0:
+        raise ValueError("ridge_cv: the grid of candidate alphas is empty")
+    if not np.all(np.isfinite(grid)) or np.any(grid < 0.0):
+        raise ValueError(f"ridge_cv: every candidate alpha must be finite and >= 0 (got {grid.tolist()})")
+    return grid
 
 
 def _influence_level(level) -> float:

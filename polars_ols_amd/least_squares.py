@@ -26,7 +26,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import PolsPanic
-from .engine import Engine, Layout, _is_torch, default_engine
+from .engine import Engine, Layout, _is_torch, _ridge_cv_grid, default_engine
 
 try:
     import torch
@@ -40,6 +40,7 @@ __all__ = [
     "compute_least_squares_from_formula", "compute_multi_target_least_squares", "predict",
     "OLSKwargs", "RLSKwargs", "RollingKwargs", "NullPolicy", "OutputMode", "SolveMethod",
     "Frame", "Expr", "col", "struct", "Coefficients", "Statistics", "Influence", "LeastSquares",
+    "compute_ridge_cv", "RidgeCV",
 ]
 
 # ---- polars_ols/least_squares.py:47-63 --------------------------------------------------------------------------
@@ -421,6 +422,38 @@ def _apply_static(frame: Frame, over, eng: Optional[Engine], target: Expr, featu
     return target.output_name, grp.untake(pred)                # back to the frame's row order
 
 
+class RidgeCV(dict):
+    """mode="cv" of a ridge path (pols_ridge_cv; the definitions are in include/pols_mi355x.h), one entry per group: ``alpha``
+    (the chosen candidate), ``alpha_index`` (its index in ``alphas``, -1 where no candidate is usable), ``score`` (its leave-one-out
+    mean squared error) [G], ``cv_scores`` [G, n_alphas] (NaN for an unusable candidate); ``alphas`` is the grid as passed and
+    ``keys`` holds the group keys of an ``.over`` (None for a whole-frame fit, where G == 1)."""
+
+    def __init__(self, out, keys, alphas):
+        super().__init__(alpha=out["alpha"], alpha_index=out["alpha_index"], score=out["score"], cv_scores=out["cv_scores"],
+                         keys=keys, alphas=alphas)
+        self.keys_ = keys
+
+
+_VALID_RIDGE_CV_MODES = ("predictions", "residuals", "coefficients", "cv")
+
+
+def _apply_ridge_cv(frame: Frame, over, eng: Optional[Engine], target: Expr, features: Sequence[Expr], sample_weights,
+                    add_intercept: bool, mode: str, grid, null_policy: str):
+    """compute_ridge_cv body: the group layout of _apply_static around Engine.ridge_cv."""
+    y, xs, names, icpt, w = _pre_process_data(frame, target, features, sample_weights, add_intercept)
+    eng = eng or default_engine(y.device.index or 0 if _is_torch(y) else 0)
+    grp = _Groups(eng, None if over is None else (frame[over] if isinstance(over, str) else over), y.shape[0])
+    moved = grp.take([y, w] + list(xs))
+    want = {"predictions": ("pred",), "residuals": ("resid",), "coefficients": ("coef",),
+            "cv": ("alpha", "alpha_index", "score", "cv_scores")}[mode]
+    out = eng.ridge_cv(moved[0], moved[2:], grp.offsets, grid, want=want, weights=moved[1], add_intercept=icpt, null_policy=null_policy)
+    if mode == "cv":
+        return "cv", RidgeCV(out, grp.keys, grid.copy())
+    if mode == "coefficients":
+        return "coefficients", Coefficients(names, out["coef"], grp.keys, grp.gid_frame(out["coef"]))
+    return target.output_name, grp.untake(out["pred"] if mode == "predictions" else out["resid"])
+
+
 def _apply_dynamic(frame: Frame, over, eng: Optional[Engine], target: Expr, features: Sequence[Expr], sample_weights,
                    add_intercept: bool, mode: str, kind: str, kw):
     """compute_recursive_least_squares / compute_rolling_least_squares bodies (ls.py:332-409 around
@@ -530,6 +563,20 @@ def compute_least_squares(target, *features, sample_weights=None, add_intercept:
     cov = None if infl is not None else _robust_cov(cov_type, cov_kwds, mode)
     t, fs = parse_into_expr(target), [parse_into_expr(f) for f in features]
     return Expr(t._name, fn=lambda frame, over, eng: _apply_static(frame, over, eng, t, fs, sample_weights, add_intercept, mode, kw, cov, infl))
+
+
+def compute_ridge_cv(target, *features, alphas, sample_weights=None, add_intercept: bool = False, mode: str = "predictions",
+                     null_policy: str = "ignore") -> Expr:
+    """Ridge with the penalty chosen per group from ``alphas`` by closed-form leave-one-out error (scikit-learn's RidgeCV for every
+    group of the frame in one call).  Modes "predictions", "residuals" and "coefficients" are those of the chosen candidate, as
+    ``ridge(alpha=chosen)`` returns them; mode="cv" returns a ``RidgeCV`` with the choice and every candidate's score."""
+    if mode not in _VALID_RIDGE_CV_MODES:
+        raise ValueError(f"'mode' must be one of {_VALID_RIDGE_CV_MODES}, got {mode!r}")
+    if null_policy not in _VALID_NULL_POLICIES:
+        raise ValueError(f"'null_policy' must be one of {sorted(_VALID_NULL_POLICIES)}, got {null_policy!r}")
+    grid = _ridge_cv_grid(alphas)
+    t, fs = parse_into_expr(target), [parse_into_expr(f) for f in features]
+    return Expr(t._name, fn=lambda frame, over, eng: _apply_ridge_cv(frame, over, eng, t, fs, sample_weights, add_intercept, mode, grid, null_policy))
 
 
 def compute_multi_target_least_squares(targets, *features, sample_weights=None, add_intercept: bool = False,
@@ -771,6 +818,11 @@ class LeastSquares:
 
     def ridge(self, *features, alpha: float, **kwargs) -> Expr:
         return self.least_squares(*features, alpha=alpha, l1_ratio=0.0, **kwargs)
+
+    def ridge_cv(self, *features, alphas, sample_weights=None, add_intercept: bool = False, mode: str = "predictions",
+                 null_policy: str = "ignore") -> Expr:
+        return compute_ridge_cv(self._expr, *features, alphas=alphas, sample_weights=sample_weights, add_intercept=add_intercept,
+                                mode=mode, null_policy=null_policy)
 
     def lasso(self, *features, alpha: float, **kwargs) -> Expr:
         return self.least_squares(*features, alpha=alpha, l1_ratio=1.0, **kwargs)
