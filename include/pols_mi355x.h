@@ -425,6 +425,58 @@ typedef struct pols_ridge_cv_out {
 int pols_ridge_cv(pols_ctx *ctx, const pols_batch *b, const pols_ols_params *p, const pols_ridge_cv_params *q, pols_out *out,
                   const pols_ridge_cv_out *cv);
 
+/* Huber / Tukey-bisquare M-estimator per group by iteratively reweighted least squares (no reference counterpart; statsmodels'
+ * RLM with its MAD scale).  Per group g, the fitted rows F_g are exactly those pols_least_squares fits -- the same null-policy
+ * filtering / zero-filling and validity-mask rules, a null weight acting as 1e-24, the ones column last -- with
+ * x~_i = sqrt(w_i) x_i, y~_i = sqrt(w_i) y_i, n = |F_g|, kt = n_features + intercept.  All arithmetic is f64 on the inputs' values,
+ * for f32 batches too.
+ *   1. Start.  b^0 is the OLS solution on F_g: an f64 Gram matrix and a Cholesky factorisation with the pivot floor of the static
+ *      entries' f64 Cholesky -- a pivot fails when d^2 <= 16 kt eps A_jj.
+ *   2. Scale.  With r_i = y~_i - x~_i'b^t over F_g:  s = median(|r_i|) / 0.6744897501960817, the normalised MAD about zero.  The
+ *      median is exact; for even n it is the mean of the two middle order statistics.
+ *   3. Robust weights.  omega_i = psi(u_i) / u_i with u_i = |r_i| / s:
+ *        POLS_RLM_HUBER    = 0:  1 for u <= c, else c / u              (default c 1.345)
+ *        POLS_RLM_BISQUARE = 1:  (1 - (u / c)^2)^2 for u < c, else 0   (default c 4.685)
+ *   4. Update.  b^(t+1) solves (sum omega_i x~_i x~_i') b = sum omega_i x~_i y~_i by the same Cholesky rule.
+ *   5. Stop.  Converged when max_j |b^(t+1)_j - b^t_j| <= tol max(max_j |b^(t+1)_j|, 1e-300); otherwise the iteration stops after
+ *      max_iter updates with status POLS_GROUP_NOT_CONVERGED and the result is still returned.  n_iter is the number of updates made.
+ * Edge rules.
+ *   - n = 0: POLS_GROUP_EMPTY, zero coefficients, scale NaN, n_iter 0.
+ *   - POLS_GROUP_FALLBACK with NaN coef, pred, resid, scale and weights: n <= kt; a start that is not finite (NaNs under "ignore");
+ *     a Cholesky failure at the start or in any update (bisquare can zero out too many rows), or an update that is not finite.
+ *   - Scale collapse: s <= 16 eps max_{F_g} |y~_i|, or s not finite.  The iteration stops there AS CONVERGED with the current
+ *     coefficients -- an exact fit is not an error.
+ *   - The reported scale is the last s computed.  The reported weights are the omega used in the last update that was made: all
+ *     ones if none was made, NaN for the rows outside F_g.
+ * out->coef / pred / resid have the shape and the null-policy masking of pols_least_squares with those coefficients (predictions
+ * un-scaled, resid = y - pred, every row predicted or masked as that entry does); out->status per group as above, else
+ * POLS_GROUP_OK.  Sums run in a fixed order without floating-point atomics: two runs are bit-identical.
+ * From pols_ols_params only null_policy is read.  POLS_ERR_INVALID: alpha != 0, positive, or has_l1_ratio with l1_ratio > 0; an
+ * unknown norm; a non-finite c; max_iter < 1; tol not positive and finite; an unknown null policy; a validity mask without a
+ * drop-family policy.  POLS_ERR_UNSUPPORTED: more than 31 columns incl. the intercept; a group too long for a workgroup's LDS
+ * with more than 2^22 rows (such groups are walked by ONE workgroup per iteration pass; a form that splits them is not built).
+ * There is no Arrow twin of this entry. */
+enum { POLS_RLM_HUBER = 0, POLS_RLM_BISQUARE = 1 };
+
+typedef struct pols_rlm_params {
+    int32_t norm;             /* POLS_RLM_HUBER / POLS_RLM_BISQUARE          */
+    double  c;                /* tuning constant; <= 0: the norm's default   */
+    int32_t max_iter;         /* >= 1                                        */
+    double  tol;              /* positive and finite                         */
+} pols_rlm_params;
+
+/* norm = POLS_RLM_HUBER, c = 0 (the norm's default), max_iter = 50, tol = 1e-8 */
+void pols_rlm_params_default(pols_rlm_params *q);
+
+typedef struct pols_rlm_out {
+    double  *scale;           /* n_groups: the last s computed               */
+    int32_t *n_iter;          /* n_groups: updates made                      */
+    void    *weights;         /* n_rows, batch dtype: omega of the last update */
+} pols_rlm_out;               /* all live where b->mem says; any may be NULL */
+
+int pols_rlm(pols_ctx *ctx, const pols_batch *b, const pols_ols_params *p, const pols_rlm_params *q, pols_out *out,
+             const pols_rlm_out *r);
+
 /* ---- group-key ingestion: `.over(key)` / `group_by(key)` ------------------------------------------------------------
  * The reference's plugin functions never see a key column: Polars partitions the frame on the host and calls them once per
  * group (README.md:19, README.md:57 and :91 `.over("group")`, tests/test_ols.py:110, :384, :860).  The batched entries

@@ -12,6 +12,7 @@ from .least_squares import (  # noqa: F401
     compute_multi_target_least_squares,
     compute_least_squares_from_formula, compute_recursive_least_squares, compute_rolling_least_squares, predict,
     compute_ridge_cv, RidgeCV,
+    compute_rlm, RLM,
 )
 
 __version__ = "0.1.0"

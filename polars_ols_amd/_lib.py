@@ -119,6 +119,19 @@ class RidgeCvOut(C.Structure):        # pols_ridge_cv_out
     _fields_ = [(n, C.c_void_p) for n in RIDGE_CV_FIELDS]
 
 
+class RlmParams(C.Structure):         # pols_rlm_params
+    _fields_ = [("norm", C.c_int32), ("c", C.c_double), ("max_iter", C.c_int32), ("tol", C.c_double)]
+
+
+# pols_rlm_out, in the struct's order; the norms under statsmodels' names (POLS_RLM_*)
+RLM_FIELDS = ("scale", "n_iter", "weights")
+RLM_NORMS = {"huber": 0, "bisquare": 1}
+
+
+class RlmOut(C.Structure):            # pols_rlm_out
+    _fields_ = [(n, C.c_void_p) for n in RLM_FIELDS]
+
+
 EXPORTS = [
     "pols_device_count", "pols_version", "pols_last_error", "pols_create", "pols_destroy", "pols_set_stream",
     "pols_use_private_stream",
@@ -137,6 +150,7 @@ EXPORTS = [
     "pols_cluster_params_default", "pols_least_squares_statistics_cluster", "pols_least_squares_statistics_cluster_arrow",
     "pols_influence_params_default", "pols_least_squares_influence", "pols_least_squares_influence_arrow",
     "pols_ridge_cv_params_default", "pols_ridge_cv",
+    "pols_rlm_params_default", "pols_rlm",
 ]
 # measurement aids (include/pols_mi355x_debug.h): not part of the reference interface
 DEBUG_EXPORTS = ["pols_timing_enable", "pols_timing_collect", "pols_last_kernel_name", "pols_stream_probe", "pols_stream_probe_ex"]
@@ -203,6 +217,8 @@ def lib() -> C.CDLL:
         L.pols_ridge_cv_params_default.argtypes, L.pols_ridge_cv_params_default.restype = [C.POINTER(RidgeCvParams)], None
         L.pols_ridge_cv.argtypes = [C.c_void_p, C.POINTER(Batch), C.POINTER(OlsParams), C.POINTER(RidgeCvParams), C.POINTER(Out),
                                     C.POINTER(RidgeCvOut)]
+        L.pols_rlm_params_default.argtypes, L.pols_rlm_params_default.restype = [C.POINTER(RlmParams)], None
+        L.pols_rlm.argtypes = [C.c_void_p, C.POINTER(Batch), C.POINTER(OlsParams), C.POINTER(RlmParams), C.POINTER(Out), C.POINTER(RlmOut)]
         L.pols_layout_create.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.POINTER(C.c_void_p)]
         L.pols_layout_destroy.argtypes = [C.c_void_p]
         L.pols_layout_destroy.restype = None

@@ -22,6 +22,7 @@
 #include "k7i_influence.hpp"
 #include "k8_wide.hpp"
 #include "k10_ridge_path.hpp"
+#include "k11_rlm.hpp"
 #include "dyn_prep.hpp"
 
 namespace pols {
@@ -218,6 +219,7 @@ bool options_set(Options &o, const char *key, const char *v) {
     else if (ieq(key, "K1T_SUB32")) o.k1t_sub32 = on ? (std::atoi(v) != 0) : d.k1t_sub32;
     else if (ieq(key, "STATIC_ENGINE")) o.static_engine = !on ? 0 : ieq(v, "stream") ? 1 : ieq(v, "k2") ? 2 : ieq(v, "nok2") ? 3 : ieq(v, "k2w") ? 4 : 0;
     else if (ieq(key, "RLS_ENGINE")) o.rls_engine = !on ? 0 : ieq(v, "seq") ? 1 : ieq(v, "scan") ? 2 : ieq(v, "chunk") ? 3 : ieq(v, "halo") ? 4 : 0;
+    else if (ieq(key, "RLM_ENGINE")) o.rlm_engine = !on ? 0 : ieq(v, "stream") ? 1 : 0;
     else if (ieq(key, "RLS_SPINS")) o.rls_spin_limit = on ? std::atoi(v) : d.rls_spin_limit;
     else if (ieq(key, "RLS_EARLY")) o.rls_early = on ? std::atoi(v) : d.rls_early;
     else if (ieq(key, "ROLLING_ENGINE")) o.rolling_engine = !on ? 0 : ieq(v, "chunk") ? 1 : ieq(v, "halo") ? 2 : ieq(v, "nocompact") ? 3 : ieq(v, "halowave") ? 4 : ieq(v, "scatter") ? 5 : 0;
@@ -230,7 +232,7 @@ bool options_set(Options &o, const char *key, const char *v) {
 void options_from_env(Options &o) {
     static const char *const keys[] = {"TIMELINE", "K1_NOOCC4", "K1_NOFAST", "K1_NOTINY", "K1_NORC1", "K1_SHAPE", "K1_F64_TEAM",
                                        "KG_NOYV", "K2_NOPREFETCH", "K1_PASSES", "K1_WG", "RLS_SPINS", "RLS_EARLY", "K1T_RC4", "K1_NT_LOADS", "STATIC_ENGINE",
-                                       "RLS_ENGINE", "ROLLING_ENGINE", "K1_ENGINE", "K9_TAKE", "K1_PERSIST", "K1_PERSIST_SUB", "K1T_SUB32", "K1_NOEDGE", "K1T_SUB8",
+                                       "RLS_ENGINE", "RLM_ENGINE", "ROLLING_ENGINE", "K1_ENGINE", "K9_TAKE", "K1_PERSIST", "K1_PERSIST_SUB", "K1T_SUB32", "K1_NOEDGE", "K1T_SUB8",
                                        "K1_XCD", "NO_SPLIT", "DEBUG_SKIP_FIXUP", "K4P_LPS", "SEG_TARGET", "K1_RC2_WIDE", "KG_SINGLE_BUFFER", "PREDICT_LOOP", "NO_CLASSES"};
     char name[64];
     for (const char *k : keys) {
@@ -2012,6 +2014,104 @@ int pols_ridge_cv(pols_ctx *ctx, const pols_batch *b, const pols_ols_params *p, 
     if (ro->alpha_index) POLS_HIP(hipMemcpyAsync(ro->alpha_index, a.alpha_index, sizeof(int32_t) * G, hipMemcpyDeviceToHost, ctx->stream));
     if (ro->cv_scores) POLS_HIP(hipMemcpyAsync(ro->cv_scores, a.cv_scores, sizeof(double) * G * (size_t)na, hipMemcpyDeviceToHost, ctx->stream));
     if (ro->coef_path) POLS_HIP(hipMemcpyAsync(ro->coef_path, a.coef_path, sz * G * (size_t)na * kt, hipMemcpyDeviceToHost, ctx->stream));
+    return unstage_outputs(ctx, b, b->n_groups, kt, o, st);
+}
+
+void pols_rlm_params_default(pols_rlm_params *q) {
+    if (!q) return;
+    q->norm = POLS_RLM_HUBER;
+    q->c = 0.0;
+    q->max_iter = 50;
+    q->tol = 1e-8;
+}
+
+// K11 (k11_rlm.hip): the whole iteration of a group in one workgroup -- one launch for the groups that stay resident in LDS, one for
+// those that are streamed -- then K10's prediction pass with the f64 coefficients.
+int pols_rlm(pols_ctx *ctx, const pols_batch *b, const pols_ols_params *p, const pols_rlm_params *q, pols_out *o, const pols_rlm_out *ro) {
+    int rc = check_ctx(ctx);
+    if (rc) return rc;
+    if (b && o && b->n_features + (b->add_intercept ? 1 : 0) > K11_KMAX)
+        return fail(POLS_ERR_UNSUPPORTED, "rlm: %d features (incl. intercept) > %d", b->n_features + (b->add_intercept ? 1 : 0), K11_KMAX);
+    if ((rc = check_batch(b, o, K11_KMAX))) return rc;
+    if (!p || !q) return fail(POLS_ERR_INVALID, "params / rlm params is NULL");
+    if (p->alpha != 0.0 || p->positive || (p->has_l1_ratio && p->l1_ratio > 0.0))
+        return fail(POLS_ERR_INVALID, "rlm: alpha / positive / l1_ratio do not apply to the M-estimator");
+    if (q->norm != POLS_RLM_HUBER && q->norm != POLS_RLM_BISQUARE) return fail(POLS_ERR_INVALID, "rlm: unknown norm %d", q->norm);
+    if (!std::isfinite(q->c)) return fail(POLS_ERR_INVALID, "rlm: c is not finite");
+    if (q->max_iter < 1) return fail(POLS_ERR_INVALID, "rlm: max_iter %d < 1", q->max_iter);
+    if (!(q->tol > 0.0) || !std::isfinite(q->tol)) return fail(POLS_ERR_INVALID, "rlm: tol %g is not positive and finite", q->tol);
+    if (p->null_policy < POLS_NULL_IGNORE || p->null_policy > POLS_NULL_DROP_WINDOW) return fail(POLS_ERR_INVALID, "unknown null_policy %d", p->null_policy);
+    const int pol = (b->null_free && !b->valid) ? POLS_NULL_IGNORE : p->null_policy;
+    if (b->valid && (pol == POLS_NULL_IGNORE || pol == POLS_NULL_ZERO))
+        return fail(POLS_ERR_INVALID, "a validity mask needs a drop-family null_policy");
+    if (b->n_groups == 0) return POLS_OK;
+    pols_rlm_out none;
+    std::memset(&none, 0, sizeof(none));
+    if (!ro) ro = &none;
+    const int kt = b->n_features + (b->add_intercept ? 1 : 0);
+    const bool host = b->mem == POLS_MEM_HOST;
+    const size_t G = (size_t)b->n_groups, sz = dtype_size(b->dtype);
+    // which form serves which group: the tiles a group spans from the 16-byte grid point at or below its first row
+    const int vec = b->dtype == POLS_F32 ? 4 : 2;
+    const int cap = ctx->opt.rlm_engine == 1 ? -1 : k11_resident_tiles(kt);
+    int64_t n_res = 0, n_str = 0, res_tiles = 0, str_rows = 0;
+    for (int64_t g = 0; g < b->n_groups; ++g) {
+        const int64_t s = b->group_offsets[g], e = b->group_offsets[g + 1];
+        if (e < s) return fail(POLS_ERR_INVALID, "group_offsets must not decrease");
+        const int64_t tiles = e > s ? (e - (s & ~(int64_t)(vec - 1)) + 255) / 256 : 0;
+        if (tiles <= cap) { ++n_res; res_tiles = std::max(res_tiles, tiles); }
+        else { ++n_str; str_rows = std::max(str_rows, e - s); }
+    }
+    if (str_rows > K11_STREAM_MAX_ROWS)
+        return fail(POLS_ERR_UNSUPPORTED, "rlm: a group of %lld rows > %lld (one workgroup walks a streamed group; the split form is not built)",
+                    (long long)str_rows, (long long)K11_STREAM_MAX_ROWS);
+    const int64_t *d_offs = nullptr;
+    int64_t max_rows = 0;
+    if ((rc = upload_offsets(ctx, b->group_offsets, b->n_groups, &d_offs, &max_rows, b->offsets_generation))) return rc;
+    Staged st;
+    if ((rc = stage_inputs(ctx, b, b->n_groups, kt, o, &st))) return rc;
+    if ((rc = fill_null_weights(ctx, b, &st))) return rc;
+    void *wc = nullptr, *wr = nullptr, *wo = nullptr;
+    if ((rc = ensure_scratch(ctx, Work::RlmCoef, round256(sizeof(double) * G * kt), &wc))) return rc;
+    if (n_str > 0 && (rc = ensure_scratch(ctx, Work::RlmRows, round256(sizeof(double) * (size_t)b->n_rows), &wr))) return rc;
+    RlmArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.y = st.y; a.w = st.w;
+    for (int j = 0; j < b->n_features; ++j) a.x[j] = st.x[(size_t)j];
+    a.offs = d_offs; a.n_groups = b->n_groups; a.n_rows = b->n_rows;
+    a.valid = st.valid; a.null_policy = pol;
+    a.k_user = b->n_features; a.kt = kt; a.f32 = b->dtype == POLS_F32 ? 1 : 0;
+    a.norm = q->norm; a.max_iter = q->max_iter; a.tol = q->tol;
+    a.c = q->c > 0.0 ? q->c : (q->norm == POLS_RLM_HUBER ? 1.345 : 4.685);
+    a.res_tiles = cap; a.ts = (int32_t)res_tiles * 256 + 1;
+    a.rows = static_cast<double *>(wr);
+    a.coef64 = static_cast<double *>(wc);
+    a.coef = st.coef; a.status = st.status;
+    const size_t vecb = round256(sizeof(double) * G), idxb = round256(sizeof(int32_t) * G), rowb = round256(sz * (size_t)b->n_rows);
+    if (host) {
+        if ((rc = ensure_scratch(ctx, Work::RlmOut, vecb + idxb + rowb, &wo))) return rc;
+        char *c = static_cast<char *>(wo);
+        if (ro->scale) a.scale = reinterpret_cast<double *>(c);
+        if (ro->n_iter) a.n_iter = reinterpret_cast<int32_t *>(c + vecb);
+        if (ro->weights) a.weights = c + vecb + idxb;
+    } else {
+        a.scale = ro->scale; a.n_iter = ro->n_iter; a.weights = ro->weights;
+    }
+    ctx->last_kernel = n_res >= n_str ? "k11_rlm_resident" : "k11_rlm_stream";
+    if (n_res > 0 && (rc = k11_rlm_launch(ctx, b->dtype, a, true))) return rc;
+    if (n_str > 0 && (rc = k11_rlm_launch(ctx, b->dtype, a, false))) return rc;
+    RidgeCvArgs pa;                                            // K10's prediction pass from the f64 coefficients
+    std::memset(&pa, 0, sizeof(pa));
+    pa.y = a.y; pa.w = a.w;
+    for (int j = 0; j < b->n_features; ++j) pa.x[j] = a.x[j];
+    pa.offs = d_offs; pa.n_groups = b->n_groups; pa.n_rows = b->n_rows;
+    pa.valid = a.valid; pa.null_policy = pol; pa.k_user = a.k_user; pa.kt = kt;
+    pa.coef64 = a.coef64; pa.pred = st.pred; pa.resid = st.resid;
+    if ((rc = k10_predict_launch(ctx, b->dtype, pa))) return rc;
+    if (!host) return POLS_OK;
+    if (ro->scale) POLS_HIP(hipMemcpyAsync(ro->scale, a.scale, sizeof(double) * G, hipMemcpyDeviceToHost, ctx->stream));
+    if (ro->n_iter) POLS_HIP(hipMemcpyAsync(ro->n_iter, a.n_iter, sizeof(int32_t) * G, hipMemcpyDeviceToHost, ctx->stream));
+    if (ro->weights) POLS_HIP(hipMemcpyAsync(ro->weights, a.weights, sz * (size_t)b->n_rows, hipMemcpyDeviceToHost, ctx->stream));
     return unstage_outputs(ctx, b, b->n_groups, kt, o, st);
 }
 

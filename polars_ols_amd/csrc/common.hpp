@@ -80,6 +80,9 @@ enum class Work : int {
     RidgeCvGram,    // ridge path (K10): Gram partials per segment / group, then V, s, V'X~'y~ and the fitted rows per group
     RidgeCvScores,  // ridge path (K10): the candidates, score partials per segment / group, the winners' coefficients in f64
     RidgeCvOut,     // ridge path (K10): alpha / score / alpha_index / cv_scores / coef_path of a HOST batch before they go home
+    RlmCoef,        // M-estimator (K11): the groups' coefficients in f64 for the prediction pass
+    RlmRows,        // M-estimator (K11): |r| / omega per row of the groups the streamed form serves (f64)
+    RlmOut,         // M-estimator (K11): scale / n_iter / weights of a HOST batch before they go home
     Count
 };
 
@@ -124,6 +127,7 @@ struct Options {
     int seg_target = 0;           // POLS_SEG_TARGET     streamed static path: rows per segment of a cut group (0: the default rule)
     int k4p_lps = 0;              // POLS_K4P_LPS        K4p / K3p (k4p_wide.hip): lanes per sequence, 0 auto, 64 / 16 (up to 16 features) / 32 (17..32, RLS)
     int k1_wg = 0;                // POLS_K1_WG          8-column team kernels: 2 / 4 = 512- / 1 024-thread workgroups (2 / 4 times the groups per workgroup, A/B)
+    int rlm_engine = 0;           // POLS_RLM_ENGINE     0 auto (groups that fit the LDS stay resident), 1 "stream" (K11's streamed form for every group)
     int k1_xcd = 0;               // POLS_K1_XCD         resident K1 kernels: 1 = XCD-contiguous workgroup -> group map (each XCD walks one eighth of the frame)
 };
 void options_from_env(Options &o);

@@ -334,6 +334,35 @@ class Engine:
         L.check(self._lib.pols_ridge_cv(self._h, C.byref(plan._b), C.byref(plan._p), C.byref(q), C.byref(plan._o), C.byref(ro)))
         return res
 
+    def rlm(self, y, x_cols: Sequence, offsets, *, norm: str = "huber", c: Optional[float] = None, max_iter: int = 50, tol: float = 1e-8,
+            want: Sequence[str] = ("coef", "status", "scale", "n_iter"), weights=None, valid=None, add_intercept: bool = False,
+            null_policy: str = "ignore") -> Dict:
+        """Huber / bisquare M-estimator for every group in one call: iteratively reweighted least squares with the MAD scale,
+        the whole iteration on the device (pols_rlm; the definitions and edge rules are in include/pols_mi355x.h).  ``norm``:
+        "huber" or "bisquare"; ``c``: the tuning constant (None: 1.345 / 4.685).  ``want``: any of ``coef pred resid status``
+        (status 3 = stopped at ``max_iter``), ``scale`` [n_groups, f64], ``n_iter`` [n_groups, int32] and the robust ``weights``
+        [n_rows, batch dtype, NaN for the rows outside the fit].  Arrays are numpy or torch and live where the inputs live."""
+        q = _rlm_params(self._lib, norm, c, max_iter, tol)
+        want = tuple(want)
+        known = ("coef", "pred", "resid", "status") + L.RLM_FIELDS
+        unknown = [w for w in want if w not in known]
+        if unknown:
+            raise ValueError(f"unknown rlm fields {unknown}; known: {list(known)}")
+        plan = self.plan_least_squares(y, x_cols, offsets, weights=weights, valid=valid, add_intercept=add_intercept,
+                                       null_policy=null_policy, want=tuple(w for w in want if w in ("coef", "pred", "resid", "status")))
+        b = plan._b
+        dev = b.mem == L.POLS_MEM_DEVICE
+        like = plan._keep[0][0]
+        res = plan.results
+        f64, i32 = (torch.float64, torch.int32) if dev else (np.float64, np.int32)
+        shapes = {"scale": ((b.n_groups,), f64), "n_iter": ((b.n_groups,), i32), "weights": ((b.n_rows,), like.dtype)}
+        for key in L.RLM_FIELDS:
+            if key in want:
+                res[key] = self._alloc(dev, shapes[key][1], shapes[key][0], like)
+        ro = L.RlmOut(**{k: self._ptr(res.get(k)) for k in L.RLM_FIELDS})
+        L.check(self._lib.pols_rlm(self._h, C.byref(plan._b), C.byref(plan._p), C.byref(q), C.byref(plan._o), C.byref(ro)))
+        return res
+
     def least_squares(self, y, x_cols: Sequence, offsets, **kwargs) -> Dict:
         """All groups of a (group-sorted) frame in one launch.  ``want`` subset of {"coef","pred","resid","status"};
         ``out`` may carry pre-allocated buffers under the same keys."""
@@ -615,6 +644,23 @@ def _ols_params(lib, alpha=0.0, l1_ratio=None, max_iter=1000, tol=1e-5, positive
     p.has_rcond, p.rcond = int(rcond is not None), float(rcond) if rcond is not None else 0.0
     p.null_policy = L.NULL_POLICIES[null_policy]
     return p
+
+
+def _rlm_params(lib, norm, c, max_iter, tol) -> "L.RlmParams":
+    """the argument checks of Engine.rlm / compute_rlm (``lib`` None: check only, no device needed)"""
+    if norm not in L.RLM_NORMS:
+        raise ValueError(f"rlm: 'norm' must be one of {sorted(L.RLM_NORMS)}, got {norm!r}")
+    if c is not None and not (np.isfinite(c) and c > 0):
+        raise ValueError(f"rlm: 'c' must be positive and finite or None (got {c!r})")
+    if int(max_iter) != max_iter or max_iter < 1:
+        raise ValueError(f"rlm: 'max_iter' must be an integer >= 1 (got {max_iter!r})")
+    if not (np.isfinite(tol) and tol > 0):
+        raise ValueError(f"rlm: 'tol' must be positive and finite (got {tol!r})")
+    q = L.RlmParams()
+    if lib is not None:
+        lib.pols_rlm_params_default(C.byref(q))
+    q.norm, q.c, q.max_iter, q.tol = L.RLM_NORMS[norm], float(c) if c is not None else 0.0, int(max_iter), float(tol)
+    return q
 
 
 def _ridge_cv_grid(alphas) -> np.ndarray:

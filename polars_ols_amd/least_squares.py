@@ -26,7 +26,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import PolsPanic
-from .engine import Engine, Layout, _is_torch, _ridge_cv_grid, default_engine
+from .engine import Engine, Layout, _is_torch, _ridge_cv_grid, _rlm_params, default_engine
 
 try:
     import torch
@@ -41,6 +41,7 @@ __all__ = [
     "OLSKwargs", "RLSKwargs", "RollingKwargs", "NullPolicy", "OutputMode", "SolveMethod",
     "Frame", "Expr", "col", "struct", "Coefficients", "Statistics", "Influence", "LeastSquares",
     "compute_ridge_cv", "RidgeCV",
+    "compute_rlm", "RLM",
 ]
 
 # ---- polars_ols/least_squares.py:47-63 --------------------------------------------------------------------------
@@ -454,6 +455,39 @@ def _apply_ridge_cv(frame: Frame, over, eng: Optional[Engine], target: Expr, fea
     return target.output_name, grp.untake(out["pred"] if mode == "predictions" else out["resid"])
 
 
+class RLM(dict):
+    """mode="rlm" of an M-estimator fit (pols_rlm; the definitions are in include/pols_mi355x.h): per group ``coef`` [G, k],
+    ``scale`` (the last MAD scale), ``n_iter`` (updates made) and ``status`` (0 converged, 1 no fit, 2 no rows, 3 stopped at
+    max_iter) [G]; ``weights`` holds the robust weights of the last update in FRAME order (NaN for the rows outside the fit);
+    ``keys`` holds the group keys of an ``.over`` (None for a whole-frame fit, where G == 1)."""
+
+    def __init__(self, out, keys, weights, norm, c):
+        super().__init__(coef=out["coef"], scale=out["scale"], n_iter=out["n_iter"], status=out["status"], weights=weights,
+                         keys=keys, norm=norm, c=c)
+        self.keys_ = keys
+
+
+_VALID_RLM_MODES = ("predictions", "residuals", "coefficients", "rlm")
+
+
+def _apply_rlm(frame: Frame, over, eng: Optional[Engine], target: Expr, features: Sequence[Expr], sample_weights,
+               add_intercept: bool, mode: str, norm: str, c, max_iter: int, tol: float, null_policy: str):
+    """compute_rlm body: the group layout of _apply_static around Engine.rlm."""
+    y, xs, names, icpt, w = _pre_process_data(frame, target, features, sample_weights, add_intercept)
+    eng = eng or default_engine(y.device.index or 0 if _is_torch(y) else 0)
+    grp = _Groups(eng, None if over is None else (frame[over] if isinstance(over, str) else over), y.shape[0])
+    moved = grp.take([y, w] + list(xs))
+    want = {"predictions": ("pred",), "residuals": ("resid",), "coefficients": ("coef",),
+            "rlm": ("coef", "status", "scale", "n_iter", "weights")}[mode]
+    out = eng.rlm(moved[0], moved[2:], grp.offsets, norm=norm, c=c, max_iter=max_iter, tol=tol, want=want, weights=moved[1],
+                  add_intercept=icpt, null_policy=null_policy)
+    if mode == "rlm":
+        return "rlm", RLM(out, grp.keys, grp.untake(out["weights"]), norm, c)
+    if mode == "coefficients":
+        return "coefficients", Coefficients(names, out["coef"], grp.keys, grp.gid_frame(out["coef"]))
+    return target.output_name, grp.untake(out["pred"] if mode == "predictions" else out["resid"])
+
+
 def _apply_dynamic(frame: Frame, over, eng: Optional[Engine], target: Expr, features: Sequence[Expr], sample_weights,
                    add_intercept: bool, mode: str, kind: str, kw):
     """compute_recursive_least_squares / compute_rolling_least_squares bodies (ls.py:332-409 around
@@ -577,6 +611,21 @@ def compute_ridge_cv(target, *features, alphas, sample_weights=None, add_interce
     grid = _ridge_cv_grid(alphas)
     t, fs = parse_into_expr(target), [parse_into_expr(f) for f in features]
     return Expr(t._name, fn=lambda frame, over, eng: _apply_ridge_cv(frame, over, eng, t, fs, sample_weights, add_intercept, mode, grid, null_policy))
+
+
+def compute_rlm(target, *features, norm: str = "huber", c: Optional[float] = None, max_iter: int = 50, tol: float = 1e-8,
+                sample_weights=None, add_intercept: bool = False, mode: str = "predictions", null_policy: str = "ignore") -> Expr:
+    """Huber / bisquare M-estimator regression per group (statsmodels' RLM with its MAD scale for every group of the frame in
+    one call).  Modes "predictions", "residuals" and "coefficients" are those of the robust coefficients; mode="rlm" returns an
+    ``RLM`` with the coefficients, scale, iteration count, status and the robust weights in frame order."""
+    if mode not in _VALID_RLM_MODES:
+        raise ValueError(f"'mode' must be one of {_VALID_RLM_MODES}, got {mode!r}")
+    if null_policy not in _VALID_NULL_POLICIES:
+        raise ValueError(f"'null_policy' must be one of {sorted(_VALID_NULL_POLICIES)}, got {null_policy!r}")
+    _rlm_params(None, norm, c, max_iter, tol)
+    t, fs = parse_into_expr(target), [parse_into_expr(f) for f in features]
+    return Expr(t._name, fn=lambda frame, over, eng: _apply_rlm(frame, over, eng, t, fs, sample_weights, add_intercept, mode, norm, c,
+                                                                max_iter, tol, null_policy))
 
 
 def compute_multi_target_least_squares(targets, *features, sample_weights=None, add_intercept: bool = False,
@@ -823,6 +872,11 @@ class LeastSquares:
                  null_policy: str = "ignore") -> Expr:
         return compute_ridge_cv(self._expr, *features, alphas=alphas, sample_weights=sample_weights, add_intercept=add_intercept,
                                 mode=mode, null_policy=null_policy)
+
+    def rlm(self, *features, norm: str = "huber", c: Optional[float] = None, max_iter: int = 50, tol: float = 1e-8,
+            sample_weights=None, add_intercept: bool = False, mode: str = "predictions", null_policy: str = "ignore") -> Expr:
+        return compute_rlm(self._expr, *features, norm=norm, c=c, max_iter=max_iter, tol=tol, sample_weights=sample_weights,
+                           add_intercept=add_intercept, mode=mode, null_policy=null_policy)
 
     def lasso(self, *features, alpha: float, **kwargs) -> Expr:
         return self.least_squares(*features, alpha=alpha, l1_ratio=1.0, **kwargs)
