@@ -477,6 +477,73 @@ typedef struct pols_rlm_out {
 int pols_rlm(pols_ctx *ctx, const pols_batch *b, const pols_ols_params *p, const pols_rlm_params *q, pols_out *out,
              const pols_rlm_out *r);
 
+/* Elastic-net / lasso regularisation path with K-fold selection of alpha, per group (no reference counterpart: the reference's
+ * lasso / elastic_net take one alpha for the whole frame; this is the job of scikit-learn's LassoCV / ElasticNetCV with
+ * fit_intercept=False and cv=KFold(n_folds)).  There is no Arrow twin of this entry.
+ * Fitted rows.  Per group g, the fitted rows F_g are exactly those pols_least_squares / pols_ridge_cv fit -- the same null-policy
+ * filtering / zero-filling and validity-mask rules, a null weight acting as 1e-24, the ones column last -- with
+ * x~_i = sqrt(w_i) x_i, y~_i = sqrt(w_i) y_i, n = |F_g|, kt = n_features + intercept.  All arithmetic is f64 on the inputs' values,
+ * for f32 batches too.
+ * Folds.  n_folds contiguous folds over the FITTED rows in row order: the fitted row of rank r (0-based among F_g) belongs to the
+ * fold scikit-learn's KFold(shuffle=False) gives it -- the first n % n_folds folds hold n / n_folds + 1 rows, the rest n / n_folds.
+ * With a drop-family policy the result therefore equals "filter, then fit".  n_f is the size of fold f.
+ * Candidates.  Explicit: params.alphas is a HOST array in any order, each finite and >= 0.  Automatic: alphas == NULL,
+ * n_alphas >= 2, 0 < eps < 1, l1_ratio > 0; per group alpha_max = max_j |X~'y~|_j / (n l1_ratio) over the full data and
+ * a_j = alpha_max eps^(j / (n_alphas - 1)) (scikit-learn's grid for fit_intercept=False), formed on the device and returned in
+ * alphas_used.  An alpha_max that is not positive and finite makes the group a POLS_GROUP_FALLBACK.
+ * Fits.  With G = X~'X~, c = X~'y~ over the rows of a fit and m the NUMBER OF ROWS OF THAT FIT (n - n_f for the training
+ * problem of fold f, n for the full data), candidate a minimises the reference's objective (solve_elastic_net,
+ * src/least_squares.rs:386-492, cyclic `cd` only) by its iteration in Gram form: one sweep updates j = 0 .. kt - 1 in order,
+ *   w_j <- S(c_j - sum_{i != j} G_ji w_i, a m l1_ratio) / (G_jj + a m (1 - l1_ratio)),   S the soft threshold (max(., 0) of it when
+ * `positive`), and the fit stops after the first sweep with ||w_new - w_old||_2 < tol, or after max_iter sweeps.  Candidates are
+ * visited in order of descending alpha, equal values in index order; the first starts from zeros, each later one from its
+ * predecessor's solution.  This is done independently for each of the n_folds training problems and for the full data.
+ * Scores.  cv_scores[g][j] = (1 / n_folds) sum_f max(0, yy_f - 2 b'c_f + b'G_f b) / n_f with b the fold-f fit at candidate j and
+ * G_f, c_f, yy_f the Gram matrix of the rows of fold f: the unweighted mean over the folds of the validation mean squared error on
+ * the scaled rows.  It is computed from the fold's Gram matrix, not from residuals, so its relative accuracy is about
+ * eps yy_f / rss_f.  Chosen: the candidate with the smallest finite score, the lowest index on an exact tie; a NaN score is never
+ * chosen.
+ * Outputs.  out->coef / pred / resid: the full-data path's coefficients at the chosen index, with the shape and the null-policy
+ * masking of pols_least_squares with those coefficients.  Because of the warm starts they differ from a cold-started
+ * elastic_net(alpha = chosen) by at most the stopping tolerance.  n_iter[g][j] is the largest sweep count among the n_folds + 1
+ * fits of candidate j.  coef_path is the full-data path.
+ * out->status per group: POLS_GROUP_EMPTY for n = 0 (zero coefficients, NaN scores, index -1); POLS_GROUP_FALLBACK for
+ * 0 < n < n_folds, a bad automatic grid or no finite score (coef, pred, resid, alpha, score NaN, index -1); in both cases, and
+ * whenever n < n_folds or the automatic grid is bad, cv_scores and coef_path are NaN, n_iter 0, and alphas_used is NaN in automatic
+ * mode (the explicit candidates otherwise).  POLS_GROUP_NOT_CONVERGED when the stop rule never fired within max_iter sweeps in one
+ * of the chosen candidate's n_folds + 1 fits (results are still returned); POLS_GROUP_OK otherwise.
+ * Sums run in a fixed order without floating-point atomics: two runs are bit-identical.
+ * From pols_ols_params only null_policy is read.  POLS_ERR_INVALID: l1_ratio outside [0, 1] or not finite; a negative or non-finite
+ * candidate; n_alphas < 1, or < 2 in automatic mode; eps outside (0, 1) or l1_ratio == 0 in automatic mode; n_folds outside
+ * 2 .. 16; max_iter < 1; tol not positive and finite; an unknown null policy; a validity mask without a drop-family policy.
+ * POLS_ERR_UNSUPPORTED: more than 31 columns incl. the intercept; more than 128 candidates. */
+typedef struct pols_enet_cv_params {
+    const double *alphas;     /* HOST array, any order, each >= 0 and finite; NULL: the automatic grid */
+    int32_t n_alphas;
+    double  eps;              /* automatic grid: alpha_min / alpha_max, in (0, 1)  */
+    double  l1_ratio;         /* in [0, 1]; 1 = lasso                              */
+    int32_t n_folds;          /* 2 .. 16                                           */
+    int32_t max_iter;         /* >= 1                                              */
+    double  tol;              /* positive and finite                               */
+    int32_t positive;         /* non-zero: coefficients >= 0                       */
+} pols_enet_cv_params;
+
+/* alphas = NULL, n_alphas = 100, eps = 1e-3, l1_ratio = 0.5, n_folds = 5, max_iter = 1000, tol = 1e-5, positive = 0 */
+void pols_enet_cv_params_default(pols_enet_cv_params *q);
+
+typedef struct pols_enet_cv_out {
+    double  *alpha;           /* n_groups: the chosen alpha                                  */
+    int32_t *alpha_index;     /* n_groups: its index among the candidates, -1 if none        */
+    double  *score;           /* n_groups: its mean validation error                         */
+    double  *cv_scores;       /* n_groups x n_alphas, row-major                              */
+    double  *alphas_used;     /* n_groups x n_alphas: every group's candidates               */
+    void    *coef_path;       /* n_groups x n_alphas x kt, batch dtype: the full-data path   */
+    int32_t *n_iter;          /* n_groups x n_alphas: most sweeps among the n_folds + 1 fits */
+} pols_enet_cv_out;           /* all live where b->mem says; any may be NULL */
+
+int pols_elastic_net_cv(pols_ctx *ctx, const pols_batch *b, const pols_ols_params *p, const pols_enet_cv_params *q, pols_out *out,
+                        const pols_enet_cv_out *cv);
+
 /* ---- group-key ingestion: `.over(key)` / `group_by(key)` ------------------------------------------------------------
  * The reference's plugin functions never see a key column: Polars partitions the frame on the host and calls them once per
  * group (README.md:19, README.md:57 and :91 `.over("group")`, tests/test_ols.py:110, :384, :860).  The batched entries

@@ -132,6 +132,21 @@ class RlmOut(C.Structure):            # pols_rlm_out
     _fields_ = [(n, C.c_void_p) for n in RLM_FIELDS]
 
 
+class EnetCvParams(C.Structure):      # pols_enet_cv_params
+    _fields_ = [("alphas", C.POINTER(C.c_double)), ("n_alphas", C.c_int32), ("eps", C.c_double), ("l1_ratio", C.c_double),
+                ("n_folds", C.c_int32), ("max_iter", C.c_int32), ("tol", C.c_double), ("positive", C.c_int32)]
+
+
+# pols_enet_cv_out, in the struct's order
+ENET_CV_FIELDS = ("alpha", "alpha_index", "score", "cv_scores", "alphas_used", "coef_path", "n_iter")
+ENET_CV_MAX_ALPHAS = 128
+ENET_CV_MAX_FOLDS = 16
+
+
+class EnetCvOut(C.Structure):         # pols_enet_cv_out
+    _fields_ = [(n, C.c_void_p) for n in ENET_CV_FIELDS]
+
+
 EXPORTS = [
     "pols_device_count", "pols_version", "pols_last_error", "pols_create", "pols_destroy", "pols_set_stream",
     "pols_use_private_stream",
@@ -151,6 +166,7 @@ EXPORTS = [
     "pols_influence_params_default", "pols_least_squares_influence", "pols_least_squares_influence_arrow",
     "pols_ridge_cv_params_default", "pols_ridge_cv",
     "pols_rlm_params_default", "pols_rlm",
+    "pols_enet_cv_params_default", "pols_elastic_net_cv",
 ]
 # measurement aids (include/pols_mi355x_debug.h): not part of the reference interface
 DEBUG_EXPORTS = ["pols_timing_enable", "pols_timing_collect", "pols_last_kernel_name", "pols_stream_probe", "pols_stream_probe_ex"]
@@ -219,6 +235,9 @@ def lib() -> C.CDLL:
                                     C.POINTER(RidgeCvOut)]
         L.pols_rlm_params_default.argtypes, L.pols_rlm_params_default.restype = [C.POINTER(RlmParams)], None
         L.pols_rlm.argtypes = [C.c_void_p, C.POINTER(Batch), C.POINTER(OlsParams), C.POINTER(RlmParams), C.POINTER(Out), C.POINTER(RlmOut)]
+        L.pols_enet_cv_params_default.argtypes, L.pols_enet_cv_params_default.restype = [C.POINTER(EnetCvParams)], None
+        L.pols_elastic_net_cv.argtypes = [C.c_void_p, C.POINTER(Batch), C.POINTER(OlsParams), C.POINTER(EnetCvParams), C.POINTER(Out),
+                                          C.POINTER(EnetCvOut)]
         L.pols_layout_create.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.POINTER(C.c_void_p)]
         L.pols_layout_destroy.argtypes = [C.c_void_p]
         L.pols_layout_destroy.restype = None

@@ -23,6 +23,7 @@
 #include "k8_wide.hpp"
 #include "k10_ridge_path.hpp"
 #include "k11_rlm.hpp"
+#include "k12_enet_cv.hpp"
 #include "dyn_prep.hpp"
 
 namespace pols {
@@ -2112,6 +2113,148 @@ int pols_rlm(pols_ctx *ctx, const pols_batch *b, const pols_ols_params *p, const
     if (ro->scale) POLS_HIP(hipMemcpyAsync(ro->scale, a.scale, sizeof(double) * G, hipMemcpyDeviceToHost, ctx->stream));
     if (ro->n_iter) POLS_HIP(hipMemcpyAsync(ro->n_iter, a.n_iter, sizeof(int32_t) * G, hipMemcpyDeviceToHost, ctx->stream));
     if (ro->weights) POLS_HIP(hipMemcpyAsync(ro->weights, a.weights, sz * (size_t)b->n_rows, hipMemcpyDeviceToHost, ctx->stream));
+    return unstage_outputs(ctx, b, b->n_groups, kt, o, st);
+}
+
+void pols_enet_cv_params_default(pols_enet_cv_params *q) {
+    if (!q) return;
+    q->alphas = nullptr;
+    q->n_alphas = 100;
+    q->eps = 1e-3;
+    q->l1_ratio = 0.5;
+    q->n_folds = 5;
+    q->max_iter = 1000;
+    q->tol = 1e-5;
+    q->positive = 0;
+}
+
+// K12 (k12_enet_cv.hip): fold Gram matrices in one pass over the frame (behind a count pass when the null policy can remove rows),
+// the (n_folds + 1) x n_alphas coordinate-descent fits on chip, pick, then K10's prediction pass with the winner's coefficients.
+int pols_elastic_net_cv(pols_ctx *ctx, const pols_batch *b, const pols_ols_params *p, const pols_enet_cv_params *q, pols_out *o,
+                        const pols_enet_cv_out *ro) {
+    int rc = check_ctx(ctx);
+    if (rc) return rc;
+    if (b && o && b->n_features + (b->add_intercept ? 1 : 0) > K12_KMAX)
+        return fail(POLS_ERR_UNSUPPORTED, "elastic_net_cv: %d features (incl. intercept) > %d", b->n_features + (b->add_intercept ? 1 : 0), K12_KMAX);
+    if ((rc = check_batch(b, o, K12_KMAX))) return rc;
+    if (!p || !q) return fail(POLS_ERR_INVALID, "params / elastic_net_cv params is NULL");
+    const bool automatic = q->alphas == nullptr;
+    if (!(q->l1_ratio >= 0.0 && q->l1_ratio <= 1.0)) return fail(POLS_ERR_INVALID, "elastic_net_cv: l1_ratio %g outside [0, 1]", q->l1_ratio);
+    if (q->n_alphas < 1) return fail(POLS_ERR_INVALID, "elastic_net_cv: the grid of candidates is empty");
+    if (q->n_alphas > K12_MAX_ALPHAS) return fail(POLS_ERR_UNSUPPORTED, "elastic_net_cv: %d candidates > %d", q->n_alphas, K12_MAX_ALPHAS);
+    if (automatic) {
+        if (q->n_alphas < 2) return fail(POLS_ERR_INVALID, "elastic_net_cv: an automatic grid needs at least 2 candidates");
+        if (!(q->eps > 0.0 && q->eps < 1.0)) return fail(POLS_ERR_INVALID, "elastic_net_cv: eps %g outside (0, 1)", q->eps);
+        if (q->l1_ratio == 0.0) return fail(POLS_ERR_INVALID, "elastic_net_cv: an automatic grid needs l1_ratio > 0");
+    } else {
+        for (int j = 0; j < q->n_alphas; ++j)
+            if (!(q->alphas[j] >= 0.0) || !std::isfinite(q->alphas[j])) return fail(POLS_ERR_INVALID, "elastic_net_cv: candidate %d is negative or not finite", j);
+    }
+    if (q->n_folds < 2 || q->n_folds > K12_MAX_FOLDS) return fail(POLS_ERR_INVALID, "elastic_net_cv: %d folds outside 2..%d", q->n_folds, K12_MAX_FOLDS);
+    if (q->max_iter < 1) return fail(POLS_ERR_INVALID, "elastic_net_cv: max_iter %d < 1", q->max_iter);
+    if (!(q->tol > 0.0) || !std::isfinite(q->tol)) return fail(POLS_ERR_INVALID, "elastic_net_cv: tol %g is not positive and finite", q->tol);
+    if (p->null_policy < POLS_NULL_IGNORE || p->null_policy > POLS_NULL_DROP_WINDOW) return fail(POLS_ERR_INVALID, "unknown null_policy %d", p->null_policy);
+    const int pol = (b->null_free && !b->valid) ? POLS_NULL_IGNORE : p->null_policy;
+    if (b->valid && (pol == POLS_NULL_IGNORE || pol == POLS_NULL_ZERO))
+        return fail(POLS_ERR_INVALID, "a validity mask needs a drop-family null_policy");
+    if (b->n_groups == 0) return POLS_OK;
+    pols_enet_cv_out none;
+    std::memset(&none, 0, sizeof(none));
+    if (!ro) ro = &none;
+    const int kt = b->n_features + (b->add_intercept ? 1 : 0), na = q->n_alphas, nf = q->n_folds;
+    const bool host = b->mem == POLS_MEM_HOST;
+    const size_t G = (size_t)b->n_groups, sz = dtype_size(b->dtype);
+    const int64_t *d_offs = nullptr;
+    int64_t max_rows = 0;
+    if ((rc = upload_offsets(ctx, b->group_offsets, b->n_groups, &d_offs, &max_rows, b->offsets_generation))) return rc;
+    Staged st;
+    if ((rc = stage_inputs(ctx, b, b->n_groups, kt, o, &st))) return rc;
+    if ((rc = fill_null_weights(ctx, b, &st))) return rc;
+    SegTables sg;
+    if ((rc = ensure_segments(ctx, b, max_rows, 0, &sg))) return rc;
+    const bool split = sg.n_seg > 0;
+    const size_t items = split ? (size_t)sg.n_seg : G;
+    const size_t per = (size_t)nf * k10_gram_stride(kt);
+    const size_t cntb = round256(sizeof(int64_t) * items), partb = round256(sizeof(double) * items * per),
+                 foldb = split ? round256(sizeof(double) * G * per) : 0;
+    const size_t alb = round256(sizeof(double) * (size_t)na + sizeof(int32_t) * (size_t)na), scb = round256(sizeof(double) * G * nf * (size_t)na),
+                 itb = round256(sizeof(int32_t) * G * (nf + 1) * (size_t)na), p64b = round256(sizeof(double) * G * (size_t)na * kt),
+                 grb = round256(sizeof(double) * G * (size_t)na), c64b = round256(sizeof(double) * G * kt);
+    void *wg = nullptr, *ws = nullptr, *wo = nullptr;
+    if ((rc = ensure_scratch(ctx, Work::EnetCvGram, cntb + partb + foldb, &wg))) return rc;
+    if ((rc = ensure_scratch(ctx, Work::EnetCvWork, alb + scb + itb + p64b + grb + c64b, &ws))) return rc;
+    {   // the candidates and the order they are visited in: descending alpha, equal values in index order
+        std::vector<char> up(sizeof(double) * (size_t)na + sizeof(int32_t) * (size_t)na);
+        double *ua = reinterpret_cast<double *>(up.data());
+        int32_t *uo = reinterpret_cast<int32_t *>(up.data() + sizeof(double) * (size_t)na);
+        for (int j = 0; j < na; ++j) { ua[j] = automatic ? 0.0 : q->alphas[j]; uo[j] = j; }
+        if (!automatic) std::stable_sort(uo, uo + na, [&](int32_t x, int32_t y) { return ua[x] > ua[y]; });
+        if ((rc = upload_small(ctx, ws, up.data(), up.size()))) return rc;
+    }
+    EnetCvArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.y = st.y; a.w = st.w;
+    for (int j = 0; j < b->n_features; ++j) a.x[j] = st.x[(size_t)j];
+    a.offs = d_offs; a.n_groups = b->n_groups; a.n_rows = b->n_rows;
+    if (split) { a.seg_offs = sg.offs; a.seg_map = sg.map; a.seg_first = sg.first; a.n_seg = sg.n_seg; }
+    a.valid = st.valid; a.null_policy = pol;
+    a.k_user = b->n_features; a.kt = kt; a.f32 = b->dtype == POLS_F32 ? 1 : 0;
+    a.n_folds = nf; a.n_alphas = na; a.automatic = automatic ? 1 : 0;
+    a.counted = (pol == POLS_NULL_DROP || pol == POLS_NULL_DROP_ZERO || pol == POLS_NULL_DROP_WINDOW || pol == POLS_NULL_DROP_Y_ZERO_X) ? 1 : 0;
+    a.max_iter = q->max_iter; a.positive = q->positive ? 1 : 0;
+    a.l1_ratio = q->l1_ratio; a.tol = q->tol; a.eps = q->eps;
+    char *cg = static_cast<char *>(wg), *cs = static_cast<char *>(ws);
+    a.item_count = reinterpret_cast<int64_t *>(cg);
+    a.fold_part = reinterpret_cast<double *>(cg + cntb);
+    a.fold_gram = split ? reinterpret_cast<double *>(cg + cntb + partb) : a.fold_part;
+    a.alphas = reinterpret_cast<const double *>(cs);
+    a.order = reinterpret_cast<const int32_t *>(cs + sizeof(double) * (size_t)na);
+    a.score_part = reinterpret_cast<double *>(cs + alb);
+    a.iters = reinterpret_cast<int32_t *>(cs + alb + scb);
+    a.path64 = reinterpret_cast<double *>(cs + alb + scb + itb);
+    a.grid = reinterpret_cast<double *>(cs + alb + scb + itb + p64b);
+    a.coef64 = reinterpret_cast<double *>(cs + alb + scb + itb + p64b + grb);
+    a.coef = st.coef; a.status = st.status;
+    // the entry's own outputs: where the caller wants them (DEVICE batches) or staged (HOST batches)
+    const size_t vecb = round256(sizeof(double) * G), idxb = round256(sizeof(int32_t) * G), cvb = round256(sizeof(double) * G * (size_t)na),
+                 pathb = round256(sz * G * (size_t)na * kt), nitb = round256(sizeof(int32_t) * G * (size_t)na);
+    if (host) {
+        if ((rc = ensure_scratch(ctx, Work::EnetCvOut, 2 * vecb + idxb + 2 * cvb + pathb + nitb, &wo))) return rc;
+        char *c = static_cast<char *>(wo);
+        if (ro->alpha) a.alpha = reinterpret_cast<double *>(c);
+        if (ro->score) a.score = reinterpret_cast<double *>(c + vecb);
+        if (ro->alpha_index) a.alpha_index = reinterpret_cast<int32_t *>(c + 2 * vecb);
+        if (ro->cv_scores) a.cv_scores = reinterpret_cast<double *>(c + 2 * vecb + idxb);
+        if (ro->alphas_used) a.alphas_used = reinterpret_cast<double *>(c + 2 * vecb + idxb + cvb);
+        if (ro->coef_path) a.coef_path = c + 2 * vecb + idxb + 2 * cvb;
+        if (ro->n_iter) a.n_iter = reinterpret_cast<int32_t *>(c + 2 * vecb + idxb + 2 * cvb + pathb);
+    } else {
+        a.alpha = ro->alpha; a.score = ro->score; a.alpha_index = ro->alpha_index; a.cv_scores = ro->cv_scores;
+        a.alphas_used = ro->alphas_used; a.coef_path = ro->coef_path; a.n_iter = ro->n_iter;
+    }
+    ctx->last_kernel = split ? "k12_enet_cv_split" : "k12_enet_cv";
+    if ((rc = k12_count_launch(ctx, b->dtype, a))) return rc;
+    if ((rc = k12_fold_gram_launch(ctx, b->dtype, a))) return rc;
+    if ((rc = k12_reduce_launch(ctx, a))) return rc;
+    if ((rc = k12_path_launch(ctx, a))) return rc;
+    if ((rc = k12_pick_launch(ctx, a))) return rc;
+    RidgeCvArgs pa;                                            // K10's prediction pass from the f64 coefficients
+    std::memset(&pa, 0, sizeof(pa));
+    pa.y = a.y; pa.w = a.w;
+    for (int j = 0; j < b->n_features; ++j) pa.x[j] = a.x[j];
+    pa.offs = d_offs; pa.n_groups = b->n_groups; pa.n_rows = b->n_rows;
+    if (split) { pa.seg_offs = sg.offs; pa.seg_map = sg.map; pa.seg_first = sg.first; pa.n_seg = sg.n_seg; }
+    pa.valid = a.valid; pa.null_policy = pol; pa.k_user = a.k_user; pa.kt = kt;
+    pa.coef64 = a.coef64; pa.pred = st.pred; pa.resid = st.resid;
+    if ((rc = k10_predict_launch(ctx, b->dtype, pa))) return rc;
+    if (!host) return POLS_OK;
+    if (ro->alpha) POLS_HIP(hipMemcpyAsync(ro->alpha, a.alpha, sizeof(double) * G, hipMemcpyDeviceToHost, ctx->stream));
+    if (ro->score) POLS_HIP(hipMemcpyAsync(ro->score, a.score, sizeof(double) * G, hipMemcpyDeviceToHost, ctx->stream));
+    if (ro->alpha_index) POLS_HIP(hipMemcpyAsync(ro->alpha_index, a.alpha_index, sizeof(int32_t) * G, hipMemcpyDeviceToHost, ctx->stream));
+    if (ro->cv_scores) POLS_HIP(hipMemcpyAsync(ro->cv_scores, a.cv_scores, sizeof(double) * G * (size_t)na, hipMemcpyDeviceToHost, ctx->stream));
+    if (ro->alphas_used) POLS_HIP(hipMemcpyAsync(ro->alphas_used, a.alphas_used, sizeof(double) * G * (size_t)na, hipMemcpyDeviceToHost, ctx->stream));
+    if (ro->coef_path) POLS_HIP(hipMemcpyAsync(ro->coef_path, a.coef_path, sz * G * (size_t)na * kt, hipMemcpyDeviceToHost, ctx->stream));
+    if (ro->n_iter) POLS_HIP(hipMemcpyAsync(ro->n_iter, a.n_iter, sizeof(int32_t) * G * (size_t)na, hipMemcpyDeviceToHost, ctx->stream));
     return unstage_outputs(ctx, b, b->n_groups, kt, o, st);
 }
 

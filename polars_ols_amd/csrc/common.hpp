@@ -83,6 +83,9 @@ enum class Work : int {
     RlmCoef,        // M-estimator (K11): the groups' coefficients in f64 for the prediction pass
     RlmRows,        // M-estimator (K11): |r| / omega per row of the groups the streamed form serves (f64)
     RlmOut,         // M-estimator (K11): scale / n_iter / weights of a HOST batch before they go home
+    EnetCvGram,     // elastic-net path (K12): fitted rows and fold Gram matrices per segment / group, then per group
+    EnetCvWork,     // elastic-net path (K12): candidates and their order, fold scores, sweep counts, the f64 path and grid, the winners' coefficients
+    EnetCvOut,      // elastic-net path (K12): the pols_enet_cv_out fields of a HOST batch before they go home
     Count
 };
 

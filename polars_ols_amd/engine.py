@@ -363,6 +363,42 @@ class Engine:
         L.check(self._lib.pols_rlm(self._h, C.byref(plan._b), C.byref(plan._p), C.byref(q), C.byref(plan._o), C.byref(ro)))
         return res
 
+    def elastic_net_cv(self, y, x_cols: Sequence, offsets, alphas=None, *, n_alphas: int = 100, eps: float = 1e-3, l1_ratio: float = 0.5,
+                       n_folds: int = 5, max_iter: int = 1000, tol: float = 1e-5, positive: bool = False,
+                       want: Sequence[str] = ("coef", "status", "alpha", "alpha_index", "score"), weights=None, valid=None,
+                       add_intercept: bool = False, null_policy: str = "ignore") -> Dict:
+        """Elastic-net / lasso regularisation path with K-fold selection of alpha for every group in one call
+        (pols_elastic_net_cv; the definitions are in include/pols_mi355x.h).  ``alphas``: explicit candidates (any order, each >= 0
+        and finite, at most 128), or None for the automatic grid of ``n_alphas`` values from every group's own alpha_max down to
+        ``eps`` times it.  ``want``: any of ``coef pred resid status`` (those of the chosen candidate on the full data; status 3 =
+        one of its fits stopped at ``max_iter``), ``alpha score`` [n_groups, f64], ``alpha_index`` [n_groups, int32, -1 where there
+        is no choice], ``cv_scores alphas_used`` [n_groups, n_alphas, f64], ``n_iter`` [n_groups, n_alphas, int32] and ``coef_path``
+        [n_groups, n_alphas, k, batch dtype].  Arrays are numpy or torch and live where the inputs live."""
+        q, grid = _enet_cv_params(self._lib, alphas, n_alphas, eps, l1_ratio, n_folds, max_iter, tol, positive)
+        want = tuple(want)
+        known = ("coef", "pred", "resid", "status") + L.ENET_CV_FIELDS
+        unknown = [w for w in want if w not in known]
+        if unknown:
+            raise ValueError(f"unknown elastic_net_cv fields {unknown}; known: {list(known)}")
+        plan = self.plan_least_squares(y, x_cols, offsets, weights=weights, valid=valid, add_intercept=add_intercept,
+                                       null_policy=null_policy, want=tuple(w for w in want if w in ("coef", "pred", "resid", "status")))
+        b = plan._b
+        kt = b.n_features + b.add_intercept
+        dev = b.mem == L.POLS_MEM_DEVICE
+        like = plan._keep[0][0]
+        res = plan.results
+        f64, i32 = (torch.float64, torch.int32) if dev else (np.float64, np.int32)
+        G, A = b.n_groups, q.n_alphas
+        shapes = {"alpha": ((G,), f64), "alpha_index": ((G,), i32), "score": ((G,), f64), "cv_scores": ((G, A), f64),
+                  "alphas_used": ((G, A), f64), "coef_path": ((G, A, kt), like.dtype), "n_iter": ((G, A), i32)}
+        for key in L.ENET_CV_FIELDS:
+            if key in want:
+                res[key] = self._alloc(dev, shapes[key][1], shapes[key][0], like)
+        ro = L.EnetCvOut(**{k: self._ptr(res.get(k)) for k in L.ENET_CV_FIELDS})
+        L.check(self._lib.pols_elastic_net_cv(self._h, C.byref(plan._b), C.byref(plan._p), C.byref(q), C.byref(plan._o), C.byref(ro)))
+        del grid                                                   # (kept alive until the call has read it)
+        return res
+
     def least_squares(self, y, x_cols: Sequence, offsets, **kwargs) -> Dict:
         """All groups of a (group-sorted) frame in one launch.  ``want`` subset of {"coef","pred","resid","status"};
         ``out`` may carry pre-allocated buffers under the same keys."""
@@ -673,6 +709,47 @@ def _ridge_cv_grid(alphas) -> np.ndarray:
     if not np.all(np.isfinite(grid)) or np.any(grid < 0.0):
         raise ValueError(f"ridge_cv: every candidate alpha must be finite and >= 0 (got {grid.tolist()})")
     return grid
+
+
+def _enet_cv_params(lib, alphas, n_alphas, eps, l1_ratio, n_folds, max_iter, tol, positive):
+    """(pols_enet_cv_params, the grid it points to or None) of an elastic-net path; ValueError for what the C entry would refuse
+    (lib None: validation only, without the library)"""
+    l1_ratio, tol = float(l1_ratio), float(tol)
+    if not 0.0 <= l1_ratio <= 1.0:
+        raise ValueError(f"elastic_net_cv: l1_ratio {l1_ratio} outside [0, 1]")
+    grid = None
+    if alphas is not None:
+        if _is_torch(alphas):
+            alphas = alphas.detach().cpu().numpy()
+        grid = np.ascontiguousarray(np.atleast_1d(np.asarray(alphas, dtype=np.float64)).ravel())
+        if grid.size == 0:
+            raise ValueError("elastic_net_cv: the grid of candidate alphas is empty")
+        if not np.all(np.isfinite(grid)) or np.any(grid < 0.0):
+            raise ValueError(f"elastic_net_cv: every candidate alpha must be finite and >= 0 (got {grid.tolist()})")
+        n_alphas = grid.size
+    else:
+        n_alphas, eps = int(n_alphas), float(eps)
+        if n_alphas < 2:
+            raise ValueError(f"elastic_net_cv: an automatic grid needs n_alphas >= 2 (got {n_alphas})")
+        if not 0.0 < eps < 1.0:
+            raise ValueError(f"elastic_net_cv: eps {eps} outside (0, 1)")
+        if l1_ratio == 0.0:
+            raise ValueError("elastic_net_cv: an automatic grid needs l1_ratio > 0")
+    if n_alphas > L.ENET_CV_MAX_ALPHAS:
+        raise ValueError(f"elastic_net_cv: {n_alphas} candidates > {L.ENET_CV_MAX_ALPHAS}")
+    if not 2 <= int(n_folds) <= L.ENET_CV_MAX_FOLDS:
+        raise ValueError(f"elastic_net_cv: n_folds {n_folds} outside 2..{L.ENET_CV_MAX_FOLDS}")
+    if int(max_iter) < 1:
+        raise ValueError(f"elastic_net_cv: max_iter {max_iter} < 1")
+    if not (tol > 0.0 and np.isfinite(tol)):
+        raise ValueError(f"elastic_net_cv: tol {tol} is not positive and finite")
+    q = L.EnetCvParams()
+    if lib is not None:
+        lib.pols_enet_cv_params_default(C.byref(q))
+    q.alphas = grid.ctypes.data_as(C.POINTER(C.c_double)) if grid is not None else None
+    q.n_alphas, q.eps, q.l1_ratio, q.n_folds = int(n_alphas), float(eps), l1_ratio, int(n_folds)
+    q.max_iter, q.tol, q.positive = int(max_iter), tol, int(bool(positive))
+    return q, grid
 
 
 def _influence_level(level) -> float:

@@ -26,7 +26,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import PolsPanic
-from .engine import Engine, Layout, _is_torch, _ridge_cv_grid, _rlm_params, default_engine
+from .engine import Engine, Layout, _enet_cv_params, _is_torch, _ridge_cv_grid, _rlm_params, default_engine
 
 try:
     import torch
@@ -41,6 +41,7 @@ __all__ = [
     "OLSKwargs", "RLSKwargs", "RollingKwargs", "NullPolicy", "OutputMode", "SolveMethod",
     "Frame", "Expr", "col", "struct", "Coefficients", "Statistics", "Influence", "LeastSquares",
     "compute_ridge_cv", "RidgeCV",
+    "compute_elastic_net_cv", "ElasticNetCV",
     "compute_rlm", "RLM",
 ]
 
@@ -455,6 +456,39 @@ def _apply_ridge_cv(frame: Frame, over, eng: Optional[Engine], target: Expr, fea
     return target.output_name, grp.untake(out["pred"] if mode == "predictions" else out["resid"])
 
 
+class ElasticNetCV(dict):
+    """mode="cv" of an elastic-net path (pols_elastic_net_cv; the definitions are in include/pols_mi355x.h), one entry per group:
+    ``alpha`` (the chosen candidate), ``alpha_index`` (its index, -1 where there is no choice), ``score`` (its mean K-fold
+    validation error), ``status`` [G], ``cv_scores``, ``alphas`` (every group's candidates) and ``n_iter`` [G, n_alphas]; ``keys``
+    holds the group keys of an ``.over`` (None for a whole-frame fit, where G == 1)."""
+
+    def __init__(self, out, keys, l1_ratio, n_folds):
+        super().__init__(alpha=out["alpha"], alpha_index=out["alpha_index"], score=out["score"], status=out["status"],
+                         cv_scores=out["cv_scores"], alphas=out["alphas_used"], n_iter=out["n_iter"], keys=keys, l1_ratio=l1_ratio,
+                         n_folds=n_folds)
+        self.keys_ = keys
+
+
+_VALID_ENET_CV_MODES = ("predictions", "residuals", "coefficients", "cv")
+
+
+def _apply_enet_cv(frame: Frame, over, eng: Optional[Engine], target: Expr, features: Sequence[Expr], sample_weights,
+                   add_intercept: bool, mode: str, null_policy: str, kw):
+    """compute_elastic_net_cv body: the group layout of _apply_static around Engine.elastic_net_cv."""
+    y, xs, names, icpt, w = _pre_process_data(frame, target, features, sample_weights, add_intercept)
+    eng = eng or default_engine(y.device.index or 0 if _is_torch(y) else 0)
+    grp = _Groups(eng, None if over is None else (frame[over] if isinstance(over, str) else over), y.shape[0])
+    moved = grp.take([y, w] + list(xs))
+    want = {"predictions": ("pred",), "residuals": ("resid",), "coefficients": ("coef",),
+            "cv": ("status", "alpha", "alpha_index", "score", "cv_scores", "alphas_used", "n_iter")}[mode]
+    out = eng.elastic_net_cv(moved[0], moved[2:], grp.offsets, want=want, weights=moved[1], add_intercept=icpt, null_policy=null_policy, **kw)
+    if mode == "cv":
+        return "cv", ElasticNetCV(out, grp.keys, kw["l1_ratio"], kw["n_folds"])
+    if mode == "coefficients":
+        return "coefficients", Coefficients(names, out["coef"], grp.keys, grp.gid_frame(out["coef"]))
+    return target.output_name, grp.untake(out["pred"] if mode == "predictions" else out["resid"])
+
+
 class RLM(dict):
     """mode="rlm" of an M-estimator fit (pols_rlm; the definitions are in include/pols_mi355x.h): per group ``coef`` [G, k],
     ``scale`` (the last MAD scale), ``n_iter`` (updates made) and ``status`` (0 converged, 1 no fit, 2 no rows, 3 stopped at
@@ -611,6 +645,23 @@ def compute_ridge_cv(target, *features, alphas, sample_weights=None, add_interce
     grid = _ridge_cv_grid(alphas)
     t, fs = parse_into_expr(target), [parse_into_expr(f) for f in features]
     return Expr(t._name, fn=lambda frame, over, eng: _apply_ridge_cv(frame, over, eng, t, fs, sample_weights, add_intercept, mode, grid, null_policy))
+
+
+def compute_elastic_net_cv(target, *features, alphas=None, n_alphas: int = 100, eps: float = 1e-3, l1_ratio: float = 0.5, n_folds: int = 5,
+                           max_iter: int = 1000, tol: float = 1e-5, positive: bool = False, sample_weights=None,
+                           add_intercept: bool = False, mode: str = "predictions", null_policy: str = "ignore") -> Expr:
+    """Elastic net with the penalty chosen per group by K-fold cross-validation over a path (scikit-learn's ElasticNetCV /
+    LassoCV with contiguous folds for every group of the frame in one call).  ``alphas`` None: every group gets its own grid of
+    ``n_alphas`` values from its alpha_max down to ``eps`` times it.  Modes "predictions", "residuals" and "coefficients" are those
+    of the chosen candidate fitted on all of the group's rows; mode="cv" returns an ``ElasticNetCV``."""
+    if mode not in _VALID_ENET_CV_MODES:
+        raise ValueError(f"'mode' must be one of {_VALID_ENET_CV_MODES}, got {mode!r}")
+    if null_policy not in _VALID_NULL_POLICIES:
+        raise ValueError(f"'null_policy' must be one of {sorted(_VALID_NULL_POLICIES)}, got {null_policy!r}")
+    _, grid = _enet_cv_params(None, alphas, n_alphas, eps, l1_ratio, n_folds, max_iter, tol, positive)
+    kw = dict(alphas=grid, n_alphas=n_alphas, eps=eps, l1_ratio=l1_ratio, n_folds=n_folds, max_iter=max_iter, tol=tol, positive=positive)
+    t, fs = parse_into_expr(target), [parse_into_expr(f) for f in features]
+    return Expr(t._name, fn=lambda frame, over, eng: _apply_enet_cv(frame, over, eng, t, fs, sample_weights, add_intercept, mode, null_policy, kw))
 
 
 def compute_rlm(target, *features, norm: str = "huber", c: Optional[float] = None, max_iter: int = 50, tol: float = 1e-8,
@@ -872,6 +923,20 @@ class LeastSquares:
                  null_policy: str = "ignore") -> Expr:
         return compute_ridge_cv(self._expr, *features, alphas=alphas, sample_weights=sample_weights, add_intercept=add_intercept,
                                 mode=mode, null_policy=null_policy)
+
+    def elastic_net_cv(self, *features, alphas=None, n_alphas: int = 100, eps: float = 1e-3, l1_ratio: float = 0.5, n_folds: int = 5,
+                       max_iter: int = 1000, tol: float = 1e-5, positive: bool = False, sample_weights=None,
+                       add_intercept: bool = False, mode: str = "predictions", null_policy: str = "ignore") -> Expr:
+        return compute_elastic_net_cv(self._expr, *features, alphas=alphas, n_alphas=n_alphas, eps=eps, l1_ratio=l1_ratio,
+                                      n_folds=n_folds, max_iter=max_iter, tol=tol, positive=positive, sample_weights=sample_weights,
+                                      add_intercept=add_intercept, mode=mode, null_policy=null_policy)
+
+    def lasso_cv(self, *features, **kwargs) -> Expr:
+        """elastic_net_cv with l1_ratio = 1"""
+        if kwargs.get("l1_ratio", 1.0) != 1.0:
+            raise ValueError("lasso_cv: l1_ratio is fixed at 1; use elastic_net_cv")
+        kwargs["l1_ratio"] = 1.0
+        return self.elastic_net_cv(*features, **kwargs)
 
     def rlm(self, *features, norm: str = "huber", c: Optional[float] = None, max_iter: int = 50, tol: float = 1e-8,
             sample_weights=None, add_intercept: bool = False, mode: str = "predictions", null_policy: str = "ignore") -> Expr:

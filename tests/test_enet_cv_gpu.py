@@ -1,0 +1,375 @@
+"""The elastic-net / lasso path with K-fold selection (pols_elastic_net_cv, K12) on the device against the numpy restatement in
+enet_cv_ref.py, on the f64 values of the inputs.  Tolerances: rtol 1e-6 for f64 batches and 1e-4 for f32 batches on coef, pred,
+resid and coef_path, atol = rtol x 1e-3; cv_scores, score and alphas_used rtol 1e-6 for BOTH dtypes (all arithmetic is f64).  Value
+tests run with tol=1e-10, max_iter=10000 so that both sides sit at the minimiser; n_iter is checked for dtype and range only (a stop
+rule can fire one sweep apart).
+
+Selection, as in test_ridge_cv_gpu: for every group the restatement's score at the device's chosen index must be within 1e-5
+relative of the restatement's minimum, and alpha_index must equal the restatement's wherever its best and runner-up differ by more
+than 1e-5 relative; the share of groups exempted from index equality is asserted to be at most 5 % per test and printed.  coef, pred
+and resid are always compared against the restatement's path at the DEVICE's chosen index.  A restatement is computed once per input
+and shared by the host / device variants of a test."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+
+from enet_cv_ref import EMPTY, FALLBACK, NOT_CONVERGED, OK, chosen_outputs, enet_cv_batch  # noqa: E402
+from test_enet_cv_cpu import gen  # noqa: E402
+
+DTYPES = [(np.float64, 1e-6), (np.float32, 1e-4)]
+SCORE_RTOL = 1e-6
+GAP = 1e-5
+ALL = ("coef", "pred", "resid", "status", "alpha", "alpha_index", "score", "cv_scores", "alphas_used", "coef_path", "n_iter")
+TIGHT = dict(tol=1e-10, max_iter=10000)
+_REFS = {}
+
+
+@pytest.fixture(scope="module")
+def eng():
+    from polars_ols_amd import Engine
+
+    e = Engine(0)
+    yield e
+    e.close()
+
+
+def _f64(a):
+    return None if a is None else np.asarray(a, dtype=np.float64)
+
+
+def _np(a):
+    return a.cpu().numpy() if hasattr(a, "cpu") else np.asarray(a)
+
+
+def _run(eng, y, cols, offs, alphas=None, w=None, device=False, valid=None, want=ALL, **kw):
+    if device:
+        import torch
+
+        y, cols = torch.from_numpy(y).cuda(), [torch.from_numpy(c).cuda() for c in cols]
+        w = None if w is None else torch.from_numpy(w).cuda()
+        valid = None if valid is None else torch.from_numpy(valid).cuda()
+    out = eng.elastic_net_cv(y, cols, offs, alphas, weights=w, valid=valid, want=want, **kw)
+    eng.synchronize()
+    return {k: _np(v) for k, v in out.items()}
+
+
+def _close(got, ref, rtol, what):
+    got, ref = np.asarray(got, dtype=np.float64), np.asarray(ref, dtype=np.float64)
+    with np.errstate(all="ignore"):
+        print(f"{what}: max rel err {np.nanmax(np.abs(got - ref) / np.maximum(np.abs(ref), 1e-300), initial=0.0):.3e}")
+    np.testing.assert_allclose(got, ref, rtol=rtol, atol=rtol * 1e-3, equal_nan=True, err_msg=what)
+
+
+def _reference(key, y, cols, offs, alphas, w, valid, kw):
+    """the restatement of one input, computed once (key names the input; the host and device variants of a test share it)"""
+    if key not in _REFS:
+        _REFS[key] = enet_cv_batch(_f64(y), [_f64(c) for c in cols], offs, None if alphas is None else _f64(alphas), weights=_f64(w),
+                                   valid=valid, **kw)
+    return _REFS[key]
+
+
+def _check(eng, key, y, cols, offs, rtol, alphas=None, w=None, device=False, valid=None, want=ALL, **kw):
+    """runs the entry and checks everything it returned against the restatement; returns (got, ref)"""
+    got = _run(eng, y, cols, offs, alphas, w, device, valid, want, **kw)
+    ref = _reference((key, np.dtype(y.dtype).name), y, cols, offs, alphas, w, valid, kw)
+    G = len(offs) - 1
+    sc, grid = ref["cv_scores"], ref["alphas_used"]
+    if "cv_scores" in got:
+        assert got["cv_scores"].dtype == np.float64
+        _close(got["cv_scores"], sc, SCORE_RTOL, "cv_scores")
+    if "alphas_used" in got:
+        _close(got["alphas_used"], grid, SCORE_RTOL, "alphas_used")
+    idx = got["alpha_index"]
+    assert idx.dtype == np.int32
+    np.testing.assert_array_equal(idx >= 0, ref["alpha_index"] >= 0)
+    has = idx >= 0
+    rows = np.arange(G)[has]
+    at_choice = sc[rows, idx[has]]
+    best = ref["score"][has]
+    assert np.isfinite(at_choice).all(), "the device chose a candidate the restatement has no finite score for"
+    assert (at_choice <= best * (1.0 + GAP)).all(), float(np.max(at_choice / best))
+    with np.errstate(all="ignore"):
+        masked = np.where(np.isfinite(sc[has]), sc[has], np.inf)
+        masked[grid[has] == grid[rows, ref["alpha_index"][has]][:, None]] = np.inf   # (the winner and its exact repeats)
+        runner_up = masked.min(axis=1)
+    decided = runner_up > best * (1.0 + GAP)
+    n_exempt = int((~decided).sum())
+    print(f"exempt from index equality: {n_exempt} of {len(rows)} groups = {100.0 * n_exempt / max(len(rows), 1):.2f} %; "
+          f"distinct winners {len(np.unique(idx[has]))}")
+    assert 20 * n_exempt <= len(rows)                          # at most 5 %
+    np.testing.assert_array_equal(idx[has][decided], ref["alpha_index"][has][decided])
+    if "alpha" in got:
+        _close(got["alpha"][has], grid[rows, idx[has]], SCORE_RTOL, "alpha")
+        if "alphas_used" in got:
+            np.testing.assert_array_equal(got["alpha"][has], got["alphas_used"][rows, idx[has]])
+        assert np.isnan(got["alpha"][~has]).all()
+    if "score" in got:
+        _close(got["score"][has], at_choice, SCORE_RTOL, "score")
+        assert np.isnan(got["score"][~has]).all()
+    if "status" in got:                                        # (NOT_CONVERGED belongs to the chosen candidate: compared where the choice is the same)
+        same = idx == ref["alpha_index"]
+        np.testing.assert_array_equal(got["status"][same], ref["status"][same])
+    if "n_iter" in got:
+        fitted = (ref["n_iter"] > 0).any(axis=1)
+        assert got["n_iter"].dtype == np.int32 and got["n_iter"].shape == sc.shape
+        assert (got["n_iter"][fitted] >= 1).all() and (got["n_iter"] <= kw.get("max_iter", 1000)).all() and (got["n_iter"][~fitted] == 0).all()
+    coef, pred, resid = chosen_outputs(ref, idx, _f64(y), [_f64(c) for c in cols], offs, _f64(w), kw.get("add_intercept", False),
+                                       kw.get("null_policy", "ignore"))
+    if "coef" in got:
+        assert got["coef"].dtype == y.dtype
+        _close(got["coef"], coef, rtol, "coef")
+    if "pred" in got:
+        _close(got["pred"], pred, rtol, "pred")
+    if "resid" in got:
+        _close(got["resid"], resid, rtol, "resid")
+    if "coef_path" in got:
+        assert got["coef_path"].dtype == y.dtype
+        _close(got["coef_path"], ref["coef_path"], rtol, "coef_path")
+    return got, ref
+
+
+EXPLICIT = np.array([0.05, 1.0, 0.002, 0.3, 0.01, 0.1, 0.0005, 0.02, 0.5, 0.005])   # unsorted on purpose
+SETTINGS = {
+    "auto_enet": dict(alphas=None, weights=False, kw=dict(n_alphas=20, l1_ratio=0.5)),
+    "auto_lasso_w_icpt": dict(alphas=None, weights=True, kw=dict(n_alphas=16, l1_ratio=1.0, add_intercept=True, n_folds=3)),
+    "grid_enet_positive_w": dict(alphas=EXPLICIT, weights=True, kw=dict(l1_ratio=0.5, positive=True)),
+    "auto_lasso_positive_icpt": dict(alphas=None, weights=False, kw=dict(n_alphas=12, l1_ratio=1.0, positive=True, add_intercept=True, n_folds=7)),
+}
+
+
+@pytest.mark.parametrize("dtype,rtol", DTYPES)
+@pytest.mark.parametrize("device", [False, True])
+@pytest.mark.parametrize("setting", list(SETTINGS))
+def test_ragged_groups(eng, dtype, rtol, device, setting):
+    """40 groups of 50-400 rows x 8: tiles straddle fold boundaries and group ends"""
+    s = SETTINGS[setting]
+    y, cols, offs, w = gen(40, 50, 400, 8, dtype, seed=11, sigma=3.0, nonneg=s["kw"].get("positive", False))
+    got, _ = _check(eng, "ragged-" + setting, y, cols, offs, rtol, s["alphas"], w if s["weights"] else None, device, **TIGHT, **s["kw"])
+    assert (got["status"] == OK).all()
+    assert eng.last_kernel == "k12_enet_cv"
+
+
+def test_the_default_grid_of_a_hundred_candidates(eng):
+    """neighbours on a 100-point grid score within 1e-5 of each other around a flat minimum: short, noisy groups keep it sharp"""
+    y, cols, offs, _ = gen(40, 30, 60, 5, np.float64, seed=31, sigma=6.0)
+    got, _ = _check(eng, "hundred", y, cols, offs, 1e-6, None, None, True, l1_ratio=1.0, **TIGHT)
+    assert got["cv_scores"].shape == (40, 100) and got["coef_path"].shape == (40, 100, 5)
+
+
+@pytest.mark.parametrize("dtype,rtol", DTYPES)
+@pytest.mark.parametrize("k,icpt", [(20, False), (30, True), (16, False), (16, True)])
+def test_wide_frames_take_thirty_two_lanes(eng, dtype, rtol, k, icpt):
+    """20 and 31 columns run 32 lanes per problem; 16 and 17 columns sit on either side of the switch"""
+    y, cols, offs, w = gen(20, 100, 300, k, dtype, seed=14)
+    _check(eng, f"wide-{k}-{icpt}", y, cols, offs, rtol, None, w, True, n_alphas=8, l1_ratio=0.9, add_intercept=icpt, **TIGHT)
+
+
+def _with_nulls(dtype, seed=9):
+    y, cols, offs, w = gen(40, 60, 400, 6, dtype, seed=seed)
+    rng = np.random.default_rng(10)
+    n = len(y)
+    y = y.copy()
+    y[rng.random(n) < 0.05] = np.nan
+    for c in cols:
+        c[rng.random(n) < 0.05 / len(cols)] = np.nan
+    w = w.copy()
+    w[rng.random(n) < 0.01] = np.nan
+    return y, cols, offs, w, (rng.random(n) > 0.03).astype(np.uint8)
+
+
+@pytest.mark.parametrize("dtype,rtol", DTYPES)
+@pytest.mark.parametrize("device", [False, True])
+@pytest.mark.parametrize("policy", ["drop", "zero", "drop_zero", "drop_y_zero_x"])
+def test_null_policies_with_nulls_and_a_validity_mask(eng, dtype, rtol, device, policy):
+    """10 % of the rows leave the fit under the drop family: ranks differ from positions"""
+    y, cols, offs, w, valid = _with_nulls(dtype)
+    valid = valid if policy != "zero" else None
+    got, ref = _check(eng, "nulls-" + policy, y, cols, offs, rtol, None, w, device, valid, n_alphas=12, add_intercept=True,
+                      null_policy=policy, **TIGHT)
+    assert (policy == "zero") == bool(ref["fit"].all())
+    if policy == "drop":
+        assert np.isnan(got["pred"][~ref["fit"]]).all() and np.isfinite(got["pred"][ref["fit"]]).all()
+    else:
+        assert np.isfinite(got["pred"]).all()
+
+
+@pytest.mark.parametrize("dtype,rtol", DTYPES)
+@pytest.mark.parametrize("policy", ["ignore", "drop"])
+def test_a_long_group_next_to_short_ones_runs_the_segments(eng, dtype, rtol, policy):
+    sizes = np.array([130, 20011, 77, 0, 9000])
+    y, cols, offs, w = gen(1, int(sizes.sum()), int(sizes.sum()), 4, dtype, seed=17, sigma=3.0)
+    offs = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+    valid = None
+    if policy == "drop":
+        rng = np.random.default_rng(18)
+        y = y.copy()
+        y[rng.random(len(y)) < 0.1] = np.nan
+        valid = (rng.random(len(y)) > 0.02).astype(np.uint8)
+    got, _ = _check(eng, "long-" + policy, y, cols, offs, rtol, None, w, True, valid, n_alphas=10, n_folds=5, add_intercept=True,
+                    null_policy=policy, **TIGHT)
+    assert eng.last_kernel == "k12_enet_cv_split"
+    assert list(got["status"]) == [OK, OK, OK, EMPTY, OK]
+
+
+def _edge_frame(dtype, extra=0):
+    """empty, n < folds, n == folds == kt, folds < n, an ordinary group, a constant-zero target (no automatic grid; with an explicit
+    one every candidate scores exactly 0), another ordinary group, then `extra` ordinary groups of 60 rows"""
+    sizes = np.array([0, 3, 5, 6, 60, 40, 50] + [60] * extra)
+    y, cols, offs, _ = gen(1, int(sizes.sum()), int(sizes.sum()), 4, dtype, seed=8, sigma=3.0)
+    offs = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+    y = y.copy()
+    y[offs[5]:offs[6]] = 0.0
+    return y, cols, offs
+
+
+@pytest.mark.parametrize("dtype,rtol", DTYPES)
+@pytest.mark.parametrize("device", [False, True])
+def test_empty_short_and_degenerate_groups(eng, dtype, rtol, device):
+    y, cols, offs = _edge_frame(dtype)
+    got, _ = _check(eng, "edge-auto", y, cols, offs, rtol, None, None, device, n_alphas=6, n_folds=5, add_intercept=True, **TIGHT)
+    assert list(got["status"]) == [EMPTY, FALLBACK, OK, OK, OK, FALLBACK, OK]
+    assert list(got["alpha_index"] >= 0) == [False, False, True, True, True, False, True]
+    assert (got["coef"][0] == 0).all()
+    for g in (1, 5):
+        s, e = offs[g], offs[g + 1]
+        assert np.isnan(got["coef"][g]).all() and np.isnan(got["pred"][s:e]).all() and np.isnan(got["resid"][s:e]).all()
+    for g in (0, 1, 5):
+        assert np.isnan(got["cv_scores"][g]).all() and np.isnan(got["alphas_used"][g]).all() and np.isnan(got["coef_path"][g]).all()
+        assert (got["n_iter"][g] == 0).all()
+    # an explicit grid: the zero target is fitted, all its scores tie at 0 and the lowest index wins (the one group of this frame
+    # that is undecided by construction: 20 ordinary groups keep the exempt share under the cap)
+    grid = np.array([0.1, 1.0, 0.01])
+    y, cols, offs = _edge_frame(dtype, extra=20)
+    got, _ = _check(eng, "edge-grid", y, cols, offs, rtol, grid, None, device, n_folds=5, add_intercept=True, **TIGHT)
+    assert list(got["status"][:7]) == [EMPTY, FALLBACK, OK, OK, OK, OK, OK]
+    np.testing.assert_array_equal(got["alphas_used"], np.tile(grid, (27, 1)))
+    assert (got["coef_path"][5] == 0).all() and got["alpha_index"][5] == 0 and (got["cv_scores"][5] == 0).all()
+
+
+@pytest.mark.parametrize("dtype,rtol", DTYPES)
+def test_one_sweep_is_not_converged_and_still_returned(eng, dtype, rtol):
+    y, cols, offs, w = gen(40, 50, 120, 6, dtype, seed=23, sigma=3.0)
+    got, ref = _check(eng, "one-sweep", y, cols, offs, rtol, None, w, True, n_alphas=8, max_iter=1, tol=1e-10)
+    assert (got["status"] == NOT_CONVERGED).all() and (ref["status"] == NOT_CONVERGED).all()
+    assert (got["n_iter"] == 1).all() and np.isfinite(got["coef"]).all() and np.isfinite(got["pred"]).all()
+
+
+def test_unsorted_grid_and_repeated_values(eng):
+    y, cols, offs, w = gen(40, 50, 150, 8, np.float64, seed=25)
+    grid = np.array([0.3, 0.001, 0.1, 0.01, 0.1, 0.03, 0.01, 1.0])
+    got, _ = _check(eng, "repeats", y, cols, offs, 1e-6, grid, w, True, l1_ratio=0.8, **TIGHT)
+    # the later twin starts from the earlier one's solution: one sweep confirms it
+    assert (got["n_iter"][:, 4] == 1).all() and (got["n_iter"][:, 6] == 1).all() and (got["n_iter"][:, [2, 3]] > 1).all()
+    np.testing.assert_allclose(got["cv_scores"][:, 4], got["cv_scores"][:, 2], rtol=1e-8)
+    np.testing.assert_array_equal(got["alphas_used"], np.tile(grid, (40, 1)))
+
+
+@pytest.mark.parametrize("dtype,rtol", DTYPES)
+def test_two_runs_and_host_and_device_are_bit_identical(eng, dtype, rtol):
+    y, cols, offs, w, valid = _with_nulls(dtype, seed=12)       # (no comparison with the restatement here)
+    kw = dict(n_alphas=10, add_intercept=True, null_policy="drop")
+    a = _run(eng, y, cols, offs, None, w, True, valid, **kw)
+    b = _run(eng, y, cols, offs, None, w, True, valid, **kw)
+    h = _run(eng, y, cols, offs, None, w, False, valid, **kw)
+    for key in ALL:
+        assert a[key].tobytes() == b[key].tobytes(), key
+        assert a[key].tobytes() == h[key].tobytes(), key
+
+
+def test_any_subset_of_outputs_gives_the_same_values(eng):
+    y, cols, offs, w = gen(9, 50, 300, 5, np.float32, seed=13)
+    full = _run(eng, y, cols, offs, None, w, True, n_alphas=7)
+    for want in (("alpha_index",), ("cv_scores", "resid"), ("coef_path",), ("coef", "alpha", "score"), ("n_iter", "alphas_used", "pred")):
+        part = _run(eng, y, cols, offs, None, w, True, want=want, n_alphas=7)
+        assert set(part) == set(want)
+        for key in want:
+            assert part[key].tobytes() == full[key].tobytes(), key
+    default = eng.elastic_net_cv(y, cols, offs)
+    assert set(default) == {"coef", "status", "alpha", "alpha_index", "score"} and default["alpha"].shape == (9,)
+
+
+def test_error_codes_through_the_c_abi(eng):
+    from polars_ols_amd import _lib as L
+    from polars_ols_amd._lib import PolsError
+
+    y, cols, offs, _ = gen(3, 100, 200, 32, np.float64, seed=15)
+    with pytest.raises(PolsError) as ei:
+        eng.elastic_net_cv(y, cols[:31], offs, [1.0], add_intercept=True)            # 32 columns
+    assert ei.value.code == -2
+    assert set(eng.elastic_net_cv(y, cols[:30], offs, np.linspace(0.1, 1.0, 128), add_intercept=True, max_iter=3, want=("alpha",))) == {"alpha"}
+    plan = eng.plan_least_squares(y, cols[:3], offs, want=("coef",))
+    idx = np.empty(3, dtype=np.int32)
+    ro = L.EnetCvOut(alpha_index=idx.ctypes.data)
+
+    def params(values=None, **kw):
+        q = L.EnetCvParams()
+        eng._lib.pols_enet_cv_params_default(C.byref(q))
+        if values is not None:
+            arr = (C.c_double * len(values))(*values)
+            q.alphas, q.n_alphas, q._keep = arr, len(values), arr
+        for k, v in kw.items():
+            setattr(q, k, v)
+        return q
+
+    def call(q, p=None):
+        return eng._lib.pols_elastic_net_cv(eng._h, C.byref(plan._b), C.byref(p or plan._p), C.byref(q) if q is not None else None,
+                                            C.byref(plan._o), C.byref(ro))
+
+    q = params()
+    assert (q.n_alphas, q.eps, q.l1_ratio, q.n_folds, q.max_iter, q.tol, q.positive) == (100, 1e-3, 0.5, 5, 1000, 1e-5, 0) and not q.alphas
+    assert call(params(n_alphas=4)) == 0 and call(params([1.0, 0.1])) == 0 and call(params([1.0], l1_ratio=0.0)) == 0
+    assert call(None) == -1
+    invalid = [params(l1_ratio=-0.1), params(l1_ratio=1.01), params(l1_ratio=float("nan")), params([-1.0]), params([1.0, float("nan")]),
+               params([float("inf")]), params(n_alphas=0), params([1.0], n_alphas=0), params(n_alphas=1), params(eps=0.0), params(eps=1.0),
+               params(l1_ratio=0.0), params(n_folds=1), params(n_folds=17), params(max_iter=0), params(tol=0.0), params(tol=float("inf")),
+               params(tol=float("nan"))]
+    for i, q in enumerate(invalid):
+        assert call(q) == -1, i
+    assert call(params(n_alphas=129)) == -2 and call(params([0.5] * 129)) == -2
+    p = L.OlsParams()
+    eng._lib.pols_ols_params_default(C.byref(p))
+    p.null_policy = 9
+    assert call(params(n_alphas=4), p) == -1
+    with pytest.raises(PolsError) as ei:                                             # a validity mask without a drop-family policy
+        eng.elastic_net_cv(y, cols[:3], offs, valid=np.ones(len(y), dtype=np.uint8), null_policy="zero")
+    assert ei.value.code == -1
+
+
+def test_namespace_over_an_unsorted_key(eng):
+    """.over(key) with arrival-order keys returns predictions in frame order; mode="cv" keys line up; lasso_cv is l1_ratio = 1"""
+    import polars_ols_amd as P
+
+    rng = np.random.default_rng(21)
+    n, G = 3000, 12
+    key = rng.integers(0, G, size=n) * 7 + 3                    # unsorted, non-contiguous keys
+    X = rng.normal(size=(n, 3))
+    beta = rng.normal(size=(G, 3))[(key - 3) // 7]
+    beta[:, 1] = 0.0
+    y = (X * beta).sum(axis=1) + 0.4 + 2.0 * rng.normal(size=n)
+    frame = P.Frame(y=y, a=X[:, 0], b=X[:, 1], c=X[:, 2], k=key)
+    ns = P.col("y").least_squares
+    kw = dict(n_alphas=10, add_intercept=True, **TIGHT)
+    pred = frame.select(ns.lasso_cv("a", "b", "c", **kw).over("k").alias("p"), engine=eng)["p"]
+    resid = frame.select(ns.elastic_net_cv("a", "b", "c", l1_ratio=1.0, mode="residuals", **kw).over("k").alias("r"), engine=eng)["r"]
+    cv = frame.select(ns.lasso_cv("a", "b", "c", mode="cv", **kw).over("k").alias("cv"), engine=eng)["cv"]
+    co = frame.select(ns.lasso_cv("a", "b", "c", mode="coefficients", **kw).over("k").alias("co"), engine=eng)["co"]
+    assert isinstance(cv, P.ElasticNetCV) and isinstance(co, P.Coefficients) and cv["l1_ratio"] == 1.0
+    keys = np.asarray(cv["keys"])
+    np.testing.assert_array_equal(keys, np.unique(key))
+    for g, kv in enumerate(keys):                              # every group on its own, through the restatement
+        rows = np.nonzero(key == kv)[0]
+        xs = [X[rows, j] for j in range(3)]
+        ref = enet_cv_batch(y[rows], xs, [0, len(rows)], None, n_alphas=10, l1_ratio=1.0, add_intercept=True, **TIGHT)
+        np.testing.assert_allclose(cv["cv_scores"][g], ref["cv_scores"][0], rtol=SCORE_RTOL)
+        np.testing.assert_allclose(cv["alphas"][g], ref["alphas_used"][0], rtol=SCORE_RTOL)
+        srt = np.sort(ref["cv_scores"][0])
+        if srt[1] > srt[0] * (1.0 + GAP):
+            assert cv["alpha_index"][g] == ref["alpha_index"][0]
+        _, p, r = chosen_outputs(ref, cv["alpha_index"][g:g + 1], y[rows], xs, [0, len(rows)], None, True)
+        np.testing.assert_allclose(pred[rows], p, rtol=1e-6, atol=1e-9)
+        np.testing.assert_allclose(resid[rows], r, rtol=1e-6, atol=1e-9)
+    one = frame.select(ns.elastic_net_cv("a", "b", "c", mode="cv", alphas=[0.1, 0.01]).alias("cv"), engine=eng)["cv"]
+    assert one["keys"] is None and one["cv_scores"].shape == (1, 2)
