@@ -477,6 +477,70 @@ typedef struct pols_rlm_out {
 int pols_rlm(pols_ctx *ctx, const pols_batch *b, const pols_ols_params *p, const pols_rlm_params *q, pols_out *out,
              const pols_rlm_out *r);
 
+/* Logistic / Poisson generalised linear model per group by iteratively reweighted least squares (no reference counterpart; R's
+ * glm / statsmodels' GLM with the canonical link, for every group of the frame in one call).
+ * Fitted rows and arithmetic.  Per group g, the fitted rows F_g are exactly those pols_least_squares / pols_rlm fit -- the same
+ * null-policy filtering / zero-filling and validity-mask rules, the ones column last -- n = |F_g|, kt = n_features + intercept.  All
+ * arithmetic is f64 on the inputs' values, for f32 batches too.
+ * Prior weights.  b->weights are prior weights w_i (frequency / variance weights): they multiply the working weight and the deviance
+ * terms; a null weight acts as 1e-24.  The rows are NOT scaled by sqrt(w).
+ * Offset.  q->offset, optional: o_i, n_rows in the batch dtype, living where b->mem says (16-byte aligned on the device); NULL
+ * means 0.  A null (NaN) offset makes its row a null row exactly as a null feature does.
+ * Families (canonical links only), eps = 2^-52:
+ *   POLS_GLM_BINOMIAL = 0:  mu = clip(1 / (1 + exp(-eta)), eps, 1 - eps),  d(mu) = mu (1 - mu),
+ *                           u(y, mu) = y log(y / mu) + (1 - y) log((1 - y) / (1 - mu))  with 0 log 0 = 0,
+ *                           domain 0 <= y <= 1 (fractions allowed),  start mu^0 = (y + 0.5) / 2
+ *   POLS_GLM_POISSON  = 1:  mu = max(exp(eta), eps),  d(mu) = mu,  u(y, mu) = y log(y / mu) - (y - mu),
+ *                           domain y >= 0,  start mu^0 = y + 0.1
+ * The deviance is D(mu) = 2 sum_{F_g} w_i u(y_i, mu_i).
+ * Iteration.
+ *   1. Start.  eta^0 = g(mu^0) (logit / log), D^0 = D(mu^0).  There is no b^0.
+ *   2. Update t -> t + 1, over F_g:  W_i = w_i d(mu_i),  z_i = eta_i - o_i + (y_i - mu_i) / d(mu_i);  b^(t+1) solves
+ *      (sum W_i x_i x_i') b = sum W_i x_i z_i by the static entries' f64 Cholesky rule -- a pivot fails when d^2 <= 16 kt eps A_jj;
+ *      then eta_i = x_i'b^(t+1) + o_i, mu as above, and D^(t+1).
+ *   3. Stop.  Converged when |D^(t+1) - D^t| <= tol (|D^(t+1)| + 0.1) (R's glm.control rule); otherwise the iteration stops after
+ *      max_iter updates with status POLS_GROUP_NOT_CONVERGED and the result is still returned.  n_iter is the number of updates made.
+ * Reported values.  coef = the last b; deviance = D at it; se_j = sqrt([(sum W x x')^-1]_jj) of the matrix factorised in the last
+ * update (dispersion 1, what statsmodels reports); out->pred = mu on the response scale, offset included; out->resid = y - mu;
+ * linpred = eta per row.  Every row is predicted or masked as pols_least_squares does for the policy (features and offsets
+ * zero-filled under every policy but "ignore", "drop" masks the rows outside the fit with NaN -- linpred too).
+ * Edge rules.
+ *   - n = 0: POLS_GROUP_EMPTY, zero coefficients, deviance / se NaN, n_iter 0.
+ *   - POLS_GROUP_FALLBACK with NaN coef, se, deviance, pred, resid and linpred: n <= kt; a fitted row with y outside the family's
+ *     domain, or a non-finite value under "ignore"; a Cholesky failure in any update; an update or a deviance that is not finite
+ *     (Poisson overflow).
+ *   - Complete separation is NOT detected: such a group ends as the stop rule says (the deviance creeps towards 0 while the
+ *     coefficients grow), usually as converged with large coefficients and standard errors.
+ *   - Otherwise POLS_GROUP_OK.
+ * Determinism.  No floating-point atomics, every sum in a fixed order: two runs are bit-identical, HOST and DEVICE batches agree
+ * bit for bit.  Groups short enough for a workgroup's LDS are fitted in one launch; longer ones, of any length, are cut into
+ * segments and iterate with two launches per update -- the entry then SYNCHRONISES THE STREAM once per update to read how many
+ * groups still iterate.  POLS_GLM_ENGINE=split (pols_set_option) sends every group that way.
+ * From pols_ols_params only null_policy is read.  POLS_ERR_INVALID: alpha != 0, positive, or has_l1_ratio with l1_ratio > 0; an
+ * unknown family; max_iter < 1; tol not positive and finite; an unknown null policy; a validity mask without a drop-family policy.
+ * POLS_ERR_UNSUPPORTED: more than 31 columns incl. the intercept.  There is no row limit, no Arrow twin and no sharded entry. */
+enum { POLS_GLM_BINOMIAL = 0, POLS_GLM_POISSON = 1 };
+
+typedef struct pols_glm_params {
+    int32_t family;           /* POLS_GLM_BINOMIAL / POLS_GLM_POISSON        */
+    int32_t max_iter;         /* >= 1                                        */
+    double  tol;              /* positive and finite                         */
+    const void *offset;       /* n_rows, batch dtype, or NULL                */
+} pols_glm_params;
+
+/* family = POLS_GLM_BINOMIAL, max_iter = 25, tol = 1e-8, offset = NULL */
+void pols_glm_params_default(pols_glm_params *q);
+
+typedef struct pols_glm_out {
+    double  *deviance;        /* n_groups: D at the returned coefficients    */
+    double  *se;              /* n_groups x kt: standard errors, dispersion 1 */
+    int32_t *n_iter;          /* n_groups: updates made                      */
+    void    *linpred;         /* n_rows, batch dtype: eta                    */
+} pols_glm_out;               /* all live where b->mem says; any may be NULL */
+
+int pols_glm(pols_ctx *ctx, const pols_batch *b, const pols_ols_params *p, const pols_glm_params *q, pols_out *out,
+             const pols_glm_out *r);
+
 /* Elastic-net / lasso regularisation path with K-fold selection of alpha, per group (no reference counterpart: the reference's
  * lasso / elastic_net take one alpha for the whole frame; this is the job of scikit-learn's LassoCV / ElasticNetCV with
  * fit_intercept=False and cv=KFold(n_folds)).  There is no Arrow twin of this entry.

@@ -31,6 +31,12 @@ int pols_stream_probe(pols_ctx *ctx, const pols_batch *b, void *pred_out);
  * n_rows is not a whole number of pieces.) */
 int pols_stream_probe_ex(pols_ctx *ctx, const pols_batch *b, void *pred_out, int mode);
 
+/* pols_glm's resident form (K13): the dynamic LDS, in bytes, of a workgroup whose longest group spans `tiles` 256-row tiles of `cols`
+ * staged columns (n_features + 1 + [weights] + [offset]) of `elem` bytes at kt columns incl. the intercept; and the 256-row tiles a
+ * group may span to stay in a launch that leaves room for `per_cu` workgroups on a CU (1 or 2).  No device needed. */
+long long pols_glm_resident_lds(int kt, int cols, int elem, int tiles);
+int pols_glm_resident_tiles(int kt, int cols, int elem, int per_cu);
+
 #ifdef __cplusplus
 }
 #endif

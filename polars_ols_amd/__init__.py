@@ -13,6 +13,7 @@ from .least_squares import (  # noqa: F401
     compute_least_squares_from_formula, compute_recursive_least_squares, compute_rolling_least_squares, predict,
     compute_ridge_cv, RidgeCV,
     compute_rlm, RLM,
+    compute_glm, GLM,
     compute_elastic_net_cv, ElasticNetCV,
 )
 

@@ -132,6 +132,19 @@ class RlmOut(C.Structure):            # pols_rlm_out
     _fields_ = [(n, C.c_void_p) for n in RLM_FIELDS]
 
 
+class GlmParams(C.Structure):         # pols_glm_params
+    _fields_ = [("family", C.c_int32), ("max_iter", C.c_int32), ("tol", C.c_double), ("offset", C.c_void_p)]
+
+
+# pols_glm_out, in the struct's order; the families (POLS_GLM_*)
+GLM_FIELDS = ("deviance", "se", "n_iter", "linpred")
+GLM_FAMILIES = {"binomial": 0, "poisson": 1}
+
+
+class GlmOut(C.Structure):            # pols_glm_out
+    _fields_ = [(n, C.c_void_p) for n in GLM_FIELDS]
+
+
 class EnetCvParams(C.Structure):      # pols_enet_cv_params
     _fields_ = [("alphas", C.POINTER(C.c_double)), ("n_alphas", C.c_int32), ("eps", C.c_double), ("l1_ratio", C.c_double),
                 ("n_folds", C.c_int32), ("max_iter", C.c_int32), ("tol", C.c_double), ("positive", C.c_int32)]
@@ -167,9 +180,11 @@ EXPORTS = [
     "pols_ridge_cv_params_default", "pols_ridge_cv",
     "pols_rlm_params_default", "pols_rlm",
     "pols_enet_cv_params_default", "pols_elastic_net_cv",
+    "pols_glm_params_default", "pols_glm",
 ]
 # measurement aids (include/pols_mi355x_debug.h): not part of the reference interface
-DEBUG_EXPORTS = ["pols_timing_enable", "pols_timing_collect", "pols_last_kernel_name", "pols_stream_probe", "pols_stream_probe_ex"]
+DEBUG_EXPORTS = ["pols_timing_enable", "pols_timing_collect", "pols_last_kernel_name", "pols_stream_probe", "pols_stream_probe_ex",
+                 "pols_glm_resident_lds", "pols_glm_resident_tiles"]
 POLS_COMM_ID_BYTES = 128
 
 
@@ -235,6 +250,10 @@ def lib() -> C.CDLL:
                                     C.POINTER(RidgeCvOut)]
         L.pols_rlm_params_default.argtypes, L.pols_rlm_params_default.restype = [C.POINTER(RlmParams)], None
         L.pols_rlm.argtypes = [C.c_void_p, C.POINTER(Batch), C.POINTER(OlsParams), C.POINTER(RlmParams), C.POINTER(Out), C.POINTER(RlmOut)]
+        L.pols_glm_resident_lds.argtypes, L.pols_glm_resident_lds.restype = [C.c_int] * 4, C.c_longlong
+        L.pols_glm_resident_tiles.argtypes = [C.c_int] * 4
+        L.pols_glm_params_default.argtypes, L.pols_glm_params_default.restype = [C.POINTER(GlmParams)], None
+        L.pols_glm.argtypes = [C.c_void_p, C.POINTER(Batch), C.POINTER(OlsParams), C.POINTER(GlmParams), C.POINTER(Out), C.POINTER(GlmOut)]
         L.pols_enet_cv_params_default.argtypes, L.pols_enet_cv_params_default.restype = [C.POINTER(EnetCvParams)], None
         L.pols_elastic_net_cv.argtypes = [C.c_void_p, C.POINTER(Batch), C.POINTER(OlsParams), C.POINTER(EnetCvParams), C.POINTER(Out),
                                           C.POINTER(EnetCvOut)]

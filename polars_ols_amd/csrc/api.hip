@@ -23,6 +23,7 @@
 #include "k8_wide.hpp"
 #include "k10_ridge_path.hpp"
 #include "k11_rlm.hpp"
+#include "k13_glm.hpp"
 #include "k12_enet_cv.hpp"
 #include "dyn_prep.hpp"
 
@@ -221,6 +222,7 @@ bool options_set(Options &o, const char *key, const char *v) {
     else if (ieq(key, "STATIC_ENGINE")) o.static_engine = !on ? 0 : ieq(v, "stream") ? 1 : ieq(v, "k2") ? 2 : ieq(v, "nok2") ? 3 : ieq(v, "k2w") ? 4 : 0;
     else if (ieq(key, "RLS_ENGINE")) o.rls_engine = !on ? 0 : ieq(v, "seq") ? 1 : ieq(v, "scan") ? 2 : ieq(v, "chunk") ? 3 : ieq(v, "halo") ? 4 : 0;
     else if (ieq(key, "RLM_ENGINE")) o.rlm_engine = !on ? 0 : ieq(v, "stream") ? 1 : 0;
+    else if (ieq(key, "GLM_ENGINE")) o.glm_engine = !on ? 0 : ieq(v, "split") ? 1 : 0;
     else if (ieq(key, "RLS_SPINS")) o.rls_spin_limit = on ? std::atoi(v) : d.rls_spin_limit;
     else if (ieq(key, "RLS_EARLY")) o.rls_early = on ? std::atoi(v) : d.rls_early;
     else if (ieq(key, "ROLLING_ENGINE")) o.rolling_engine = !on ? 0 : ieq(v, "chunk") ? 1 : ieq(v, "halo") ? 2 : ieq(v, "nocompact") ? 3 : ieq(v, "halowave") ? 4 : ieq(v, "scatter") ? 5 : 0;
@@ -233,7 +235,7 @@ bool options_set(Options &o, const char *key, const char *v) {
 void options_from_env(Options &o) {
     static const char *const keys[] = {"TIMELINE", "K1_NOOCC4", "K1_NOFAST", "K1_NOTINY", "K1_NORC1", "K1_SHAPE", "K1_F64_TEAM",
                                        "KG_NOYV", "K2_NOPREFETCH", "K1_PASSES", "K1_WG", "RLS_SPINS", "RLS_EARLY", "K1T_RC4", "K1_NT_LOADS", "STATIC_ENGINE",
-                                       "RLS_ENGINE", "RLM_ENGINE", "ROLLING_ENGINE", "K1_ENGINE", "K9_TAKE", "K1_PERSIST", "K1_PERSIST_SUB", "K1T_SUB32", "K1_NOEDGE", "K1T_SUB8",
+                                       "RLS_ENGINE", "RLM_ENGINE", "GLM_ENGINE", "ROLLING_ENGINE", "K1_ENGINE", "K9_TAKE", "K1_PERSIST", "K1_PERSIST_SUB", "K1T_SUB32", "K1_NOEDGE", "K1T_SUB8",
                                        "K1_XCD", "NO_SPLIT", "DEBUG_SKIP_FIXUP", "K4P_LPS", "SEG_TARGET", "K1_RC2_WIDE", "KG_SINGLE_BUFFER", "PREDICT_LOOP", "NO_CLASSES"};
     char name[64];
     for (const char *k : keys) {
@@ -2113,6 +2115,140 @@ int pols_rlm(pols_ctx *ctx, const pols_batch *b, const pols_ols_params *p, const
     if (ro->scale) POLS_HIP(hipMemcpyAsync(ro->scale, a.scale, sizeof(double) * G, hipMemcpyDeviceToHost, ctx->stream));
     if (ro->n_iter) POLS_HIP(hipMemcpyAsync(ro->n_iter, a.n_iter, sizeof(int32_t) * G, hipMemcpyDeviceToHost, ctx->stream));
     if (ro->weights) POLS_HIP(hipMemcpyAsync(ro->weights, a.weights, sz * (size_t)b->n_rows, hipMemcpyDeviceToHost, ctx->stream));
+    return unstage_outputs(ctx, b, b->n_groups, kt, o, st);
+}
+
+long long pols_glm_resident_lds(int kt, int cols, int elem, int tiles) { return (long long)k13_resident_lds(kt, cols, (size_t)elem, tiles); }
+int pols_glm_resident_tiles(int kt, int cols, int elem, int per_cu) { return k13_resident_tiles(kt, cols, (size_t)elem, per_cu); }
+
+void pols_glm_params_default(pols_glm_params *q) {
+    if (!q) return;
+    q->family = POLS_GLM_BINOMIAL;
+    q->max_iter = 25;
+    q->tol = 1e-8;
+    q->offset = nullptr;
+}
+
+// K13 (k13_glm.hip): the groups that stay resident in LDS iterate in one launch; the others are cut into segments and iterate with a
+// segment pass and a per-group pass per update, until the device counter of iterating groups reads zero; then K13's prediction pass
+// with the f64 coefficients.
+int pols_glm(pols_ctx *ctx, const pols_batch *b, const pols_ols_params *p, const pols_glm_params *q, pols_out *o, const pols_glm_out *ro) {
+    int rc = check_ctx(ctx);
+    if (rc) return rc;
+    if (b && o && b->n_features + (b->add_intercept ? 1 : 0) > K13_KMAX)
+        return fail(POLS_ERR_UNSUPPORTED, "glm: %d features (incl. intercept) > %d", b->n_features + (b->add_intercept ? 1 : 0), K13_KMAX);
+    if ((rc = check_batch(b, o, K13_KMAX))) return rc;
+    if (!p || !q) return fail(POLS_ERR_INVALID, "params / glm params is NULL");
+    if (p->alpha != 0.0 || p->positive || (p->has_l1_ratio && p->l1_ratio > 0.0))
+        return fail(POLS_ERR_INVALID, "glm: alpha / positive / l1_ratio do not apply (penalised GLMs are not built)");
+    if (q->family != POLS_GLM_BINOMIAL && q->family != POLS_GLM_POISSON) return fail(POLS_ERR_INVALID, "glm: unknown family %d", q->family);
+    if (q->max_iter < 1) return fail(POLS_ERR_INVALID, "glm: max_iter %d < 1", q->max_iter);
+    if (!(q->tol > 0.0) || !std::isfinite(q->tol)) return fail(POLS_ERR_INVALID, "glm: tol %g is not positive and finite", q->tol);
+    if (p->null_policy < POLS_NULL_IGNORE || p->null_policy > POLS_NULL_DROP_WINDOW) return fail(POLS_ERR_INVALID, "unknown null_policy %d", p->null_policy);
+    const int pol = (b->null_free && !b->valid) ? POLS_NULL_IGNORE : p->null_policy;
+    if (b->valid && (pol == POLS_NULL_IGNORE || pol == POLS_NULL_ZERO))
+        return fail(POLS_ERR_INVALID, "a validity mask needs a drop-family null_policy");
+    if (b->n_groups == 0) return POLS_OK;
+    pols_glm_out none;
+    std::memset(&none, 0, sizeof(none));
+    if (!ro) ro = &none;
+    const int kt = b->n_features + (b->add_intercept ? 1 : 0);
+    const bool host = b->mem == POLS_MEM_HOST;
+    const size_t G = (size_t)b->n_groups, sz = dtype_size(b->dtype);
+    // which form serves which group: the tiles a group spans from the 16-byte grid point at or below its first row
+    const int vec = b->dtype == POLS_F32 ? 4 : 2;
+    const int cols = b->n_features + 1 + (b->weights ? 1 : 0) + (q->offset ? 1 : 0);
+    // (two resident launches: the groups whose LDS request leaves room for a second workgroup on a CU, and the longer ones -- one long
+    //  group must not size the request of a whole frame of short ones)
+    const int cap = ctx->opt.glm_engine == 1 ? -1 : k13_resident_tiles(kt, cols, sz, 1);
+    const int cap2 = std::min(cap, k13_resident_tiles(kt, cols, sz, 2));
+    int64_t n_res = 0, n_spl = 0, res_tiles = 0, res2_tiles = 0, n_res1 = 0;
+    for (int64_t g = 0; g < b->n_groups; ++g) {
+        const int64_t s = b->group_offsets[g], e = b->group_offsets[g + 1];
+        if (e < s) return fail(POLS_ERR_INVALID, "group_offsets must not decrease");
+        const int64_t tiles = e > s ? (e - (s & ~(int64_t)(vec - 1)) + 255) / 256 : 0;
+        if (tiles <= cap2) { ++n_res; res2_tiles = std::max(res2_tiles, tiles); }
+        else if (tiles <= cap) { ++n_res; ++n_res1; res_tiles = std::max(res_tiles, tiles); }
+        else ++n_spl;
+    }
+    const int64_t *d_offs = nullptr;
+    int64_t max_rows = 0;
+    if ((rc = upload_offsets(ctx, b->group_offsets, b->n_groups, &d_offs, &max_rows, b->offsets_generation))) return rc;
+    Staged st;
+    if ((rc = stage_inputs(ctx, b, b->n_groups, kt, o, &st))) return rc;
+    if ((rc = fill_null_weights(ctx, b, &st))) return rc;
+    const size_t colb = round256(sz * (size_t)b->n_rows);
+    const void *d_off = q->offset;
+    if (q->offset && host && b->n_rows > 0) {
+        void *wf = nullptr;
+        if ((rc = ensure_scratch(ctx, Work::GlmOffset, colb, &wf))) return rc;
+        POLS_HIP(hipMemcpyAsync(wf, q->offset, sz * (size_t)b->n_rows, hipMemcpyHostToDevice, ctx->stream));
+        d_off = wf;
+    }
+    if (!host && (!aligned16(d_off) || !aligned16(ro->linpred))) return fail(POLS_ERR_INVALID, "device columns must be 16-byte aligned");
+    SegTables sg;
+    if (n_spl > 0 && (rc = ensure_segments(ctx, b, max_rows, sizeof(double) * k13_part_stride(kt), &sg))) return rc;
+    void *wc = nullptr, *ws = nullptr, *wo = nullptr;
+    if ((rc = ensure_scratch(ctx, Work::GlmCoef, round256(sizeof(double) * G * kt), &wc))) return rc;
+    const size_t stateb = round256(sizeof(double) * G * k13_state_stride(kt)), partb = sg.n_seg > 0 ? 0 : round256(sizeof(double) * G * k13_part_stride(kt));
+    if (n_spl > 0 && (rc = ensure_scratch(ctx, Work::GlmState, 256 + stateb + partb, &ws))) return rc;
+    GlmArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.y = st.y; a.w = st.w; a.o = d_off;
+    for (int j = 0; j < b->n_features; ++j) a.x[j] = st.x[(size_t)j];
+    a.offs = d_offs; a.n_groups = b->n_groups; a.n_rows = b->n_rows;
+    if (sg.n_seg > 0) { a.seg_offs = sg.offs; a.seg_map = sg.map; a.seg_first = sg.first; a.n_seg = sg.n_seg; }
+    a.valid = st.valid; a.null_policy = pol;
+    a.k_user = b->n_features; a.kt = kt; a.f32 = b->dtype == POLS_F32 ? 1 : 0;
+    a.family = q->family; a.max_iter = q->max_iter; a.tol = q->tol;
+    a.res_tiles = cap;
+    if (n_spl > 0) {
+        char *c = static_cast<char *>(ws);
+        a.active = reinterpret_cast<int32_t *>(c);
+        a.state = reinterpret_cast<double *>(c + 256);
+        a.part = sg.n_seg > 0 ? reinterpret_cast<double *>(sg.extra) : reinterpret_cast<double *>(c + 256 + stateb);
+    }
+    a.coef64 = static_cast<double *>(wc);
+    a.coef = st.coef; a.status = st.status;
+    const size_t vecb = round256(sizeof(double) * G), seb = round256(sizeof(double) * G * kt), idxb = round256(sizeof(int32_t) * G);
+    if (host) {
+        if ((rc = ensure_scratch(ctx, Work::GlmOut, vecb + seb + idxb + colb, &wo))) return rc;
+        char *c = static_cast<char *>(wo);
+        if (ro->deviance) a.deviance = reinterpret_cast<double *>(c);
+        if (ro->se) a.se = reinterpret_cast<double *>(c + vecb);
+        if (ro->n_iter) a.n_iter = reinterpret_cast<int32_t *>(c + vecb + seb);
+        if (ro->linpred) a.linpred = c + vecb + seb + idxb;
+    } else {
+        a.deviance = ro->deviance; a.se = ro->se; a.n_iter = ro->n_iter; a.linpred = ro->linpred;
+    }
+    ctx->last_kernel = n_res >= n_spl ? "k13_glm_resident" : "k13_glm_split";
+    if (n_res > n_res1) {
+        a.res_from = -1; a.res_to = cap2; a.ts = (int32_t)res2_tiles * 256 + 1;
+        if ((rc = k13_resident_launch(ctx, b->dtype, a))) return rc;
+    }
+    if (n_res1 > 0) {
+        a.res_from = cap2; a.res_to = cap; a.ts = (int32_t)res_tiles * 256 + 1;
+        if ((rc = k13_resident_launch(ctx, b->dtype, a))) return rc;
+    }
+    if (n_spl > 0) {
+        const int32_t n_active = (int32_t)std::min<int64_t>(n_spl, 0x7fffffff);
+        if ((rc = upload_small(ctx, a.active, &n_active, sizeof(n_active)))) return rc;
+        // one update per turn: at most max_iter updates and the start, then every group has stopped
+        for (int turn = 0; turn <= q->max_iter; ++turn) {
+            if ((rc = k13_split_launch(ctx, b->dtype, a, turn == 0))) return rc;
+            int32_t left = 0;
+            POLS_HIP(hipMemcpyAsync(&left, a.active, sizeof(left), hipMemcpyDeviceToHost, ctx->stream));
+            POLS_HIP(hipStreamSynchronize(ctx->stream));           // the host decides whether another update is launched
+            if (left <= 0) break;
+        }
+    }
+    a.pred = st.pred; a.resid = st.resid;
+    if ((rc = k13_predict_launch(ctx, b->dtype, a))) return rc;
+    if (!host) return POLS_OK;
+    if (ro->deviance) POLS_HIP(hipMemcpyAsync(ro->deviance, a.deviance, sizeof(double) * G, hipMemcpyDeviceToHost, ctx->stream));
+    if (ro->se) POLS_HIP(hipMemcpyAsync(ro->se, a.se, sizeof(double) * G * kt, hipMemcpyDeviceToHost, ctx->stream));
+    if (ro->n_iter) POLS_HIP(hipMemcpyAsync(ro->n_iter, a.n_iter, sizeof(int32_t) * G, hipMemcpyDeviceToHost, ctx->stream));
+    if (ro->linpred) POLS_HIP(hipMemcpyAsync(ro->linpred, a.linpred, sz * (size_t)b->n_rows, hipMemcpyDeviceToHost, ctx->stream));
     return unstage_outputs(ctx, b, b->n_groups, kt, o, st);
 }
 

@@ -86,6 +86,10 @@ enum class Work : int {
     EnetCvGram,     // elastic-net path (K12): fitted rows and fold Gram matrices per segment / group, then per group
     EnetCvWork,     // elastic-net path (K12): candidates and their order, fold scores, sweep counts, the f64 path and grid, the winners' coefficients
     EnetCvOut,      // elastic-net path (K12): the pols_enet_cv_out fields of a HOST batch before they go home
+    GlmCoef,        // GLM (K13): the groups' coefficients in f64 for the prediction pass
+    GlmState,       // GLM (K13): split form -- the counter of iterating groups, the groups' state, Gram partials of a frame without segment tables
+    GlmOffset,      // GLM (K13): the offset column of a HOST batch
+    GlmOut,         // GLM (K13): deviance / se / n_iter / linpred of a HOST batch before they go home
     Count
 };
 
@@ -131,6 +135,7 @@ struct Options {
     int k4p_lps = 0;              // POLS_K4P_LPS        K4p / K3p (k4p_wide.hip): lanes per sequence, 0 auto, 64 / 16 (up to 16 features) / 32 (17..32, RLS)
     int k1_wg = 0;                // POLS_K1_WG          8-column team kernels: 2 / 4 = 512- / 1 024-thread workgroups (2 / 4 times the groups per workgroup, A/B)
     int rlm_engine = 0;           // POLS_RLM_ENGINE     0 auto (groups that fit the LDS stay resident), 1 "stream" (K11's streamed form for every group)
+    int glm_engine = 0;           // POLS_GLM_ENGINE     0 auto (groups that fit the LDS stay resident), 1 "split" (K13's split form for every group)
     int k1_xcd = 0;               // POLS_K1_XCD         resident K1 kernels: 1 = XCD-contiguous workgroup -> group map (each XCD walks one eighth of the frame)
 };
 void options_from_env(Options &o);

@@ -27,9 +27,10 @@
 //   weigh     omega_i over the work column, then the weighted Gram matrix [X~ | y~]' diag(omega) [X~ | y~] with k10_gram_kernel's
 //             assignment of the (kt + 1)(kt + 2) / 2 entries to threads (row partitions summed in partition order);
 //   solve     wave 0: right-looking Cholesky in LDS (the trailing update spread over the lanes), the two substitutions, the
-//             finiteness check; every thread then evaluates the stop test on the broadcast result.
+//             finiteness check (k11_solve.inl); every thread then evaluates the stop test on the broadcast result.
 #include "k11_rlm.hpp"
 #include "k10_stage.inl"
+#include "k11_solve.inl"
 
 namespace pols {
 
@@ -54,11 +55,6 @@ int k11_resident_tiles(int kt) {
 
 __device__ __forceinline__ double k11_nan() { return __longlong_as_double(0x7ff8000000000000LL); }
 __device__ __forceinline__ unsigned long long k11_bits(double v) { return (unsigned long long)__double_as_longlong(v); }
-// LDS traffic between the lanes of ONE wave: its LDS operations complete in order, the compiler must not move them
-__device__ __forceinline__ void k11_wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 __device__ __forceinline__ double k11_omega(const int norm, const double c, const double u) {
     double om;
     if (norm == POLS_RLM_HUBER) om = u <= c ? 1.0 : c / u;
@@ -137,48 +133,7 @@ __global__ void __launch_bounds__(256) k11_rlm_kernel(const RlmArgs a) {
     // Gm -> coefficients in rhs, ok_s; wave 0 works, ends on a barrier
     auto solve = [&]() {
         if (wv == 0) {
-            for (int en = lane; en < ne; en += 64) {
-                int i = 0, t = en;
-                while (t >= nz - i) { t -= nz - i; ++i; }
-                const int j = i + t;
-                const double v = Gm[en];
-                if (j == kt) { if (i < kt) rhs[i] = v; }
-                else { A[i * LD + j] = v; A[j * LD + i] = v; if (i == j) d0[i] = v; }
-            }
-            k11_wave_sync();
-            bool ok = true;
-            const double noise = 16.0 * (double)kt * K11_EPS;
-            for (int j = 0; j < kt; ++j) {
-                const double d = A[j * LD + j];
-                if (!(d > noise * d0[j])) { ok = false; break; }   // (wave-uniform: every lane read the same word)
-                const double sd = sqrt(d);
-                k11_wave_sync();
-                if (lane >= j && lane < kt) A[lane * LD + j] = lane == j ? sd : A[lane * LD + j] / sd;
-                k11_wave_sync();
-                for (int p = lane; p < kt * kt; p += 64) {         // the trailing lower triangle: A[i][c] -= L[i][j] L[c][j], j < c <= i
-                    const int i = p / kt, c = p - i * kt;
-                    if (c > j && c <= i) A[i * LD + c] -= A[i * LD + j] * A[c * LD + j];
-                }
-                k11_wave_sync();
-            }
-            if (ok) {
-                for (int j = 0; j < kt; ++j) {                     // L z = X~'y~
-                    const double z = rhs[j] / A[j * LD + j];
-                    k11_wave_sync();
-                    if (lane == j) rhs[j] = z;
-                    else if (lane > j && lane < kt) rhs[lane] -= A[lane * LD + j] * z;
-                    k11_wave_sync();
-                }
-                for (int j = kt - 1; j >= 0; --j) {                // L'b = z
-                    const double z = rhs[j] / A[j * LD + j];
-                    k11_wave_sync();
-                    if (lane == j) rhs[j] = z;
-                    else if (lane < j) rhs[lane] -= A[j * LD + lane] * z;
-                    k11_wave_sync();
-                }
-                const double v = lane < kt ? rhs[lane] : 0.0;
-                ok = __ballot(!(fabs(v) <= 1.79769313486231570815e308)) == 0;   // every coefficient finite
-            }
+            const bool ok = k11_chol_solve(Gm, A, rhs, d0, kt, lane);
             if (lane == 0) ok_s = ok ? 1 : 0;
         }
         __syncthreads();

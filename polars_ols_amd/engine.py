@@ -363,6 +363,45 @@ class Engine:
         L.check(self._lib.pols_rlm(self._h, C.byref(plan._b), C.byref(plan._p), C.byref(q), C.byref(plan._o), C.byref(ro)))
         return res
 
+    def glm(self, y, x_cols: Sequence, offsets, *, family: str = "binomial", offset=None, max_iter: int = 25, tol: float = 1e-8,
+            want: Sequence[str] = ("coef", "status", "deviance", "n_iter"), weights=None, valid=None, add_intercept: bool = False,
+            null_policy: str = "ignore") -> Dict:
+        """Logistic / Poisson generalised linear model (canonical link) for every group in one call: iteratively reweighted least
+        squares, the whole iteration on the device (pols_glm; the definitions and edge rules are in include/pols_mi355x.h).
+        ``family``: "binomial" or "poisson"; ``offset``: optional per-row offset of the linear predictor; ``weights`` are prior
+        weights.  ``want``: any of ``coef status`` (status 3 = stopped at ``max_iter``), ``pred`` (the mean mu), ``resid`` (y - mu),
+        ``deviance`` [n_groups, f64], ``se`` [n_groups, k, f64], ``n_iter`` [n_groups, int32] and ``linpred`` [n_rows, batch dtype].
+        Arrays are numpy or torch and live where the inputs live.  Groups too long for a workgroup's LDS iterate with launches of
+        their own and synchronise the stream once per update."""
+        q = _glm_params(self._lib, family, max_iter, tol)
+        want = tuple(want)
+        known = ("coef", "pred", "resid", "status") + L.GLM_FIELDS
+        unknown = [w for w in want if w not in known]
+        if unknown:
+            raise ValueError(f"unknown glm fields {unknown}; known: {list(known)}")
+        plan = self.plan_least_squares(y, x_cols, offsets, weights=weights, valid=valid, add_intercept=add_intercept,
+                                       null_policy=null_policy, want=tuple(w for w in want if w in ("coef", "pred", "resid", "status")))
+        b = plan._b
+        dev = b.mem == L.POLS_MEM_DEVICE
+        like = plan._keep[0][0]
+        res = plan.results
+        off = None
+        if offset is not None:
+            off = offset.to(like.dtype).contiguous() if dev else np.ascontiguousarray(offset, dtype=like.dtype)
+            if tuple(off.shape) != (b.n_rows,):
+                raise ValueError(f"glm: 'offset' must have one value per row ({b.n_rows}), got shape {tuple(off.shape)}")
+            q.offset = self._ptr(off)
+        f64, i32 = (torch.float64, torch.int32) if dev else (np.float64, np.int32)
+        kt = b.n_features + b.add_intercept
+        shapes = {"deviance": ((b.n_groups,), f64), "se": ((b.n_groups, kt), f64), "n_iter": ((b.n_groups,), i32),
+                  "linpred": ((b.n_rows,), like.dtype)}
+        for key in L.GLM_FIELDS:
+            if key in want:
+                res[key] = self._alloc(dev, shapes[key][1], shapes[key][0], like)
+        ro = L.GlmOut(**{k: self._ptr(res.get(k)) for k in L.GLM_FIELDS})
+        L.check(self._lib.pols_glm(self._h, C.byref(plan._b), C.byref(plan._p), C.byref(q), C.byref(plan._o), C.byref(ro)))
+        return res
+
     def elastic_net_cv(self, y, x_cols: Sequence, offsets, alphas=None, *, n_alphas: int = 100, eps: float = 1e-3, l1_ratio: float = 0.5,
                        n_folds: int = 5, max_iter: int = 1000, tol: float = 1e-5, positive: bool = False,
                        want: Sequence[str] = ("coef", "status", "alpha", "alpha_index", "score"), weights=None, valid=None,
@@ -680,6 +719,21 @@ def _ols_params(lib, alpha=0.0, l1_ratio=None, max_iter=1000, tol=1e-5, positive
     p.has_rcond, p.rcond = int(rcond is not None), float(rcond) if rcond is not None else 0.0
     p.null_policy = L.NULL_POLICIES[null_policy]
     return p
+
+
+def _glm_params(lib, family, max_iter, tol) -> "L.GlmParams":
+    """the argument checks of Engine.glm / compute_glm (``lib`` None: check only, no device needed)"""
+    if family not in L.GLM_FAMILIES:
+        raise ValueError(f"glm: 'family' must be one of {sorted(L.GLM_FAMILIES)}, got {family!r}")
+    if isinstance(max_iter, bool) or int(max_iter) != max_iter or max_iter < 1:
+        raise ValueError(f"glm: 'max_iter' must be an integer >= 1 (got {max_iter!r})")
+    if not (tol > 0.0 and np.isfinite(tol)):
+        raise ValueError(f"glm: 'tol' must be positive and finite (got {tol!r})")
+    q = L.GlmParams()
+    if lib is not None:
+        lib.pols_glm_params_default(C.byref(q))
+    q.family, q.max_iter, q.tol, q.offset = L.GLM_FAMILIES[family], int(max_iter), float(tol), None
+    return q
 
 
 def _rlm_params(lib, norm, c, max_iter, tol) -> "L.RlmParams":

@@ -26,7 +26,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import PolsPanic
-from .engine import Engine, Layout, _enet_cv_params, _is_torch, _ridge_cv_grid, _rlm_params, default_engine
+from .engine import Engine, Layout, _enet_cv_params, _is_torch, _glm_params, _ridge_cv_grid, _rlm_params, default_engine
 
 try:
     import torch
@@ -43,6 +43,7 @@ __all__ = [
     "compute_ridge_cv", "RidgeCV",
     "compute_elastic_net_cv", "ElasticNetCV",
     "compute_rlm", "RLM",
+    "compute_glm", "GLM",
 ]
 
 # ---- polars_ols/least_squares.py:47-63 --------------------------------------------------------------------------
@@ -522,6 +523,40 @@ def _apply_rlm(frame: Frame, over, eng: Optional[Engine], target: Expr, features
     return target.output_name, grp.untake(out["pred"] if mode == "predictions" else out["resid"])
 
 
+class GLM(dict):
+    """mode="glm" of a generalised linear model fit (pols_glm; the definitions are in include/pols_mi355x.h): per group ``coef`` and
+    ``se`` (standard errors, dispersion 1) [G, k], ``deviance``, ``n_iter`` (updates made) and ``status`` (0 converged, 1 no fit,
+    2 no rows, 3 stopped at max_iter) [G]; ``linpred`` holds the linear predictor eta in FRAME order; ``keys`` holds the group keys
+    of an ``.over`` (None for a whole-frame fit, where G == 1)."""
+
+    def __init__(self, out, keys, linpred, family):
+        super().__init__(coef=out["coef"], se=out["se"], deviance=out["deviance"], n_iter=out["n_iter"], status=out["status"],
+                         linpred=linpred, keys=keys, family=family)
+        self.keys_ = keys
+
+
+_VALID_GLM_MODES = ("predictions", "residuals", "coefficients", "glm")
+
+
+def _apply_glm(frame: Frame, over, eng: Optional[Engine], target: Expr, features: Sequence[Expr], sample_weights, offset,
+               add_intercept: bool, mode: str, family: str, max_iter: int, tol: float, null_policy: str):
+    """compute_glm body: the group layout of _apply_static around Engine.glm."""
+    y, xs, names, icpt, w = _pre_process_data(frame, target, features, sample_weights, add_intercept)
+    off = None if offset is None else parse_into_expr(offset)._column(frame)
+    eng = eng or default_engine(y.device.index or 0 if _is_torch(y) else 0)
+    grp = _Groups(eng, None if over is None else (frame[over] if isinstance(over, str) else over), y.shape[0])
+    moved = grp.take([y, w, off] + list(xs))
+    want = {"predictions": ("pred",), "residuals": ("resid",), "coefficients": ("coef",),
+            "glm": ("coef", "status", "deviance", "se", "n_iter", "linpred")}[mode]
+    out = eng.glm(moved[0], moved[3:], grp.offsets, family=family, offset=moved[2], max_iter=max_iter, tol=tol, want=want,
+                  weights=moved[1], add_intercept=icpt, null_policy=null_policy)
+    if mode == "glm":
+        return "glm", GLM(out, grp.keys, grp.untake(out["linpred"]), family)
+    if mode == "coefficients":
+        return "coefficients", Coefficients(names, out["coef"], grp.keys, grp.gid_frame(out["coef"]))
+    return target.output_name, grp.untake(out["pred"] if mode == "predictions" else out["resid"])
+
+
 def _apply_dynamic(frame: Frame, over, eng: Optional[Engine], target: Expr, features: Sequence[Expr], sample_weights,
                    add_intercept: bool, mode: str, kind: str, kw):
     """compute_recursive_least_squares / compute_rolling_least_squares bodies (ls.py:332-409 around
@@ -677,6 +712,22 @@ def compute_rlm(target, *features, norm: str = "huber", c: Optional[float] = Non
     t, fs = parse_into_expr(target), [parse_into_expr(f) for f in features]
     return Expr(t._name, fn=lambda frame, over, eng: _apply_rlm(frame, over, eng, t, fs, sample_weights, add_intercept, mode, norm, c,
                                                                 max_iter, tol, null_policy))
+
+
+def compute_glm(target, *features, family: str = "binomial", offset=None, max_iter: int = 25, tol: float = 1e-8, sample_weights=None,
+                add_intercept: bool = False, mode: str = "predictions", null_policy: str = "ignore") -> Expr:
+    """Logistic ("binomial") / Poisson regression per group with the canonical link (R's glm / statsmodels' GLM for every group of
+    the frame in one call); ``offset`` is an optional column added to the linear predictor, ``sample_weights`` are prior weights.
+    Mode "predictions" returns the fitted means, "residuals" y minus them, "coefficients" the coefficients; mode="glm" returns a
+    ``GLM`` with the coefficients, standard errors, deviance, iteration count, status and the linear predictor in frame order."""
+    if mode not in _VALID_GLM_MODES:
+        raise ValueError(f"'mode' must be one of {_VALID_GLM_MODES}, got {mode!r}")
+    if null_policy not in _VALID_NULL_POLICIES:
+        raise ValueError(f"'null_policy' must be one of {sorted(_VALID_NULL_POLICIES)}, got {null_policy!r}")
+    _glm_params(None, family, max_iter, tol)
+    t, fs = parse_into_expr(target), [parse_into_expr(f) for f in features]
+    return Expr(t._name, fn=lambda frame, over, eng: _apply_glm(frame, over, eng, t, fs, sample_weights, offset, add_intercept, mode,
+                                                                family, max_iter, tol, null_policy))
 
 
 def compute_multi_target_least_squares(targets, *features, sample_weights=None, add_intercept: bool = False,
@@ -942,6 +993,11 @@ class LeastSquares:
             sample_weights=None, add_intercept: bool = False, mode: str = "predictions", null_policy: str = "ignore") -> Expr:
         return compute_rlm(self._expr, *features, norm=norm, c=c, max_iter=max_iter, tol=tol, sample_weights=sample_weights,
                            add_intercept=add_intercept, mode=mode, null_policy=null_policy)
+
+    def glm(self, *features, family: str = "binomial", offset=None, max_iter: int = 25, tol: float = 1e-8, sample_weights=None,
+            add_intercept: bool = False, mode: str = "predictions", null_policy: str = "ignore") -> Expr:
+        return compute_glm(self._expr, *features, family=family, offset=offset, max_iter=max_iter, tol=tol,
+                           sample_weights=sample_weights, add_intercept=add_intercept, mode=mode, null_policy=null_policy)
 
     def lasso(self, *features, alpha: float, **kwargs) -> Expr:
         return self.least_squares(*features, alpha=alpha, l1_ratio=1.0, **kwargs)

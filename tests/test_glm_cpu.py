@@ -1,0 +1,214 @@
+"""The numpy restatement of the per-group logistic / Poisson GLM (tests/glm_ref.py, the yardstick of tests/test_glm_gpu.py) against
+scikit-learn and scipy, its edge rules, the Python argument checks of the glm entry and the resources of the K13 code objects.
+No GPU here."""
+import re
+from pathlib import Path
+
+import numpy as np
+import pytest
+
+from glm_ref import (EMPTY, FALLBACK, FAMILIES, NOT_CONVERGED, OK, decided, deviance, gen_panel_glm, glm_batch, glm_group, mean,
+                     outputs)
+
+ROOT = Path(__file__).resolve().parent.parent
+# name: (groups, fewest rows, most rows, columns incl. the intercept, seed) -- the frames of tests/test_glm_gpu.py
+SHAPES = {
+    "under_one_tile": (200, 24, 60, 3, 5),
+    "short": (200, 40, 120, 5, 5),
+    "several_tiles": (40, 300, 700, 8, 5),
+    "wide": (12, 100, 300, 20, 6),
+    "split_forced": (40, 600, 1500, 8, 5),
+    "long": (3, 5000, 9000, 6, 5),
+}
+
+
+def _one_group(family, n=400, k=4, seed=3):
+    """features with the ones column last, y, weights, offset of one group"""
+    y, cols, offs, w, off = gen_panel_glm(1, n, n, k, np.float64, family, seed)
+    X = np.column_stack(cols + [np.ones(n)])
+    return X, y, w, off
+
+
+def test_binomial_coefficients_agree_with_scikit_learn():
+    from sklearn.linear_model import LogisticRegression
+
+    X, y, w, _ = _one_group("binomial")
+    for sw in (None, w):
+        res = glm_group(X, y, np.ones(len(y)) if sw is None else sw, np.zeros(len(y)), "binomial", 100, 1e-12)
+        assert res["status"] == OK
+        sk = LogisticRegression(penalty=None, fit_intercept=False, tol=1e-12, max_iter=10000).fit(X, y, sample_weight=sw)
+        print("binomial: max |coef - sklearn|", np.abs(res["coef"] - sk.coef_[0]).max())
+        np.testing.assert_allclose(res["coef"], sk.coef_[0], rtol=1e-6, atol=1e-6)
+
+
+def test_poisson_coefficients_agree_with_scikit_learn():
+    from sklearn.linear_model import PoissonRegressor
+
+    X, y, w, _ = _one_group("poisson")
+    res = glm_group(X, y, w, np.zeros(len(y)), "poisson", 100, 1e-12)
+    assert res["status"] == OK
+    sk = PoissonRegressor(alpha=0.0, fit_intercept=False, tol=1e-12, max_iter=10000).fit(X, y, sample_weight=w)
+    print("poisson: max |coef - sklearn|", np.abs(res["coef"] - sk.coef_).max())
+    np.testing.assert_allclose(res["coef"], sk.coef_, rtol=1e-6, atol=1e-6)
+
+
+@pytest.mark.parametrize("family", FAMILIES)
+def test_coefficients_minimise_the_deviance_with_an_offset_and_se_is_the_inverse_information(family):
+    """BFGS with the analytic gradient X'(w (mu - y)) of D / 2, stopped at a gradient norm of 1e-9: with an information matrix whose
+    smallest eigenvalue is above 1 on this data, that is an error below 1e-8 in the coefficients -- compared at 1e-6."""
+    from scipy.optimize import minimize
+
+    X, y, w, off = _one_group(family)
+    res = glm_group(X, y, w, off, family, 100, 1e-12)
+    assert res["status"] == OK
+
+    def half_deviance(b):
+        mu, _ = mean(X @ b + off, family)
+        return 0.5 * deviance(y, mu, w, family), X.T @ (w * (mu - y))
+
+    opt = minimize(half_deviance, np.zeros(X.shape[1]), jac=True, method="BFGS", options=dict(gtol=1e-9, maxiter=1000))
+    print(family, "max |coef - BFGS|", np.abs(res["coef"] - opt.x).max())
+    np.testing.assert_allclose(res["coef"], opt.x, rtol=1e-6, atol=1e-6)
+    mu, d = mean(X @ res["coef"] + off, family)
+    info = (X * (w * d)[:, None]).T @ X
+    assert np.linalg.eigvalsh(info).min() > 1.0
+    np.testing.assert_allclose(res["se"], np.sqrt(np.diag(np.linalg.inv(info))), rtol=1e-3)
+    assert res["deviance"] == deviance(y, mu, w, family)
+
+
+def test_the_stop_rule_and_n_iter():
+    X, y, w, off = _one_group("poisson")
+    full = glm_group(X, y, w, off, "poisson", 100, 1e-10)
+    assert full["status"] == OK and len(full["ratios"]) == full["n_iter"] and full["ratios"][-1] <= 1.0
+    assert all(r > 1.0 for r in full["ratios"][:-1])
+    two = glm_group(X, y, w, off, "poisson", 2, 1e-10)
+    assert two["status"] == NOT_CONVERGED and two["n_iter"] == 2 and np.isfinite(two["coef"]).all() and np.isfinite(two["se"]).all()
+    assert two["ratios"] == full["ratios"][:2]
+
+
+def test_edge_rules():
+    X, y, w, off = _one_group("binomial", n=60, k=3)
+    one, zero = np.ones(60), np.zeros(60)
+
+    def nan_result(r):
+        return (r["status"] == FALLBACK and np.isnan(r["coef"]).all() and np.isnan(r["se"]).all() and np.isnan(r["deviance"]))
+
+    r = glm_group(X[:0], y[:0], one[:0], zero[:0])
+    assert r["status"] == EMPTY and (r["coef"] == 0).all() and np.isnan(r["se"]).all() and np.isnan(r["deviance"]) and r["n_iter"] == 0
+    assert nan_result(glm_group(X[:3], y[:3], one[:3], zero[:3]))                # n <= kt
+    y2 = y.copy()
+    y2[5] = 2.0
+    assert nan_result(glm_group(X, y2, one, zero, "binomial"))                    # outside [0, 1]
+    assert glm_group(X, y2, one, zero, "poisson")["status"] == OK                 # ... a count for Poisson
+    y2[5] = -1.0
+    assert nan_result(glm_group(X, y2, one, zero, "poisson"))
+    y2[5] = 0.25                                                                  # fractions are allowed
+    assert glm_group(X, y2, one, zero, "binomial")["status"] == OK
+    for what in range(4):                                                         # a non-finite value anywhere
+        args = [X.copy(), y.copy(), one.copy(), zero.copy()]
+        args[what][7] = np.nan
+        assert nan_result(glm_group(*args))
+    Xd = np.column_stack([X[:, 0], X[:, 0], X[:, 2]])                             # a duplicated column: no Cholesky factor
+    assert nan_result(glm_group(Xd, y, one, zero))
+    big = zero.copy()
+    big[0] = 800.0                                                                # exp overflows: the deviance is not finite
+    yp = np.round(np.exp(0.3 * X[:, 0]))
+    assert nan_result(glm_group(X, yp, one, big, "poisson"))
+    # through the batch: a NaN under "ignore" fails its group alone, "drop" removes the row; a null offset is a null feature
+    y, cols, offs, w, off = gen_panel_glm(3, 50, 50, 3, np.float64, "binomial", 7)
+    off = off.copy()
+    off[60] = np.nan
+    b = glm_batch(y, cols, offs, "binomial", off, add_intercept=True)
+    assert list(b["status"]) == [OK, FALLBACK, OK]
+    b = glm_batch(y, cols, offs, "binomial", off, add_intercept=True, null_policy="drop")
+    assert list(b["status"]) == [OK, OK, OK] and not b["fit"][60] and b["n"][1] == 49
+    eta, mu, resid = outputs(b["coef"], b["fit"], y, cols, offs, "binomial", off, True, "drop")
+    assert np.isnan(eta[60]) and np.isnan(mu[60]) and np.isfinite(np.delete(mu, 60)).all()
+    keep = np.arange(150) != 60
+    f = glm_batch(y[keep], [c[keep] for c in cols], [0, 50, 99, 149], "binomial", off[keep], add_intercept=True)
+    np.testing.assert_array_equal(b["coef"], f["coef"])                           # "drop" equals filter-then-fit
+    z = glm_batch(y, cols, offs, "binomial", off, add_intercept=True, null_policy="zero")
+    assert z["fit"].all() and z["status"][1] == OK
+
+
+@pytest.mark.parametrize("shape", list(SHAPES))
+def test_the_undecided_share_of_the_gpu_frames_is_at_most_five_percent(shape):
+    """the frames of tests/test_glm_gpu.py at its parameters (tol 1e-10, max_iter 100): at most 5 % of the groups have a step whose
+    stop ratio lies in [0.5, 2], and none fails to converge.  Seed 5; the 12 wide groups use seed 6 (seed 5 leaves 1 - 2 of 12
+    undecided in the binomial fits)."""
+    G, lo, hi, kt, seed = SHAPES[shape]
+    for family in FAMILIES:
+        for dtype in (np.float64, np.float32):
+            for full in (False, True):
+                y, cols, offs, w, off = gen_panel_glm(G, lo, hi, kt, dtype, family, seed)
+                ref = glm_batch(y, cols, offs, family, off if full else None, 100, 1e-10, w if full else None, add_intercept=True)
+                n_und = int((~decided(ref)).sum())
+                print(shape, family, np.dtype(dtype).name, full, "undecided", n_und, "of", G, "max |coef|", np.abs(ref["coef"]).max())
+                assert 20 * n_und <= G and (ref["status"] == OK).all()
+
+
+def test_python_argument_checks_and_the_exported_pair():
+    import polars_ols_amd as P
+    from polars_ols_amd import _lib
+    from polars_ols_amd.engine import _glm_params
+
+    header = (ROOT / "include" / "pols_mi355x.h").read_text()
+    code = re.sub(r"/\*.*?\*/", "", header, flags=re.S)
+    for name in ("pols_glm", "pols_glm_params_default"):
+        assert name in _lib.EXPORTS and re.search(rf"\b{name}\s*\(", header)
+    for name, val in _lib.GLM_FAMILIES.items():
+        assert re.search(rf"POLS_GLM_{name.upper()}\s*=\s*{val}\b", header)
+    m = re.search(r"typedef struct pols_glm_params \{(.*?)\} pols_glm_params;", code, re.S)
+    assert re.findall(r"\b\*?(\w+);", m.group(1)) == [f for f, _ in _lib.GlmParams._fields_]
+    m = re.search(r"typedef struct pols_glm_out \{(.*?)\} pols_glm_out;", code, re.S)
+    assert re.findall(r"\*(\w+);", m.group(1)) == list(_lib.GLM_FIELDS)
+    q = _glm_params(None, "poisson", 7, 1e-6)
+    assert (q.family, q.max_iter, q.tol, q.offset) == (1, 7, 1e-6, None)
+    for bad in (dict(family="gamma"), dict(max_iter=0), dict(max_iter=2.5), dict(tol=0.0), dict(tol=float("inf")), dict(tol=float("nan"))):
+        kw = dict(family="binomial", max_iter=25, tol=1e-8)
+        kw.update(bad)
+        with pytest.raises(ValueError):
+            _glm_params(None, **kw)
+    ns = P.col("y").least_squares
+    assert isinstance(ns.glm("a", "b", family="poisson", offset="o", mode="glm"), P.Expr)
+    assert isinstance(P.compute_glm("y", "a", add_intercept=True), P.Expr)
+    with pytest.raises(ValueError):
+        ns.glm("a", mode="rlm")
+    with pytest.raises(ValueError):
+        ns.glm("a", null_policy="nope")
+    with pytest.raises(ValueError):
+        ns.glm("a", family="gaussian")
+    assert issubclass(P.GLM, dict)
+
+
+def test_k13_kernels_use_no_scratch_and_no_agprs():
+    import sys
+
+    from polars_ols_amd import _lib
+
+    sys.path.insert(0, str(ROOT / "scripts"))
+    from check_scratch import LLVM, kernel_scratch
+
+    if not (LLVM / "llvm-objdump").exists():
+        pytest.skip("ROCm LLVM tools not present")
+    ks = {k: v for k, v in kernel_scratch(_lib.LIB_PATH).items() if "k13_glm" in k}
+    assert len(ks) == 7, sorted(ks)                            # resident, segment pass, prediction: f32 and f64; the group pass
+    for name, (scratch, vgpr, agpr) in ks.items():
+        assert scratch == 0 and agpr == 0 and vgpr > 0, (name, scratch, vgpr, agpr)
+
+
+def test_the_resident_form_leaves_room_for_two_workgroups_at_1000_rows_of_8_f32_columns():
+    """the library's own LDS formula (no device): 1 000 rows x 8 f32 columns -- four 256-row tiles -- ask for at most half of a CU's
+    160 KB, with and without weights and offset; groups up to the two-per-CU tile count get a launch of their own (the budgets keep 256 bytes back)"""
+    from polars_ols_amd import _lib
+
+    L = _lib.lib()
+    for cols in (9, 10, 11):                                   # x, y, [w], [o]
+        lds = L.pols_glm_resident_lds(8, cols, 4, 4)
+        print(cols, "columns:", lds, "bytes")
+        assert 0 < lds <= 80 * 1024
+        two, one = L.pols_glm_resident_tiles(8, cols, 4, 2), L.pols_glm_resident_tiles(8, cols, 4, 1)
+        assert 4 <= two < one
+        assert L.pols_glm_resident_lds(8, cols, 4, two) <= 80 * 1024 - 256 < L.pols_glm_resident_lds(8, cols, 4, two + 1)
+        assert L.pols_glm_resident_lds(8, cols, 4, one) <= 160 * 1024 - 256 < L.pols_glm_resident_lds(8, cols, 4, one + 1)
+    assert L.pols_glm_resident_lds(8, 9, 4, 4) == 57104
