@@ -608,6 +608,67 @@ typedef struct pols_enet_cv_out {
 int pols_elastic_net_cv(pols_ctx *ctx, const pols_batch *b, const pols_ols_params *p, const pols_enet_cv_params *q, pols_out *out,
                         const pols_enet_cv_out *cv);
 
+/* Two-stage least squares (instrumental variables) per group with first-stage and over-identification diagnostics (no reference
+ * counterpart; linearmodels' IV2SLS / statsmodels' IV2SLS for every group of the frame in one call).
+ * Fitted rows.  Per group g, the fitted rows F_g are those pols_least_squares fits -- the same null-policy filtering / zero-filling
+ * and validity-mask rules, a null weight acting as 1e-24 -- with the excluded-instrument columns counted as features for every null
+ * rule: a null instrument makes its row a null row, and is zero-filled where features are.  Rows are scaled by sqrt(w) (x~, z~, y~);
+ * n = |F_g|.
+ * Columns.  b->x_cols holds first the n_features - n_endog exogenous regressors X1, then the n_endog endogenous ones X2; the ones
+ * column (add_intercept) is last and exogenous; kt = n_features + intercept, and the coefficients are in that order.  q->z_cols holds
+ * the m = n_instruments excluded instruments Z2, m >= n_endog >= 1, each n_rows in the batch dtype, living where b->mem says
+ * (16-byte aligned on the device).  X = [X1 | X2 | 1], Z = [X1 | 1 | Z2] with L = kt - n_endog + m columns, T = kt + m <= 31.
+ * Moments and solve.  A = Z~'Z~, C = Z~'X~; Cholesky A = R R' by the static entries' f64 pivot rule (a pivot fails when
+ * d^2 <= 16 dim eps A_jj); Q = R^-1 C, r = R^-1 Z~'y~, M = Q'Q (= X^'X^); b solves M b = Q'r by the same Cholesky;
+ * Pi = R^-T Q, so that x^_i = Pi'z~_i.
+ * Residuals.  e~_i = y~_i - x~_i'b with the ACTUAL regressors; RSS = sum e~_i^2, summed over the rows and not taken from the moments.
+ * Covariance, q->cov_type.  POLS_COV_NONROBUST: V = sigma2 M^-1, sigma2 = RSS / df.  POLS_COV_HC0: V = M^-1 (sum e~_i^2 x^_i x^_i') M^-1.
+ * POLS_COV_HC1: that x n / df.  Anything else is POLS_ERR_INVALID.  small_sample = 1: df = n - kt and p-values are two-sided
+ * Student-t(df); small_sample = 0: df = n and p-values are two-sided normal.  se_j = sqrt(V_jj), t_j = b_j / se_j.  sigma2 is RSS / df
+ * for every cov_type.
+ * Diagnostics, all from the moments.  For endogenous column j, with q the column of Q that belongs to x2j: RSS_u = x~2j'x~2j - q'q;
+ * D = sum of q_l^2 over the rows of Q that belong to Z2 (Z2 is last in Z, so D is the drop in the first stage's RSS from adding the
+ * excluded instruments); first_stage_f[j] = (D / m) / (RSS_u / (n - L)); partial_r2[j] = D / (D + RSS_u).  Sargan's statistic
+ * S = n |r - Q b|^2 / RSS, sargan_p its chi2(m - n_endog) upper tail; both are NaN when m = n_endog.
+ * Outputs.  out->pred = x_i'b from the actual x, out->resid = y - pred, both unscaled, with every row predicted or masked exactly as
+ * pols_least_squares does for the policy ("drop" also masks the rows with a null instrument).
+ * out->status per group: POLS_GROUP_EMPTY for n = 0 (zero coefficients, everything else NaN); POLS_GROUP_BAD_DOF for 0 < n <= L
+ * (everything NaN); POLS_GROUP_FALLBACK with everything NaN when A or M has no factorisation (collinear instruments, or the rank
+ * condition fails) or any moment is not finite under "ignore"; otherwise POLS_GROUP_OK.  n_obs = n in every case.
+ * All arithmetic is f64 on the inputs' values, for f32 batches too; coef / pred / resid are in the batch dtype, everything else is
+ * f64.  No floating-point atomics, every sum in a fixed order: two runs are bit-identical, HOST and DEVICE batches agree bit for bit.
+ * Groups may have any length.  When none of se / t_values / p_values / cov / sigma2 / sargan / sargan_p is asked for, the columns are
+ * read once (and once more for pred / resid).
+ * From pols_ols_params only null_policy is read.  POLS_ERR_INVALID: alpha != 0, positive, or has_l1_ratio with l1_ratio > 0;
+ * n_endog < 1, n_endog > n_features, n_instruments < n_endog, a NULL instrument pointer; an unknown cov_type or null policy; a
+ * validity mask without a drop-family policy.  POLS_ERR_UNSUPPORTED: T > 31.  There is no Arrow twin and no sharded entry. */
+typedef struct pols_iv_params {
+    int32_t n_endog;            /* the LAST n_endog of b->x_cols are endogenous  */
+    const void *const *z_cols;  /* n_instruments excluded instruments            */
+    int32_t n_instruments;
+    int32_t cov_type;           /* POLS_COV_NONROBUST / POLS_COV_HC0 / POLS_COV_HC1 */
+    int32_t small_sample;       /* non-zero: df = n - kt and Student-t p-values  */
+} pols_iv_params;
+
+/* n_endog = 0, z_cols = NULL, n_instruments = 0, cov_type = POLS_COV_NONROBUST, small_sample = 1 */
+void pols_iv_params_default(pols_iv_params *q);
+
+typedef struct pols_iv_out {
+    double  *se;                /* n_groups x kt                                 */
+    double  *t_values;          /* n_groups x kt                                 */
+    double  *p_values;          /* n_groups x kt                                 */
+    double  *cov;               /* n_groups x kt x kt, row-major: V              */
+    double  *sigma2;            /* n_groups: RSS / df                            */
+    double  *first_stage_f;     /* n_groups x n_endog                            */
+    double  *partial_r2;        /* n_groups x n_endog                            */
+    double  *sargan;            /* n_groups                                      */
+    double  *sargan_p;          /* n_groups                                      */
+    int64_t *n_obs;             /* n_groups: fitted rows                         */
+} pols_iv_out;                  /* all live where b->mem says; any may be NULL */
+
+int pols_iv2sls(pols_ctx *ctx, const pols_batch *b, const pols_ols_params *p, const pols_iv_params *q, pols_out *out,
+                const pols_iv_out *r);
+
 /* ---- group-key ingestion: `.over(key)` / `group_by(key)` ------------------------------------------------------------
  * The reference's plugin functions never see a key column: Polars partitions the frame on the host and calls them once per
  * group (README.md:19, README.md:57 and :91 `.over("group")`, tests/test_ols.py:110, :384, :860).  The batched entries

@@ -14,6 +14,7 @@ from .least_squares import (  # noqa: F401
     compute_ridge_cv, RidgeCV,
     compute_rlm, RLM,
     compute_glm, GLM,
+    compute_iv2sls, IV2SLS,
     compute_elastic_net_cv, ElasticNetCV,
 )
 

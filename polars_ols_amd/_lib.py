@@ -160,6 +160,21 @@ class EnetCvOut(C.Structure):         # pols_enet_cv_out
     _fields_ = [(n, C.c_void_p) for n in ENET_CV_FIELDS]
 
 
+class IvParams(C.Structure):          # pols_iv_params
+    _fields_ = [("n_endog", C.c_int32), ("z_cols", C.POINTER(C.c_void_p)), ("n_instruments", C.c_int32), ("cov_type", C.c_int32),
+                ("small_sample", C.c_int32)]
+
+
+# pols_iv_out, in the struct's order; the covariance estimators of the entry (a subset of COV_TYPES)
+IV_FIELDS = ("se", "t_values", "p_values", "cov", "sigma2", "first_stage_f", "partial_r2", "sargan", "sargan_p", "n_obs")
+IV_COV_TYPES = ("nonrobust", "HC0", "HC1")
+IV_MAX_COLUMNS = 31
+
+
+class IvOut(C.Structure):             # pols_iv_out
+    _fields_ = [(n, C.c_void_p) for n in IV_FIELDS]
+
+
 EXPORTS = [
     "pols_device_count", "pols_version", "pols_last_error", "pols_create", "pols_destroy", "pols_set_stream",
     "pols_use_private_stream",
@@ -181,6 +196,7 @@ EXPORTS = [
     "pols_rlm_params_default", "pols_rlm",
     "pols_enet_cv_params_default", "pols_elastic_net_cv",
     "pols_glm_params_default", "pols_glm",
+    "pols_iv_params_default", "pols_iv2sls",
 ]
 # measurement aids (include/pols_mi355x_debug.h): not part of the reference interface
 DEBUG_EXPORTS = ["pols_timing_enable", "pols_timing_collect", "pols_last_kernel_name", "pols_stream_probe", "pols_stream_probe_ex",
@@ -254,6 +270,8 @@ def lib() -> C.CDLL:
         L.pols_glm_resident_tiles.argtypes = [C.c_int] * 4
         L.pols_glm_params_default.argtypes, L.pols_glm_params_default.restype = [C.POINTER(GlmParams)], None
         L.pols_glm.argtypes = [C.c_void_p, C.POINTER(Batch), C.POINTER(OlsParams), C.POINTER(GlmParams), C.POINTER(Out), C.POINTER(GlmOut)]
+        L.pols_iv_params_default.argtypes, L.pols_iv_params_default.restype = [C.POINTER(IvParams)], None
+        L.pols_iv2sls.argtypes = [C.c_void_p, C.POINTER(Batch), C.POINTER(OlsParams), C.POINTER(IvParams), C.POINTER(Out), C.POINTER(IvOut)]
         L.pols_enet_cv_params_default.argtypes, L.pols_enet_cv_params_default.restype = [C.POINTER(EnetCvParams)], None
         L.pols_elastic_net_cv.argtypes = [C.c_void_p, C.POINTER(Batch), C.POINTER(OlsParams), C.POINTER(EnetCvParams), C.POINTER(Out),
                                           C.POINTER(EnetCvOut)]

@@ -24,6 +24,7 @@
 #include "k10_ridge_path.hpp"
 #include "k11_rlm.hpp"
 #include "k13_glm.hpp"
+#include "k14_iv.hpp"
 #include "k12_enet_cv.hpp"
 #include "dyn_prep.hpp"
 
@@ -2250,6 +2251,151 @@ int pols_glm(pols_ctx *ctx, const pols_batch *b, const pols_ols_params *p, const
     if (ro->n_iter) POLS_HIP(hipMemcpyAsync(ro->n_iter, a.n_iter, sizeof(int32_t) * G, hipMemcpyDeviceToHost, ctx->stream));
     if (ro->linpred) POLS_HIP(hipMemcpyAsync(ro->linpred, a.linpred, sz * (size_t)b->n_rows, hipMemcpyDeviceToHost, ctx->stream));
     return unstage_outputs(ctx, b, b->n_groups, kt, o, st);
+}
+
+void pols_iv_params_default(pols_iv_params *q) {
+    if (!q) return;
+    q->n_endog = 0;
+    q->z_cols = nullptr;
+    q->n_instruments = 0;
+    q->cov_type = POLS_COV_NONROBUST;
+    q->small_sample = 1;
+}
+
+// K14 (k14_iv.hip): K10's Gram launch over the concatenated columns [X1 | X2 | Z2], the per-group solve, the row pass for RSS and the
+// robust meat (only when a wanted output needs it), the per-group finish, then K10's prediction pass with the f64 coefficients.
+int pols_iv2sls(pols_ctx *ctx, const pols_batch *b, const pols_ols_params *p, const pols_iv_params *q, pols_out *o, const pols_iv_out *ro) {
+    int rc = check_ctx(ctx);
+    if (rc) return rc;
+    if (!p || !q) return fail(POLS_ERR_INVALID, "params / iv params is NULL");
+    if ((rc = check_batch(b, o, K14_TMAX))) return rc;
+    if (p->alpha != 0.0 || p->positive || (p->has_l1_ratio && p->l1_ratio > 0.0))
+        return fail(POLS_ERR_INVALID, "iv2sls: alpha / positive / l1_ratio do not apply");
+    if (q->n_endog < 1 || q->n_endog > b->n_features) return fail(POLS_ERR_INVALID, "iv2sls: n_endog %d outside 1..%d", q->n_endog, b->n_features);
+    if (q->n_instruments < q->n_endog) return fail(POLS_ERR_INVALID, "iv2sls: %d instruments < %d endogenous regressors", q->n_instruments, q->n_endog);
+    if (!q->z_cols) return fail(POLS_ERR_INVALID, "iv2sls: z_cols is NULL");
+    for (int j = 0; j < q->n_instruments; ++j)
+        if (!q->z_cols[j] && b->n_rows) return fail(POLS_ERR_INVALID, "iv2sls: z_cols[%d] is NULL", j);
+    if (q->cov_type != POLS_COV_NONROBUST && q->cov_type != POLS_COV_HC0 && q->cov_type != POLS_COV_HC1)
+        return fail(POLS_ERR_INVALID, "iv2sls: cov_type %d is not NONROBUST / HC0 / HC1", q->cov_type);
+    const int nf = b->n_features, m = q->n_instruments, icpt = b->add_intercept ? 1 : 0, kx = nf + icpt, T = kx + m, L = kx - q->n_endog + m;
+    if (T > K14_TMAX) return fail(POLS_ERR_UNSUPPORTED, "iv2sls: %d regressors (incl. intercept) + %d instruments > %d", kx, m, K14_TMAX);
+    if (p->null_policy < POLS_NULL_IGNORE || p->null_policy > POLS_NULL_DROP_WINDOW) return fail(POLS_ERR_INVALID, "unknown null_policy %d", p->null_policy);
+    const int pol = (b->null_free && !b->valid) ? POLS_NULL_IGNORE : p->null_policy;
+    if (b->valid && (pol == POLS_NULL_IGNORE || pol == POLS_NULL_ZERO))
+        return fail(POLS_ERR_INVALID, "a validity mask needs a drop-family null_policy");
+    if (b->n_groups == 0) return POLS_OK;
+    pols_iv_out none;
+    std::memset(&none, 0, sizeof(none));
+    if (!ro) ro = &none;
+    const bool host = b->mem == POLS_MEM_HOST;
+    const bool robust = q->cov_type != POLS_COV_NONROBUST;
+    const bool need_rows = ro->se || ro->t_values || ro->p_values || ro->cov || ro->sigma2 || ro->sargan || ro->sargan_p;
+    const size_t G = (size_t)b->n_groups, sz = dtype_size(b->dtype);
+    const int64_t *d_offs = nullptr;
+    int64_t max_rows = 0;
+    if ((rc = upload_offsets(ctx, b->group_offsets, b->n_groups, &d_offs, &max_rows, b->offsets_generation))) return rc;
+    Staged st;
+    if ((rc = stage_inputs(ctx, b, b->n_groups, kx, o, &st))) return rc;
+    if ((rc = fill_null_weights(ctx, b, &st))) return rc;
+    const size_t colb = round256(sz * (size_t)b->n_rows);
+    std::vector<const void *> zc((size_t)m);
+    if (host) {
+        void *wz = nullptr;
+        if ((rc = ensure_scratch(ctx, Work::IvInputs, colb * (size_t)m, &wz))) return rc;
+        for (int j = 0; j < m; ++j) {
+            zc[(size_t)j] = static_cast<char *>(wz) + colb * (size_t)j;
+            if (b->n_rows > 0) POLS_HIP(hipMemcpyAsync(const_cast<void *>(zc[(size_t)j]), q->z_cols[j], sz * (size_t)b->n_rows, hipMemcpyHostToDevice, ctx->stream));
+        }
+    } else {
+        for (int j = 0; j < m; ++j) {
+            zc[(size_t)j] = q->z_cols[j];
+            if (!aligned16(zc[(size_t)j])) return fail(POLS_ERR_INVALID, "device columns must be 16-byte aligned");
+        }
+    }
+    SegTables sg;
+    if ((rc = ensure_segments(ctx, b, max_rows, 0, &sg))) return rc;
+    const size_t items = sg.n_seg > 0 ? (size_t)sg.n_seg : G;
+    const bool pred_all = pol == POLS_NULL_DROP && (st.pred || st.resid);   // the one policy whose prediction pass masks rows
+    const size_t gramb = round256(sizeof(double) * items * k10_gram_stride(T)), rowsb = round256(sizeof(double) * items * k14_rows_stride(kx, robust));
+    const size_t stateb = round256(sizeof(double) * G * k14_state_stride(kx, L)), coefb = round256(sizeof(double) * G * (size_t)(pred_all ? T : kx));
+    void *wm = nullptr, *ws = nullptr, *wo = nullptr;
+    if ((rc = ensure_scratch(ctx, Work::IvMoments, gramb + rowsb, &wm))) return rc;
+    if ((rc = ensure_scratch(ctx, Work::IvState, stateb + coefb, &ws))) return rc;
+    RidgeCvArgs ga;                                            // K10's Gram launch and, later, its prediction pass
+    std::memset(&ga, 0, sizeof(ga));
+    IvArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.y = ga.y = st.y; a.w = ga.w = st.w;
+    for (int j = 0; j < nf; ++j) a.x[j] = ga.x[j] = st.x[(size_t)j];
+    for (int j = 0; j < m; ++j) a.x[nf + j] = ga.x[nf + j] = zc[(size_t)j];
+    a.offs = ga.offs = d_offs; a.n_groups = ga.n_groups = b->n_groups; a.n_rows = ga.n_rows = b->n_rows;
+    if (sg.n_seg > 0) {
+        a.seg_offs = ga.seg_offs = sg.offs; a.seg_map = ga.seg_map = sg.map; a.seg_first = ga.seg_first = sg.first; a.n_seg = ga.n_seg = sg.n_seg;
+    }
+    a.valid = ga.valid = st.valid; a.null_policy = ga.null_policy = pol;
+    a.k_user = ga.k_user = nf + m; a.kt = ga.kt = T;
+    a.n_feat = nf; a.n_endog = q->n_endog; a.n_inst = m; a.icpt = icpt;
+    a.f32 = b->dtype == POLS_F32 ? 1 : 0;
+    a.cov_type = q->cov_type; a.small_sample = q->small_sample ? 1 : 0; a.pred_all = pred_all ? 1 : 0;
+    ga.gram_part = static_cast<double *>(wm);
+    a.gram_part = ga.gram_part;
+    a.rows_part = reinterpret_cast<double *>(static_cast<char *>(wm) + gramb);
+    a.state = static_cast<double *>(ws);
+    a.coefp = reinterpret_cast<double *>(static_cast<char *>(ws) + stateb);
+    a.coef = st.coef; a.status = st.status;
+    const size_t kb = round256(sizeof(double) * G * kx), kkb = round256(sizeof(double) * G * kx * kx), vecb = round256(sizeof(double) * G),
+                 eb = round256(sizeof(double) * G * (size_t)q->n_endog), nb = round256(sizeof(int64_t) * G);
+    if (host) {
+        if ((rc = ensure_scratch(ctx, Work::IvOut, 3 * kb + kkb + 3 * vecb + 2 * eb + nb, &wo))) return rc;
+        char *c = static_cast<char *>(wo);
+        if (ro->se) a.se = reinterpret_cast<double *>(c);
+        if (ro->t_values) a.t_values = reinterpret_cast<double *>(c + kb);
+        if (ro->p_values) a.p_values = reinterpret_cast<double *>(c + 2 * kb);
+        if (ro->cov) a.cov = reinterpret_cast<double *>(c + 3 * kb);
+        c += 3 * kb + kkb;
+        if (ro->sigma2) a.sigma2 = reinterpret_cast<double *>(c);
+        if (ro->sargan) a.sargan = reinterpret_cast<double *>(c + vecb);
+        if (ro->sargan_p) a.sargan_p = reinterpret_cast<double *>(c + 2 * vecb);
+        c += 3 * vecb;
+        if (ro->first_stage_f) a.first_stage_f = reinterpret_cast<double *>(c);
+        if (ro->partial_r2) a.partial_r2 = reinterpret_cast<double *>(c + eb);
+        if (ro->n_obs) a.n_obs = reinterpret_cast<int64_t *>(c + 2 * eb);
+    } else {
+        a.se = ro->se; a.t_values = ro->t_values; a.p_values = ro->p_values; a.cov = ro->cov; a.sigma2 = ro->sigma2;
+        a.first_stage_f = ro->first_stage_f; a.partial_r2 = ro->partial_r2; a.sargan = ro->sargan; a.sargan_p = ro->sargan_p; a.n_obs = ro->n_obs;
+    }
+    ctx->last_kernel = sg.n_seg > 0 ? "k14_iv2sls_split" : "k14_iv2sls";
+    if ((rc = k10_gram_launch(ctx, b->dtype, ga))) return rc;
+    if ((rc = k14_solve_launch(ctx, a))) return rc;
+    if (need_rows) {
+        // the plain RSS needs the regressors and y alone: the instruments are staged only where the robust meat reads them or their nulls drop rows
+        IvArgs ra = a;
+        const bool z_drops = pol == POLS_NULL_DROP || pol == POLS_NULL_DROP_ZERO || pol == POLS_NULL_DROP_WINDOW;
+        if (!robust && !z_drops) { ra.k_user = nf; ra.kt = kx; }
+        if ((rc = k14_rows_launch(ctx, b->dtype, ra))) return rc;
+        if ((rc = k14_finish_launch(ctx, a))) return rc;
+    }
+    // the prediction pass: the regressors alone, or -- "drop" -- the whole list with zero coefficients for the instruments, whose nulls mask rows
+    ga.k_user = pred_all ? nf + m : nf; ga.kt = pred_all ? T : kx;
+    ga.coef64 = a.coefp; ga.pred = st.pred; ga.resid = st.resid;
+    if ((rc = k10_predict_launch(ctx, b->dtype, ga))) return rc;
+    if (!host) return POLS_OK;
+    auto home = [&](void *dst, const void *src, size_t bytes) -> int {
+        if (dst) POLS_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, ctx->stream));
+        return POLS_OK;
+    };
+    if ((rc = home(ro->se, a.se, sizeof(double) * G * kx))) return rc;
+    if ((rc = home(ro->t_values, a.t_values, sizeof(double) * G * kx))) return rc;
+    if ((rc = home(ro->p_values, a.p_values, sizeof(double) * G * kx))) return rc;
+    if ((rc = home(ro->cov, a.cov, sizeof(double) * G * kx * kx))) return rc;
+    if ((rc = home(ro->sigma2, a.sigma2, sizeof(double) * G))) return rc;
+    if ((rc = home(ro->sargan, a.sargan, sizeof(double) * G))) return rc;
+    if ((rc = home(ro->sargan_p, a.sargan_p, sizeof(double) * G))) return rc;
+    if ((rc = home(ro->first_stage_f, a.first_stage_f, sizeof(double) * G * (size_t)q->n_endog))) return rc;
+    if ((rc = home(ro->partial_r2, a.partial_r2, sizeof(double) * G * (size_t)q->n_endog))) return rc;
+    if ((rc = home(ro->n_obs, a.n_obs, sizeof(int64_t) * G))) return rc;
+    return unstage_outputs(ctx, b, b->n_groups, kx, o, st);
 }
 
 void pols_enet_cv_params_default(pols_enet_cv_params *q) {

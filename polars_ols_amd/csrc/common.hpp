@@ -90,6 +90,10 @@ enum class Work : int {
     GlmState,       // GLM (K13): split form -- the counter of iterating groups, the groups' state, Gram partials of a frame without segment tables
     GlmOffset,      // GLM (K13): the offset column of a HOST batch
     GlmOut,         // GLM (K13): deviance / se / n_iter / linpred of a HOST batch before they go home
+    IvMoments,      // 2SLS (K14): cross-moment partials per segment / group (K10's Gram launch), then the RSS / meat partials of the rows launch
+    IvState,        // 2SLS (K14): n, usable, Sargan numerator, b, M^-1 and Pi per group (f64), then the coefficients for the prediction pass
+    IvInputs,       // 2SLS (K14): the instrument columns of a HOST batch
+    IvOut,          // 2SLS (K14): the pols_iv_out fields of a HOST batch before they go home
     Count
 };
 

@@ -37,19 +37,6 @@ namespace pols {
 
 __device__ __forceinline__ double k10_nan() { return __longlong_as_double(0x7ff8000000000000LL); }
 
-constexpr int K10_GRAM_TS = 257;      // column stride of the Gram launch's tile (odd: conflict-free across columns)
-
-// the item of this workgroup: its group, its rows, and the first row of its tile grid (the columns' 16-byte grid)
-template <typename T>
-__device__ __forceinline__ void k10_item(const RidgeCvArgs &a, int64_t &g, int64_t &s, int64_t &e, int64_t &base, int64_t &ntiles) {
-    const int64_t sgi = blockIdx.x;
-    g = a.seg_offs ? (int64_t)a.seg_map[sgi] : sgi;
-    s = a.seg_offs ? a.seg_offs[sgi] : a.offs[g];
-    e = a.seg_offs ? a.seg_offs[sgi + 1] : a.offs[g + 1];
-    base = s & ~(int64_t)(Vec16<T>::N - 1);
-    ntiles = e > s ? (e - base + K10_TILE - 1) / K10_TILE : 0;
-}
-
 // ---------------------------------------------------------------- gram
 template <typename T>
 __global__ void __launch_bounds__(256) k10_gram_kernel(const RidgeCvArgs a) {
@@ -61,17 +48,9 @@ __global__ void __launch_bounds__(256) k10_gram_kernel(const RidgeCvArgs a) {
     k10_item<T>(a, g, s, e, base, ntiles);
     const int parts = ne < 256 ? 256 / ne : 1;
     const int part = parts > 1 ? tid / ne : 0;
-    // the thread's entries: (i, j) of slot q, i <= j, in the order of the packed upper triangle
     int ei[3], ej[3];
     bool on[3];
-#pragma unroll
-    for (int q = 0; q < 3; ++q) {
-        const int en = parts > 1 ? tid - part * ne : tid + 256 * q;
-        on[q] = parts > 1 ? (q == 0 && part < parts) : en < ne;
-        int i = 0, t = on[q] ? en : 0;
-        while (t >= nz - i) { t -= nz - i; ++i; }
-        ei[q] = i; ej[q] = i + t;
-    }
+    k10_entries(nz, parts, part, ei, ej, on);
     double acc[3] = {0.0, 0.0, 0.0};
     int nfit = 0;
     for (int64_t it = 0; it < ntiles; ++it) {

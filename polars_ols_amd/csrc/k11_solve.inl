@@ -1,5 +1,6 @@
-// k11_solve.inl -- the one-wave Cholesky solve of K11 (k11_rlm.hip), shared with K13 (k13_glm.hip): a packed Gram matrix in LDS goes
-// to the coefficients by a right-looking factorisation (the trailing update spread over the lanes) and the two substitutions.
+// k11_solve.inl -- the one-wave Cholesky solve of K11 (k11_rlm.hip), shared with K13 (k13_glm.hip) and K14 (k14_iv.hip): a packed
+// Gram matrix in LDS goes to the coefficients by a right-looking factorisation (the trailing update spread over the lanes) and the
+// two substitutions; K14 also takes the factorisation alone.
 #pragma once
 #include "common.hpp"
 
@@ -8,6 +9,29 @@ namespace pols {
 // LDS traffic between the lanes of ONE wave: its LDS operations complete in order, the compiler must not move them
 __device__ __forceinline__ void k11_wave_sync() {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// A: a symmetric kt x kt matrix in LDS (row stride kt + 1), d0 its diagonal.  Right-looking factorisation in place: the factor L ends in
+// the lower triangle of A.  A pivot fails when d^2 <= 16 kt eps A_jj; the result is false (in every lane) then.  All 64 lanes of one
+// wave call it, behind a k11_wave_sync() after A and d0 were written.
+__device__ __forceinline__ bool k11_chol_factor(double *A, const double *d0, const int kt, const int lane) {
+    const int LD = kt + 1;
+    bool ok = true;
+    const double noise = 16.0 * (double)kt * 2.220446049250313e-16;
+    for (int j = 0; j < kt; ++j) {
+        const double d = A[j * LD + j];
+        if (!(d > noise * d0[j])) { ok = false; break; }   // (wave-uniform: every lane read the same word)
+        const double sd = sqrt(d);
+        k11_wave_sync();
+        if (lane >= j && lane < kt) A[lane * LD + j] = lane == j ? sd : A[lane * LD + j] / sd;
+        k11_wave_sync();
+        for (int p = lane; p < kt * kt; p += 64) {         // the trailing lower triangle: A[i][c] -= L[i][j] L[c][j], j < c <= i
+            const int i = p / kt, c = p - i * kt;
+            if (c > j && c <= i) A[i * LD + c] -= A[i * LD + j] * A[c * LD + j];
+        }
+        k11_wave_sync();
+    }
+    return ok;
 }
 
 // Gm: the packed upper triangle of the (kt + 1) x (kt + 1) matrix [A g; g' .] (row i holds the entries (i, i) .. (i, kt)).  Solves
@@ -25,21 +49,7 @@ __device__ __forceinline__ bool k11_chol_solve(const double *Gm, double *A, doub
         else { A[i * LD + j] = v; A[j * LD + i] = v; if (i == j) d0[i] = v; }
     }
     k11_wave_sync();
-    bool ok = true;
-    const double noise = 16.0 * (double)kt * 2.220446049250313e-16;
-    for (int j = 0; j < kt; ++j) {
-        const double d = A[j * LD + j];
-        if (!(d > noise * d0[j])) { ok = false; break; }   // (wave-uniform: every lane read the same word)
-        const double sd = sqrt(d);
-        k11_wave_sync();
-        if (lane >= j && lane < kt) A[lane * LD + j] = lane == j ? sd : A[lane * LD + j] / sd;
-        k11_wave_sync();
-        for (int p = lane; p < kt * kt; p += 64) {         // the trailing lower triangle: A[i][c] -= L[i][j] L[c][j], j < c <= i
-            const int i = p / kt, c = p - i * kt;
-            if (c > j && c <= i) A[i * LD + c] -= A[i * LD + j] * A[c * LD + j];
-        }
-        k11_wave_sync();
-    }
+    bool ok = k11_chol_factor(A, d0, kt, lane);
     if (ok) {
         for (int j = 0; j < kt; ++j) {                     // L z = g
             const double z = rhs[j] / A[j * LD + j];

@@ -68,6 +68,38 @@ __device__ inline double k7_betai(double a, double b, double x) {
     return 1.0 - bt * k7_betacf(b, a, 1.0 - x) / b;
 }
 
+// regularised upper incomplete gamma Q(a, x) = Gamma(a, x) / Gamma(a), the chi2(2a) upper tail at 2x: the series of P below
+// x < a + 1, Lentz' continued fraction of Q above (K14's Sargan p-value)
+__device__ inline double k7_gammaq(double a, double x) {
+    if (!(x >= 0.0) || !(a > 0.0)) return __longlong_as_double(0x7ff8000000000000LL);
+    if (x == 0.0) return 1.0;
+    if (x > 1.79769313486231570815e308) return 0.0;
+    const double ft = exp(a * log(x) - x - lgamma(a));
+    if (x < a + 1.0) {
+        double ap = a, del = 1.0 / a, sum = del;
+        for (int m = 1; m <= 1000; ++m) {
+            ap += 1.0;
+            del *= x / ap;
+            sum += del;
+            if (fabs(del) < fabs(sum) * 1e-16) break;
+        }
+        return 1.0 - sum * ft;
+    }
+    const double tiny = 1e-300;
+    double b = x + 1.0 - a, c = 1.0 / tiny, d = 1.0 / b, h = d;
+    for (int m = 1; m <= 1000; ++m) {
+        const double an = -(double)m * ((double)m - a);
+        b += 2.0;
+        d = an * d + b; if (fabs(d) < tiny) d = tiny;
+        c = b + an / c; if (fabs(c) < tiny) c = tiny;
+        d = 1.0 / d;
+        const double del = d * c;
+        h *= del;
+        if (fabs(del - 1.0) < 1e-16) break;
+    }
+    return ft * h;
+}
+
 // wave 0 of the group: A = X'X + lambda I factored, A^-1 X'y and diag(A^-1) (src/statistics.rs:100-121), the dispatcher's coefficients.
 // Shared by K7 and the robust covariance kernels (K7r), which keep all of M = L^-1 to form the whole A^-1 = M'M.
 template <typename T>

@@ -402,6 +402,47 @@ class Engine:
         L.check(self._lib.pols_glm(self._h, C.byref(plan._b), C.byref(plan._p), C.byref(q), C.byref(plan._o), C.byref(ro)))
         return res
 
+    def iv2sls(self, y, x_cols: Sequence, z_cols: Sequence, offsets, *, n_endog: int, cov_type: str = "nonrobust", small_sample: bool = True,
+               want: Sequence[str] = ("coef", "status", "se", "first_stage_f", "sargan", "sargan_p"), weights=None, valid=None,
+               add_intercept: bool = False, null_policy: str = "ignore") -> Dict:
+        """Two-stage least squares (instrumental variables) for every group in one call (pols_iv2sls; the definitions and edge
+        rules are in include/pols_mi355x.h).  ``x_cols``: the exogenous regressors first, then the ``n_endog`` endogenous ones;
+        ``z_cols``: the excluded instruments (at least ``n_endog``); regressors incl. the intercept plus instruments: at most 31.
+        ``cov_type``: "nonrobust", "HC0" or "HC1"; ``small_sample``: df = n - k and Student-t p-values (else df = n, normal).
+        ``want``: any of ``coef pred resid status`` (status 4 = no degrees of freedom), ``se t_values p_values`` [n_groups, k, f64],
+        ``cov`` [n_groups, k, k, f64], ``sigma2 sargan sargan_p`` [n_groups, f64], ``first_stage_f partial_r2`` [n_groups,
+        n_endog, f64] and ``n_obs`` [n_groups, int64].  Arrays are numpy or torch and live where the inputs live.  Without any of
+        ``se t_values p_values cov sigma2 sargan sargan_p`` the columns are read once."""
+        x_cols, z_cols = list(x_cols), list(z_cols)
+        q = _iv_params(self._lib, len(x_cols), len(z_cols), n_endog, cov_type, small_sample, add_intercept)
+        want = tuple(want)
+        known = ("coef", "pred", "resid", "status") + L.IV_FIELDS
+        unknown = [w for w in want if w not in known]
+        if unknown:
+            raise ValueError(f"unknown iv2sls fields {unknown}; known: {list(known)}")
+        plan = self.plan_least_squares(y, x_cols, offsets, weights=weights, valid=valid, add_intercept=add_intercept,
+                                       null_policy=null_policy, want=tuple(w for w in want if w in ("coef", "pred", "resid", "status")))
+        b = plan._b
+        dev = b.mem == L.POLS_MEM_DEVICE
+        like = plan._keep[0][0]
+        res = plan.results
+        zs = [z.to(like.dtype).contiguous() if dev else np.ascontiguousarray(z, dtype=like.dtype) for z in z_cols]
+        for z in zs:
+            if tuple(z.shape) != (b.n_rows,):
+                raise ValueError("all input series passed must be of equal length")
+        zp = (C.c_void_p * len(zs))(*[self._ptr(z) for z in zs])
+        q.z_cols = C.cast(zp, C.POINTER(C.c_void_p))
+        f64, i64 = (torch.float64, torch.int64) if dev else (np.float64, np.int64)
+        G, kt = b.n_groups, b.n_features + b.add_intercept
+        shapes = {"se": (G, kt), "t_values": (G, kt), "p_values": (G, kt), "cov": (G, kt, kt), "sigma2": (G,),
+                  "first_stage_f": (G, q.n_endog), "partial_r2": (G, q.n_endog), "sargan": (G,), "sargan_p": (G,), "n_obs": (G,)}
+        for key in L.IV_FIELDS:
+            if key in want:
+                res[key] = self._alloc(dev, i64 if key == "n_obs" else f64, shapes[key], like)
+        ro = L.IvOut(**{k: self._ptr(res.get(k)) for k in L.IV_FIELDS})
+        L.check(self._lib.pols_iv2sls(self._h, C.byref(plan._b), C.byref(plan._p), C.byref(q), C.byref(plan._o), C.byref(ro)))
+        return res
+
     def elastic_net_cv(self, y, x_cols: Sequence, offsets, alphas=None, *, n_alphas: int = 100, eps: float = 1e-3, l1_ratio: float = 0.5,
                        n_folds: int = 5, max_iter: int = 1000, tol: float = 1e-5, positive: bool = False,
                        want: Sequence[str] = ("coef", "status", "alpha", "alpha_index", "score"), weights=None, valid=None,
@@ -719,6 +760,24 @@ def _ols_params(lib, alpha=0.0, l1_ratio=None, max_iter=1000, tol=1e-5, positive
     p.has_rcond, p.rcond = int(rcond is not None), float(rcond) if rcond is not None else 0.0
     p.null_policy = L.NULL_POLICIES[null_policy]
     return p
+
+
+def _iv_params(lib, n_features, n_instruments, n_endog, cov_type, small_sample, add_intercept) -> "L.IvParams":
+    """the argument checks of Engine.iv2sls / compute_iv2sls (``lib`` None: check only, no device needed)"""
+    if isinstance(n_endog, bool) or int(n_endog) != n_endog or not (1 <= n_endog <= n_features):
+        raise ValueError(f"iv2sls: 'n_endog' must be an integer in 1..{n_features}, the number of regressors (got {n_endog!r})")
+    if n_instruments < n_endog:
+        raise ValueError(f"iv2sls: {n_instruments} instruments do not identify {n_endog} endogenous regressors")
+    if cov_type not in L.IV_COV_TYPES:
+        raise ValueError(f"iv2sls: 'cov_type' must be one of {list(L.IV_COV_TYPES)}, got {cov_type!r}")
+    total = n_features + int(bool(add_intercept)) + n_instruments
+    if total > L.IV_MAX_COLUMNS:
+        raise ValueError(f"iv2sls: {total} regressors (incl. intercept) plus instruments > {L.IV_MAX_COLUMNS}")
+    q = L.IvParams()
+    if lib is not None:
+        lib.pols_iv_params_default(C.byref(q))
+    q.n_endog, q.n_instruments, q.cov_type, q.small_sample = int(n_endog), int(n_instruments), L.COV_TYPES[cov_type], int(bool(small_sample))
+    return q
 
 
 def _glm_params(lib, family, max_iter, tol) -> "L.GlmParams":

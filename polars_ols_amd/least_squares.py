@@ -26,7 +26,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import PolsPanic
-from .engine import Engine, Layout, _enet_cv_params, _is_torch, _glm_params, _ridge_cv_grid, _rlm_params, default_engine
+from .engine import Engine, Layout, _enet_cv_params, _is_torch, _glm_params, _iv_params, _ridge_cv_grid, _rlm_params, default_engine
 
 try:
     import torch
@@ -44,6 +44,7 @@ __all__ = [
     "compute_elastic_net_cv", "ElasticNetCV",
     "compute_rlm", "RLM",
     "compute_glm", "GLM",
+    "compute_iv2sls", "IV2SLS",
 ]
 
 # ---- polars_ols/least_squares.py:47-63 --------------------------------------------------------------------------
@@ -557,6 +558,44 @@ def _apply_glm(frame: Frame, over, eng: Optional[Engine], target: Expr, features
     return target.output_name, grp.untake(out["pred"] if mode == "predictions" else out["resid"])
 
 
+class IV2SLS(dict):
+    """mode="statistics" of a two-stage least squares fit (pols_iv2sls; the definitions are in include/pols_mi355x.h): per group
+    ``coefficients standard_errors t_values p_values`` [G, k] (``feature_names``: exogenous, endogenous, const), ``cov`` [G, k, k],
+    ``sigma2 sargan sargan_p n_obs status`` [G] and ``first_stage_f partial_r2`` [G, n_endog] (``endog_names``); ``keys`` holds the
+    group keys of an ``.over`` (None for a whole-frame fit, where G == 1)."""
+
+    def __init__(self, names, endog_names, out, keys, cov_type):
+        super().__init__(feature_names=list(names), endog_names=list(endog_names), coefficients=out["coef"], standard_errors=out["se"],
+                         t_values=out["t_values"], p_values=out["p_values"], cov=out["cov"], sigma2=out["sigma2"],
+                         first_stage_f=out["first_stage_f"], partial_r2=out["partial_r2"], sargan=out["sargan"],
+                         sargan_p=out["sargan_p"], n_obs=out["n_obs"], status=out["status"], keys=keys, cov_type=cov_type)
+        self.keys_ = keys
+
+
+_VALID_IV_MODES = ("predictions", "residuals", "coefficients", "statistics")
+
+
+def _apply_iv2sls(frame: Frame, over, eng: Optional[Engine], target: Expr, exog: Sequence[Expr], endog: Sequence[Expr],
+                  instruments: Sequence[Expr], sample_weights, add_intercept: bool, mode: str, cov_type: str, small_sample: bool,
+                  null_policy: str):
+    """compute_iv2sls body: the group layout of _apply_static around Engine.iv2sls."""
+    feats = list(exog) + list(endog)
+    y, xs, names, icpt, w = _pre_process_data(frame, target, feats, sample_weights, add_intercept)
+    zs = [z._column(frame) for z in instruments]
+    eng = eng or default_engine(y.device.index or 0 if _is_torch(y) else 0)
+    grp = _Groups(eng, None if over is None else (frame[over] if isinstance(over, str) else over), y.shape[0])
+    moved = grp.take([y, w] + list(xs) + zs)
+    want = {"predictions": ("pred",), "residuals": ("resid",), "coefficients": ("coef",),
+            "statistics": ("coef", "status") + _lib.IV_FIELDS}[mode]
+    out = eng.iv2sls(moved[0], moved[2:2 + len(xs)], moved[2 + len(xs):], grp.offsets, n_endog=len(endog), cov_type=cov_type,
+                     small_sample=small_sample, want=want, weights=moved[1], add_intercept=icpt, null_policy=null_policy)
+    if mode == "statistics":
+        return "statistics", IV2SLS(names, [e.output_name for e in endog], out, grp.keys, cov_type)
+    if mode == "coefficients":
+        return "coefficients", Coefficients(names, out["coef"], grp.keys, grp.gid_frame(out["coef"]))
+    return target.output_name, grp.untake(out["pred"] if mode == "predictions" else out["resid"])
+
+
 def _apply_dynamic(frame: Frame, over, eng: Optional[Engine], target: Expr, features: Sequence[Expr], sample_weights,
                    add_intercept: bool, mode: str, kind: str, kw):
     """compute_recursive_least_squares / compute_rolling_least_squares bodies (ls.py:332-409 around
@@ -728,6 +767,27 @@ def compute_glm(target, *features, family: str = "binomial", offset=None, max_it
     t, fs = parse_into_expr(target), [parse_into_expr(f) for f in features]
     return Expr(t._name, fn=lambda frame, over, eng: _apply_glm(frame, over, eng, t, fs, sample_weights, offset, add_intercept, mode,
                                                                 family, max_iter, tol, null_policy))
+
+
+def compute_iv2sls(target, *exog, endog, instruments, cov_type: str = "nonrobust", small_sample: bool = True, sample_weights=None,
+                   add_intercept: bool = False, mode: str = "predictions", null_policy: str = "ignore") -> Expr:
+    """Two-stage least squares per group (linearmodels' / statsmodels' IV2SLS for every group of the frame in one call): ``exog``
+    are the exogenous regressors, ``endog`` the endogenous ones and ``instruments`` the excluded instruments (at least as many as
+    ``endog``).  Modes "predictions" (x'b from the actual regressors), "residuals" and "coefficients" (exogenous, endogenous,
+    const); mode="statistics" returns an ``IV2SLS`` with standard errors (``cov_type`` "nonrobust" / "HC0" / "HC1"), t and p
+    values, the covariance matrix, the first-stage F and partial R2 of every endogenous regressor and Sargan's test."""
+    if mode not in _VALID_IV_MODES:
+        raise ValueError(f"'mode' must be one of {_VALID_IV_MODES}, got {mode!r}")
+    if null_policy not in _VALID_NULL_POLICIES:
+        raise ValueError(f"'null_policy' must be one of {sorted(_VALID_NULL_POLICIES)}, got {null_policy!r}")
+    endog = [endog] if isinstance(endog, (str, Expr)) else list(endog)
+    instruments = [instruments] if isinstance(instruments, (str, Expr)) else list(instruments)
+    t, ex = parse_into_expr(target), [parse_into_expr(f) for f in exog]
+    en, zs = [parse_into_expr(f) for f in endog], [parse_into_expr(f) for f in instruments]
+    icpt = add_intercept and not any(f.output_name == "const" for f in ex + en)
+    _iv_params(None, len(ex) + len(en), len(zs), len(en), cov_type, small_sample, icpt)
+    return Expr(t._name, fn=lambda frame, over, eng: _apply_iv2sls(frame, over, eng, t, ex, en, zs, sample_weights, add_intercept, mode,
+                                                                   cov_type, small_sample, null_policy))
 
 
 def compute_multi_target_least_squares(targets, *features, sample_weights=None, add_intercept: bool = False,
@@ -998,6 +1058,11 @@ class LeastSquares:
             add_intercept: bool = False, mode: str = "predictions", null_policy: str = "ignore") -> Expr:
         return compute_glm(self._expr, *features, family=family, offset=offset, max_iter=max_iter, tol=tol,
                            sample_weights=sample_weights, add_intercept=add_intercept, mode=mode, null_policy=null_policy)
+
+    def iv2sls(self, *exog, endog, instruments, cov_type: str = "nonrobust", small_sample: bool = True, sample_weights=None,
+               add_intercept: bool = False, mode: str = "predictions", null_policy: str = "ignore") -> Expr:
+        return compute_iv2sls(self._expr, *exog, endog=endog, instruments=instruments, cov_type=cov_type, small_sample=small_sample,
+                              sample_weights=sample_weights, add_intercept=add_intercept, mode=mode, null_policy=null_policy)
 
     def lasso(self, *features, alpha: float, **kwargs) -> Expr:
         return self.least_squares(*features, alpha=alpha, l1_ratio=1.0, **kwargs)
