@@ -9,6 +9,7 @@
 #include <thread>
 
 #include "common.hpp"
+#include "api_internal.hpp"
 #include "k1_gram_chol.hpp"
 #include "k2_resident.hpp"
 #include "k2w_resident.hpp"
@@ -282,22 +283,11 @@ void timing_end(pols_ctx *ctx) {
     ctx->timed_used++;
 }
 
-static int check_ctx(pols_ctx *ctx) {
+int check_ctx(pols_ctx *ctx) {
     if (!ctx) return fail(POLS_ERR_INVALID, "ctx is NULL");
     POLS_HIP(hipSetDevice(ctx->device));
     return POLS_OK;
 }
-
-static bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
-// Host-resident batch: stage every column into device scratch (PCIe-inclusive path).
-struct Staged {
-    const void *y = nullptr, *w = nullptr;
-    const uint8_t *valid = nullptr;
-    std::vector<const void *> x;     // n_features column pointers (device)
-    void *coef = nullptr, *pred = nullptr, *resid = nullptr;
-    int32_t *status = nullptr;
-};
 
 
 // Null sample weights of the static entries: sqrt_w = w.sqrt().fill_null(1e-12) in the reference's Python layer
@@ -320,7 +310,7 @@ __global__ void __launch_bounds__(256) null_weights_kernel(const T *w, T *out, i
     }
 }
 
-static int fill_null_weights(pols_ctx *ctx, const pols_batch *b, Staged *st) {
+int fill_null_weights(pols_ctx *ctx, const pols_batch *b, Staged *st) {
     if (!st->w || b->null_free || b->n_rows <= 0) return POLS_OK;
     void *dst = const_cast<void *>(st->w);                     // HOST batch: the staged copy is ours -- in place
     if (b->mem == POLS_MEM_DEVICE) {                           // DEVICE batch: the caller's column stays untouched
@@ -336,7 +326,7 @@ static int fill_null_weights(pols_ctx *ctx, const pols_batch *b, Staged *st) {
     return POLS_OK;
 }
 
-static int stage_inputs(pols_ctx *ctx, const pols_batch *b, int64_t coef_rows, int kt, const pols_out *o, Staged *st) {
+int stage_inputs(pols_ctx *ctx, const pols_batch *b, int64_t coef_rows, int kt, const pols_out *o, Staged *st) {
     const size_t sz = dtype_size(b->dtype);
     const size_t colb = round256(sz * (size_t)b->n_rows);
     st->x.assign((size_t)b->n_features, nullptr);
@@ -386,7 +376,7 @@ static int stage_inputs(pols_ctx *ctx, const pols_batch *b, int64_t coef_rows, i
     return POLS_OK;
 }
 
-static int unstage_outputs(pols_ctx *ctx, const pols_batch *b, int64_t coef_rows, int kt, const pols_out *o, const Staged &st) {
+int unstage_outputs(pols_ctx *ctx, const pols_batch *b, int64_t coef_rows, int kt, const pols_out *o, const Staged &st) {
     if (b->mem == POLS_MEM_DEVICE) return POLS_OK;
     const size_t sz = dtype_size(b->dtype);
     if (o->coef) POLS_HIP(hipMemcpyAsync(o->coef, st.coef, sz * (size_t)coef_rows * kt, hipMemcpyDeviceToHost, ctx->stream));
@@ -397,7 +387,7 @@ static int unstage_outputs(pols_ctx *ctx, const pols_batch *b, int64_t coef_rows
     return POLS_OK;
 }
 
-static int check_batch(const pols_batch *b, const pols_out *o, int max_features = POLS_MAX_FEATURES) {
+int check_batch(const pols_batch *b, const pols_out *o, int max_features) {
     if (!b || !o) return fail(POLS_ERR_INVALID, "batch / out is NULL");
     if (b->dtype != POLS_F32 && b->dtype != POLS_F64) return fail(POLS_ERR_INVALID, "dtype must be POLS_F32 or POLS_F64");
     if (b->mem != POLS_MEM_HOST && b->mem != POLS_MEM_DEVICE) return fail(POLS_ERR_INVALID, "mem must be POLS_MEM_HOST or POLS_MEM_DEVICE");
@@ -844,21 +834,10 @@ static int wide_static(pols_ctx *ctx, const pols_batch *b, const pols_ols_params
     return unstage_outputs(ctx, b, b->n_groups * m, kt, o, st);
 }
 
-// Long groups cut into segments (the streamed static path, the statistics of long groups): a group is one workgroup in those
-// kernels, so ONE regression over a 10M-row frame used to be one CU's work.  Groups longer than two segments are cut into pieces
-// of about N / (8 x CUs) rows (256-row multiples), the others are one segment each; tables in ctx->seg_cache -- segment offsets,
-// segment -> group, group -> first segment -- followed by `extra_per_seg` bytes per segment for the caller's partial results.
-// n_seg = 0: nothing is longer than two segments (or POLS_NO_SPLIT).  Cached per frame.
-struct SegTables {
-    const int64_t *offs = nullptr;
-    const int32_t *map = nullptr, *first = nullptr;
-    int64_t n_seg = 0, max_len = 0, max_seg = 0;      // rows of the longest segment; most segments of one group
-    char *extra = nullptr;
-};
-// ids (size classes): the tables cover only the listed groups (ascending), `offs` holds (start, end) PAIRS per segment, `map` gives the segment's
-// position in the list and `first` is indexed by list position; class_key tells such tables apart in the cache (0 = the whole frame).
-static int ensure_segments(pols_ctx *ctx, const pols_batch *b, int64_t max_rows, size_t extra_per_seg, SegTables *t,
-                           const std::vector<int32_t> *ids = nullptr, int64_t class_key = 0) {
+// Long groups cut into segments: SegTables and what ensure_segments builds are described in api_internal.hpp.  (C++ linkage, as declared
+// there: this definition sits inside the extern "C" block.)
+extern "C++" int ensure_segments(pols_ctx *ctx, const pols_batch *b, int64_t max_rows, size_t extra_per_seg, SegTables *t,
+                                 const std::vector<int32_t> *ids, int64_t class_key) {
     *t = SegTables();
     const int64_t seg_target = ctx->opt.seg_target > 0 ? std::max<int64_t>(256, ctx->opt.seg_target)
                                                       : std::max<int64_t>(4096, ((b->n_rows / std::max<int64_t>(1, 8 * (int64_t)ctx->num_cus) + 1023) / 1024) * 1024);
@@ -1927,617 +1906,6 @@ int pols_least_squares_influence(pols_ctx *ctx, const pols_batch *b, const pols_
     std::memset(&none, 0, sizeof(none));
     InflCall ic{q, infl};
     return statistics_body(ctx, b, p, nullptr, nullptr, o, &none, &ic);
-}
-
-void pols_ridge_cv_params_default(pols_ridge_cv_params *q) {
-    if (!q) return;
-    q->alphas = nullptr;
-    q->n_alphas = 0;
-}
-
-// K10 (k10_ridge_path.hip): Gram pass, eigendecomposition, row pass over the candidates, pick, prediction pass with the winner's
-// coefficients.  Null policies are fused into the tile staging and into the prediction pass, as in ls_core's streamed path.
-int pols_ridge_cv(pols_ctx *ctx, const pols_batch *b, const pols_ols_params *p, const pols_ridge_cv_params *q, pols_out *o,
-                  const pols_ridge_cv_out *ro) {
-    int rc = check_ctx(ctx);
-    if (rc) return rc;
-    if (b && o && b->n_features + (b->add_intercept ? 1 : 0) > K10_KMAX)
-        return fail(POLS_ERR_UNSUPPORTED, "ridge_cv: %d features (incl. intercept) > %d", b->n_features + (b->add_intercept ? 1 : 0), K10_KMAX);
-    if ((rc = check_batch(b, o, K10_KMAX))) return rc;
-    if (!p || !q) return fail(POLS_ERR_INVALID, "params / ridge_cv params is NULL");
-    if (!q->alphas || q->n_alphas < 1) return fail(POLS_ERR_INVALID, "ridge_cv: the grid of candidates is empty");
-    if (q->n_alphas > K10_MAX_ALPHAS) return fail(POLS_ERR_UNSUPPORTED, "ridge_cv: %d candidates > %d", q->n_alphas, K10_MAX_ALPHAS);
-    for (int j = 0; j < q->n_alphas; ++j)
-        if (!(q->alphas[j] >= 0.0) || !std::isfinite(q->alphas[j])) return fail(POLS_ERR_INVALID, "ridge_cv: candidate %d is negative or not finite", j);
-    if (p->positive || (p->has_l1_ratio && p->l1_ratio > 0.0))
-        return fail(POLS_ERR_INVALID, "ridge_cv: positive / l1_ratio fits have no hat matrix");
-    if (p->null_policy < POLS_NULL_IGNORE || p->null_policy > POLS_NULL_DROP_WINDOW) return fail(POLS_ERR_INVALID, "unknown null_policy %d", p->null_policy);
-    const int pol = (b->null_free && !b->valid) ? POLS_NULL_IGNORE : p->null_policy;
-    if (b->valid && (pol == POLS_NULL_IGNORE || pol == POLS_NULL_ZERO))
-        return fail(POLS_ERR_INVALID, "a validity mask needs a drop-family null_policy");
-    if (b->n_groups == 0) return POLS_OK;
-    pols_ridge_cv_out none;
-    std::memset(&none, 0, sizeof(none));
-    if (!ro) ro = &none;
-    const int kt = b->n_features + (b->add_intercept ? 1 : 0), na = q->n_alphas;
-    const bool host = b->mem == POLS_MEM_HOST;
-    const size_t G = (size_t)b->n_groups, sz = dtype_size(b->dtype);
-    const int64_t *d_offs = nullptr;
-    int64_t max_rows = 0;
-    if ((rc = upload_offsets(ctx, b->group_offsets, b->n_groups, &d_offs, &max_rows, b->offsets_generation))) return rc;
-    Staged st;
-    if ((rc = stage_inputs(ctx, b, b->n_groups, kt, o, &st))) return rc;
-    if ((rc = fill_null_weights(ctx, b, &st))) return rc;
-    SegTables sg;
-    if ((rc = ensure_segments(ctx, b, max_rows, 0, &sg))) return rc;
-    const size_t items = sg.n_seg > 0 ? (size_t)sg.n_seg : G;
-    const size_t gramb = round256(sizeof(double) * items * k10_gram_stride(kt)), eigb = round256(sizeof(double) * G * k10_eig_stride(kt));
-    const size_t alb = round256(sizeof(double) * (size_t)na), partb = round256(sizeof(double) * items * (size_t)na), c64b = round256(sizeof(double) * G * kt);
-    void *wg = nullptr, *ws = nullptr, *wo = nullptr;
-    if ((rc = ensure_scratch(ctx, Work::RidgeCvGram, gramb + eigb, &wg))) return rc;
-    if ((rc = ensure_scratch(ctx, Work::RidgeCvScores, alb + partb + c64b, &ws))) return rc;
-    if ((rc = upload_small(ctx, ws, q->alphas, sizeof(double) * (size_t)na))) return rc;
-    RidgeCvArgs a;
-    std::memset(&a, 0, sizeof(a));
-    a.y = st.y; a.w = st.w;
-    for (int j = 0; j < b->n_features; ++j) a.x[j] = st.x[(size_t)j];
-    a.offs = d_offs; a.n_groups = b->n_groups; a.n_rows = b->n_rows;
-    if (sg.n_seg > 0) { a.seg_offs = sg.offs; a.seg_map = sg.map; a.seg_first = sg.first; a.n_seg = sg.n_seg; }
-    a.valid = st.valid; a.null_policy = pol;
-    a.k_user = b->n_features; a.kt = kt; a.f32 = b->dtype == POLS_F32 ? 1 : 0;
-    a.alphas = static_cast<const double *>(ws); a.n_alphas = na;
-    a.gram_part = static_cast<double *>(wg);
-    a.eig = reinterpret_cast<double *>(static_cast<char *>(wg) + gramb);
-    a.score_part = reinterpret_cast<double *>(static_cast<char *>(ws) + alb);
-    a.coef64 = reinterpret_cast<double *>(static_cast<char *>(ws) + alb + partb);
-    a.coef = st.coef; a.status = st.status;
-    // the entry's own outputs: where the caller wants them (DEVICE batches) or staged (HOST batches)
-    const size_t vecb = round256(sizeof(double) * G), idxb = round256(sizeof(int32_t) * G), cvb = round256(sizeof(double) * G * (size_t)na),
-                 pathb = round256(sz * G * (size_t)na * kt);
-    if (host) {
-        if ((rc = ensure_scratch(ctx, Work::RidgeCvOut, 2 * vecb + idxb + cvb + pathb, &wo))) return rc;
-        char *c = static_cast<char *>(wo);
-        if (ro->alpha) a.alpha = reinterpret_cast<double *>(c);
-        if (ro->score) a.score = reinterpret_cast<double *>(c + vecb);
-        if (ro->alpha_index) a.alpha_index = reinterpret_cast<int32_t *>(c + 2 * vecb);
-        if (ro->cv_scores) a.cv_scores = reinterpret_cast<double *>(c + 2 * vecb + idxb);
-        if (ro->coef_path) a.coef_path = c + 2 * vecb + idxb + cvb;
-    } else {
-        a.alpha = ro->alpha; a.score = ro->score; a.alpha_index = ro->alpha_index; a.cv_scores = ro->cv_scores; a.coef_path = ro->coef_path;
-    }
-    ctx->last_kernel = sg.n_seg > 0 ? "k10_ridge_path_split" : "k10_ridge_path";
-    if ((rc = k10_gram_launch(ctx, b->dtype, a))) return rc;
-    if ((rc = k10_eig_launch(ctx, a))) return rc;
-    if ((rc = k10_rows_launch(ctx, b->dtype, a))) return rc;
-    if ((rc = k10_pick_launch(ctx, a))) return rc;
-    a.pred = st.pred; a.resid = st.resid;
-    if ((rc = k10_predict_launch(ctx, b->dtype, a))) return rc;
-    if (!host) return POLS_OK;
-    if (ro->alpha) POLS_HIP(hipMemcpyAsync(ro->alpha, a.alpha, sizeof(double) * G, hipMemcpyDeviceToHost, ctx->stream));
-    if (ro->score) POLS_HIP(hipMemcpyAsync(ro->score, a.score, sizeof(double) * G, hipMemcpyDeviceToHost, ctx->stream));
-    if (ro->alpha_index) POLS_HIP(hipMemcpyAsync(ro->alpha_index, a.alpha_index, sizeof(int32_t) * G, hipMemcpyDeviceToHost, ctx->stream));
-    if (ro->cv_scores) POLS_HIP(hipMemcpyAsync(ro->cv_scores, a.cv_scores, sizeof(double) * G * (size_t)na, hipMemcpyDeviceToHost, ctx->stream));
-    if (ro->coef_path) POLS_HIP(hipMemcpyAsync(ro->coef_path, a.coef_path, sz * G * (size_t)na * kt, hipMemcpyDeviceToHost, ctx->stream));
-    return unstage_outputs(ctx, b, b->n_groups, kt, o, st);
-}
-
-void pols_rlm_params_default(pols_rlm_params *q) {
-    if (!q) return;
-    q->norm = POLS_RLM_HUBER;
-    q->c = 0.0;
-    q->max_iter = 50;
-    q->tol = 1e-8;
-}
-
-// K11 (k11_rlm.hip): the whole iteration of a group in one workgroup -- one launch for the groups that stay resident in LDS, one for
-// those that are streamed -- then K10's prediction pass with the f64 coefficients.
-int pols_rlm(pols_ctx *ctx, const pols_batch *b, const pols_ols_params *p, const pols_rlm_params *q, pols_out *o, const pols_rlm_out *ro) {
-    int rc = check_ctx(ctx);
-    if (rc) return rc;
-    if (b && o && b->n_features + (b->add_intercept ? 1 : 0) > K11_KMAX)
-        return fail(POLS_ERR_UNSUPPORTED, "rlm: %d features (incl. intercept) > %d", b->n_features + (b->add_intercept ? 1 : 0), K11_KMAX);
-    if ((rc = check_batch(b, o, K11_KMAX))) return rc;
-    if (!p || !q) return fail(POLS_ERR_INVALID, "params / rlm params is NULL");
-    if (p->alpha != 0.0 || p->positive || (p->has_l1_ratio && p->l1_ratio > 0.0))
-        return fail(POLS_ERR_INVALID, "rlm: alpha / positive / l1_ratio do not apply to the M-estimator");
-    if (q->norm != POLS_RLM_HUBER && q->norm != POLS_RLM_BISQUARE) return fail(POLS_ERR_INVALID, "rlm: unknown norm %d", q->norm);
-    if (!std::isfinite(q->c)) return fail(POLS_ERR_INVALID, "rlm: c is not finite");
-    if (q->max_iter < 1) return fail(POLS_ERR_INVALID, "rlm: max_iter %d < 1", q->max_iter);
-    if (!(q->tol > 0.0) || !std::isfinite(q->tol)) return fail(POLS_ERR_INVALID, "rlm: tol %g is not positive and finite", q->tol);
-    if (p->null_policy < POLS_NULL_IGNORE || p->null_policy > POLS_NULL_DROP_WINDOW) return fail(POLS_ERR_INVALID, "unknown null_policy %d", p->null_policy);
-    const int pol = (b->null_free && !b->valid) ? POLS_NULL_IGNORE : p->null_policy;
-    if (b->valid && (pol == POLS_NULL_IGNORE || pol == POLS_NULL_ZERO))
-        return fail(POLS_ERR_INVALID, "a validity mask needs a drop-family null_policy");
-    if (b->n_groups == 0) return POLS_OK;
-    pols_rlm_out none;
-    std::memset(&none, 0, sizeof(none));
-    if (!ro) ro = &none;
-    const int kt = b->n_features + (b->add_intercept ? 1 : 0);
-    const bool host = b->mem == POLS_MEM_HOST;
-    const size_t G = (size_t)b->n_groups, sz = dtype_size(b->dtype);
-    // which form serves which group: the tiles a group spans from the 16-byte grid point at or below its first row
-    const int vec = b->dtype == POLS_F32 ? 4 : 2;
-    const int cap = ctx->opt.rlm_engine == 1 ? -1 : k11_resident_tiles(kt);
-    int64_t n_res = 0, n_str = 0, res_tiles = 0, str_rows = 0;
-    for (int64_t g = 0; g < b->n_groups; ++g) {
-        const int64_t s = b->group_offsets[g], e = b->group_offsets[g + 1];
-        if (e < s) return fail(POLS_ERR_INVALID, "group_offsets must not decrease");
-        const int64_t tiles = e > s ? (e - (s & ~(int64_t)(vec - 1)) + 255) / 256 : 0;
-        if (tiles <= cap) { ++n_res; res_tiles = std::max(res_tiles, tiles); }
-        else { ++n_str; str_rows = std::max(str_rows, e - s); }
-    }
-    if (str_rows > K11_STREAM_MAX_ROWS)
-        return fail(POLS_ERR_UNSUPPORTED, "rlm: a group of %lld rows > %lld (one workgroup walks a streamed group; the split form is not built)",
-                    (long long)str_rows, (long long)K11_STREAM_MAX_ROWS);
-    const int64_t *d_offs = nullptr;
-    int64_t max_rows = 0;
-    if ((rc = upload_offsets(ctx, b->group_offsets, b->n_groups, &d_offs, &max_rows, b->offsets_generation))) return rc;
-    Staged st;
-    if ((rc = stage_inputs(ctx, b, b->n_groups, kt, o, &st))) return rc;
-    if ((rc = fill_null_weights(ctx, b, &st))) return rc;
-    void *wc = nullptr, *wr = nullptr, *wo = nullptr;
-    if ((rc = ensure_scratch(ctx, Work::RlmCoef, round256(sizeof(double) * G * kt), &wc))) return rc;
-    if (n_str > 0 && (rc = ensure_scratch(ctx, Work::RlmRows, round256(sizeof(double) * (size_t)b->n_rows), &wr))) return rc;
-    RlmArgs a;
-    std::memset(&a, 0, sizeof(a));
-    a.y = st.y; a.w = st.w;
-    for (int j = 0; j < b->n_features; ++j) a.x[j] = st.x[(size_t)j];
-    a.offs = d_offs; a.n_groups = b->n_groups; a.n_rows = b->n_rows;
-    a.valid = st.valid; a.null_policy = pol;
-    a.k_user = b->n_features; a.kt = kt; a.f32 = b->dtype == POLS_F32 ? 1 : 0;
-    a.norm = q->norm; a.max_iter = q->max_iter; a.tol = q->tol;
-    a.c = q->c > 0.0 ? q->c : (q->norm == POLS_RLM_HUBER ? 1.345 : 4.685);
-    a.res_tiles = cap; a.ts = (int32_t)res_tiles * 256 + 1;
-    a.rows = static_cast<double *>(wr);
-    a.coef64 = static_cast<double *>(wc);
-    a.coef = st.coef; a.status = st.status;
-    const size_t vecb = round256(sizeof(double) * G), idxb = round256(sizeof(int32_t) * G), rowb = round256(sz * (size_t)b->n_rows);
-    if (host) {
-        if ((rc = ensure_scratch(ctx, Work::RlmOut, vecb + idxb + rowb, &wo))) return rc;
-        char *c = static_cast<char *>(wo);
-        if (ro->scale) a.scale = reinterpret_cast<double *>(c);
-        if (ro->n_iter) a.n_iter = reinterpret_cast<int32_t *>(c + vecb);
-        if (ro->weights) a.weights = c + vecb + idxb;
-    } else {
-        a.scale = ro->scale; a.n_iter = ro->n_iter; a.weights = ro->weights;
-    }
-    ctx->last_kernel = n_res >= n_str ? "k11_rlm_resident" : "k11_rlm_stream";
-    if (n_res > 0 && (rc = k11_rlm_launch(ctx, b->dtype, a, true))) return rc;
-    if (n_str > 0 && (rc = k11_rlm_launch(ctx, b->dtype, a, false))) return rc;
-    RidgeCvArgs pa;                                            // K10's prediction pass from the f64 coefficients
-    std::memset(&pa, 0, sizeof(pa));
-    pa.y = a.y; pa.w = a.w;
-    for (int j = 0; j < b->n_features; ++j) pa.x[j] = a.x[j];
-    pa.offs = d_offs; pa.n_groups = b->n_groups; pa.n_rows = b->n_rows;
-    pa.valid = a.valid; pa.null_policy = pol; pa.k_user = a.k_user; pa.kt = kt;
-    pa.coef64 = a.coef64; pa.pred = st.pred; pa.resid = st.resid;
-    if ((rc = k10_predict_launch(ctx, b->dtype, pa))) return rc;
-    if (!host) return POLS_OK;
-    if (ro->scale) POLS_HIP(hipMemcpyAsync(ro->scale, a.scale, sizeof(double) * G, hipMemcpyDeviceToHost, ctx->stream));
-    if (ro->n_iter) POLS_HIP(hipMemcpyAsync(ro->n_iter, a.n_iter, sizeof(int32_t) * G, hipMemcpyDeviceToHost, ctx->stream));
-    if (ro->weights) POLS_HIP(hipMemcpyAsync(ro->weights, a.weights, sz * (size_t)b->n_rows, hipMemcpyDeviceToHost, ctx->stream));
-    return unstage_outputs(ctx, b, b->n_groups, kt, o, st);
-}
-
-long long pols_glm_resident_lds(int kt, int cols, int elem, int tiles) { return (long long)k13_resident_lds(kt, cols, (size_t)elem, tiles); }
-int pols_glm_resident_tiles(int kt, int cols, int elem, int per_cu) { return k13_resident_tiles(kt, cols, (size_t)elem, per_cu); }
-
-void pols_glm_params_default(pols_glm_params *q) {
-    if (!q) return;
-    q->family = POLS_GLM_BINOMIAL;
-    q->max_iter = 25;
-    q->tol = 1e-8;
-    q->offset = nullptr;
-}
-
-// K13 (k13_glm.hip): the groups that stay resident in LDS iterate in one launch; the others are cut into segments and iterate with a
-// segment pass and a per-group pass per update, until the device counter of iterating groups reads zero; then K13's prediction pass
-// with the f64 coefficients.
-int pols_glm(pols_ctx *ctx, const pols_batch *b, const pols_ols_params *p, const pols_glm_params *q, pols_out *o, const pols_glm_out *ro) {
-    int rc = check_ctx(ctx);
-    if (rc) return rc;
-    if (b && o && b->n_features + (b->add_intercept ? 1 : 0) > K13_KMAX)
-        return fail(POLS_ERR_UNSUPPORTED, "glm: %d features (incl. intercept) > %d", b->n_features + (b->add_intercept ? 1 : 0), K13_KMAX);
-    if ((rc = check_batch(b, o, K13_KMAX))) return rc;
-    if (!p || !q) return fail(POLS_ERR_INVALID, "params / glm params is NULL");
-    if (p->alpha != 0.0 || p->positive || (p->has_l1_ratio && p->l1_ratio > 0.0))
-        return fail(POLS_ERR_INVALID, "glm: alpha / positive / l1_ratio do not apply (penalised GLMs are not built)");
-    if (q->family != POLS_GLM_BINOMIAL && q->family != POLS_GLM_POISSON) return fail(POLS_ERR_INVALID, "glm: unknown family %d", q->family);
-    if (q->max_iter < 1) return fail(POLS_ERR_INVALID, "glm: max_iter %d < 1", q->max_iter);
-    if (!(q->tol > 0.0) || !std::isfinite(q->tol)) return fail(POLS_ERR_INVALID, "glm: tol %g is not positive and finite", q->tol);
-    if (p->null_policy < POLS_NULL_IGNORE || p->null_policy > POLS_NULL_DROP_WINDOW) return fail(POLS_ERR_INVALID, "unknown null_policy %d", p->null_policy);
-    const int pol = (b->null_free && !b->valid) ? POLS_NULL_IGNORE : p->null_policy;
-    if (b->valid && (pol == POLS_NULL_IGNORE || pol == POLS_NULL_ZERO))
-        return fail(POLS_ERR_INVALID, "a validity mask needs a drop-family null_policy");
-    if (b->n_groups == 0) return POLS_OK;
-    pols_glm_out none;
-    std::memset(&none, 0, sizeof(none));
-    if (!ro) ro = &none;
-    const int kt = b->n_features + (b->add_intercept ? 1 : 0);
-    const bool host = b->mem == POLS_MEM_HOST;
-    const size_t G = (size_t)b->n_groups, sz = dtype_size(b->dtype);
-    // which form serves which group: the tiles a group spans from the 16-byte grid point at or below its first row
-    const int vec = b->dtype == POLS_F32 ? 4 : 2;
-    const int cols = b->n_features + 1 + (b->weights ? 1 : 0) + (q->offset ? 1 : 0);
-    // (two resident launches: the groups whose LDS request leaves room for a second workgroup on a CU, and the longer ones -- one long
-    //  group must not size the request of a whole frame of short ones)
-    const int cap = ctx->opt.glm_engine == 1 ? -1 : k13_resident_tiles(kt, cols, sz, 1);
-    const int cap2 = std::min(cap, k13_resident_tiles(kt, cols, sz, 2));
-    int64_t n_res = 0, n_spl = 0, res_tiles = 0, res2_tiles = 0, n_res1 = 0;
-    for (int64_t g = 0; g < b->n_groups; ++g) {
-        const int64_t s = b->group_offsets[g], e = b->group_offsets[g + 1];
-        if (e < s) return fail(POLS_ERR_INVALID, "group_offsets must not decrease");
-        const int64_t tiles = e > s ? (e - (s & ~(int64_t)(vec - 1)) + 255) / 256 : 0;
-        if (tiles <= cap2) { ++n_res; res2_tiles = std::max(res2_tiles, tiles); }
-        else if (tiles <= cap) { ++n_res; ++n_res1; res_tiles = std::max(res_tiles, tiles); }
-        else ++n_spl;
-    }
-    const int64_t *d_offs = nullptr;
-    int64_t max_rows = 0;
-    if ((rc = upload_offsets(ctx, b->group_offsets, b->n_groups, &d_offs, &max_rows, b->offsets_generation))) return rc;
-    Staged st;
-    if ((rc = stage_inputs(ctx, b, b->n_groups, kt, o, &st))) return rc;
-    if ((rc = fill_null_weights(ctx, b, &st))) return rc;
-    const size_t colb = round256(sz * (size_t)b->n_rows);
-    const void *d_off = q->offset;
-    if (q->offset && host && b->n_rows > 0) {
-        void *wf = nullptr;
-        if ((rc = ensure_scratch(ctx, Work::GlmOffset, colb, &wf))) return rc;
-        POLS_HIP(hipMemcpyAsync(wf, q->offset, sz * (size_t)b->n_rows, hipMemcpyHostToDevice, ctx->stream));
-        d_off = wf;
-    }
-    if (!host && (!aligned16(d_off) || !aligned16(ro->linpred))) return fail(POLS_ERR_INVALID, "device columns must be 16-byte aligned");
-    SegTables sg;
-    if (n_spl > 0 && (rc = ensure_segments(ctx, b, max_rows, sizeof(double) * k13_part_stride(kt), &sg))) return rc;
-    void *wc = nullptr, *ws = nullptr, *wo = nullptr;
-    if ((rc = ensure_scratch(ctx, Work::GlmCoef, round256(sizeof(double) * G * kt), &wc))) return rc;
-    const size_t stateb = round256(sizeof(double) * G * k13_state_stride(kt)), partb = sg.n_seg > 0 ? 0 : round256(sizeof(double) * G * k13_part_stride(kt));
-    if (n_spl > 0 && (rc = ensure_scratch(ctx, Work::GlmState, 256 + stateb + partb, &ws))) return rc;
-    GlmArgs a;
-    std::memset(&a, 0, sizeof(a));
-    a.y = st.y; a.w = st.w; a.o = d_off;
-    for (int j = 0; j < b->n_features; ++j) a.x[j] = st.x[(size_t)j];
-    a.offs = d_offs; a.n_groups = b->n_groups; a.n_rows = b->n_rows;
-    if (sg.n_seg > 0) { a.seg_offs = sg.offs; a.seg_map = sg.map; a.seg_first = sg.first; a.n_seg = sg.n_seg; }
-    a.valid = st.valid; a.null_policy = pol;
-    a.k_user = b->n_features; a.kt = kt; a.f32 = b->dtype == POLS_F32 ? 1 : 0;
-    a.family = q->family; a.max_iter = q->max_iter; a.tol = q->tol;
-    a.res_tiles = cap;
-    if (n_spl > 0) {
-        char *c = static_cast<char *>(ws);
-        a.active = reinterpret_cast<int32_t *>(c);
-        a.state = reinterpret_cast<double *>(c + 256);
-        a.part = sg.n_seg > 0 ? reinterpret_cast<double *>(sg.extra) : reinterpret_cast<double *>(c + 256 + stateb);
-    }
-    a.coef64 = static_cast<double *>(wc);
-    a.coef = st.coef; a.status = st.status;
-    const size_t vecb = round256(sizeof(double) * G), seb = round256(sizeof(double) * G * kt), idxb = round256(sizeof(int32_t) * G);
-    if (host) {
-        if ((rc = ensure_scratch(ctx, Work::GlmOut, vecb + seb + idxb + colb, &wo))) return rc;
-        char *c = static_cast<char *>(wo);
-        if (ro->deviance) a.deviance = reinterpret_cast<double *>(c);
-        if (ro->se) a.se = reinterpret_cast<double *>(c + vecb);
-        if (ro->n_iter) a.n_iter = reinterpret_cast<int32_t *>(c + vecb + seb);
-        if (ro->linpred) a.linpred = c + vecb + seb + idxb;
-    } else {
-        a.deviance = ro->deviance; a.se = ro->se; a.n_iter = ro->n_iter; a.linpred = ro->linpred;
-    }
-    ctx->last_kernel = n_res >= n_spl ? "k13_glm_resident" : "k13_glm_split";
-    if (n_res > n_res1) {
-        a.res_from = -1; a.res_to = cap2; a.ts = (int32_t)res2_tiles * 256 + 1;
-        if ((rc = k13_resident_launch(ctx, b->dtype, a))) return rc;
-    }
-    if (n_res1 > 0) {
-        a.res_from = cap2; a.res_to = cap; a.ts = (int32_t)res_tiles * 256 + 1;
-        if ((rc = k13_resident_launch(ctx, b->dtype, a))) return rc;
-    }
-    if (n_spl > 0) {
-        const int32_t n_active = (int32_t)std::min<int64_t>(n_spl, 0x7fffffff);
-        if ((rc = upload_small(ctx, a.active, &n_active, sizeof(n_active)))) return rc;
-        // one update per turn: at most max_iter updates and the start, then every group has stopped
-        for (int turn = 0; turn <= q->max_iter; ++turn) {
-            if ((rc = k13_split_launch(ctx, b->dtype, a, turn == 0))) return rc;
-            int32_t left = 0;
-            POLS_HIP(hipMemcpyAsync(&left, a.active, sizeof(left), hipMemcpyDeviceToHost, ctx->stream));
-            POLS_HIP(hipStreamSynchronize(ctx->stream));           // the host decides whether another update is launched
-            if (left <= 0) break;
-        }
-    }
-    a.pred = st.pred; a.resid = st.resid;
-    if ((rc = k13_predict_launch(ctx, b->dtype, a))) return rc;
-    if (!host) return POLS_OK;
-    if (ro->deviance) POLS_HIP(hipMemcpyAsync(ro->deviance, a.deviance, sizeof(double) * G, hipMemcpyDeviceToHost, ctx->stream));
-    if (ro->se) POLS_HIP(hipMemcpyAsync(ro->se, a.se, sizeof(double) * G * kt, hipMemcpyDeviceToHost, ctx->stream));
-    if (ro->n_iter) POLS_HIP(hipMemcpyAsync(ro->n_iter, a.n_iter, sizeof(int32_t) * G, hipMemcpyDeviceToHost, ctx->stream));
-    if (ro->linpred) POLS_HIP(hipMemcpyAsync(ro->linpred, a.linpred, sz * (size_t)b->n_rows, hipMemcpyDeviceToHost, ctx->stream));
-    return unstage_outputs(ctx, b, b->n_groups, kt, o, st);
-}
-
-void pols_iv_params_default(pols_iv_params *q) {
-    if (!q) return;
-    q->n_endog = 0;
-    q->z_cols = nullptr;
-    q->n_instruments = 0;
-    q->cov_type = POLS_COV_NONROBUST;
-    q->small_sample = 1;
-}
-
-// K14 (k14_iv.hip): K10's Gram launch over the concatenated columns [X1 | X2 | Z2], the per-group solve, the row pass for RSS and the
-// robust meat (only when a wanted output needs it), the per-group finish, then K10's prediction pass with the f64 coefficients.
-int pols_iv2sls(pols_ctx *ctx, const pols_batch *b, const pols_ols_params *p, const pols_iv_params *q, pols_out *o, const pols_iv_out *ro) {
-    int rc = check_ctx(ctx);
-    if (rc) return rc;
-    if (!p || !q) return fail(POLS_ERR_INVALID, "params / iv params is NULL");
-    if ((rc = check_batch(b, o, K14_TMAX))) return rc;
-    if (p->alpha != 0.0 || p->positive || (p->has_l1_ratio && p->l1_ratio > 0.0))
-        return fail(POLS_ERR_INVALID, "iv2sls: alpha / positive / l1_ratio do not apply");
-    if (q->n_endog < 1 || q->n_endog > b->n_features) return fail(POLS_ERR_INVALID, "iv2sls: n_endog %d outside 1..%d", q->n_endog, b->n_features);
-    if (q->n_instruments < q->n_endog) return fail(POLS_ERR_INVALID, "iv2sls: %d instruments < %d endogenous regressors", q->n_instruments, q->n_endog);
-    if (!q->z_cols) return fail(POLS_ERR_INVALID, "iv2sls: z_cols is NULL");
-    for (int j = 0; j < q->n_instruments; ++j)
-        if (!q->z_cols[j] && b->n_rows) return fail(POLS_ERR_INVALID, "iv2sls: z_cols[%d] is NULL", j);
-    if (q->cov_type != POLS_COV_NONROBUST && q->cov_type != POLS_COV_HC0 && q->cov_type != POLS_COV_HC1)
-        return fail(POLS_ERR_INVALID, "iv2sls: cov_type %d is not NONROBUST / HC0 / HC1", q->cov_type);
-    const int nf = b->n_features, m = q->n_instruments, icpt = b->add_intercept ? 1 : 0, kx = nf + icpt, T = kx + m, L = kx - q->n_endog + m;
-    if (T > K14_TMAX) return fail(POLS_ERR_UNSUPPORTED, "iv2sls: %d regressors (incl. intercept) + %d instruments > %d", kx, m, K14_TMAX);
-    if (p->null_policy < POLS_NULL_IGNORE || p->null_policy > POLS_NULL_DROP_WINDOW) return fail(POLS_ERR_INVALID, "unknown null_policy %d", p->null_policy);
-    const int pol = (b->null_free && !b->valid) ? POLS_NULL_IGNORE : p->null_policy;
-    if (b->valid && (pol == POLS_NULL_IGNORE || pol == POLS_NULL_ZERO))
-        return fail(POLS_ERR_INVALID, "a validity mask needs a drop-family null_policy");
-    if (b->n_groups == 0) return POLS_OK;
-    pols_iv_out none;
-    std::memset(&none, 0, sizeof(none));
-    if (!ro) ro = &none;
-    const bool host = b->mem == POLS_MEM_HOST;
-    const bool robust = q->cov_type != POLS_COV_NONROBUST;
-    const bool need_rows = ro->se || ro->t_values || ro->p_values || ro->cov || ro->sigma2 || ro->sargan || ro->sargan_p;
-    const size_t G = (size_t)b->n_groups, sz = dtype_size(b->dtype);
-    const int64_t *d_offs = nullptr;
-    int64_t max_rows = 0;
-    if ((rc = upload_offsets(ctx, b->group_offsets, b->n_groups, &d_offs, &max_rows, b->offsets_generation))) return rc;
-    Staged st;
-    if ((rc = stage_inputs(ctx, b, b->n_groups, kx, o, &st))) return rc;
-    if ((rc = fill_null_weights(ctx, b, &st))) return rc;
-    const size_t colb = round256(sz * (size_t)b->n_rows);
-    std::vector<const void *> zc((size_t)m);
-    if (host) {
-        void *wz = nullptr;
-        if ((rc = ensure_scratch(ctx, Work::IvInputs, colb * (size_t)m, &wz))) return rc;
-        for (int j = 0; j < m; ++j) {
-            zc[(size_t)j] = static_cast<char *>(wz) + colb * (size_t)j;
-            if (b->n_rows > 0) POLS_HIP(hipMemcpyAsync(const_cast<void *>(zc[(size_t)j]), q->z_cols[j], sz * (size_t)b->n_rows, hipMemcpyHostToDevice, ctx->stream));
-        }
-    } else {
-        for (int j = 0; j < m; ++j) {
-            zc[(size_t)j] = q->z_cols[j];
-            if (!aligned16(zc[(size_t)j])) return fail(POLS_ERR_INVALID, "device columns must be 16-byte aligned");
-        }
-    }
-    SegTables sg;
-    if ((rc = ensure_segments(ctx, b, max_rows, 0, &sg))) return rc;
-    const size_t items = sg.n_seg > 0 ? (size_t)sg.n_seg : G;
-    const bool pred_all = pol == POLS_NULL_DROP && (st.pred || st.resid);   // the one policy whose prediction pass masks rows
-    const size_t gramb = round256(sizeof(double) * items * k10_gram_stride(T)), rowsb = round256(sizeof(double) * items * k14_rows_stride(kx, robust));
-    const size_t stateb = round256(sizeof(double) * G * k14_state_stride(kx, L)), coefb = round256(sizeof(double) * G * (size_t)(pred_all ? T : kx));
-    void *wm = nullptr, *ws = nullptr, *wo = nullptr;
-    if ((rc = ensure_scratch(ctx, Work::IvMoments, gramb + rowsb, &wm))) return rc;
-    if ((rc = ensure_scratch(ctx, Work::IvState, stateb + coefb, &ws))) return rc;
-    RidgeCvArgs ga;                                            // K10's Gram launch and, later, its prediction pass
-    std::memset(&ga, 0, sizeof(ga));
-    IvArgs a;
-    std::memset(&a, 0, sizeof(a));
-    a.y = ga.y = st.y; a.w = ga.w = st.w;
-    for (int j = 0; j < nf; ++j) a.x[j] = ga.x[j] = st.x[(size_t)j];
-    for (int j = 0; j < m; ++j) a.x[nf + j] = ga.x[nf + j] = zc[(size_t)j];
-    a.offs = ga.offs = d_offs; a.n_groups = ga.n_groups = b->n_groups; a.n_rows = ga.n_rows = b->n_rows;
-    if (sg.n_seg > 0) {
-        a.seg_offs = ga.seg_offs = sg.offs; a.seg_map = ga.seg_map = sg.map; a.seg_first = ga.seg_first = sg.first; a.n_seg = ga.n_seg = sg.n_seg;
-    }
-    a.valid = ga.valid = st.valid; a.null_policy = ga.null_policy = pol;
-    a.k_user = ga.k_user = nf + m; a.kt = ga.kt = T;
-    a.n_feat = nf; a.n_endog = q->n_endog; a.n_inst = m; a.icpt = icpt;
-    a.f32 = b->dtype == POLS_F32 ? 1 : 0;
-    a.cov_type = q->cov_type; a.small_sample = q->small_sample ? 1 : 0; a.pred_all = pred_all ? 1 : 0;
-    ga.gram_part = static_cast<double *>(wm);
-    a.gram_part = ga.gram_part;
-    a.rows_part = reinterpret_cast<double *>(static_cast<char *>(wm) + gramb);
-    a.state = static_cast<double *>(ws);
-    a.coefp = reinterpret_cast<double *>(static_cast<char *>(ws) + stateb);
-    a.coef = st.coef; a.status = st.status;
-    const size_t kb = round256(sizeof(double) * G * kx), kkb = round256(sizeof(double) * G * kx * kx), vecb = round256(sizeof(double) * G),
-                 eb = round256(sizeof(double) * G * (size_t)q->n_endog), nb = round256(sizeof(int64_t) * G);
-    if (host) {
-        if ((rc = ensure_scratch(ctx, Work::IvOut, 3 * kb + kkb + 3 * vecb + 2 * eb + nb, &wo))) return rc;
-        char *c = static_cast<char *>(wo);
-        if (ro->se) a.se = reinterpret_cast<double *>(c);
-        if (ro->t_values) a.t_values = reinterpret_cast<double *>(c + kb);
-        if (ro->p_values) a.p_values = reinterpret_cast<double *>(c + 2 * kb);
-        if (ro->cov) a.cov = reinterpret_cast<double *>(c + 3 * kb);
-        c += 3 * kb + kkb;
-        if (ro->sigma2) a.sigma2 = reinterpret_cast<double *>(c);
-        if (ro->sargan) a.sargan = reinterpret_cast<double *>(c + vecb);
-        if (ro->sargan_p) a.sargan_p = reinterpret_cast<double *>(c + 2 * vecb);
-        c += 3 * vecb;
-        if (ro->first_stage_f) a.first_stage_f = reinterpret_cast<double *>(c);
-        if (ro->partial_r2) a.partial_r2 = reinterpret_cast<double *>(c + eb);
-        if (ro->n_obs) a.n_obs = reinterpret_cast<int64_t *>(c + 2 * eb);
-    } else {
-        a.se = ro->se; a.t_values = ro->t_values; a.p_values = ro->p_values; a.cov = ro->cov; a.sigma2 = ro->sigma2;
-        a.first_stage_f = ro->first_stage_f; a.partial_r2 = ro->partial_r2; a.sargan = ro->sargan; a.sargan_p = ro->sargan_p; a.n_obs = ro->n_obs;
-    }
-    ctx->last_kernel = sg.n_seg > 0 ? "k14_iv2sls_split" : "k14_iv2sls";
-    if ((rc = k10_gram_launch(ctx, b->dtype, ga))) return rc;
-    if ((rc = k14_solve_launch(ctx, a))) return rc;
-    if (need_rows) {
-        // the plain RSS needs the regressors and y alone: the instruments are staged only where the robust meat reads them or their nulls drop rows
-        IvArgs ra = a;
-        const bool z_drops = pol == POLS_NULL_DROP || pol == POLS_NULL_DROP_ZERO || pol == POLS_NULL_DROP_WINDOW;
-        if (!robust && !z_drops) { ra.k_user = nf; ra.kt = kx; }
-        if ((rc = k14_rows_launch(ctx, b->dtype, ra))) return rc;
-        if ((rc = k14_finish_launch(ctx, a))) return rc;
-    }
-    // the prediction pass: the regressors alone, or -- "drop" -- the whole list with zero coefficients for the instruments, whose nulls mask rows
-    ga.k_user = pred_all ? nf + m : nf; ga.kt = pred_all ? T : kx;
-    ga.coef64 = a.coefp; ga.pred = st.pred; ga.resid = st.resid;
-    if ((rc = k10_predict_launch(ctx, b->dtype, ga))) return rc;
-    if (!host) return POLS_OK;
-    auto home = [&](void *dst, const void *src, size_t bytes) -> int {
-        if (dst) POLS_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, ctx->stream));
-        return POLS_OK;
-    };
-    if ((rc = home(ro->se, a.se, sizeof(double) * G * kx))) return rc;
-    if ((rc = home(ro->t_values, a.t_values, sizeof(double) * G * kx))) return rc;
-    if ((rc = home(ro->p_values, a.p_values, sizeof(double) * G * kx))) return rc;
-    if ((rc = home(ro->cov, a.cov, sizeof(double) * G * kx * kx))) return rc;
-    if ((rc = home(ro->sigma2, a.sigma2, sizeof(double) * G))) return rc;
-    if ((rc = home(ro->sargan, a.sargan, sizeof(double) * G))) return rc;
-    if ((rc = home(ro->sargan_p, a.sargan_p, sizeof(double) * G))) return rc;
-    if ((rc = home(ro->first_stage_f, a.first_stage_f, sizeof(double) * G * (size_t)q->n_endog))) return rc;
-    if ((rc = home(ro->partial_r2, a.partial_r2, sizeof(double) * G * (size_t)q->n_endog))) return rc;
-    if ((rc = home(ro->n_obs, a.n_obs, sizeof(int64_t) * G))) return rc;
-    return unstage_outputs(ctx, b, b->n_groups, kx, o, st);
-}
-
-void pols_enet_cv_params_default(pols_enet_cv_params *q) {
-    if (!q) return;
-    q->alphas = nullptr;
-    q->n_alphas = 100;
-    q->eps = 1e-3;
-    q->l1_ratio = 0.5;
-    q->n_folds = 5;
-    q->max_iter = 1000;
-    q->tol = 1e-5;
-    q->positive = 0;
-}
-
-// K12 (k12_enet_cv.hip): fold Gram matrices in one pass over the frame (behind a count pass when the null policy can remove rows),
-// the (n_folds + 1) x n_alphas coordinate-descent fits on chip, pick, then K10's prediction pass with the winner's coefficients.
-int pols_elastic_net_cv(pols_ctx *ctx, const pols_batch *b, const pols_ols_params *p, const pols_enet_cv_params *q, pols_out *o,
-                        const pols_enet_cv_out *ro) {
-    int rc = check_ctx(ctx);
-    if (rc) return rc;
-    if (b && o && b->n_features + (b->add_intercept ? 1 : 0) > K12_KMAX)
-        return fail(POLS_ERR_UNSUPPORTED, "elastic_net_cv: %d features (incl. intercept) > %d", b->n_features + (b->add_intercept ? 1 : 0), K12_KMAX);
-    if ((rc = check_batch(b, o, K12_KMAX))) return rc;
-    if (!p || !q) return fail(POLS_ERR_INVALID, "params / elastic_net_cv params is NULL");
-    const bool automatic = q->alphas == nullptr;
-    if (!(q->l1_ratio >= 0.0 && q->l1_ratio <= 1.0)) return fail(POLS_ERR_INVALID, "elastic_net_cv: l1_ratio %g outside [0, 1]", q->l1_ratio);
-    if (q->n_alphas < 1) return fail(POLS_ERR_INVALID, "elastic_net_cv: the grid of candidates is empty");
-    if (q->n_alphas > K12_MAX_ALPHAS) return fail(POLS_ERR_UNSUPPORTED, "elastic_net_cv: %d candidates > %d", q->n_alphas, K12_MAX_ALPHAS);
-    if (automatic) {
-        if (q->n_alphas < 2) return fail(POLS_ERR_INVALID, "elastic_net_cv: an automatic grid needs at least 2 candidates");
-        if (!(q->eps > 0.0 && q->eps < 1.0)) return fail(POLS_ERR_INVALID, "elastic_net_cv: eps %g outside (0, 1)", q->eps);
-        if (q->l1_ratio == 0.0) return fail(POLS_ERR_INVALID, "elastic_net_cv: an automatic grid needs l1_ratio > 0");
-    } else {
-        for (int j = 0; j < q->n_alphas; ++j)
-            if (!(q->alphas[j] >= 0.0) || !std::isfinite(q->alphas[j])) return fail(POLS_ERR_INVALID, "elastic_net_cv: candidate %d is negative or not finite", j);
-    }
-    if (q->n_folds < 2 || q->n_folds > K12_MAX_FOLDS) return fail(POLS_ERR_INVALID, "elastic_net_cv: %d folds outside 2..%d", q->n_folds, K12_MAX_FOLDS);
-    if (q->max_iter < 1) return fail(POLS_ERR_INVALID, "elastic_net_cv: max_iter %d < 1", q->max_iter);
-    if (!(q->tol > 0.0) || !std::isfinite(q->tol)) return fail(POLS_ERR_INVALID, "elastic_net_cv: tol %g is not positive and finite", q->tol);
-    if (p->null_policy < POLS_NULL_IGNORE || p->null_policy > POLS_NULL_DROP_WINDOW) return fail(POLS_ERR_INVALID, "unknown null_policy %d", p->null_policy);
-    const int pol = (b->null_free && !b->valid) ? POLS_NULL_IGNORE : p->null_policy;
-    if (b->valid && (pol == POLS_NULL_IGNORE || pol == POLS_NULL_ZERO))
-        return fail(POLS_ERR_INVALID, "a validity mask needs a drop-family null_policy");
-    if (b->n_groups == 0) return POLS_OK;
-    pols_enet_cv_out none;
-    std::memset(&none, 0, sizeof(none));
-    if (!ro) ro = &none;
-    const int kt = b->n_features + (b->add_intercept ? 1 : 0), na = q->n_alphas, nf = q->n_folds;
-    const bool host = b->mem == POLS_MEM_HOST;
-    const size_t G = (size_t)b->n_groups, sz = dtype_size(b->dtype);
-    const int64_t *d_offs = nullptr;
-    int64_t max_rows = 0;
-    if ((rc = upload_offsets(ctx, b->group_offsets, b->n_groups, &d_offs, &max_rows, b->offsets_generation))) return rc;
-    Staged st;
-    if ((rc = stage_inputs(ctx, b, b->n_groups, kt, o, &st))) return rc;
-    if ((rc = fill_null_weights(ctx, b, &st))) return rc;
-    SegTables sg;
-    if ((rc = ensure_segments(ctx, b, max_rows, 0, &sg))) return rc;
-    const bool split = sg.n_seg > 0;
-    const size_t items = split ? (size_t)sg.n_seg : G;
-    const size_t per = (size_t)nf * k10_gram_stride(kt);
-    const size_t cntb = round256(sizeof(int64_t) * items), partb = round256(sizeof(double) * items * per),
-                 foldb = split ? round256(sizeof(double) * G * per) : 0;
-    const size_t alb = round256(sizeof(double) * (size_t)na + sizeof(int32_t) * (size_t)na), scb = round256(sizeof(double) * G * nf * (size_t)na),
-                 itb = round256(sizeof(int32_t) * G * (nf + 1) * (size_t)na), p64b = round256(sizeof(double) * G * (size_t)na * kt),
-                 grb = round256(sizeof(double) * G * (size_t)na), c64b = round256(sizeof(double) * G * kt);
-    void *wg = nullptr, *ws = nullptr, *wo = nullptr;
-    if ((rc = ensure_scratch(ctx, Work::EnetCvGram, cntb + partb + foldb, &wg))) return rc;
-    if ((rc = ensure_scratch(ctx, Work::EnetCvWork, alb + scb + itb + p64b + grb + c64b, &ws))) return rc;
-    {   // the candidates and the order they are visited in: descending alpha, equal values in index order
-        std::vector<char> up(sizeof(double) * (size_t)na + sizeof(int32_t) * (size_t)na);
-        double *ua = reinterpret_cast<double *>(up.data());
-        int32_t *uo = reinterpret_cast<int32_t *>(up.data() + sizeof(double) * (size_t)na);
-        for (int j = 0; j < na; ++j) { ua[j] = automatic ? 0.0 : q->alphas[j]; uo[j] = j; }
-        if (!automatic) std::stable_sort(uo, uo + na, [&](int32_t x, int32_t y) { return ua[x] > ua[y]; });
-        if ((rc = upload_small(ctx, ws, up.data(), up.size()))) return rc;
-    }
-    EnetCvArgs a;
-    std::memset(&a, 0, sizeof(a));
-    a.y = st.y; a.w = st.w;
-    for (int j = 0; j < b->n_features; ++j) a.x[j] = st.x[(size_t)j];
-    a.offs = d_offs; a.n_groups = b->n_groups; a.n_rows = b->n_rows;
-    if (split) { a.seg_offs = sg.offs; a.seg_map = sg.map; a.seg_first = sg.first; a.n_seg = sg.n_seg; }
-    a.valid = st.valid; a.null_policy = pol;
-    a.k_user = b->n_features; a.kt = kt; a.f32 = b->dtype == POLS_F32 ? 1 : 0;
-    a.n_folds = nf; a.n_alphas = na; a.automatic = automatic ? 1 : 0;
-    a.counted = (pol == POLS_NULL_DROP || pol == POLS_NULL_DROP_ZERO || pol == POLS_NULL_DROP_WINDOW || pol == POLS_NULL_DROP_Y_ZERO_X) ? 1 : 0;
-    a.max_iter = q->max_iter; a.positive = q->positive ? 1 : 0;
-    a.l1_ratio = q->l1_ratio; a.tol = q->tol; a.eps = q->eps;
-    char *cg = static_cast<char *>(wg), *cs = static_cast<char *>(ws);
-    a.item_count = reinterpret_cast<int64_t *>(cg);
-    a.fold_part = reinterpret_cast<double *>(cg + cntb);
-    a.fold_gram = split ? reinterpret_cast<double *>(cg + cntb + partb) : a.fold_part;
-    a.alphas = reinterpret_cast<const double *>(cs);
-    a.order = reinterpret_cast<const int32_t *>(cs + sizeof(double) * (size_t)na);
-    a.score_part = reinterpret_cast<double *>(cs + alb);
-    a.iters = reinterpret_cast<int32_t *>(cs + alb + scb);
-    a.path64 = reinterpret_cast<double *>(cs + alb + scb + itb);
-    a.grid = reinterpret_cast<double *>(cs + alb + scb + itb + p64b);
-    a.coef64 = reinterpret_cast<double *>(cs + alb + scb + itb + p64b + grb);
-    a.coef = st.coef; a.status = st.status;
-    // the entry's own outputs: where the caller wants them (DEVICE batches) or staged (HOST batches)
-    const size_t vecb = round256(sizeof(double) * G), idxb = round256(sizeof(int32_t) * G), cvb = round256(sizeof(double) * G * (size_t)na),
-                 pathb = round256(sz * G * (size_t)na * kt), nitb = round256(sizeof(int32_t) * G * (size_t)na);
-    if (host) {
-        if ((rc = ensure_scratch(ctx, Work::EnetCvOut, 2 * vecb + idxb + 2 * cvb + pathb + nitb, &wo))) return rc;
-        char *c = static_cast<char *>(wo);
-        if (ro->alpha) a.alpha = reinterpret_cast<double *>(c);
-        if (ro->score) a.score = reinterpret_cast<double *>(c + vecb);
-        if (ro->alpha_index) a.alpha_index = reinterpret_cast<int32_t *>(c + 2 * vecb);
-        if (ro->cv_scores) a.cv_scores = reinterpret_cast<double *>(c + 2 * vecb + idxb);
-        if (ro->alphas_used) a.alphas_used = reinterpret_cast<double *>(c + 2 * vecb + idxb + cvb);
-        if (ro->coef_path) a.coef_path = c + 2 * vecb + idxb + 2 * cvb;
-        if (ro->n_iter) a.n_iter = reinterpret_cast<int32_t *>(c + 2 * vecb + idxb + 2 * cvb + pathb);
-    } else {
-        a.alpha = ro->alpha; a.score = ro->score; a.alpha_index = ro->alpha_index; a.cv_scores = ro->cv_scores;
-        a.alphas_used = ro->alphas_used; a.coef_path = ro->coef_path; a.n_iter = ro->n_iter;
-    }
-    ctx->last_kernel = split ? "k12_enet_cv_split" : "k12_enet_cv";
-    if ((rc = k12_count_launch(ctx, b->dtype, a))) return rc;
-    if ((rc = k12_fold_gram_launch(ctx, b->dtype, a))) return rc;
-    if ((rc = k12_reduce_launch(ctx, a))) return rc;
-    if ((rc = k12_path_launch(ctx, a))) return rc;
-    if ((rc = k12_pick_launch(ctx, a))) return rc;
-    RidgeCvArgs pa;                                            // K10's prediction pass from the f64 coefficients
-    std::memset(&pa, 0, sizeof(pa));
-    pa.y = a.y; pa.w = a.w;
-    for (int j = 0; j < b->n_features; ++j) pa.x[j] = a.x[j];
-    pa.offs = d_offs; pa.n_groups = b->n_groups; pa.n_rows = b->n_rows;
-    if (split) { pa.seg_offs = sg.offs; pa.seg_map = sg.map; pa.seg_first = sg.first; pa.n_seg = sg.n_seg; }
-    pa.valid = a.valid; pa.null_policy = pol; pa.k_user = a.k_user; pa.kt = kt;
-    pa.coef64 = a.coef64; pa.pred = st.pred; pa.resid = st.resid;
-    if ((rc = k10_predict_launch(ctx, b->dtype, pa))) return rc;
-    if (!host) return POLS_OK;
-    if (ro->alpha) POLS_HIP(hipMemcpyAsync(ro->alpha, a.alpha, sizeof(double) * G, hipMemcpyDeviceToHost, ctx->stream));
-    if (ro->score) POLS_HIP(hipMemcpyAsync(ro->score, a.score, sizeof(double) * G, hipMemcpyDeviceToHost, ctx->stream));
-    if (ro->alpha_index) POLS_HIP(hipMemcpyAsync(ro->alpha_index, a.alpha_index, sizeof(int32_t) * G, hipMemcpyDeviceToHost, ctx->stream));
-    if (ro->cv_scores) POLS_HIP(hipMemcpyAsync(ro->cv_scores, a.cv_scores, sizeof(double) * G * (size_t)na, hipMemcpyDeviceToHost, ctx->stream));
-    if (ro->alphas_used) POLS_HIP(hipMemcpyAsync(ro->alphas_used, a.alphas_used, sizeof(double) * G * (size_t)na, hipMemcpyDeviceToHost, ctx->stream));
-    if (ro->coef_path) POLS_HIP(hipMemcpyAsync(ro->coef_path, a.coef_path, sz * G * (size_t)na * kt, hipMemcpyDeviceToHost, ctx->stream));
-    if (ro->n_iter) POLS_HIP(hipMemcpyAsync(ro->n_iter, a.n_iter, sizeof(int32_t) * G * (size_t)na, hipMemcpyDeviceToHost, ctx->stream));
-    return unstage_outputs(ctx, b, b->n_groups, kt, o, st);
 }
 
 void pols_cluster_params_default(pols_cluster_params *c) {

@@ -1,0 +1,559 @@
+// api_fits.hip -- the per-group fit entries of the C-ABI: pols_ridge_cv (K10), pols_rlm (K11), pols_elastic_net_cv (K12), pols_glm
+// (K13), pols_iv2sls (K14).  Host code only.  What they share is written once, up front: the opening checks and the staging
+// (FitCall), the common fields of the kernel argument structs (fit_frame, fit_segments), the entry's own outputs (ExtraOut), K10's
+// prediction pass (fit_predict) and extra input columns (stage_extra_columns).  DESIGN.md, "Adding a per-group fit entry".
+#include <algorithm>
+#include <cassert>
+#include <cmath>
+
+#include "api_internal.hpp"
+#include "k10_ridge_path.hpp"
+#include "k11_rlm.hpp"
+#include "k12_enet_cv.hpp"
+#include "k13_glm.hpp"
+#include "k14_iv.hpp"
+
+using namespace pols;
+
+namespace {
+
+// What every entry derives before its own work.
+struct FitCall {
+    int kt = 0;                      // the frame's columns: n_features + intercept
+    int pol = 0;                     // the null policy the kernels see
+    bool host = false;
+    size_t G = 0, sz = 0;            // groups; bytes per value of the batch dtype
+    const int64_t *d_offs = nullptr; // fit_stage: the offsets on the device, the longest group, the columns
+    int64_t max_rows = 0;
+    Staged st;
+};
+
+// The shared checks.  `name` words the messages, `cap` is the entry's limit on the frame's columns (incl. the intercept).
+int fit_check(pols_ctx *ctx, const pols_batch *b, const pols_ols_params *p, const void *q, const pols_out *o, const char *name, int cap,
+              FitCall *fc) {
+    int rc = check_ctx(ctx);
+    if (rc) return rc;
+    if (b && o && b->n_features + (b->add_intercept ? 1 : 0) > cap)
+        return fail(POLS_ERR_UNSUPPORTED, "%s: %d features (incl. intercept) > %d", name, b->n_features + (b->add_intercept ? 1 : 0), cap);
+    if ((rc = check_batch(b, o, cap))) return rc;
+    if (!p || !q) return fail(POLS_ERR_INVALID, "params / %s params is NULL", name);
+    if (p->null_policy < POLS_NULL_IGNORE || p->null_policy > POLS_NULL_DROP_WINDOW) return fail(POLS_ERR_INVALID, "unknown null_policy %d", p->null_policy);
+    fc->pol = (b->null_free && !b->valid) ? POLS_NULL_IGNORE : p->null_policy;
+    if (b->valid && (fc->pol == POLS_NULL_IGNORE || fc->pol == POLS_NULL_ZERO))
+        return fail(POLS_ERR_INVALID, "a validity mask needs a drop-family null_policy");
+    fc->kt = b->n_features + (b->add_intercept ? 1 : 0);
+    fc->host = b->mem == POLS_MEM_HOST;
+    fc->G = (size_t)b->n_groups;
+    fc->sz = dtype_size(b->dtype);
+    return POLS_OK;
+}
+
+int fit_stage(pols_ctx *ctx, const pols_batch *b, const pols_out *o, FitCall *fc) {
+    int rc = upload_offsets(ctx, b->group_offsets, b->n_groups, &fc->d_offs, &fc->max_rows, b->offsets_generation);
+    if (rc) return rc;
+    if ((rc = stage_inputs(ctx, b, b->n_groups, fc->kt, o, &fc->st))) return rc;
+    return fill_null_weights(ctx, b, &fc->st);
+}
+
+// an entry called without its own output struct wants none of its fields
+template <typename O> const O *or_none(const O *ro) {
+    static const O none = {};
+    return ro ? ro : &none;
+}
+
+// The fields every argument struct of the family has (templates: the structs stay as the kernels know them).
+template <typename A> void fit_frame(A &a, const pols_batch *b, const FitCall &fc) {
+    a.y = fc.st.y; a.w = fc.st.w;
+    for (int j = 0; j < b->n_features; ++j) a.x[j] = fc.st.x[(size_t)j];
+    a.offs = fc.d_offs; a.n_groups = b->n_groups; a.n_rows = b->n_rows;
+    a.valid = fc.st.valid; a.null_policy = fc.pol;
+    a.k_user = b->n_features; a.kt = fc.kt; a.f32 = b->dtype == POLS_F32 ? 1 : 0;
+    a.coef = fc.st.coef; a.status = fc.st.status;
+}
+template <typename A> void fit_segments(A &a, const SegTables &sg) {
+    if (sg.n_seg > 0) { a.seg_offs = sg.offs; a.seg_map = sg.map; a.seg_first = sg.first; a.n_seg = sg.n_seg; }
+}
+
+// The entry's own outputs, each registered once: the caller's pointer, the slot of the argument struct, the bytes.  place(): the
+// slot of a DEVICE batch is the caller's pointer; the wanted fields of a HOST batch are carved out of `w` at 256-byte steps and
+// an unwanted one's slot stays nullptr.  home(): the wanted fields of a HOST batch go home, then the pols_out ones (unstage_outputs).
+struct ExtraOut {
+    struct Field {
+        void *home, *slot, *dev;
+        size_t bytes;
+        void (*set)(void *slot, void *p);
+    };
+    static constexpr int CAP = 16;
+    Field f[CAP];
+    int n = 0;
+
+    template <typename T> void add(T *home, T *&slot, size_t bytes) {
+        assert(n < CAP);
+        f[n++] = Field{home, &slot, nullptr, bytes, [](void *s, void *p) { *static_cast<T **>(s) = static_cast<T *>(p); }};
+    }
+    int place(pols_ctx *ctx, const FitCall &fc, Work w) {
+        size_t total = 0;
+        void *buf = nullptr;
+        for (int i = 0; i < n; ++i)
+            if (f[i].home && fc.host) total += round256(f[i].bytes);
+        if (total > 0) {
+            int rc = ensure_scratch(ctx, w, total, &buf);
+            if (rc) return rc;
+        }
+        char *c = static_cast<char *>(buf);
+        for (int i = 0; i < n; ++i) {
+            if (!f[i].home) continue;
+            f[i].dev = fc.host ? c : f[i].home;
+            f[i].set(f[i].slot, f[i].dev);
+            if (fc.host) c += round256(f[i].bytes);
+        }
+        return POLS_OK;
+    }
+    int home(pols_ctx *ctx, const pols_batch *b, const pols_out *o, const FitCall &fc) const {
+        if (!fc.host) return POLS_OK;
+        for (int i = 0; i < n; ++i)
+            if (f[i].home && f[i].bytes > 0) POLS_HIP(hipMemcpyAsync(f[i].home, f[i].dev, f[i].bytes, hipMemcpyDeviceToHost, ctx->stream));
+        return unstage_outputs(ctx, b, b->n_groups, fc.kt, o, fc.st);
+    }
+};
+
+// K10's launches over a column list of the caller's: the frame, the columns x[0 .. k_user) and kt coefficients per group.
+RidgeCvArgs k10_frame(const pols_batch *b, const FitCall &fc, const SegTables *sg, const void *const *x, int k_user, int kt) {
+    RidgeCvArgs a = {};
+    a.y = fc.st.y; a.w = fc.st.w;
+    for (int j = 0; j < k_user; ++j) a.x[j] = x[j];
+    a.offs = fc.d_offs; a.n_groups = b->n_groups; a.n_rows = b->n_rows;
+    if (sg) fit_segments(a, *sg);
+    a.valid = fc.st.valid; a.null_policy = fc.pol; a.k_user = k_user; a.kt = kt;
+    return a;
+}
+
+// K10's prediction pass from f64 coefficients (kt per group): pred / resid of the pols_out.  sg: the segment tables, or nullptr.
+int fit_predict(pols_ctx *ctx, const pols_batch *b, const FitCall &fc, const SegTables *sg, const void *const *x, int k_user, int kt,
+                double *coef64) {
+    RidgeCvArgs pa = k10_frame(b, fc, sg, x, k_user, kt);
+    pa.coef64 = coef64; pa.pred = fc.st.pred; pa.resid = fc.st.resid;
+    return k10_predict_launch(ctx, b->dtype, pa);
+}
+
+// n further columns of n_rows batch-dtype values (the GLM offset, the instruments): a HOST batch's are copied into `w`, a DEVICE
+// batch's are taken where they are.
+int stage_extra_columns(pols_ctx *ctx, const pols_batch *b, Work w, const void *const *src, int n, const void **dst) {
+    const size_t bytes = dtype_size(b->dtype) * (size_t)b->n_rows, colb = round256(bytes);
+    const bool copy = b->mem == POLS_MEM_HOST && bytes > 0 && n > 0;
+    void *buf = nullptr;
+    if (copy) {
+        int rc = ensure_scratch(ctx, w, colb * (size_t)n, &buf);
+        if (rc) return rc;
+    }
+    for (int j = 0; j < n; ++j) {
+        dst[j] = copy ? static_cast<char *>(buf) + colb * (size_t)j : src[j];
+        if (copy) POLS_HIP(hipMemcpyAsync(const_cast<void *>(dst[j]), src[j], bytes, hipMemcpyHostToDevice, ctx->stream));
+        else if (b->mem == POLS_MEM_DEVICE && !aligned16(src[j])) return fail(POLS_ERR_INVALID, "device columns must be 16-byte aligned");
+    }
+    return POLS_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+void pols_ridge_cv_params_default(pols_ridge_cv_params *q) {
+    if (!q) return;
+    q->alphas = nullptr;
+    q->n_alphas = 0;
+}
+
+// K10 (k10_ridge_path.hip): Gram pass, eigendecomposition, row pass over the candidates, pick, prediction pass with the winner's
+// coefficients.  Null policies are fused into the tile staging and into the prediction pass, as in ls_core's streamed path.
+int pols_ridge_cv(pols_ctx *ctx, const pols_batch *b, const pols_ols_params *p, const pols_ridge_cv_params *q, pols_out *o,
+                  const pols_ridge_cv_out *ro) {
+    FitCall fc;
+    int rc = fit_check(ctx, b, p, q, o, "ridge_cv", K10_KMAX, &fc);
+    if (rc) return rc;
+    if (!q->alphas || q->n_alphas < 1) return fail(POLS_ERR_INVALID, "ridge_cv: the grid of candidates is empty");
+    if (q->n_alphas > K10_MAX_ALPHAS) return fail(POLS_ERR_UNSUPPORTED, "ridge_cv: %d candidates > %d", q->n_alphas, K10_MAX_ALPHAS);
+    for (int j = 0; j < q->n_alphas; ++j)
+        if (!(q->alphas[j] >= 0.0) || !std::isfinite(q->alphas[j])) return fail(POLS_ERR_INVALID, "ridge_cv: candidate %d is negative or not finite", j);
+    if (p->positive || (p->has_l1_ratio && p->l1_ratio > 0.0))
+        return fail(POLS_ERR_INVALID, "ridge_cv: positive / l1_ratio fits have no hat matrix");
+    if (b->n_groups == 0) return POLS_OK;
+    ro = or_none(ro);
+    if ((rc = fit_stage(ctx, b, o, &fc))) return rc;
+    const int kt = fc.kt, na = q->n_alphas;
+    const size_t G = fc.G;
+    SegTables sg;
+    if ((rc = ensure_segments(ctx, b, fc.max_rows, 0, &sg))) return rc;
+    const size_t items = sg.n_seg > 0 ? (size_t)sg.n_seg : G;
+    const size_t gramb = round256(sizeof(double) * items * k10_gram_stride(kt)), eigb = round256(sizeof(double) * G * k10_eig_stride(kt));
+    const size_t alb = round256(sizeof(double) * (size_t)na), partb = round256(sizeof(double) * items * (size_t)na);
+    void *wg = nullptr, *ws = nullptr;
+    if ((rc = ensure_scratch(ctx, Work::RidgeCvGram, gramb + eigb, &wg))) return rc;
+    if ((rc = ensure_scratch(ctx, Work::RidgeCvScores, alb + partb + round256(sizeof(double) * G * kt), &ws))) return rc;
+    if ((rc = upload_small(ctx, ws, q->alphas, sizeof(double) * (size_t)na))) return rc;
+    RidgeCvArgs a = {};
+    fit_frame(a, b, fc);
+    fit_segments(a, sg);
+    a.alphas = static_cast<const double *>(ws); a.n_alphas = na;
+    a.gram_part = static_cast<double *>(wg);
+    a.eig = reinterpret_cast<double *>(static_cast<char *>(wg) + gramb);
+    a.score_part = reinterpret_cast<double *>(static_cast<char *>(ws) + alb);
+    a.coef64 = reinterpret_cast<double *>(static_cast<char *>(ws) + alb + partb);
+    ExtraOut xo;
+    xo.add(ro->alpha, a.alpha, sizeof(double) * G);
+    xo.add(ro->score, a.score, sizeof(double) * G);
+    xo.add(ro->alpha_index, a.alpha_index, sizeof(int32_t) * G);
+    xo.add(ro->cv_scores, a.cv_scores, sizeof(double) * G * (size_t)na);
+    xo.add(ro->coef_path, a.coef_path, fc.sz * G * (size_t)na * kt);
+    if ((rc = xo.place(ctx, fc, Work::RidgeCvOut))) return rc;
+    ctx->last_kernel = sg.n_seg > 0 ? "k10_ridge_path_split" : "k10_ridge_path";
+    if ((rc = k10_gram_launch(ctx, b->dtype, a))) return rc;
+    if ((rc = k10_eig_launch(ctx, a))) return rc;
+    if ((rc = k10_rows_launch(ctx, b->dtype, a))) return rc;
+    if ((rc = k10_pick_launch(ctx, a))) return rc;
+    a.pred = fc.st.pred; a.resid = fc.st.resid;
+    if ((rc = k10_predict_launch(ctx, b->dtype, a))) return rc;
+    return xo.home(ctx, b, o, fc);
+}
+
+void pols_rlm_params_default(pols_rlm_params *q) {
+    if (!q) return;
+    q->norm = POLS_RLM_HUBER;
+    q->c = 0.0;
+    q->max_iter = 50;
+    q->tol = 1e-8;
+}
+
+// K11 (k11_rlm.hip): the whole iteration of a group in one workgroup -- one launch for the groups that stay resident in LDS, one for
+// those that are streamed -- then K10's prediction pass with the f64 coefficients.
+int pols_rlm(pols_ctx *ctx, const pols_batch *b, const pols_ols_params *p, const pols_rlm_params *q, pols_out *o, const pols_rlm_out *ro) {
+    FitCall fc;
+    int rc = fit_check(ctx, b, p, q, o, "rlm", K11_KMAX, &fc);
+    if (rc) return rc;
+    if (p->alpha != 0.0 || p->positive || (p->has_l1_ratio && p->l1_ratio > 0.0))
+        return fail(POLS_ERR_INVALID, "rlm: alpha / positive / l1_ratio do not apply to the M-estimator");
+    if (q->norm != POLS_RLM_HUBER && q->norm != POLS_RLM_BISQUARE) return fail(POLS_ERR_INVALID, "rlm: unknown norm %d", q->norm);
+    if (!std::isfinite(q->c)) return fail(POLS_ERR_INVALID, "rlm: c is not finite");
+    if (q->max_iter < 1) return fail(POLS_ERR_INVALID, "rlm: max_iter %d < 1", q->max_iter);
+    if (!(q->tol > 0.0) || !std::isfinite(q->tol)) return fail(POLS_ERR_INVALID, "rlm: tol %g is not positive and finite", q->tol);
+    if (b->n_groups == 0) return POLS_OK;
+    ro = or_none(ro);
+    const int kt = fc.kt;
+    const size_t G = fc.G;
+    // which form serves which group: the tiles a group spans from the 16-byte grid point at or below its first row
+    const int vec = b->dtype == POLS_F32 ? 4 : 2;
+    const int cap = ctx->opt.rlm_engine == 1 ? -1 : k11_resident_tiles(kt);
+    int64_t n_res = 0, n_str = 0, res_tiles = 0, str_rows = 0;
+    for (int64_t g = 0; g < b->n_groups; ++g) {
+        const int64_t s = b->group_offsets[g], e = b->group_offsets[g + 1];
+        if (e < s) return fail(POLS_ERR_INVALID, "group_offsets must not decrease");
+        const int64_t tiles = e > s ? (e - (s & ~(int64_t)(vec - 1)) + 255) / 256 : 0;
+        if (tiles <= cap) { ++n_res; res_tiles = std::max(res_tiles, tiles); }
+        else { ++n_str; str_rows = std::max(str_rows, e - s); }
+    }
+    if (str_rows > K11_STREAM_MAX_ROWS)
+        return fail(POLS_ERR_UNSUPPORTED, "rlm: a group of %lld rows > %lld (one workgroup walks a streamed group; the split form is not built)",
+                    (long long)str_rows, (long long)K11_STREAM_MAX_ROWS);
+    if ((rc = fit_stage(ctx, b, o, &fc))) return rc;
+    void *wc = nullptr, *wr = nullptr;
+    if ((rc = ensure_scratch(ctx, Work::RlmCoef, round256(sizeof(double) * G * kt), &wc))) return rc;
+    if (n_str > 0 && (rc = ensure_scratch(ctx, Work::RlmRows, round256(sizeof(double) * (size_t)b->n_rows), &wr))) return rc;
+    RlmArgs a = {};
+    fit_frame(a, b, fc);
+    a.norm = q->norm; a.max_iter = q->max_iter; a.tol = q->tol;
+    a.c = q->c > 0.0 ? q->c : (q->norm == POLS_RLM_HUBER ? 1.345 : 4.685);
+    a.res_tiles = cap; a.ts = (int32_t)res_tiles * 256 + 1;
+    a.rows = static_cast<double *>(wr);
+    a.coef64 = static_cast<double *>(wc);
+    ExtraOut xo;
+    xo.add(ro->scale, a.scale, sizeof(double) * G);
+    xo.add(ro->n_iter, a.n_iter, sizeof(int32_t) * G);
+    xo.add(ro->weights, a.weights, fc.sz * (size_t)b->n_rows);
+    if ((rc = xo.place(ctx, fc, Work::RlmOut))) return rc;
+    ctx->last_kernel = n_res >= n_str ? "k11_rlm_resident" : "k11_rlm_stream";
+    if (n_res > 0 && (rc = k11_rlm_launch(ctx, b->dtype, a, true))) return rc;
+    if (n_str > 0 && (rc = k11_rlm_launch(ctx, b->dtype, a, false))) return rc;
+    if ((rc = fit_predict(ctx, b, fc, nullptr, a.x, a.k_user, kt, a.coef64))) return rc;
+    return xo.home(ctx, b, o, fc);
+}
+
+long long pols_glm_resident_lds(int kt, int cols, int elem, int tiles) { return (long long)k13_resident_lds(kt, cols, (size_t)elem, tiles); }
+int pols_glm_resident_tiles(int kt, int cols, int elem, int per_cu) { return k13_resident_tiles(kt, cols, (size_t)elem, per_cu); }
+
+void pols_glm_params_default(pols_glm_params *q) {
+    if (!q) return;
+    q->family = POLS_GLM_BINOMIAL;
+    q->max_iter = 25;
+    q->tol = 1e-8;
+    q->offset = nullptr;
+}
+
+// K13 (k13_glm.hip): the groups that stay resident in LDS iterate in one launch; the others are cut into segments and iterate with a
+// segment pass and a per-group pass per update, until the device counter of iterating groups reads zero; then K13's prediction pass
+// with the f64 coefficients.
+int pols_glm(pols_ctx *ctx, const pols_batch *b, const pols_ols_params *p, const pols_glm_params *q, pols_out *o, const pols_glm_out *ro) {
+    FitCall fc;
+    int rc = fit_check(ctx, b, p, q, o, "glm", K13_KMAX, &fc);
+    if (rc) return rc;
+    if (p->alpha != 0.0 || p->positive || (p->has_l1_ratio && p->l1_ratio > 0.0))
+        return fail(POLS_ERR_INVALID, "glm: alpha / positive / l1_ratio do not apply (penalised GLMs are not built)");
+    if (q->family != POLS_GLM_BINOMIAL && q->family != POLS_GLM_POISSON) return fail(POLS_ERR_INVALID, "glm: unknown family %d", q->family);
+    if (q->max_iter < 1) return fail(POLS_ERR_INVALID, "glm: max_iter %d < 1", q->max_iter);
+    if (!(q->tol > 0.0) || !std::isfinite(q->tol)) return fail(POLS_ERR_INVALID, "glm: tol %g is not positive and finite", q->tol);
+    if (b->n_groups == 0) return POLS_OK;
+    ro = or_none(ro);
+    const int kt = fc.kt;
+    const size_t G = fc.G, sz = fc.sz;
+    // which form serves which group: the tiles a group spans from the 16-byte grid point at or below its first row
+    const int vec = b->dtype == POLS_F32 ? 4 : 2;
+    const int cols = b->n_features + 1 + (b->weights ? 1 : 0) + (q->offset ? 1 : 0);
+    // (two resident launches: the groups whose LDS request leaves room for a second workgroup on a CU, and the longer ones -- one long
+    //  group must not size the request of a whole frame of short ones)
+    const int cap = ctx->opt.glm_engine == 1 ? -1 : k13_resident_tiles(kt, cols, sz, 1);
+    const int cap2 = std::min(cap, k13_resident_tiles(kt, cols, sz, 2));
+    int64_t n_res = 0, n_spl = 0, res_tiles = 0, res2_tiles = 0, n_res1 = 0;
+    for (int64_t g = 0; g < b->n_groups; ++g) {
+        const int64_t s = b->group_offsets[g], e = b->group_offsets[g + 1];
+        if (e < s) return fail(POLS_ERR_INVALID, "group_offsets must not decrease");
+        const int64_t tiles = e > s ? (e - (s & ~(int64_t)(vec - 1)) + 255) / 256 : 0;
+        if (tiles <= cap2) { ++n_res; res2_tiles = std::max(res2_tiles, tiles); }
+        else if (tiles <= cap) { ++n_res; ++n_res1; res_tiles = std::max(res_tiles, tiles); }
+        else ++n_spl;
+    }
+    if ((rc = fit_stage(ctx, b, o, &fc))) return rc;
+    const void *d_off = nullptr;
+    if ((rc = stage_extra_columns(ctx, b, Work::GlmOffset, &q->offset, q->offset ? 1 : 0, &d_off))) return rc;
+    if (!fc.host && !aligned16(ro->linpred)) return fail(POLS_ERR_INVALID, "device columns must be 16-byte aligned");
+    SegTables sg;
+    if (n_spl > 0 && (rc = ensure_segments(ctx, b, fc.max_rows, sizeof(double) * k13_part_stride(kt), &sg))) return rc;
+    void *wc = nullptr, *ws = nullptr;
+    if ((rc = ensure_scratch(ctx, Work::GlmCoef, round256(sizeof(double) * G * kt), &wc))) return rc;
+    const size_t stateb = round256(sizeof(double) * G * k13_state_stride(kt)), partb = sg.n_seg > 0 ? 0 : round256(sizeof(double) * G * k13_part_stride(kt));
+    if (n_spl > 0 && (rc = ensure_scratch(ctx, Work::GlmState, 256 + stateb + partb, &ws))) return rc;
+    GlmArgs a = {};
+    fit_frame(a, b, fc);
+    fit_segments(a, sg);
+    a.o = d_off;
+    a.family = q->family; a.max_iter = q->max_iter; a.tol = q->tol;
+    a.res_tiles = cap;
+    if (n_spl > 0) {
+        char *c = static_cast<char *>(ws);
+        a.active = reinterpret_cast<int32_t *>(c);
+        a.state = reinterpret_cast<double *>(c + 256);
+        a.part = sg.n_seg > 0 ? reinterpret_cast<double *>(sg.extra) : reinterpret_cast<double *>(c + 256 + stateb);
+    }
+    a.coef64 = static_cast<double *>(wc);
+    ExtraOut xo;
+    xo.add(ro->deviance, a.deviance, sizeof(double) * G);
+    xo.add(ro->se, a.se, sizeof(double) * G * kt);
+    xo.add(ro->n_iter, a.n_iter, sizeof(int32_t) * G);
+    xo.add(ro->linpred, a.linpred, sz * (size_t)b->n_rows);
+    if ((rc = xo.place(ctx, fc, Work::GlmOut))) return rc;
+    ctx->last_kernel = n_res >= n_spl ? "k13_glm_resident" : "k13_glm_split";
+    if (n_res > n_res1) {
+        a.res_from = -1; a.res_to = cap2; a.ts = (int32_t)res2_tiles * 256 + 1;
+        if ((rc = k13_resident_launch(ctx, b->dtype, a))) return rc;
+    }
+    if (n_res1 > 0) {
+        a.res_from = cap2; a.res_to = cap; a.ts = (int32_t)res_tiles * 256 + 1;
+        if ((rc = k13_resident_launch(ctx, b->dtype, a))) return rc;
+    }
+    if (n_spl > 0) {
+        const int32_t n_active = (int32_t)std::min<int64_t>(n_spl, 0x7fffffff);
+        if ((rc = upload_small(ctx, a.active, &n_active, sizeof(n_active)))) return rc;
+        // one update per turn: at most max_iter updates and the start, then every group has stopped
+        for (int turn = 0; turn <= q->max_iter; ++turn) {
+            if ((rc = k13_split_launch(ctx, b->dtype, a, turn == 0))) return rc;
+            int32_t left = 0;
+            POLS_HIP(hipMemcpyAsync(&left, a.active, sizeof(left), hipMemcpyDeviceToHost, ctx->stream));
+            POLS_HIP(hipStreamSynchronize(ctx->stream));           // the host decides whether another update is launched
+            if (left <= 0) break;
+        }
+    }
+    a.pred = fc.st.pred; a.resid = fc.st.resid;
+    if ((rc = k13_predict_launch(ctx, b->dtype, a))) return rc;
+    return xo.home(ctx, b, o, fc);
+}
+
+void pols_iv_params_default(pols_iv_params *q) {
+    if (!q) return;
+    q->n_endog = 0;
+    q->z_cols = nullptr;
+    q->n_instruments = 0;
+    q->cov_type = POLS_COV_NONROBUST;
+    q->small_sample = 1;
+}
+
+// K14 (k14_iv.hip): K10's Gram launch over the concatenated columns [X1 | X2 | Z2], the per-group solve, the row pass for RSS and the
+// robust meat (only when a wanted output needs it), the per-group finish, then K10's prediction pass with the f64 coefficients.
+int pols_iv2sls(pols_ctx *ctx, const pols_batch *b, const pols_ols_params *p, const pols_iv_params *q, pols_out *o, const pols_iv_out *ro) {
+    FitCall fc;
+    int rc = fit_check(ctx, b, p, q, o, "iv", K14_TMAX, &fc);
+    if (rc) return rc;
+    if (p->alpha != 0.0 || p->positive || (p->has_l1_ratio && p->l1_ratio > 0.0))
+        return fail(POLS_ERR_INVALID, "iv2sls: alpha / positive / l1_ratio do not apply");
+    if (q->n_endog < 1 || q->n_endog > b->n_features) return fail(POLS_ERR_INVALID, "iv2sls: n_endog %d outside 1..%d", q->n_endog, b->n_features);
+    if (q->n_instruments < q->n_endog) return fail(POLS_ERR_INVALID, "iv2sls: %d instruments < %d endogenous regressors", q->n_instruments, q->n_endog);
+    if (!q->z_cols) return fail(POLS_ERR_INVALID, "iv2sls: z_cols is NULL");
+    for (int j = 0; j < q->n_instruments; ++j)
+        if (!q->z_cols[j] && b->n_rows) return fail(POLS_ERR_INVALID, "iv2sls: z_cols[%d] is NULL", j);
+    if (q->cov_type != POLS_COV_NONROBUST && q->cov_type != POLS_COV_HC0 && q->cov_type != POLS_COV_HC1)
+        return fail(POLS_ERR_INVALID, "iv2sls: cov_type %d is not NONROBUST / HC0 / HC1", q->cov_type);
+    // the frame's columns are the regressors (fc.kt = kx: what is staged and what coef holds); the cap counts the instruments too
+    const int nf = b->n_features, m = q->n_instruments, icpt = b->add_intercept ? 1 : 0, kx = fc.kt, T = kx + m, L = kx - q->n_endog + m;
+    if (T > K14_TMAX) return fail(POLS_ERR_UNSUPPORTED, "iv2sls: %d regressors (incl. intercept) + %d instruments > %d", kx, m, K14_TMAX);
+    if (b->n_groups == 0) return POLS_OK;
+    ro = or_none(ro);
+    const int pol = fc.pol;
+    const bool robust = q->cov_type != POLS_COV_NONROBUST;
+    const bool need_rows = ro->se || ro->t_values || ro->p_values || ro->cov || ro->sigma2 || ro->sargan || ro->sargan_p;
+    const size_t G = fc.G;
+    if ((rc = fit_stage(ctx, b, o, &fc))) return rc;
+    IvArgs a = {};
+    fit_frame(a, b, fc);
+    if ((rc = stage_extra_columns(ctx, b, Work::IvInputs, q->z_cols, m, a.x + nf))) return rc;
+    SegTables sg;
+    if ((rc = ensure_segments(ctx, b, fc.max_rows, 0, &sg))) return rc;
+    fit_segments(a, sg);
+    const size_t items = sg.n_seg > 0 ? (size_t)sg.n_seg : G;
+    const bool pred_all = pol == POLS_NULL_DROP && (fc.st.pred || fc.st.resid);   // the one policy whose prediction pass masks rows
+    const size_t gramb = round256(sizeof(double) * items * k10_gram_stride(T)), rowsb = round256(sizeof(double) * items * k14_rows_stride(kx, robust));
+    const size_t stateb = round256(sizeof(double) * G * k14_state_stride(kx, L)), coefb = round256(sizeof(double) * G * (size_t)(pred_all ? T : kx));
+    void *wm = nullptr, *ws = nullptr;
+    if ((rc = ensure_scratch(ctx, Work::IvMoments, gramb + rowsb, &wm))) return rc;
+    if ((rc = ensure_scratch(ctx, Work::IvState, stateb + coefb, &ws))) return rc;
+    a.k_user = nf + m; a.kt = T;                               // of the staged list [X1 | X2 | Z2]
+    a.n_feat = nf; a.n_endog = q->n_endog; a.n_inst = m; a.icpt = icpt;
+    a.cov_type = q->cov_type; a.small_sample = q->small_sample ? 1 : 0; a.pred_all = pred_all ? 1 : 0;
+    a.gram_part = static_cast<double *>(wm);
+    a.rows_part = reinterpret_cast<double *>(static_cast<char *>(wm) + gramb);
+    a.state = static_cast<double *>(ws);
+    a.coefp = reinterpret_cast<double *>(static_cast<char *>(ws) + stateb);
+    ExtraOut xo;
+    xo.add(ro->se, a.se, sizeof(double) * G * kx);
+    xo.add(ro->t_values, a.t_values, sizeof(double) * G * kx);
+    xo.add(ro->p_values, a.p_values, sizeof(double) * G * kx);
+    xo.add(ro->cov, a.cov, sizeof(double) * G * kx * kx);
+    xo.add(ro->sigma2, a.sigma2, sizeof(double) * G);
+    xo.add(ro->sargan, a.sargan, sizeof(double) * G);
+    xo.add(ro->sargan_p, a.sargan_p, sizeof(double) * G);
+    xo.add(ro->first_stage_f, a.first_stage_f, sizeof(double) * G * (size_t)q->n_endog);
+    xo.add(ro->partial_r2, a.partial_r2, sizeof(double) * G * (size_t)q->n_endog);
+    xo.add(ro->n_obs, a.n_obs, sizeof(int64_t) * G);
+    if ((rc = xo.place(ctx, fc, Work::IvOut))) return rc;
+    ctx->last_kernel = sg.n_seg > 0 ? "k14_iv2sls_split" : "k14_iv2sls";
+    RidgeCvArgs ga = k10_frame(b, fc, &sg, a.x, nf + m, T);    // K10's Gram launch over the whole list
+    ga.gram_part = static_cast<double *>(wm);
+    if ((rc = k10_gram_launch(ctx, b->dtype, ga))) return rc;
+    if ((rc = k14_solve_launch(ctx, a))) return rc;
+    if (need_rows) {
+        // the plain RSS needs the regressors and y alone: the instruments are staged only where the robust meat reads them or their nulls drop rows
+        IvArgs ra = a;
+        const bool z_drops = pol == POLS_NULL_DROP || pol == POLS_NULL_DROP_ZERO || pol == POLS_NULL_DROP_WINDOW;
+        if (!robust && !z_drops) { ra.k_user = nf; ra.kt = kx; }
+        if ((rc = k14_rows_launch(ctx, b->dtype, ra))) return rc;
+        if ((rc = k14_finish_launch(ctx, a))) return rc;
+    }
+    // the prediction pass: the regressors alone, or -- "drop" -- the whole list with zero coefficients for the instruments, whose nulls mask rows
+    if ((rc = fit_predict(ctx, b, fc, &sg, a.x, pred_all ? nf + m : nf, pred_all ? T : kx, a.coefp))) return rc;
+    return xo.home(ctx, b, o, fc);
+}
+
+void pols_enet_cv_params_default(pols_enet_cv_params *q) {
+    if (!q) return;
+    q->alphas = nullptr;
+    q->n_alphas = 100;
+    q->eps = 1e-3;
+    q->l1_ratio = 0.5;
+    q->n_folds = 5;
+    q->max_iter = 1000;
+    q->tol = 1e-5;
+    q->positive = 0;
+}
+
+// K12 (k12_enet_cv.hip): fold Gram matrices in one pass over the frame (behind a count pass when the null policy can remove rows),
+// the (n_folds + 1) x n_alphas coordinate-descent fits on chip, pick, then K10's prediction pass with the winner's coefficients.
+int pols_elastic_net_cv(pols_ctx *ctx, const pols_batch *b, const pols_ols_params *p, const pols_enet_cv_params *q, pols_out *o,
+                        const pols_enet_cv_out *ro) {
+    FitCall fc;
+    int rc = fit_check(ctx, b, p, q, o, "elastic_net_cv", K12_KMAX, &fc);
+    if (rc) return rc;
+    const bool automatic = q->alphas == nullptr;
+    if (!(q->l1_ratio >= 0.0 && q->l1_ratio <= 1.0)) return fail(POLS_ERR_INVALID, "elastic_net_cv: l1_ratio %g outside [0, 1]", q->l1_ratio);
+    if (q->n_alphas < 1) return fail(POLS_ERR_INVALID, "elastic_net_cv: the grid of candidates is empty");
+    if (q->n_alphas > K12_MAX_ALPHAS) return fail(POLS_ERR_UNSUPPORTED, "elastic_net_cv: %d candidates > %d", q->n_alphas, K12_MAX_ALPHAS);
+    if (automatic) {
+        if (q->n_alphas < 2) return fail(POLS_ERR_INVALID, "elastic_net_cv: an automatic grid needs at least 2 candidates");
+        if (!(q->eps > 0.0 && q->eps < 1.0)) return fail(POLS_ERR_INVALID, "elastic_net_cv: eps %g outside (0, 1)", q->eps);
+        if (q->l1_ratio == 0.0) return fail(POLS_ERR_INVALID, "elastic_net_cv: an automatic grid needs l1_ratio > 0");
+    } else {
+        for (int j = 0; j < q->n_alphas; ++j)
+            if (!(q->alphas[j] >= 0.0) || !std::isfinite(q->alphas[j])) return fail(POLS_ERR_INVALID, "elastic_net_cv: candidate %d is negative or not finite", j);
+    }
+    if (q->n_folds < 2 || q->n_folds > K12_MAX_FOLDS) return fail(POLS_ERR_INVALID, "elastic_net_cv: %d folds outside 2..%d", q->n_folds, K12_MAX_FOLDS);
+    if (q->max_iter < 1) return fail(POLS_ERR_INVALID, "elastic_net_cv: max_iter %d < 1", q->max_iter);
+    if (!(q->tol > 0.0) || !std::isfinite(q->tol)) return fail(POLS_ERR_INVALID, "elastic_net_cv: tol %g is not positive and finite", q->tol);
+    if (b->n_groups == 0) return POLS_OK;
+    ro = or_none(ro);
+    if ((rc = fit_stage(ctx, b, o, &fc))) return rc;
+    const int kt = fc.kt, na = q->n_alphas, nf = q->n_folds, pol = fc.pol;
+    const size_t G = fc.G;
+    SegTables sg;
+    if ((rc = ensure_segments(ctx, b, fc.max_rows, 0, &sg))) return rc;
+    const bool split = sg.n_seg > 0;
+    const size_t items = split ? (size_t)sg.n_seg : G;
+    const size_t per = (size_t)nf * k10_gram_stride(kt);
+    const size_t cntb = round256(sizeof(int64_t) * items), partb = round256(sizeof(double) * items * per),
+                 foldb = split ? round256(sizeof(double) * G * per) : 0;
+    const size_t alb = round256(sizeof(double) * (size_t)na + sizeof(int32_t) * (size_t)na), scb = round256(sizeof(double) * G * nf * (size_t)na),
+                 itb = round256(sizeof(int32_t) * G * (nf + 1) * (size_t)na), p64b = round256(sizeof(double) * G * (size_t)na * kt),
+                 grb = round256(sizeof(double) * G * (size_t)na), c64b = round256(sizeof(double) * G * kt);
+    void *wg = nullptr, *ws = nullptr;
+    if ((rc = ensure_scratch(ctx, Work::EnetCvGram, cntb + partb + foldb, &wg))) return rc;
+    if ((rc = ensure_scratch(ctx, Work::EnetCvWork, alb + scb + itb + p64b + grb + c64b, &ws))) return rc;
+    {   // the candidates and the order they are visited in: descending alpha, equal values in index order
+        std::vector<char> up(sizeof(double) * (size_t)na + sizeof(int32_t) * (size_t)na);
+        double *ua = reinterpret_cast<double *>(up.data());
+        int32_t *uo = reinterpret_cast<int32_t *>(up.data() + sizeof(double) * (size_t)na);
+        for (int j = 0; j < na; ++j) { ua[j] = automatic ? 0.0 : q->alphas[j]; uo[j] = j; }
+        if (!automatic) std::stable_sort(uo, uo + na, [&](int32_t x, int32_t y) { return ua[x] > ua[y]; });
+        if ((rc = upload_small(ctx, ws, up.data(), up.size()))) return rc;
+    }
+    EnetCvArgs a = {};
+    fit_frame(a, b, fc);
+    fit_segments(a, sg);
+    a.n_folds = nf; a.n_alphas = na; a.automatic = automatic ? 1 : 0;
+    a.counted = (pol == POLS_NULL_DROP || pol == POLS_NULL_DROP_ZERO || pol == POLS_NULL_DROP_WINDOW || pol == POLS_NULL_DROP_Y_ZERO_X) ? 1 : 0;
+    a.max_iter = q->max_iter; a.positive = q->positive ? 1 : 0;
+    a.l1_ratio = q->l1_ratio; a.tol = q->tol; a.eps = q->eps;
+    char *cg = static_cast<char *>(wg), *cs = static_cast<char *>(ws);
+    a.item_count = reinterpret_cast<int64_t *>(cg);
+    a.fold_part = reinterpret_cast<double *>(cg + cntb);
+    a.fold_gram = split ? reinterpret_cast<double *>(cg + cntb + partb) : a.fold_part;
+    a.alphas = reinterpret_cast<const double *>(cs);
+    a.order = reinterpret_cast<const int32_t *>(cs + sizeof(double) * (size_t)na);
+    a.score_part = reinterpret_cast<double *>(cs + alb);
+    a.iters = reinterpret_cast<int32_t *>(cs + alb + scb);
+    a.path64 = reinterpret_cast<double *>(cs + alb + scb + itb);
+    a.grid = reinterpret_cast<double *>(cs + alb + scb + itb + p64b);
+    a.coef64 = reinterpret_cast<double *>(cs + alb + scb + itb + p64b + grb);
+    ExtraOut xo;
+    xo.add(ro->alpha, a.alpha, sizeof(double) * G);
+    xo.add(ro->score, a.score, sizeof(double) * G);
+    xo.add(ro->alpha_index, a.alpha_index, sizeof(int32_t) * G);
+    xo.add(ro->cv_scores, a.cv_scores, sizeof(double) * G * (size_t)na);
+    xo.add(ro->alphas_used, a.alphas_used, sizeof(double) * G * (size_t)na);
+    xo.add(ro->coef_path, a.coef_path, fc.sz * G * (size_t)na * kt);
+    xo.add(ro->n_iter, a.n_iter, sizeof(int32_t) * G * (size_t)na);
+    if ((rc = xo.place(ctx, fc, Work::EnetCvOut))) return rc;
+    ctx->last_kernel = split ? "k12_enet_cv_split" : "k12_enet_cv";
+    if ((rc = k12_count_launch(ctx, b->dtype, a))) return rc;
+    if ((rc = k12_fold_gram_launch(ctx, b->dtype, a))) return rc;
+    if ((rc = k12_reduce_launch(ctx, a))) return rc;
+    if ((rc = k12_path_launch(ctx, a))) return rc;
+    if ((rc = k12_pick_launch(ctx, a))) return rc;
+    if ((rc = fit_predict(ctx, b, fc, &sg, a.x, a.k_user, kt, a.coef64))) return rc;
+    return xo.home(ctx, b, o, fc);
+}
+
+}  // extern "C"

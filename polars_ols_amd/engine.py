@@ -298,6 +298,32 @@ class Engine:
                                                        C.byref(io)))
         return res
 
+    def _fit_entry(self, name, fn, fields, out_cls, q, shapes, want, y, x_cols, offsets, plan_kw, extra=None, keep=()):
+        """What ridge_cv / rlm / glm / iv2sls / elastic_net_cv share: the ``want`` check, the plan of the frame, the entry's own
+        outputs and the call of the C entry named ``fn`` with (ctx, batch, params, q, out, out_cls(...)); returns the results.
+        ``shapes(G, N, kt)`` gives {field: (shape, "f64" | "i32" | "i64" | "batch")} for ``fields``.  ``extra(b, like, dev)`` is
+        called once the frame is known: it brings along what ``q`` is to point at (a grid, further columns), points ``q`` at it
+        and returns it.  ``keep`` and what ``extra`` returns are referenced by this frame until the C entry has returned."""
+        want = tuple(want)
+        base = ("coef", "pred", "resid", "status")
+        unknown = [w for w in want if w not in base + fields]
+        if unknown:
+            raise ValueError(f"unknown {name} fields {unknown}; known: {list(base + fields)}")
+        plan = self.plan_least_squares(y, x_cols, offsets, want=tuple(w for w in want if w in base), **plan_kw)
+        b, res, like = plan._b, plan.results, plan._keep[0][0]
+        dev = b.mem == L.POLS_MEM_DEVICE
+        if extra is not None:
+            keep = (keep, extra(b, like, dev))
+        dts = {"f64": torch.float64, "i32": torch.int32, "i64": torch.int64} if dev else {"f64": np.float64, "i32": np.int32, "i64": np.int64}
+        dts["batch"] = like.dtype
+        table = shapes(b.n_groups, b.n_rows, b.n_features + b.add_intercept)
+        for key in fields:
+            if key in want:
+                res[key] = self._alloc(dev, dts[table[key][1]], table[key][0], like)
+        ro = out_cls(**{k: self._ptr(res.get(k)) for k in fields})
+        L.check(getattr(self._lib, fn)(self._h, C.byref(plan._b), C.byref(plan._p), C.byref(q), C.byref(plan._o), C.byref(ro)))
+        return res
+
     def ridge_cv(self, y, x_cols: Sequence, offsets, alphas, *, want: Sequence[str] = ("coef", "alpha", "alpha_index", "score"),
                  weights=None, valid=None, add_intercept: bool = False, null_policy: str = "ignore", null_free: bool = False) -> Dict:
         """Ridge regularisation path with leave-one-out selection of alpha for every group in one call (pols_ridge_cv; the
@@ -307,32 +333,18 @@ class Engine:
         [n_groups, n_alphas, f64] and ``coef_path`` [n_groups, n_alphas, k, batch dtype].  Arrays are numpy or torch and live
         where the inputs live."""
         grid = _ridge_cv_grid(alphas)
-        want = tuple(want)
-        known = ("coef", "pred", "resid", "status") + L.RIDGE_CV_FIELDS
-        unknown = [w for w in want if w not in known]
-        if unknown:
-            raise ValueError(f"unknown ridge_cv fields {unknown}; known: {list(known)}")
-        plan = self.plan_least_squares(y, x_cols, offsets, weights=weights, valid=valid, add_intercept=add_intercept,
-                                       null_policy=null_policy, null_free=null_free,
-                                       want=tuple(w for w in want if w in ("coef", "pred", "resid", "status")))
-        b = plan._b
-        kt = b.n_features + b.add_intercept
-        dev = b.mem == L.POLS_MEM_DEVICE
-        like = plan._keep[0][0]
-        res = plan.results
-        f64, i32 = (torch.float64, torch.int32) if dev else (np.float64, np.int32)
-        shapes = {"alpha": ((b.n_groups,), f64), "alpha_index": ((b.n_groups,), i32), "score": ((b.n_groups,), f64),
-                  "cv_scores": ((b.n_groups, len(grid)), f64), "coef_path": ((b.n_groups, len(grid), kt), like.dtype)}
-        for key in L.RIDGE_CV_FIELDS:
-            if key in want:
-                res[key] = self._alloc(dev, shapes[key][1], shapes[key][0], like)
-        ro = L.RidgeCvOut(**{k: self._ptr(res.get(k)) for k in L.RIDGE_CV_FIELDS})
-        q = L.RidgeCvParams()
-        self._lib.pols_ridge_cv_params_default(C.byref(q))
-        q.alphas = grid.ctypes.data_as(C.POINTER(C.c_double))
-        q.n_alphas = len(grid)
-        L.check(self._lib.pols_ridge_cv(self._h, C.byref(plan._b), C.byref(plan._p), C.byref(q), C.byref(plan._o), C.byref(ro)))
-        return res
+        q, A = L.RidgeCvParams(), len(grid)
+
+        def bring_grid(b, like, dev):
+            self._lib.pols_ridge_cv_params_default(C.byref(q))
+            q.alphas, q.n_alphas = grid.ctypes.data_as(C.POINTER(C.c_double)), A
+            return grid
+
+        return self._fit_entry("ridge_cv", "pols_ridge_cv", L.RIDGE_CV_FIELDS, L.RidgeCvOut, q,
+                               lambda G, N, kt: {"alpha": ((G,), "f64"), "alpha_index": ((G,), "i32"), "score": ((G,), "f64"),
+                                                 "cv_scores": ((G, A), "f64"), "coef_path": ((G, A, kt), "batch")},
+                               want, y, x_cols, offsets, dict(weights=weights, valid=valid, add_intercept=add_intercept,
+                                                              null_policy=null_policy, null_free=null_free), extra=bring_grid)
 
     def rlm(self, y, x_cols: Sequence, offsets, *, norm: str = "huber", c: Optional[float] = None, max_iter: int = 50, tol: float = 1e-8,
             want: Sequence[str] = ("coef", "status", "scale", "n_iter"), weights=None, valid=None, add_intercept: bool = False,
@@ -343,25 +355,9 @@ class Engine:
         (status 3 = stopped at ``max_iter``), ``scale`` [n_groups, f64], ``n_iter`` [n_groups, int32] and the robust ``weights``
         [n_rows, batch dtype, NaN for the rows outside the fit].  Arrays are numpy or torch and live where the inputs live."""
         q = _rlm_params(self._lib, norm, c, max_iter, tol)
-        want = tuple(want)
-        known = ("coef", "pred", "resid", "status") + L.RLM_FIELDS
-        unknown = [w for w in want if w not in known]
-        if unknown:
-            raise ValueError(f"unknown rlm fields {unknown}; known: {list(known)}")
-        plan = self.plan_least_squares(y, x_cols, offsets, weights=weights, valid=valid, add_intercept=add_intercept,
-                                       null_policy=null_policy, want=tuple(w for w in want if w in ("coef", "pred", "resid", "status")))
-        b = plan._b
-        dev = b.mem == L.POLS_MEM_DEVICE
-        like = plan._keep[0][0]
-        res = plan.results
-        f64, i32 = (torch.float64, torch.int32) if dev else (np.float64, np.int32)
-        shapes = {"scale": ((b.n_groups,), f64), "n_iter": ((b.n_groups,), i32), "weights": ((b.n_rows,), like.dtype)}
-        for key in L.RLM_FIELDS:
-            if key in want:
-                res[key] = self._alloc(dev, shapes[key][1], shapes[key][0], like)
-        ro = L.RlmOut(**{k: self._ptr(res.get(k)) for k in L.RLM_FIELDS})
-        L.check(self._lib.pols_rlm(self._h, C.byref(plan._b), C.byref(plan._p), C.byref(q), C.byref(plan._o), C.byref(ro)))
-        return res
+        return self._fit_entry("rlm", "pols_rlm", L.RLM_FIELDS, L.RlmOut, q,
+                               lambda G, N, kt: {"scale": ((G,), "f64"), "n_iter": ((G,), "i32"), "weights": ((N,), "batch")},
+                               want, y, x_cols, offsets, dict(weights=weights, valid=valid, add_intercept=add_intercept, null_policy=null_policy))
 
     def glm(self, y, x_cols: Sequence, offsets, *, family: str = "binomial", offset=None, max_iter: int = 25, tol: float = 1e-8,
             want: Sequence[str] = ("coef", "status", "deviance", "n_iter"), weights=None, valid=None, add_intercept: bool = False,
@@ -374,33 +370,21 @@ class Engine:
         Arrays are numpy or torch and live where the inputs live.  Groups too long for a workgroup's LDS iterate with launches of
         their own and synchronise the stream once per update."""
         q = _glm_params(self._lib, family, max_iter, tol)
-        want = tuple(want)
-        known = ("coef", "pred", "resid", "status") + L.GLM_FIELDS
-        unknown = [w for w in want if w not in known]
-        if unknown:
-            raise ValueError(f"unknown glm fields {unknown}; known: {list(known)}")
-        plan = self.plan_least_squares(y, x_cols, offsets, weights=weights, valid=valid, add_intercept=add_intercept,
-                                       null_policy=null_policy, want=tuple(w for w in want if w in ("coef", "pred", "resid", "status")))
-        b = plan._b
-        dev = b.mem == L.POLS_MEM_DEVICE
-        like = plan._keep[0][0]
-        res = plan.results
-        off = None
-        if offset is not None:
+
+        def bring_offset(b, like, dev):
+            if offset is None:
+                return None
             off = offset.to(like.dtype).contiguous() if dev else np.ascontiguousarray(offset, dtype=like.dtype)
             if tuple(off.shape) != (b.n_rows,):
                 raise ValueError(f"glm: 'offset' must have one value per row ({b.n_rows}), got shape {tuple(off.shape)}")
             q.offset = self._ptr(off)
-        f64, i32 = (torch.float64, torch.int32) if dev else (np.float64, np.int32)
-        kt = b.n_features + b.add_intercept
-        shapes = {"deviance": ((b.n_groups,), f64), "se": ((b.n_groups, kt), f64), "n_iter": ((b.n_groups,), i32),
-                  "linpred": ((b.n_rows,), like.dtype)}
-        for key in L.GLM_FIELDS:
-            if key in want:
-                res[key] = self._alloc(dev, shapes[key][1], shapes[key][0], like)
-        ro = L.GlmOut(**{k: self._ptr(res.get(k)) for k in L.GLM_FIELDS})
-        L.check(self._lib.pols_glm(self._h, C.byref(plan._b), C.byref(plan._p), C.byref(q), C.byref(plan._o), C.byref(ro)))
-        return res
+            return off
+
+        return self._fit_entry("glm", "pols_glm", L.GLM_FIELDS, L.GlmOut, q,
+                               lambda G, N, kt: {"deviance": ((G,), "f64"), "se": ((G, kt), "f64"), "n_iter": ((G,), "i32"),
+                                                 "linpred": ((N,), "batch")},
+                               want, y, x_cols, offsets, dict(weights=weights, valid=valid, add_intercept=add_intercept, null_policy=null_policy),
+                               extra=bring_offset)
 
     def iv2sls(self, y, x_cols: Sequence, z_cols: Sequence, offsets, *, n_endog: int, cov_type: str = "nonrobust", small_sample: bool = True,
                want: Sequence[str] = ("coef", "status", "se", "first_stage_f", "sargan", "sargan_p"), weights=None, valid=None,
@@ -415,33 +399,24 @@ class Engine:
         ``se t_values p_values cov sigma2 sargan sargan_p`` the columns are read once."""
         x_cols, z_cols = list(x_cols), list(z_cols)
         q = _iv_params(self._lib, len(x_cols), len(z_cols), n_endog, cov_type, small_sample, add_intercept)
-        want = tuple(want)
-        known = ("coef", "pred", "resid", "status") + L.IV_FIELDS
-        unknown = [w for w in want if w not in known]
-        if unknown:
-            raise ValueError(f"unknown iv2sls fields {unknown}; known: {list(known)}")
-        plan = self.plan_least_squares(y, x_cols, offsets, weights=weights, valid=valid, add_intercept=add_intercept,
-                                       null_policy=null_policy, want=tuple(w for w in want if w in ("coef", "pred", "resid", "status")))
-        b = plan._b
-        dev = b.mem == L.POLS_MEM_DEVICE
-        like = plan._keep[0][0]
-        res = plan.results
-        zs = [z.to(like.dtype).contiguous() if dev else np.ascontiguousarray(z, dtype=like.dtype) for z in z_cols]
-        for z in zs:
-            if tuple(z.shape) != (b.n_rows,):
-                raise ValueError("all input series passed must be of equal length")
-        zp = (C.c_void_p * len(zs))(*[self._ptr(z) for z in zs])
-        q.z_cols = C.cast(zp, C.POINTER(C.c_void_p))
-        f64, i64 = (torch.float64, torch.int64) if dev else (np.float64, np.int64)
-        G, kt = b.n_groups, b.n_features + b.add_intercept
-        shapes = {"se": (G, kt), "t_values": (G, kt), "p_values": (G, kt), "cov": (G, kt, kt), "sigma2": (G,),
-                  "first_stage_f": (G, q.n_endog), "partial_r2": (G, q.n_endog), "sargan": (G,), "sargan_p": (G,), "n_obs": (G,)}
-        for key in L.IV_FIELDS:
-            if key in want:
-                res[key] = self._alloc(dev, i64 if key == "n_obs" else f64, shapes[key], like)
-        ro = L.IvOut(**{k: self._ptr(res.get(k)) for k in L.IV_FIELDS})
-        L.check(self._lib.pols_iv2sls(self._h, C.byref(plan._b), C.byref(plan._p), C.byref(q), C.byref(plan._o), C.byref(ro)))
-        return res
+
+        def bring_instruments(b, like, dev):
+            zs = [z.to(like.dtype).contiguous() if dev else np.ascontiguousarray(z, dtype=like.dtype) for z in z_cols]
+            for z in zs:
+                if tuple(z.shape) != (b.n_rows,):
+                    raise ValueError("all input series passed must be of equal length")
+            zp = (C.c_void_p * len(zs))(*[self._ptr(z) for z in zs])
+            q.z_cols = C.cast(zp, C.POINTER(C.c_void_p))
+            return zs, zp
+
+        E = q.n_endog
+        return self._fit_entry("iv2sls", "pols_iv2sls", L.IV_FIELDS, L.IvOut, q,
+                               lambda G, N, kt: {"se": ((G, kt), "f64"), "t_values": ((G, kt), "f64"), "p_values": ((G, kt), "f64"),
+                                                 "cov": ((G, kt, kt), "f64"), "sigma2": ((G,), "f64"), "first_stage_f": ((G, E), "f64"),
+                                                 "partial_r2": ((G, E), "f64"), "sargan": ((G,), "f64"), "sargan_p": ((G,), "f64"),
+                                                 "n_obs": ((G,), "i64")},
+                               want, y, x_cols, offsets, dict(weights=weights, valid=valid, add_intercept=add_intercept, null_policy=null_policy),
+                               extra=bring_instruments)
 
     def elastic_net_cv(self, y, x_cols: Sequence, offsets, alphas=None, *, n_alphas: int = 100, eps: float = 1e-3, l1_ratio: float = 0.5,
                        n_folds: int = 5, max_iter: int = 1000, tol: float = 1e-5, positive: bool = False,
@@ -455,29 +430,13 @@ class Engine:
         is no choice], ``cv_scores alphas_used`` [n_groups, n_alphas, f64], ``n_iter`` [n_groups, n_alphas, int32] and ``coef_path``
         [n_groups, n_alphas, k, batch dtype].  Arrays are numpy or torch and live where the inputs live."""
         q, grid = _enet_cv_params(self._lib, alphas, n_alphas, eps, l1_ratio, n_folds, max_iter, tol, positive)
-        want = tuple(want)
-        known = ("coef", "pred", "resid", "status") + L.ENET_CV_FIELDS
-        unknown = [w for w in want if w not in known]
-        if unknown:
-            raise ValueError(f"unknown elastic_net_cv fields {unknown}; known: {list(known)}")
-        plan = self.plan_least_squares(y, x_cols, offsets, weights=weights, valid=valid, add_intercept=add_intercept,
-                                       null_policy=null_policy, want=tuple(w for w in want if w in ("coef", "pred", "resid", "status")))
-        b = plan._b
-        kt = b.n_features + b.add_intercept
-        dev = b.mem == L.POLS_MEM_DEVICE
-        like = plan._keep[0][0]
-        res = plan.results
-        f64, i32 = (torch.float64, torch.int32) if dev else (np.float64, np.int32)
-        G, A = b.n_groups, q.n_alphas
-        shapes = {"alpha": ((G,), f64), "alpha_index": ((G,), i32), "score": ((G,), f64), "cv_scores": ((G, A), f64),
-                  "alphas_used": ((G, A), f64), "coef_path": ((G, A, kt), like.dtype), "n_iter": ((G, A), i32)}
-        for key in L.ENET_CV_FIELDS:
-            if key in want:
-                res[key] = self._alloc(dev, shapes[key][1], shapes[key][0], like)
-        ro = L.EnetCvOut(**{k: self._ptr(res.get(k)) for k in L.ENET_CV_FIELDS})
-        L.check(self._lib.pols_elastic_net_cv(self._h, C.byref(plan._b), C.byref(plan._p), C.byref(q), C.byref(plan._o), C.byref(ro)))
-        del grid                                                   # (kept alive until the call has read it)
-        return res
+        A = q.n_alphas
+        return self._fit_entry("elastic_net_cv", "pols_elastic_net_cv", L.ENET_CV_FIELDS, L.EnetCvOut, q,
+                               lambda G, N, kt: {"alpha": ((G,), "f64"), "alpha_index": ((G,), "i32"), "score": ((G,), "f64"),
+                                                 "cv_scores": ((G, A), "f64"), "alphas_used": ((G, A), "f64"),
+                                                 "coef_path": ((G, A, kt), "batch"), "n_iter": ((G, A), "i32")},
+                               want, y, x_cols, offsets, dict(weights=weights, valid=valid, add_intercept=add_intercept, null_policy=null_policy),
+                               keep=grid)
 
     def least_squares(self, y, x_cols: Sequence, offsets, **kwargs) -> Dict:
         """All groups of a (group-sorted) frame in one launch.  ``want`` subset of {"coef","pred","resid","status"};

@@ -291,6 +291,20 @@ def test_any_subset_of_outputs_gives_the_same_values(eng):
     assert set(default) == {"coef", "status", "alpha", "alpha_index", "score"} and default["alpha"].shape == (9,)
 
 
+@pytest.mark.parametrize("device", [True, False])
+def test_each_output_alone_equals_the_same_output_with_all(eng, device):
+    """every field of pols_enet_cv_out alone, then a per-row output with a per-group one, on one Engine: where a HOST batch's fields
+    are staged depends on which are wanted"""
+    y, cols, offs, w = gen(9, 50, 300, 5, np.float32, seed=12)
+    kw = dict(n_alphas=7, add_intercept=True)
+    full = _run(eng, y, cols, offs, None, w, device, **kw)
+    for want in (("alpha",), ("alpha_index",), ("score",), ("cv_scores",), ("alphas_used",), ("coef_path",), ("n_iter",), ("pred", "alpha")):
+        part = _run(eng, y, cols, offs, None, w, device, want=want, **kw)
+        assert set(part) == set(want)
+        for key in want:
+            assert part[key].tobytes() == full[key].tobytes(), key
+
+
 def test_error_codes_through_the_c_abi(eng):
     from polars_ols_amd import _lib as L
     from polars_ols_amd._lib import PolsError

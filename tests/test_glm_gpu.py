@@ -261,12 +261,13 @@ def test_edge_groups_in_one_frame(eng, engine, family, dtype, rtol, device):
     _compare(got2, ref2, y, cols, offs, off, family, rtol)
 
 
-def test_each_output_alone_equals_the_same_output_with_all(eng):
+@pytest.mark.parametrize("device", [True, False])
+def test_each_output_alone_equals_the_same_output_with_all(eng, device):
     y, cols, offs, w, off, _ = _panel(200, 24, 60, 3, 5, np.float32, "binomial", True)
-    full = _run(eng, y, cols, offs, w, off, device=True)
+    full = _run(eng, y, cols, offs, w, off, device=device)
     assert set(full) == set(ALL)
     for key in ("pred", "se", "linpred"):
-        part = _run(eng, y, cols, offs, w, off, device=True, want=(key,))
+        part = _run(eng, y, cols, offs, w, off, device=device, want=(key,))
         assert set(part) == {key}
         assert part[key].tobytes() == full[key].tobytes(), key
     default = eng.glm(y, cols, offs, add_intercept=True)

@@ -245,12 +245,13 @@ def test_instruments_equal_to_the_endogenous_columns_match_least_squares(eng, dt
         np.testing.assert_allclose(got["partial_r2"], 1.0, rtol=1e-9)   # the instruments explain the endogenous columns exactly
 
 
-def test_each_output_alone_equals_the_same_output_with_all(eng):
+@pytest.mark.parametrize("device", [True, False])
+def test_each_output_alone_equals_the_same_output_with_all(eng, device):
     y, cols, zs, offs, w = _frame("short", np.float32)
-    full = _run(eng, y, cols, zs, offs, 1, w, device=True, cov_type="HC0")
+    full = _run(eng, y, cols, zs, offs, 1, w, device=device, cov_type="HC0")
     assert set(full) == set(ALL)
     for want in (("coef", "first_stage_f"), ("pred",), ("se",), ("sargan_p",), ("cov", "n_obs"), ("partial_r2", "status", "resid")):
-        part = _run(eng, y, cols, zs, offs, 1, w, device=True, want=want, cov_type="HC0")
+        part = _run(eng, y, cols, zs, offs, 1, w, device=device, want=want, cov_type="HC0")
         assert set(part) == set(want)
         for key in want:
             assert part[key].tobytes() == full[key].tobytes(), key

@@ -319,6 +319,19 @@ def test_any_subset_of_outputs_gives_the_same_values(eng):
     assert set(default) == {"coef", "alpha", "alpha_index", "score"}
 
 
+@pytest.mark.parametrize("device", [True, False])
+def test_each_output_alone_equals_the_same_output_with_all(eng, device):
+    """every field of pols_ridge_cv_out alone, then a per-row output with a per-group one, on one Engine: where a HOST batch's fields
+    are staged depends on which are wanted"""
+    y, cols, offs, w = _ragged(12, np.float32, G=9)
+    full = _run(eng, y, cols, offs, ALPHAS[:8], w, device=device, add_intercept=True)
+    for want in (("alpha",), ("alpha_index",), ("score",), ("cv_scores",), ("coef_path",), ("resid", "score")):
+        part = _run(eng, y, cols, offs, ALPHAS[:8], w, device=device, want=want, add_intercept=True)
+        assert set(part) == set(want)
+        for key in want:
+            assert part[key].tobytes() == full[key].tobytes(), key
+
+
 def test_error_codes_through_the_c_abi(eng):
     from polars_ols_amd import _lib as L
     from polars_ols_amd._lib import PolsError

@@ -198,11 +198,12 @@ def test_two_runs_and_host_and_device_are_bit_identical(eng, engine, norm):
         assert a[key].tobytes() == h[key].tobytes(), key
 
 
-def test_each_output_alone_equals_the_same_output_with_all(eng):
+@pytest.mark.parametrize("device", [True, False])
+def test_each_output_alone_equals_the_same_output_with_all(eng, device):
     y, cols, offs, w, _, _ = _panel(200, 12, 40, 3, 5, np.float32, "huber", True)
-    full = _run(eng, y, cols, offs, w, device=True)
+    full = _run(eng, y, cols, offs, w, device=device)
     for key in ALL:
-        part = _run(eng, y, cols, offs, w, device=True, want=(key,))
+        part = _run(eng, y, cols, offs, w, device=device, want=(key,))
         assert set(part) == {key}
         assert part[key].tobytes() == full[key].tobytes(), key
     default = eng.rlm(y, cols, offs, add_intercept=True)
