@@ -13,9 +13,8 @@
 // Everything is f64 on the inputs' values, for f32 batches too.  No atomics, every sum in a fixed order: two runs are bit-identical.
 //
 // Launches (one workgroup per segment of a long group -- ensure_segments -- or per group, unless said otherwise):
-//   gram   256-row tiles of the columns go to LDS as f64: 16-byte loads on the columns' 16-byte grid (column q of the tile is one wave's
-//          work, every load of a lane issued before the first use), then one thread per row applies the null policy and sqrt(w).
-//          The (kt + 1)(kt + 2) / 2 entries of [X~ | y~]'[X~ | y~] are spread over the threads: with few entries several row
+//   gram   256-row tiles of the columns go to LDS as f64 with the null policy and sqrt(w) applied (fit_stage, fit_tile.inl).  The
+//          (kt + 1)(kt + 2) / 2 entries of [X~ | y~]'[X~ | y~] are spread over the threads (tri_spread): with few entries several row
 //          partitions per entry (summed in partition order at the end), beyond 256 entries up to three per thread.  The tile's
 //          column stride is odd, so the lanes of a wave -- different columns, the same row -- hit different banks.
 //   eig    one wave per group: the segments' Gram matrices summed in segment order, cyclic Jacobi rotations on A and V in LDS (lane l
@@ -28,24 +27,36 @@
 //          on a tie), b = V (d o c) of every candidate (coef_path) and of the winner (coef, and in f64 for the prediction pass), status.
 //   predict  pred = x_i'b, resid = y_i - pred with the winner's coefficients, over every row of the frame as pols_least_squares leaves
 //          them: features zero-filled under every policy but "ignore", "drop" masks the rows outside the fit, a zero weight gives NaN
-//          (the reference's (sqrt(w) x)'b / sqrt(w)).  A lane owns 16 bytes of every column (streaming loads, all issued before the first
-//          use; streaming stores), sums in f64 and rounds once: an f32 prediction is the f64 one to half an ulp.
+//          (the reference's (sqrt(w) x)'b / sqrt(w)).  The walk is fit_predict_rows (fit_tile.inl): sums in f64, rounds once -- an f32
+//          prediction is the f64 one to half an ulp.
 #include "k10_ridge_path.hpp"
-#include "k10_stage.inl"
+#include "fit_launch.hpp"
+#include "fit_tile.inl"
 
 namespace pols {
 
-__device__ __forceinline__ double k10_nan() { return __longlong_as_double(0x7ff8000000000000LL); }
-
 // ---------------------------------------------------------------- gram
+// tri_spread (fit_tile.inl) into plain arrays, and below its accumulate and reduce steps written out.  This launch is most of
+// pols_ridge_cv and of pols_iv2sls's coefficients; through TriSpread, tri_accumulate and tri_reduce the compiler orders the kernel's
+// argument loads and parks its scalars differently (50 VGPRs for 52), and both entries measured 0.4 - 2.6 % slower.
+__device__ __forceinline__ void k10_entries(const int nz, const int parts, const int part, int (&ei)[3], int (&ej)[3], bool (&on)[3]) {
+    const int tid = threadIdx.x, ne = nz * (nz + 1) / 2;
+#pragma unroll
+    for (int q = 0; q < 3; ++q) {
+        const int en = parts > 1 ? tid - part * ne : tid + 256 * q;
+        on[q] = parts > 1 ? (q == 0 && part < parts) : en < ne;
+        tri_unpack(on[q] ? en : 0, nz, ei[q], ej[q]);
+    }
+}
+
 template <typename T>
 __global__ void __launch_bounds__(256) k10_gram_kernel(const RidgeCvArgs a) {
     extern __shared__ __attribute__((aligned(16))) double dyn[];
-    double *xs = dyn;                                              // (kt + 2) x K10_GRAM_TS
+    double *xs = dyn;                                              // (kt + 2) x FIT_TS
     const int tid = threadIdx.x, kt = a.kt, nz = kt + 1, ne = nz * (nz + 1) / 2;
-    const int ts = K10_GRAM_TS;
+    const int ts = FIT_TS;
     int64_t g, s, e, base, ntiles;
-    k10_item<T>(a, g, s, e, base, ntiles);
+    fit_item<T>(a, g, s, e, base, ntiles);
     const int parts = ne < 256 ? 256 / ne : 1;
     const int part = parts > 1 ? tid / ne : 0;
     int ei[3], ej[3];
@@ -54,9 +65,9 @@ __global__ void __launch_bounds__(256) k10_gram_kernel(const RidgeCvArgs a) {
     double acc[3] = {0.0, 0.0, 0.0};
     int nfit = 0;
     for (int64_t it = 0; it < ntiles; ++it) {
-        const int64_t t0 = base + it * K10_TILE;
-        nfit += k10_stage<T, false>(a, s, e, t0, xs, ts) ? 1 : 0;
-        const int rows_here = (int)min((int64_t)K10_TILE, e - t0);
+        const int64_t t0 = base + it * FIT_TILE;
+        nfit += fit_stage<T, false>(a, s, e, t0, xs, ts) ? 1 : 0;
+        const int rows_here = (int)min((int64_t)FIT_TILE, e - t0);
 #pragma unroll
         for (int q = 0; q < 3; ++q) {
             if (!on[q]) continue;
@@ -91,28 +102,12 @@ __global__ void __launch_bounds__(256) k10_gram_kernel(const RidgeCvArgs a) {
     }
 }
 
-static size_t k10_gram_lds(int kt) { return sizeof(double) * (size_t)(kt + 2) * K10_GRAM_TS; }
-
-constexpr size_t K10_LDS_BUDGET = 160 * 1024 - 256;
-
-template <typename K>
-static int k10_raise_lds(pols_ctx *ctx, K kernel, OncePerDevice &once) {
-    if (once.needed(ctx->device)) {
-        POLS_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)K10_LDS_BUDGET));
-        once.done(ctx->device);
-    }
-    return POLS_OK;
-}
+static size_t k10_gram_lds(int kt) { return sizeof(double) * (size_t)(kt + 2) * FIT_TS; }
 
 template <typename T>
 static int k10_gram_launch_t(pols_ctx *ctx, const RidgeCvArgs &a) {
     static OncePerDevice once;
-    int rc = k10_raise_lds(ctx, &k10_gram_kernel<T>, once);
-    if (rc) return rc;
-    const int64_t n_items = a.seg_offs ? a.n_seg : a.n_groups;
-    hipLaunchKernelGGL(k10_gram_kernel<T>, dim3((unsigned)n_items), dim3(256), k10_gram_lds(a.kt), ctx->stream, a);
-    POLS_HIP(hipGetLastError());
-    return POLS_OK;
+    return fit_launch(ctx, &k10_gram_kernel<T>, once, fit_items(a), 256, k10_gram_lds(a.kt), FIT_LDS_BUDGET, a);
 }
 
 int k10_gram_launch(pols_ctx *ctx, int dtype, const RidgeCvArgs &a) {
@@ -134,9 +129,8 @@ __global__ void __launch_bounds__(64) k10_eig_kernel(const RidgeCvArgs a) {
         double v = 0.0;
         for (int64_t it = v0; it < v1; ++it) v += a.gram_part[(size_t)it * gs + en];
         if (en == ne) { E[kt * kt + 2 * kt] = v; continue; }       // the group's fitted rows
-        int i = 0, t = en;
-        while (t >= nz - i) { t -= nz - i; ++i; }
-        const int j = i + t;
+        int i, j;
+        tri_unpack(en, nz, i, j);
         if (j == kt) { if (i < kt) gy[i] = v; }
         else { A[i * LD + j] = v; A[j * LD + i] = v; }
     }
@@ -202,7 +196,7 @@ template <typename T, int KT>
 __global__ void __launch_bounds__(256) k10_rows_kernel(const RidgeCvArgs a) {
     extern __shared__ __attribute__((aligned(16))) double dyn[];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, kt = KT > 0 ? KT : a.kt, na = a.n_alphas;
-    constexpr int ts = K10_TILE;
+    constexpr int ts = FIT_TILE;
     double *xs = dyn;                                              // (kt + 2) x 256
     double *zs = xs + (size_t)(kt + 2) * ts;                       // KT == 0: kt x 256
     double *Vs = zs + (KT > 0 ? 0 : (size_t)kt * ts);              // kt x kt
@@ -210,7 +204,7 @@ __global__ void __launch_bounds__(256) k10_rows_kernel(const RidgeCvArgs a) {
     double *D = cs + kt;                                           // na x kt: 1 / (s_m + a_j)
     double *red = D + na * kt;                                     // na x 4
     int64_t g, s, e, base, ntiles;
-    k10_item<T>(a, g, s, e, base, ntiles);
+    fit_item<T>(a, g, s, e, base, ntiles);
     {
         const double *E = a.eig + (size_t)g * k10_eig_stride(kt);
         for (int q = tid; q < kt * kt; q += 256) Vs[q] = E[q];
@@ -219,8 +213,8 @@ __global__ void __launch_bounds__(256) k10_rows_kernel(const RidgeCvArgs a) {
         for (int q = tid; q < na * 4; q += 256) red[q] = 0.0;
     }
     for (int64_t it = 0; it < ntiles; ++it) {
-        const int64_t t0 = base + it * K10_TILE;
-        const bool fit = k10_stage<T, true>(a, s, e, t0, xs, ts);  // (its first barrier also covers the tables above)
+        const int64_t t0 = base + it * FIT_TILE;
+        const bool fit = fit_stage<T, true>(a, s, e, t0, xs, ts);  // (its first barrier also covers the tables above)
         const double yt = xs[(size_t)kt * ts + tid];
         if constexpr (KT > 0) {
             double x[KT], zz[KT], zc[KT];
@@ -240,7 +234,7 @@ __global__ void __launch_bounds__(256) k10_rows_kernel(const RidgeCvArgs a) {
 #pragma unroll
                 for (int m = 0; m < KT; ++m) { const double dm = d[m]; h = fma(zz[m], dm, h); f = fma(zc[m], dm, f); }
                 const double om = 1.0 - h, r = (yt - f) / om;
-                const double term = !fit ? 0.0 : (om >= 1e-10 ? r * r : k10_nan());
+                const double term = !fit ? 0.0 : (om >= 1e-10 ? r * r : fit_nan());
                 const double v = wave_sum_row3(term);
                 if (lane == 63) red[j * 4 + wv] += v;
             }
@@ -260,7 +254,7 @@ __global__ void __launch_bounds__(256) k10_rows_kernel(const RidgeCvArgs a) {
                 double h = 0.0, f = 0.0;
                 for (int m = 0; m < kt; ++m) { const double dm = d[m]; h = fma(zs[m * ts + tid], dm, h); f = fma(xs[m * ts + tid], dm, f); }
                 const double om = 1.0 - h, r = (yt - f) / om;
-                const double term = !fit ? 0.0 : (om >= 1e-10 ? r * r : k10_nan());
+                const double term = !fit ? 0.0 : (om >= 1e-10 ? r * r : fit_nan());
                 const double v = wave_sum_row3(term);
                 if (lane == 63) red[j * 4 + wv] += v;
             }
@@ -272,20 +266,15 @@ __global__ void __launch_bounds__(256) k10_rows_kernel(const RidgeCvArgs a) {
 }
 
 static size_t k10_rows_lds(int kt, int na, bool parked) {
-    return sizeof(double) * ((size_t)(kt + 2) * K10_TILE + (parked ? (size_t)kt * K10_TILE : 0) + (size_t)kt * kt + kt + (size_t)na * kt + (size_t)na * 4);
+    return sizeof(double) * ((size_t)(kt + 2) * FIT_TILE + (parked ? (size_t)kt * FIT_TILE : 0) + (size_t)kt * kt + kt + (size_t)na * kt + (size_t)na * 4);
 }
 
 template <typename T, int KT>
 static int k10_rows_launch_kt(pols_ctx *ctx, const RidgeCvArgs &a) {
     const size_t lds = k10_rows_lds(a.kt, a.n_alphas, KT == 0);
-    if (lds > K10_LDS_BUDGET) return fail(POLS_ERR_UNSUPPORTED, "ridge_cv: %d columns x %d candidates exceed the LDS of a workgroup", a.kt, a.n_alphas);
+    if (lds > FIT_LDS_BUDGET) return fail(POLS_ERR_UNSUPPORTED, "ridge_cv: %d columns x %d candidates exceed the LDS of a workgroup", a.kt, a.n_alphas);
     static OncePerDevice once;
-    int rc = k10_raise_lds(ctx, &k10_rows_kernel<T, KT>, once);
-    if (rc) return rc;
-    const int64_t n_items = a.seg_offs ? a.n_seg : a.n_groups;
-    hipLaunchKernelGGL((k10_rows_kernel<T, KT>), dim3((unsigned)n_items), dim3(256), lds, ctx->stream, a);
-    POLS_HIP(hipGetLastError());
-    return POLS_OK;
+    return fit_launch(ctx, &k10_rows_kernel<T, KT>, once, fit_items(a), 256, lds, FIT_LDS_BUDGET, a);
 }
 
 template <typename T>
@@ -318,13 +307,13 @@ __global__ void __launch_bounds__(64) k10_pick_kernel(const RidgeCvArgs a) {
     const double n = E[kt * kt + 2 * kt];
     __syncthreads();
     const double aj = lane < na ? a.alphas[lane] : 0.0;
-    double sc = k10_nan();
+    double sc = fit_nan();
     if (lane < na && n > 0.0) {
         double tot = 0.0;
         for (int64_t it = v0; it < v1; ++it) tot += a.score_part[(size_t)it * na + lane];
         double smin = ss[0], smax = ss[0];
         for (int m = 1; m < kt; ++m) { smin = fmin(smin, ss[m]); smax = fmax(smax, ss[m]); }
-        const bool factors = smin + aj > 16.0 * (double)kt * 2.220446049250313e-16 * (smax + aj);   // (false for NaN too)
+        const bool factors = smin + aj > 16.0 * (double)kt * FIT_EPS * (smax + aj);   // (false for NaN too)
         if (factors) sc = tot / n;
     }
     if (lane < na) {
@@ -342,7 +331,7 @@ __global__ void __launch_bounds__(64) k10_pick_kernel(const RidgeCvArgs a) {
         for (int i = 0; i < kt; ++i) {
             double bi = 0.0;
             for (int m = 0; m < kt; ++m) bi = fma(Vs[i * kt + m], cs[m] / (ss[m] + aj), bi);
-            if (!(sc == sc)) bi = k10_nan();
+            if (!(sc == sc)) bi = fit_nan();
             if (a.coef_path) put(a.coef_path, ((size_t)g * na + lane) * kt + i, bi);
             if (lane == best) {
                 if (a.coef) put(a.coef, (size_t)g * kt + i, bi);
@@ -352,15 +341,15 @@ __global__ void __launch_bounds__(64) k10_pick_kernel(const RidgeCvArgs a) {
     }
     if (lane == 0) {
         if (best < 0) {
-            const double fillv = n > 0.0 ? k10_nan() : 0.0;        // no rows: zeros, as the existing entry; nothing usable: NaN
+            const double fillv = n > 0.0 ? fit_nan() : 0.0;        // no rows: zeros, as the existing entry; nothing usable: NaN
             for (int i = 0; i < kt; ++i) {
                 if (a.coef) put(a.coef, (size_t)g * kt + i, fillv);
                 a.coef64[(size_t)g * kt + i] = fillv;
             }
         }
-        if (a.alpha) a.alpha[g] = best >= 0 ? a.alphas[best] : k10_nan();
+        if (a.alpha) a.alpha[g] = best >= 0 ? a.alphas[best] : fit_nan();
         if (a.alpha_index) a.alpha_index[g] = best;
-        if (a.score) a.score[g] = best >= 0 ? bv : k10_nan();
+        if (a.score) a.score[g] = best >= 0 ? bv : fit_nan();
         if (a.status) a.status[g] = best >= 0 ? POLS_GROUP_OK : (n > 0.0 ? POLS_GROUP_FALLBACK : POLS_GROUP_EMPTY);
     }
 }
@@ -375,82 +364,25 @@ int k10_pick_launch(pols_ctx *ctx, const RidgeCvArgs &a) {
 // ---------------------------------------------------------------- predict
 template <typename T>
 __global__ void __launch_bounds__(256) k10_predict_kernel(const RidgeCvArgs a) {
-    using V = typename Vec16<T>::type;
-    constexpr int VEC = Vec16<T>::N;
-    const int tid = threadIdx.x, ku = a.k_user, kt = a.kt, pol = a.null_policy;
+    const int ku = a.k_user, kt = a.kt;
     int64_t g, s, e, base, ntiles;
-    k10_item<T>(a, g, s, e, base, ntiles);
+    fit_item<T>(a, g, s, e, base, ntiles);
     if (e <= s) return;
     const double *cg = a.coef64 + (size_t)g * kt;
-    const double icpt = kt > ku ? cg[ku] : 0.0;
-    const T *yp = static_cast<const T *>(a.y), *wp = static_cast<const T *>(a.w);
-    T *pred = static_cast<T *>(a.pred), *resid = static_cast<T *>(a.resid);
-    const int64_t nch = (e - base + VEC - 1) / VEC;
-    for (int64_t c = tid; c < nch; c += 256) {
-        const int64_t row0 = base + c * VEC;
-        const bool whole = row0 + VEC <= a.n_rows;                 // (else: the one chunk across the end of the columns, row by row)
-        const bool full = whole && row0 >= s && row0 + VEC <= e;
-        double p[VEC];
-        bool nullx[VEC];
-#pragma unroll
-        for (int v = 0; v < VEC; ++v) { p[v] = icpt; nullx[v] = false; }
-#pragma unroll
-        for (int j = 0; j < POLS_MAX_FEATURES; ++j) {
-            if (j < ku) {
-                const T *xp = static_cast<const T *>(a.x[j]);
-                const double cj = cg[j];
-                T xv[VEC];
-                if (whole) {
-                    const V ld = load_stream(reinterpret_cast<const V *>(xp + row0));
-#pragma unroll
-                    for (int v = 0; v < VEC; ++v) xv[v] = vget<T>(ld, v);
-                } else {
-#pragma unroll
-                    for (int v = 0; v < VEC; ++v) xv[v] = row0 + v < a.n_rows ? xp[row0 + v] : T(0);
-                }
-#pragma unroll
-                for (int v = 0; v < VEC; ++v) {
-                    nullx[v] = nullx[v] || xv[v] != xv[v];
-                    p[v] = fma((double)null_fill<T>(pol, xv[v]), cj, p[v]);
-                }
-            }
-        }
-        T pv[VEC], rv[VEC];
-#pragma unroll
-        for (int v = 0; v < VEC; ++v) {
-            const int64_t r = row0 + v;
-            const bool in = r >= s && r < e;
-            const T yv = in ? yp[r] : T(0);
-            double q = p[v];
-            if (wp) { const double sw = sqrt((double)(in ? wp[r] : T(1))); q = (q * sw) * (1.0 / sw); }
-            if (pol == POLS_NULL_DROP) {                           // the rows that were not part of the fit (ex.rs:409-417)
-                const bool fit = !(a.valid && in && !a.valid[r]) && yv == yv && !nullx[v];
-                if (!fit) q = k10_nan();
-            }
-            pv[v] = (T)q;
-            rv[v] = (T)((double)yv - q);
-        }
-        if (full) {
-            if constexpr (VEC == 4) {
-                if (pred) store_stream(reinterpret_cast<V *>(pred + row0), V{pv[0], pv[1], pv[2], pv[3]});
-                if (resid) store_stream(reinterpret_cast<V *>(resid + row0), V{rv[0], rv[1], rv[2], rv[3]});
-            } else {
-                if (pred) store_stream(reinterpret_cast<V *>(pred + row0), V{pv[0], pv[1]});
-                if (resid) store_stream(reinterpret_cast<V *>(resid + row0), V{rv[0], rv[1]});
-            }
-        } else {
-#pragma unroll
-            for (int v = 0; v < VEC; ++v) {
-                const int64_t r = row0 + v;
-                if (r >= s && r < e) { if (pred) pred[r] = pv[v]; if (resid) resid[r] = rv[v]; }
-            }
-        }
-    }
+    const T *wp = static_cast<const T *>(a.w);
+    T *const out[3] = {static_cast<T *>(a.pred), static_cast<T *>(a.resid), nullptr};
+    fit_predict_rows<T>(a, s, e, base, cg, kt > ku ? cg[ku] : 0.0, (const T *)nullptr, out,
+                        [&](double q, const double yv, const int64_t r, const bool in, const bool fit, double (&o)[3]) {
+                            if (wp) { const double sw = sqrt((double)(in ? wp[r] : T(1))); q = (q * sw) * (1.0 / sw); }
+                            if (!fit) q = fit_nan();
+                            o[0] = q;
+                            o[1] = yv - q;
+                        });
 }
 
 int k10_predict_launch(pols_ctx *ctx, int dtype, const RidgeCvArgs &a) {
     if (a.n_groups == 0 || a.n_rows == 0 || (!a.pred && !a.resid)) return POLS_OK;
-    const int64_t n_items = a.seg_offs ? a.n_seg : a.n_groups;
+    const int64_t n_items = fit_items(a);
     if (dtype == POLS_F32) hipLaunchKernelGGL(k10_predict_kernel<float>, dim3((unsigned)n_items), dim3(256), 0, ctx->stream, a);
     else hipLaunchKernelGGL(k10_predict_kernel<double>, dim3((unsigned)n_items), dim3(256), 0, ctx->stream, a);
     POLS_HIP(hipGetLastError());

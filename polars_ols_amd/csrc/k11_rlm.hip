@@ -11,7 +11,7 @@
 //
 // ONE 256-thread workgroup per group runs the whole iteration in one launch, in one of two forms of the same kernel:
 //   resident  the group's scaled rows [X~ | y~] and a work column (|r| or omega, sign bit set on the rows outside the fit) are staged
-//             into LDS ONCE -- k10_stage: 16-byte streaming loads on the columns' 16-byte grid, null policy and sqrt(w) applied -- and
+//             into LDS ONCE -- fit_stage: 16-byte streaming loads on the columns' 16-byte grid, null policy and sqrt(w) applied -- and
 //             every iteration runs from there: the frame is read once however many iterations its groups need.  The dynamic LDS is
 //             sized to the longest resident group of the launch, so short-group frames get several workgroups per CU; the column
 //             stride is odd (tiles x 256 + 1), so the lanes of a wave -- different columns, the same row -- hit different banks.
@@ -24,19 +24,16 @@
 //             histogram in LDS (integer counters; the lanes of a wave that share a bin add once), one wave scans the bins and narrows
 //             the prefix; for even n one more pass takes the smallest key above the lower middle value unless that value's own
 //             multiplicity already covers the upper one;
-//   weigh     omega_i over the work column, then the weighted Gram matrix [X~ | y~]' diag(omega) [X~ | y~] with k10_gram_kernel's
-//             assignment of the (kt + 1)(kt + 2) / 2 entries to threads (row partitions summed in partition order);
+//   weigh     omega_i over the work column, then the weighted Gram matrix [X~ | y~]' diag(omega) [X~ | y~] with K10's assignment of
+//             the (kt + 1)(kt + 2) / 2 entries to threads (tri_spread's, written out; row partitions summed in partition order);
 //   solve     wave 0: right-looking Cholesky in LDS (the trailing update spread over the lanes), the two substitutions, the
-//             finiteness check (k11_solve.inl); every thread then evaluates the stop test on the broadcast result.
+//             finiteness check (fit_solve.inl); every thread then evaluates the stop test on the broadcast result.
 #include "k11_rlm.hpp"
-#include "k10_stage.inl"
-#include "k11_solve.inl"
+#include "fit_launch.hpp"
+#include "fit_solve.inl"
 
 namespace pols {
 
-constexpr int K11_STREAM_TS = 257;                 // column stride of the streamed form's tile (odd, as K10's)
-constexpr size_t K11_LDS_BUDGET = 160 * 1024 - 256;
-constexpr double K11_EPS = 2.220446049250313e-16;
 constexpr double K11_MAD = 0.6744897501960817;     // the 0.75 quantile of the standard normal
 
 // doubles behind the tile: Gram partials (256), the packed Gram matrix, the Cholesky work (kt x (kt + 1)), b, the previous b, the
@@ -49,11 +46,10 @@ static size_t k11_lds(int kt, int ts) { return sizeof(double) * ((size_t)(kt + 2
 
 int k11_resident_tiles(int kt) {
     int nt = 0;
-    while (k11_lds(kt, (nt + 1) * K10_TILE + 1) <= K11_LDS_BUDGET) ++nt;
+    while (k11_lds(kt, (nt + 1) * FIT_TILE + 1) <= FIT_LDS_BUDGET) ++nt;
     return nt;
 }
 
-__device__ __forceinline__ double k11_nan() { return __longlong_as_double(0x7ff8000000000000LL); }
 __device__ __forceinline__ unsigned long long k11_bits(double v) { return (unsigned long long)__double_as_longlong(v); }
 __device__ __forceinline__ double k11_omega(const int norm, const double c, const double u) {
     double om;
@@ -71,8 +67,8 @@ __global__ void __launch_bounds__(256) k11_rlm_kernel(const RlmArgs a) {
     __shared__ int nfit_s, krem_s, cnt_s, ok_s;
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, kt = a.kt, nz = kt + 1, ne = nz * (nz + 1) / 2, LD = kt + 1;
     const int64_t g = blockIdx.x, s = a.offs[g], e = a.offs[g + 1];
-    const int64_t base = s & ~(int64_t)(VEC - 1);                  // the tile grid starts on the columns' 16-byte grid
-    const int ntiles = e > s ? (int)((e - base + K10_TILE - 1) / K10_TILE) : 0;
+    const int64_t base = s & ~(int64_t)(VEC - 1);                  // the tile grid starts on the columns' 16-byte grid (fit_base)
+    const int ntiles = e > s ? (int)((e - base + FIT_TILE - 1) / FIT_TILE) : 0;
     if (RES ? ntiles > a.res_tiles : ntiles <= a.res_tiles) return;   // the other form's group
     const int ts = a.ts;
     double *xs = dyn;                                              // (kt + 2) x ts: x~ (ones column at k_user), y~ at kt, the work column at kt + 1
@@ -83,7 +79,9 @@ __global__ void __launch_bounds__(256) k11_rlm_kernel(const RlmArgs a) {
     int *hist = reinterpret_cast<int *>(d0 + kt);                  // 256
     const size_t wc = (size_t)(kt + 1) * ts;                       // the work column
 
-    // the thread's entries of the packed upper triangle, as k10_gram_kernel spreads them
+    // The thread's entries of the packed upper triangle, the accumulate and the reduce step: tri_spread, tri_accumulate and tri_reduce
+    // (fit_tile.inl) written out.  This kernel keeps some 180 scalars (streamed: 330) in lanes of spare VGPRs, and with the shared
+    // forms the compiler places them differently: the resident form then measures 0.2 - 0.5 % slower on 10 000 groups x 1 000 rows.
     const int parts = ne < 256 ? 256 / ne : 1;
     const int part = parts > 1 ? tid / ne : 0;
     int ei[3], ej[3];
@@ -133,7 +131,7 @@ __global__ void __launch_bounds__(256) k11_rlm_kernel(const RlmArgs a) {
     // Gm -> coefficients in rhs, ok_s; wave 0 works, ends on a barrier
     auto solve = [&]() {
         if (wv == 0) {
-            const bool ok = k11_chol_solve(Gm, A, rhs, d0, kt, lane);
+            const bool ok = fit_chol_solve(Gm, A, rhs, d0, kt, lane);
             if (lane == 0) ok_s = ok ? 1 : 0;
         }
         __syncthreads();
@@ -141,23 +139,23 @@ __global__ void __launch_bounds__(256) k11_rlm_kernel(const RlmArgs a) {
     // the tile `it` with its work column in LDS; returns this thread's work value.  Streamed: stages the tile (two barriers inside).
     auto open = [&](const int it, double *&xt) -> double {
         if constexpr (RES) {
-            xt = xs + (size_t)it * K10_TILE;
+            xt = xs + (size_t)it * FIT_TILE;
             return xt[wc + tid];
         } else {
-            const int64_t t0 = base + (int64_t)it * K10_TILE, row = t0 + tid;
+            const int64_t t0 = base + (int64_t)it * FIT_TILE, row = t0 + tid;
             xt = xs;
-            k10_stage<T, false>(a, s, e, t0, xs, ts);
+            fit_stage<T, false>(a, s, e, t0, xs, ts);
             return row >= s && row < e ? a.rows[row] : -1.0;
         }
     };
     auto put = [&](const int it, double *xt, const double v) {    // this thread's work value
         xt[wc + tid] = v;
         if constexpr (!RES) {
-            const int64_t row = base + (int64_t)it * K10_TILE + tid;
+            const int64_t row = base + (int64_t)it * FIT_TILE + tid;
             if (row >= s && row < e) a.rows[row] = v;
         }
     };
-    auto rows_of = [&](const int it) { return (int)min((int64_t)K10_TILE, e - (base + (int64_t)it * K10_TILE)); };
+    auto rows_of = [&](const int it) { return (int)min((int64_t)FIT_TILE, e - (base + (int64_t)it * FIT_TILE)); };
     auto residual = [&](const double *bb) {                        // work <- |y~ - x~'b| on the fitted rows; ends on a barrier
         for (int it = 0; it < ntiles; ++it) {
             double *xt;
@@ -188,7 +186,7 @@ __global__ void __launch_bounds__(256) k11_rlm_kernel(const RlmArgs a) {
     // every work value of the group, in any order, the same trip count in every lane (a key with the sign bit set: no fitted row)
     auto each_key = [&](auto &&f) {
         if constexpr (RES) {
-            for (int i = tid; i < ntiles * K10_TILE; i += 256) f(k11_bits(xs[wc + i]));
+            for (int i = tid; i < ntiles * FIT_TILE; i += 256) f(k11_bits(xs[wc + i]));
         } else {
             for (int64_t r0 = s; r0 < e; r0 += 256 * 8) {          // eight loads in flight per lane
                 unsigned long long k[8];
@@ -272,9 +270,9 @@ __global__ void __launch_bounds__(256) k11_rlm_kernel(const RlmArgs a) {
     __syncthreads();
     unsigned long long ym = 0;
     for (int it = 0; it < ntiles; ++it) {
-        const int64_t t0 = base + (int64_t)it * K10_TILE;
-        double *xt = RES ? xs + (size_t)it * K10_TILE : xs;
-        const bool fit = k10_stage<T, RES>(a, s, e, t0, xt, ts);   // (resident: the one read of the frame, streaming loads)
+        const int64_t t0 = base + (int64_t)it * FIT_TILE;
+        double *xt = RES ? xs + (size_t)it * FIT_TILE : xs;
+        const bool fit = fit_stage<T, RES>(a, s, e, t0, xt, ts);   // (resident: the one read of the frame, streaming loads)
         put(it, xt, fit ? 1.0 : -1.0);
         const unsigned long long m = __ballot(fit);
         if (lane == 0 && m) atomicAdd(&nfit_s, (int)__popcll(m));
@@ -288,7 +286,7 @@ __global__ void __launch_bounds__(256) k11_rlm_kernel(const RlmArgs a) {
     const int n = nfit_s;
     const double ymax = __longlong_as_double((long long)ymax_s);
     int status = POLS_GROUP_OK, iters = 0;
-    double sc = k11_nan();
+    double sc = fit_nan();
     if (n == 0) status = POLS_GROUP_EMPTY;
     else if (n <= kt) status = POLS_GROUP_FALLBACK;
     else {
@@ -302,7 +300,7 @@ __global__ void __launch_bounds__(256) k11_rlm_kernel(const RlmArgs a) {
             for (;;) {
                 residual(bc);
                 sc = median(n) / K11_MAD;
-                if (!(sc > 16.0 * K11_EPS * ymax) || !(sc <= 1.79769313486231570815e308)) {   // the scale collapsed: converged where it is
+                if (!(sc > 16.0 * FIT_EPS * ymax) || !(sc <= FIT_DBL_MAX)) {   // the scale collapsed: converged where it is
                     if (iters > 0) residual(bp);
                     reweigh(iters == 0, sprev, false);
                     break;
@@ -327,13 +325,13 @@ __global__ void __launch_bounds__(256) k11_rlm_kernel(const RlmArgs a) {
     // ---- outputs
     const bool failed = status == POLS_GROUP_FALLBACK;
     if (tid < kt) {
-        const double v = failed ? k11_nan() : (status == POLS_GROUP_EMPTY ? 0.0 : bc[tid]);
+        const double v = failed ? fit_nan() : (status == POLS_GROUP_EMPTY ? 0.0 : bc[tid]);
         a.coef64[(size_t)g * kt + tid] = v;
         if (a.coef) { if (a.f32) static_cast<float *>(a.coef)[(size_t)g * kt + tid] = (float)v; else static_cast<double *>(a.coef)[(size_t)g * kt + tid] = v; }
     }
     if (tid == 0) {
         if (a.status) a.status[g] = status;
-        if (a.scale) a.scale[g] = failed ? k11_nan() : sc;
+        if (a.scale) a.scale[g] = failed ? fit_nan() : sc;
         if (a.n_iter) a.n_iter[g] = iters;
     }
     if (a.weights && e > s) {                                      // omega of the last update; NaN outside the fit and for a failed group
@@ -348,7 +346,7 @@ __global__ void __launch_bounds__(256) k11_rlm_kernel(const RlmArgs a) {
                 const int64_t r = row0 + v;
                 double wv_ = -1.0;
                 if (r >= s && r < e) wv_ = RES ? xs[wc + (size_t)(r - base)] : a.rows[r];
-                ov[v] = (T)((failed || __double_as_longlong(wv_) < 0) ? k11_nan() : wv_);
+                ov[v] = (T)((failed || __double_as_longlong(wv_) < 0) ? fit_nan() : wv_);
             }
             if (al && row0 >= s && row0 + VEC <= e) {
                 if constexpr (VEC == 4) store_stream(reinterpret_cast<V *>(wo + row0), V{ov[0], ov[1], ov[2], ov[3]});
@@ -364,22 +362,16 @@ __global__ void __launch_bounds__(256) k11_rlm_kernel(const RlmArgs a) {
 template <typename T, bool RES>
 static int k11_launch_t(pols_ctx *ctx, const RlmArgs &a) {
     const size_t lds = k11_lds(a.kt, a.ts);
-    if (lds > K11_LDS_BUDGET) return fail(POLS_ERR_UNSUPPORTED, "rlm: %d columns x %d rows exceed the LDS of a workgroup", a.kt, a.ts);
+    if (lds > FIT_LDS_BUDGET) return fail(POLS_ERR_UNSUPPORTED, "rlm: %d columns x %d rows exceed the LDS of a workgroup", a.kt, a.ts);
     static OncePerDevice once;
-    if (once.needed(ctx->device)) {
-        POLS_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k11_rlm_kernel<T, RES>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)K11_LDS_BUDGET));
-        once.done(ctx->device);
-    }
-    hipLaunchKernelGGL((k11_rlm_kernel<T, RES>), dim3((unsigned)a.n_groups), dim3(256), lds, ctx->stream, a);
-    POLS_HIP(hipGetLastError());
-    return POLS_OK;
+    return fit_launch(ctx, &k11_rlm_kernel<T, RES>, once, a.n_groups, 256, lds, FIT_LDS_BUDGET, a);
 }
 
 int k11_rlm_launch(pols_ctx *ctx, int dtype, const RlmArgs &a, bool resident) {
     if (a.kt < 1 || a.kt > K11_KMAX) return fail(POLS_ERR_UNSUPPORTED, "rlm: %d features (incl. intercept) outside 1..%d", a.kt, K11_KMAX);
     if (a.n_groups == 0) return POLS_OK;
     RlmArgs b = a;
-    if (!resident) b.ts = K11_STREAM_TS;
+    if (!resident) b.ts = FIT_TS;
     if (dtype == POLS_F32) return resident ? k11_launch_t<float, true>(ctx, b) : k11_launch_t<float, false>(ctx, b);
     return resident ? k11_launch_t<double, true>(ctx, b) : k11_launch_t<double, false>(ctx, b);
 }

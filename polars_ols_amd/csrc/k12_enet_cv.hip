@@ -1,6 +1,6 @@
 // k12_enet_cv.hip -- K12: elastic-net / lasso regularisation path with K-fold selection of alpha per group (pols_elastic_net_cv).
 //
-// Per group g, on the rows F_g that pols_least_squares fits (k10_stage: null policy, sqrt(w) scaling, ones column last), n = |F_g|,
+// Per group g, on the rows F_g that pols_least_squares fits (fit_stage: null policy, sqrt(w) scaling, ones column last), n = |F_g|,
 // the fitted rows are cut in row order into n_folds contiguous folds (the first n % n_folds hold n / n_folds + 1 rows).  With
 // Z = [X~ | y~], fold f has its own Gram matrix Z_f'Z_f = [[G_f, c_f], [c_f', yy_f]]; the training matrix of fold f is the sum of the
 // others, the validation error of coefficients b is (yy_f - 2 b'c_f + b'G_f b) / n_f.  So the frame is read once and every one of
@@ -10,10 +10,10 @@
 // Launches:
 //   count      (only when the null policy can remove rows) one workgroup per segment / group: the item's fitted rows, so that
 //              every item knows the rank of its first fitted row.  Without it rank = row - group start.
-//   fold_gram  one workgroup per segment / group, K10's 256-row tiles (k10_stage, 16-byte column loads).  A wave ballot and a
+//   fold_gram  one workgroup per segment / group, K10's 256-row tiles (fit_stage, 16-byte column loads).  A wave ballot and a
 //              four-entry prefix give every row its rank among the fitted rows, hence its fold; fold ids are monotone down the rows, so a tile
 //              is cut into at most n_folds + 1 row ranges [bnd[f], bnd[f + 1]) and the threads -- each owns up to three entries of the packed
-//              upper triangle, or one entry of a row partition, as in K10's Gram launch -- sum a range in registers and add it to the
+//              upper triangle, or one entry of a row partition (tri_spread), as in K10's Gram launch -- sum a range in registers and add it to the
 //              thread's own LDS slot of that fold: no branch per row (rows outside the fit are zero in the tile).
 //   reduce     (only with segments) per group and entry one wave: lane l sums the segments l, l + 64, ... in order, then a fixed DPP tree.
 //   path       one problem = (group, fold) or (group, full data); 16 lanes per problem up to 16 columns, 32 beyond.  Lane l keeps column l
@@ -24,38 +24,17 @@
 //   pick       per group: mean over the folds, the winner (smallest finite score, lowest index on a tie), status, n_iter, the
 //              chosen coefficients in f64 for K10's prediction pass.
 #include "k12_enet_cv.hpp"
-#include "k10_stage.inl"
+#include "fit_launch.hpp"
+#include "fit_tile.inl"
 
 namespace pols {
 
-__device__ __forceinline__ double k12_nan() { return __longlong_as_double(0x7ff8000000000000LL); }
-
-constexpr int K12_TS = 257;           // column stride of the tile (odd: conflict-free across columns)
 constexpr size_t K12_LDS_BUDGET = 160 * 1024 - 2048;   // dynamic LDS a launch may ask for (the kernels keep about 1 KB of static LDS beside it)
-
-template <typename T>
-__device__ __forceinline__ void k12_item(const EnetCvArgs &a, int64_t &g, int64_t &s, int64_t &e, int64_t &base, int64_t &ntiles) {
-    const int64_t sgi = blockIdx.x;
-    g = a.seg_offs ? (int64_t)a.seg_map[sgi] : sgi;
-    s = a.seg_offs ? a.seg_offs[sgi] : a.offs[g];
-    e = a.seg_offs ? a.seg_offs[sgi + 1] : a.offs[g + 1];
-    base = s & ~(int64_t)(Vec16<T>::N - 1);
-    ntiles = e > s ? (e - base + K10_TILE - 1) / K10_TILE : 0;
-}
 
 // first rank of fold f among n fitted rows (f = n_folds: n)
 __device__ __forceinline__ int64_t k12_fold_start(int64_t n, int nf, int f) {
     const int64_t q = n / nf, rem = n - q * nf;
     return (int64_t)f * q + min((int64_t)f, rem);
-}
-
-template <typename K>
-static int k12_raise_lds(pols_ctx *ctx, K kernel, OncePerDevice &once) {
-    if (once.needed(ctx->device)) {
-        POLS_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)K12_LDS_BUDGET));
-        once.done(ctx->device);
-    }
-    return POLS_OK;
 }
 
 // ---------------------------------------------------------------- count
@@ -65,10 +44,10 @@ __global__ void __launch_bounds__(256) k12_count_kernel(const EnetCvArgs a) {
     __shared__ int wcnt[4];
     const int tid = threadIdx.x;
     int64_t g, s, e, base, ntiles;
-    k12_item<T>(a, g, s, e, base, ntiles);
+    fit_item<T>(a, g, s, e, base, ntiles);
     int64_t run = 0;
     for (int64_t it = 0; it < ntiles; ++it) {
-        const bool fit = k10_stage<T, false>(a, s, e, base + it * K10_TILE, dyn, K12_TS);
+        const bool fit = fit_stage<T, false>(a, s, e, base + it * FIT_TILE, dyn, FIT_TS);
         const unsigned long long bal = __ballot(fit);
         if ((tid & 63) == 0) wcnt[tid >> 6] = __popcll(bal);
         __syncthreads();
@@ -82,16 +61,15 @@ __global__ void __launch_bounds__(256) k12_count_kernel(const EnetCvArgs a) {
 template <typename T>
 __global__ void __launch_bounds__(256) k12_fold_gram_kernel(const EnetCvArgs a) {
     extern __shared__ __attribute__((aligned(16))) double dyn[];
-    __shared__ int wcnt[4], bnd[K12_MAX_FOLDS + 1], fold_s[K10_TILE];
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, kt = a.kt, nz = kt + 1, ne = nz * (nz + 1) / 2, nf = a.n_folds;
-    constexpr int ts = K12_TS;
-    double *xs = dyn;                                              // (kt + 2) x K12_TS
+    __shared__ int wcnt[4], bnd[K12_MAX_FOLDS + 1], fold_s[FIT_TILE];
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, kt = a.kt, nf = a.n_folds;
+    constexpr int ts = FIT_TS;
+    double *xs = dyn;                                              // (kt + 2) x FIT_TS
     double *facc = xs + (size_t)(kt + 2) * ts;                     // n_folds x sf: a slot per fold and thread entry
     int64_t g, s, e, base, ntiles;
-    k12_item<T>(a, g, s, e, base, ntiles);
-    const int parts = ne < 256 ? 256 / ne : 1;
-    const int part = parts > 1 ? tid / ne : 0;
-    const int sf = parts > 1 ? parts * ne : ne;
+    fit_item<T>(a, g, s, e, base, ntiles);
+    const TriSpread sp = tri_spread(kt + 1, tid);
+    const int ne = sp.ne, parts = sp.parts, sf = parts > 1 ? parts * ne : ne;
     // the group's fitted rows and the rank of this item's first fitted row
     int64_t n, rank0;
     if (a.counted) {
@@ -103,25 +81,15 @@ __global__ void __launch_bounds__(256) k12_fold_gram_kernel(const EnetCvArgs a) 
         rank0 = s - a.offs[g];
     }
     const int64_t fq = n / nf, frem = n - fq * nf, fcut = frem * (fq + 1);      // ranks below fcut sit in folds of fq + 1 rows
-    int ei[3], ej[3];
-    bool on[3];
-#pragma unroll
-    for (int q = 0; q < 3; ++q) {
-        const int en = parts > 1 ? tid - part * ne : tid + 256 * q;
-        on[q] = parts > 1 ? (q == 0 && part < parts) : en < ne;
-        int i = 0, t = on[q] ? en : 0;
-        while (t >= nz - i) { t -= nz - i; ++i; }
-        ei[q] = i; ej[q] = i + t;
-    }
     for (int q = tid; q < nf * sf; q += 256) facc[q] = 0.0;
     int64_t run = 0;                                               // fitted rows of the tiles behind
     for (int64_t it = 0; it < ntiles; ++it) {
-        const int64_t t0 = base + it * K10_TILE;
-        const bool fit = k10_stage<T, false>(a, s, e, t0, xs, ts);
-        const int rows_here = (int)min((int64_t)K10_TILE, e - t0);
+        const int64_t t0 = base + it * FIT_TILE;
+        const bool fit = fit_stage<T, false>(a, s, e, t0, xs, ts);
+        const int rows_here = (int)min((int64_t)FIT_TILE, e - t0);
         const unsigned long long bal = __ballot(fit);
         if (lane == 0) wcnt[wv] = __popcll(bal);
-        if (tid <= nf) bnd[tid] = K10_TILE;
+        if (tid <= nf) bnd[tid] = FIT_TILE;
         __syncthreads();
         int before = __popcll(bal & ((1ull << lane) - 1ull));
         for (int w = 0; w < wv; ++w) before += wcnt[w];
@@ -138,17 +106,13 @@ __global__ void __launch_bounds__(256) k12_fold_gram_kernel(const EnetCvArgs a) 
             for (int f = prev + 1; f <= fo; ++f) bnd[f] = tid;     // first row of the tile whose fold is >= f
         }
         __syncthreads();
-        const int flo = fold_s[0], fhi = fold_s[K10_TILE - 1];
+        const int flo = fold_s[0], fhi = fold_s[FIT_TILE - 1];
         for (int f = flo; f <= fhi; ++f) {
-            const int r0 = bnd[f], r1 = min(bnd[f + 1], rows_here);
+            double v[3] = {0.0, 0.0, 0.0};
+            tri_accumulate(sp, v, xs, ts, bnd[f], min(bnd[f + 1], rows_here));
 #pragma unroll
-            for (int q = 0; q < 3; ++q) {
-                if (!on[q]) continue;
-                const double *ci = xs + (size_t)ei[q] * ts, *cj = xs + (size_t)ej[q] * ts;
-                double v = 0.0;
-                for (int r = r0 + part; r < r1; r += parts) v = fma(ci[r], cj[r], v);
-                facc[f * sf + (parts > 1 ? tid : tid + 256 * q)] += v;
-            }
+            for (int q = 0; q < 3; ++q)
+                if (sp.on[q]) facc[f * sf + (parts > 1 ? tid : tid + 256 * q)] += v[q];
         }
         run += total;
         __syncthreads();                                           // the next tile overwrites xs, wcnt, bnd and fold_s
@@ -169,7 +133,7 @@ __global__ void __launch_bounds__(256) k12_fold_gram_kernel(const EnetCvArgs a) 
     }
 }
 
-static size_t k12_tile_lds(int kt) { return sizeof(double) * (size_t)(kt + 2) * K12_TS; }
+static size_t k12_tile_lds(int kt) { return sizeof(double) * (size_t)(kt + 2) * FIT_TS; }
 static size_t k12_fold_lds(int kt, int nf) {
     const int ne = (kt + 1) * (kt + 2) / 2;
     const int sf = ne < 256 ? (256 / ne) * ne : ne;
@@ -179,12 +143,7 @@ static size_t k12_fold_lds(int kt, int nf) {
 template <typename T>
 static int k12_count_launch_t(pols_ctx *ctx, const EnetCvArgs &a) {
     static OncePerDevice once;
-    int rc = k12_raise_lds(ctx, &k12_count_kernel<T>, once);
-    if (rc) return rc;
-    const int64_t n_items = a.seg_offs ? a.n_seg : a.n_groups;
-    hipLaunchKernelGGL(k12_count_kernel<T>, dim3((unsigned)n_items), dim3(256), k12_tile_lds(a.kt), ctx->stream, a);
-    POLS_HIP(hipGetLastError());
-    return POLS_OK;
+    return fit_launch(ctx, &k12_count_kernel<T>, once, fit_items(a), 256, k12_tile_lds(a.kt), K12_LDS_BUDGET, a);
 }
 
 int k12_count_launch(pols_ctx *ctx, int dtype, const EnetCvArgs &a) {
@@ -195,14 +154,11 @@ int k12_count_launch(pols_ctx *ctx, int dtype, const EnetCvArgs &a) {
 template <typename T>
 static int k12_fold_gram_launch_t(pols_ctx *ctx, const EnetCvArgs &a) {
     static OncePerDevice once;
-    int rc = k12_raise_lds(ctx, &k12_fold_gram_kernel<T>, once);
+    const int rc = fit_raise_lds(ctx, &k12_fold_gram_kernel<T>, once, K12_LDS_BUDGET);   // (up front: a failure here is reported before the size)
     if (rc) return rc;
     const size_t lds = k12_fold_lds(a.kt, a.n_folds);
     if (lds > K12_LDS_BUDGET) return fail(POLS_ERR_UNSUPPORTED, "elastic_net_cv: %d columns x %d folds exceed the LDS of a workgroup", a.kt, a.n_folds);
-    const int64_t n_items = a.seg_offs ? a.n_seg : a.n_groups;
-    hipLaunchKernelGGL(k12_fold_gram_kernel<T>, dim3((unsigned)n_items), dim3(256), lds, ctx->stream, a);
-    POLS_HIP(hipGetLastError());
-    return POLS_OK;
+    return fit_launch(ctx, &k12_fold_gram_kernel<T>, once, fit_items(a), 256, lds, K12_LDS_BUDGET, a);
 }
 
 int k12_fold_gram_launch(pols_ctx *ctx, int dtype, const EnetCvArgs &a) {
@@ -251,9 +207,6 @@ __device__ __forceinline__ double k12_team_sum(double v) {
     return v;
 }
 
-// index of entry (i, j), i <= j, in the packed upper triangle of an nz x nz matrix
-__device__ __forceinline__ int k12_tri(int i, int j, int nz) { return i * nz - i * (i - 1) / 2 + (j - i); }
-
 template <int LPG>   // lanes per problem = the most columns it handles
 __global__ void __launch_bounds__(64) k12_path_kernel(const EnetCvArgs a) {
     const int lane = threadIdx.x, sub = lane & (LPG - 1);
@@ -275,7 +228,7 @@ __global__ void __launch_bounds__(64) k12_path_kernel(const EnetCvArgs a) {
     for (int i = 0; i < LPG; ++i) {
         double v = 0.0;
         if (i < kt && mine) {
-            const int at = k12_tri(min(i, su), max(i, su), nz);
+            const int at = tri_index(min(i, su), max(i, su), nz);
             for (int f = 0; f < nf; ++f) if (f != p) v += FG[(size_t)f * gs + at];
         }
         col[i] = v;
@@ -283,7 +236,7 @@ __global__ void __launch_bounds__(64) k12_path_kernel(const EnetCvArgs a) {
     double cme = 0.0, dme = 1.0, cfull = 0.0;                      // c_sub and G_sub,sub of the training problem; c_sub of the full data
     if (mine) {
         dme = 0.0;
-        const int ac = k12_tri(su, kt, nz), ad = k12_tri(su, su, nz);
+        const int ac = tri_index(su, kt, nz), ad = tri_index(su, su, nz);
         for (int f = 0; f < nf; ++f) {
             const double c = FG[(size_t)f * gs + ac];
             cfull += c;
@@ -337,23 +290,23 @@ __global__ void __launch_bounds__(64) k12_path_kernel(const EnetCvArgs a) {
             double acc = 0.0;
             for (int i = 0; i < kt; ++i) {
                 const double wi = __shfl(wme, i, LPG);
-                const double gv = mine ? VG[k12_tri(min(i, su), max(i, su), nz)] : 0.0;
+                const double gv = mine ? VG[tri_index(min(i, su), max(i, su), nz)] : 0.0;
                 acc = fma(gv, wi, acc);
             }
-            const double cv = mine ? VG[k12_tri(su, kt, nz)] : 0.0;
+            const double cv = mine ? VG[tri_index(su, kt, nz)] : 0.0;
             double tot = k12_team_sum<LPG>(mine ? wme * (acc - 2.0 * cv) : 0.0) + VG[ne - 1];
             if (tot < 0.0) tot = 0.0;                              // (a NaN stays a NaN)
-            if (live && sub == 0) a.score_part[((size_t)g * nf + p) * na + j] = go ? tot / n_val : k12_nan();
+            if (live && sub == 0) a.score_part[((size_t)g * nf + p) * na + j] = go ? tot / n_val : fit_nan();
         } else if (live) {
             if (mine) {
-                const double v = go ? wme : k12_nan();
+                const double v = go ? wme : fit_nan();
                 a.path64[((size_t)g * na + j) * kt + sub] = v;
                 if (a.coef_path) {
                     if (a.f32) static_cast<float *>(a.coef_path)[((size_t)g * na + j) * kt + sub] = (float)v;
                     else static_cast<double *>(a.coef_path)[((size_t)g * na + j) * kt + sub] = v;
                 }
             }
-            if (sub == 0) a.grid[(size_t)g * na + j] = (a.automatic && !go) ? k12_nan() : alpha;
+            if (sub == 0) a.grid[(size_t)g * na + j] = (a.automatic && !go) ? fit_nan() : alpha;
         }
         if (live && sub == 0) a.iters[((size_t)g * (nf + 1) + p) * na + j] = sweeps | (stopped ? K12_STOPPED : 0);
     }
@@ -403,16 +356,16 @@ __global__ void __launch_bounds__(K12_MAX_ALPHAS) k12_pick_kernel(const EnetCvAr
             if (fabs(v) < __longlong_as_double(0x7ff0000000000000LL) && (best < 0 || v < bv)) { best = j; bv = v; }   // (false for NaN)
         }
         best_s = best;
-        if (a.alpha) a.alpha[g] = best >= 0 ? a.grid[(size_t)g * na + best] : k12_nan();
+        if (a.alpha) a.alpha[g] = best >= 0 ? a.grid[(size_t)g * na + best] : fit_nan();
         if (a.alpha_index) a.alpha_index[g] = best;
-        if (a.score) a.score[g] = best >= 0 ? bv : k12_nan();
+        if (a.score) a.score[g] = best >= 0 ? bv : fit_nan();
     }
     __syncthreads();
     const int best = best_s;
     if (tid == (best >= 0 ? best : 0) && a.status)
         a.status[g] = best >= 0 ? (stopped ? POLS_GROUP_NOT_CONVERGED : POLS_GROUP_OK) : (n > 0.0 ? POLS_GROUP_FALLBACK : POLS_GROUP_EMPTY);
     if (tid < kt) {
-        const double v = best >= 0 ? a.path64[((size_t)g * na + best) * kt + tid] : (n > 0.0 ? k12_nan() : 0.0);
+        const double v = best >= 0 ? a.path64[((size_t)g * na + best) * kt + tid] : (n > 0.0 ? fit_nan() : 0.0);
         a.coef64[(size_t)g * kt + tid] = v;
         if (a.coef) {
             if (a.f32) static_cast<float *>(a.coef)[(size_t)g * kt + tid] = (float)v;

@@ -19,9 +19,9 @@
 //             different banks in the Gram pass.
 //             row pass   one thread per row of a tile: eta as one FMA chain over the columns in order, mu, the deviance term (summed
 //                        per thread over its tiles, then over the wave by DPP, then waves ((0 + 1) + (2 + 3))), W and z
-//             gram       [X | z]' diag(W) [X | z] with k10_gram_kernel's assignment of the (kt + 1)(kt + 2) / 2 entries to threads
-//                        (row partitions summed in partition order); the ones column is the constant 1
-//             solve      wave 0: K11's Cholesky solve (k11_solve.inl); the standard errors come from the factor left in LDS
+//             gram       [X | z]' diag(W) [X | z] with K10's assignment of the (kt + 1)(kt + 2) / 2 entries to threads (tri_spread;
+//                        row partitions summed in partition order); the ones column is the constant 1
+//             solve      wave 0: the family's Cholesky solve (fit_solve.inl); the standard errors come from the factor left in LDS
 //   split     every other group, of any length: the segments of ensure_segments, two launches per iteration --
 //             segment pass  a workgroup per segment: the row pass from the group's current f64 coefficients (the start values in the
 //                        first pass) and the Gram partials of its 256-row tiles, written per segment
@@ -30,19 +30,15 @@
 //             The segments and the wave of a finished group exit at once.  The host launches the pair until a device counter of the
 //             groups that still iterate reads zero.
 //   predict   pred = mu, resid = y - mu, linpred = eta over every row of the frame as pols_least_squares leaves them: features and
-//             offsets zero-filled under every policy but "ignore", "drop" masks the rows outside the fit.  A lane owns 16 bytes of
-//             every column (streaming loads and stores), sums in f64 and rounds once.
+//             offsets zero-filled under every policy but "ignore", "drop" masks the rows outside the fit.  The walk is
+//             fit_predict_rows (fit_tile.inl): sums in f64 and rounds once.
 #include "k13_glm.hpp"
-#include "k11_solve.inl"
+#include "fit_launch.hpp"
+#include "fit_solve.inl"
 
 namespace pols {
 
-constexpr int K13_TILE = 256;                      // rows of a tile: one per thread
-constexpr int K13_SEG_TS = 257;                    // column stride of the segment pass's tile (odd, as K10's)
-constexpr size_t K13_LDS_BUDGET = 160 * 1024 - 256;
 constexpr size_t K13_LDS_HALF = 80 * 1024 - 256;   // a request up to here leaves room for a second workgroup on the CU
-constexpr double K13_EPS = 2.220446049250313e-16;
-constexpr double K13_DMAX = 1.79769313486231570815e308;
 
 // doubles in front of the tile: W and z per row, Gram partials (256), the packed Gram matrix, the Cholesky work and the inverse of
 // its factor (kt x (kt + 1) each), right-hand side, Gram diagonal, coefficients, four wave sums, two integer pairs
@@ -52,30 +48,29 @@ __host__ __device__ inline size_t k13_small(int kt) {
 }
 
 size_t k13_resident_lds(int kt, int cols, size_t elem, int tiles) {
-    const size_t rows = (size_t)tiles * K13_TILE;
+    const size_t rows = (size_t)tiles * FIT_TILE;
     return (sizeof(double) * (2 * rows + k13_small(kt)) + elem * (size_t)cols * (rows + 1) + 15) & ~(size_t)15;
 }
 
 int k13_resident_tiles(int kt, int cols, size_t elem, int per_cu) {
-    const size_t budget = per_cu >= 2 ? K13_LDS_HALF : K13_LDS_BUDGET;
+    const size_t budget = per_cu >= 2 ? K13_LDS_HALF : FIT_LDS_BUDGET;
     int nt = 0;
     while (k13_resident_lds(kt, cols, elem, nt + 1) <= budget) ++nt;
     return nt;
 }
 
-__device__ __forceinline__ double k13_nan() { return __longlong_as_double(0x7ff8000000000000LL); }
-__device__ __forceinline__ bool k13_finite(const double v) { return fabs(v) <= K13_DMAX; }
+__device__ __forceinline__ bool k13_finite(const double v) { return fabs(v) <= FIT_DBL_MAX; }
 
 // mu = g^-1(eta) clipped to the family's open range, and d(mu); a NaN stays a NaN
 __device__ __forceinline__ void k13_mean(const int family, const double eta, double &mu, double &d) {
     if (family == POLS_GLM_BINOMIAL) {
         double m = 1.0 / (1.0 + exp(-eta));
-        m = m < K13_EPS ? K13_EPS : m;
-        m = m > 1.0 - K13_EPS ? 1.0 - K13_EPS : m;
+        m = m < FIT_EPS ? FIT_EPS : m;
+        m = m > 1.0 - FIT_EPS ? 1.0 - FIT_EPS : m;
         mu = m; d = m * (1.0 - m);
     } else {
         double m = exp(eta);
-        m = m < K13_EPS ? K13_EPS : m;
+        m = m < FIT_EPS ? FIT_EPS : m;
         mu = m; d = m;
     }
 }
@@ -101,16 +96,6 @@ __device__ __forceinline__ void k13_work(const int family, const double y, const
     dev = w * k13_unit_deviance(family, y, mu);
 }
 
-// the sum of v over the 256 threads in a fixed order, in every thread; red: four doubles.  Two barriers.
-__device__ __forceinline__ double k13_block_sum(double v, double *red, const int lane, const int wv) {
-    v = wave_sum_row3(v);
-    if (lane == 63) red[wv] = v;
-    __syncthreads();
-    const double r = (red[0] + red[1]) + (red[2] + red[3]);
-    __syncthreads();
-    return r;
-}
-
 // rows [t0, t0 + 256) of the item [s, e) into xt (column stride ts, batch dtype): features 0 .. ku - 1 (nulls zero-filled unless
 // "ignore"), y at ku (NaN for a row outside the fit), then w and o where the batch has them.  Returns whether this thread's row
 // (t0 + tid) is a fitted row and, if so, its y, w, o; bad: a fitted row whose y is outside the family's domain.  Ends on a barrier.
@@ -118,10 +103,10 @@ template <typename T, bool STREAM>
 __device__ __forceinline__ bool k13_stage(const GlmArgs &a, const int64_t s, const int64_t e, const int64_t t0, T *xt, const int ts,
                                           double &yv, double &wv, double &ov, bool &bad) {
     using V = typename Vec16<T>::type;
-    constexpr int VEC = Vec16<T>::N, CH = K13_TILE / VEC;
+    constexpr int VEC = Vec16<T>::N, CH = FIT_TILE / VEC;
     const int tid = threadIdx.x, ku = a.k_user;
     const int wc = ku + 1, oc = ku + 1 + (a.w ? 1 : 0), nld = oc + (a.o ? 1 : 0);
-    for (int p = tid; p < nld * CH; p += 256) {
+    for (int p = tid; p < nld * CH; p += 256) {                    // (fit_stage's load loop, in the batch dtype and with the offset column)
         const int q = __builtin_amdgcn_readfirstlane(p / CH), ch = p - q * CH;     // (CH is 64 or 128: a wave stays inside one column)
         const int64_t row0 = t0 + (int64_t)ch * VEC;
         if (row0 >= e) continue;
@@ -163,34 +148,15 @@ __device__ __forceinline__ bool k13_stage(const GlmArgs &a, const int64_t s, con
     }
     if (a.o) xt[(size_t)oc * ts + tid] = fit ? (T)ov : T(0);
     bad = fit && !k13_in_domain(a.family, yv);
-    xt[(size_t)ku * ts + tid] = fit ? (T)yv : (T)k13_nan();
+    xt[(size_t)ku * ts + tid] = fit ? (T)yv : (T)fit_nan();
     __syncthreads();
     return fit;
 }
 
-// the thread's entries (i, j), i <= j, of the packed upper triangle of the (kt + 1) x (kt + 1) Gram matrix, as k10_gram_kernel spreads
-// them: with few entries several row partitions per entry, beyond 256 entries up to three per thread
-struct K13Entries {
-    int ei[3], ej[3];
-    bool on[3];
-    int parts, part;
-};
-__device__ __forceinline__ void k13_entries(const int kt, const int tid, K13Entries &en) {
-    const int nz = kt + 1, ne = nz * (nz + 1) / 2;
-    en.parts = ne < 256 ? 256 / ne : 1;
-    en.part = en.parts > 1 ? tid / ne : 0;
-#pragma unroll
-    for (int q = 0; q < 3; ++q) {
-        const int n = en.parts > 1 ? tid - en.part * ne : tid + 256 * q;
-        en.on[q] = en.parts > 1 ? (q == 0 && en.part < en.parts) : n < ne;
-        int i = 0, t = en.on[q] ? n : 0;
-        while (t >= nz - i) { t -= nz - i; ++i; }
-        en.ei[q] = i; en.ej[q] = i + t;
-    }
-}
-// acc += sum over the rows [0, rows) of W x_i x_j; column c of [X | z]: c < ku the tile's, ku < kt the ones column, kt the z column
+// tri_accumulate with the terms W x_i x_j over the rows [0, rows); column c of [X | z]: c < ku the tile's, ku < kt the ones column, kt
+// the z column
 template <typename T>
-__device__ __forceinline__ void k13_accumulate(const K13Entries &en, double (&acc)[3], const T *xt, const int ts, const double *Wv,
+__device__ __forceinline__ void k13_accumulate(const TriSpread &en, double (&acc)[3], const T *xt, const int ts, const double *Wv,
                                                const double *zv, const int rows, const int ku, const int kt) {
 #pragma unroll
     for (int q = 0; q < 3; ++q) {
@@ -207,26 +173,6 @@ __device__ __forceinline__ void k13_accumulate(const K13Entries &en, double (&ac
         acc[q] = v;
     }
 }
-// acc -> out[0 .. ne) (LDS or global); gp: 256 doubles of LDS.  Ends on a barrier.
-__device__ __forceinline__ void k13_reduce(const K13Entries &en, double (&acc)[3], double *gp, double *out, const int kt, const int tid) {
-    const int nz = kt + 1, ne = nz * (nz + 1) / 2;
-    if (en.parts > 1) {
-        if (en.on[0]) gp[en.part * ne + (tid - en.part * ne)] = acc[0];
-        __syncthreads();
-        if (tid < ne) {
-            double v = 0.0;
-            for (int p = 0; p < en.parts; ++p) v += gp[p * ne + tid];
-            out[tid] = v;
-        }
-    } else {
-#pragma unroll
-        for (int q = 0; q < 3; ++q)
-            if (en.on[q]) out[tid + 256 * q] = acc[q];
-    }
-    acc[0] = acc[1] = acc[2] = 0.0;
-    __syncthreads();
-}
-
 // se_j = sqrt([(L L')^-1]_jj) from the factor L in the lower triangle of A: lane j builds column j of L^-1 in Li.  One wave.
 __device__ __forceinline__ double k13_std_error(const double *A, double *Li, const int kt, const int lane) {
     const int LD = kt + 1;
@@ -248,11 +194,10 @@ __device__ __forceinline__ void k13_put_coef(const GlmArgs &a, const int64_t g, 
     if (a.coef) { if (a.f32) static_cast<float *>(a.coef)[(size_t)g * a.kt + j] = (float)v; else static_cast<double *>(a.coef)[(size_t)g * a.kt + j] = v; }
 }
 
+// the tiles of group g, whatever its segments
 template <typename T>
 __device__ __forceinline__ int k13_group_tiles(const GlmArgs &a, const int64_t g) {
-    const int64_t s = a.offs[g], e = a.offs[g + 1];
-    const int64_t t = e > s ? (e - (s & ~(int64_t)(Vec16<T>::N - 1)) + K13_TILE - 1) / K13_TILE : 0;
-    return (int)min(t, (int64_t)0x7fffffff);
+    return (int)min(fit_tiles<T>(a.offs[g], a.offs[g + 1]), (int64_t)0x7fffffff);
 }
 
 // ---------------------------------------------------------------- resident
@@ -260,18 +205,16 @@ template <typename T>
 __global__ void __launch_bounds__(256) k13_glm_resident(const GlmArgs a) {
     extern __shared__ __attribute__((aligned(16))) double dyn[];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, kt = a.kt, ku = a.k_user, nz = kt + 1, ne = nz * (nz + 1) / 2, LD = kt + 1;
-    const int64_t g = blockIdx.x, s = a.offs[g], e = a.offs[g + 1];
-    const int64_t base = s & ~(int64_t)(Vec16<T>::N - 1);          // the tile grid starts on the columns' 16-byte grid
-    const int ntiles = k13_group_tiles<T>(a, g);
-    if (ntiles <= a.res_from || ntiles > a.res_to) return;         // the other resident launch's or the split form's group
+    const int64_t g = blockIdx.x, s = a.offs[g], e = a.offs[g + 1], base = fit_base<T>(s), gt = fit_tiles<T>(s, e);
+    if (gt <= a.res_from || gt > a.res_to) return;                 // the other resident launch's or the split form's group
+    const int ntiles = (int)gt;
     const int ts = a.ts, R = ts - 1, fam = a.family;
     double *Wv = dyn, *zv = Wv + R, *gp = zv + R, *Gm = gp + 256;
     double *A = Gm + ((ne + 1) & ~1), *Li = A + kt * LD, *rhs = Li + kt * LD, *d0 = rhs + kt, *bc = d0 + kt, *red = bc + kt;
     int *cnt = reinterpret_cast<int *>(red + 4);                   // fitted rows, rows outside the domain, the solve's verdict
     T *xs = reinterpret_cast<T *>(red + 6);                        // (k_user + 1 + [w] + [o]) x ts
     const int wc = ku + 1, oc = ku + 1 + (a.w ? 1 : 0);
-    K13Entries en;
-    k13_entries(kt, tid, en);
+    const TriSpread en = tri_spread(kt + 1, tid);
     double acc[3] = {0.0, 0.0, 0.0};
 
     // ---- start: stage, count, mu0 / eta0 / D0, the first W and z
@@ -281,7 +224,7 @@ __global__ void __launch_bounds__(256) k13_glm_resident(const GlmArgs a) {
     for (int it = 0; it < ntiles; ++it) {
         double yv, w, o;
         bool bad;
-        const bool fit = k13_stage<T, true>(a, s, e, base + (int64_t)it * K13_TILE, xs + (size_t)it * K13_TILE, ts, yv, w, o, bad);
+        const bool fit = k13_stage<T, true>(a, s, e, base + (int64_t)it * FIT_TILE, xs + (size_t)it * FIT_TILE, ts, yv, w, o, bad);
         double W = 0.0, z = 0.0;
         if (fit && !bad) {
             double mu, eta, dev;
@@ -290,13 +233,13 @@ __global__ void __launch_bounds__(256) k13_glm_resident(const GlmArgs a) {
             k13_work(fam, yv, w, o, eta, mu, d, W, z, dev);
             dsum += dev;
         }
-        Wv[it * K13_TILE + tid] = W;
-        zv[it * K13_TILE + tid] = z;
+        Wv[it * FIT_TILE + tid] = W;
+        zv[it * FIT_TILE + tid] = z;
         const unsigned long long m = __ballot(fit);
         if (lane == 0 && m) atomicAdd(&cnt[0], (int)__popcll(m));
         if (bad) cnt[1] = 1;
     }
-    double D = 2.0 * k13_block_sum(dsum, red, lane, wv);
+    double D = 2.0 * fit_block_sum(dsum, red, lane, wv);
     const int n = cnt[0];
     int status = POLS_GROUP_OK, iters = 0;
     if (n == 0) status = POLS_GROUP_EMPTY;
@@ -305,9 +248,9 @@ __global__ void __launch_bounds__(256) k13_glm_resident(const GlmArgs a) {
         const int nr = (int)(e - base);
         for (;;) {
             k13_accumulate<T>(en, acc, xs, ts, Wv, zv, nr, ku, kt);
-            k13_reduce(en, acc, gp, Gm, kt, tid);
+            tri_reduce(en, acc, gp, Gm);
             if (wv == 0) {
-                const bool ok = k11_chol_solve(Gm, A, rhs, d0, kt, lane);
+                const bool ok = fit_chol_solve(Gm, A, rhs, d0, kt, lane);
                 if (lane == 0) cnt[2] = ok ? 1 : 0;
             }
             __syncthreads();
@@ -317,7 +260,7 @@ __global__ void __launch_bounds__(256) k13_glm_resident(const GlmArgs a) {
             dsum = 0.0;
             const double icpt = kt > ku ? bc[ku] : 0.0;
             for (int it = 0; it < ntiles; ++it) {                  // the row pass: eta, mu, the deviance term, the next W and z
-                const int r = it * K13_TILE + tid;
+                const int r = it * FIT_TILE + tid;
                 const double yv = (double)xs[(size_t)ku * ts + r];
                 if (yv == yv) {
                     double eta = icpt;
@@ -331,7 +274,7 @@ __global__ void __launch_bounds__(256) k13_glm_resident(const GlmArgs a) {
                     dsum += dev;
                 }
             }
-            const double Dn = 2.0 * k13_block_sum(dsum, red, lane, wv);
+            const double Dn = 2.0 * fit_block_sum(dsum, red, lane, wv);
             ++iters;
             if (!k13_finite(Dn)) { status = POLS_GROUP_FALLBACK; break; }
             const bool conv = fabs(Dn - D) <= a.tol * (fabs(Dn) + 0.1);
@@ -343,14 +286,14 @@ __global__ void __launch_bounds__(256) k13_glm_resident(const GlmArgs a) {
     __syncthreads();
     // ---- outputs
     const bool fitted = status == POLS_GROUP_OK || status == POLS_GROUP_NOT_CONVERGED;
-    if (tid < kt) k13_put_coef(a, g, tid, fitted ? bc[tid] : (status == POLS_GROUP_EMPTY ? 0.0 : k13_nan()));
+    if (tid < kt) k13_put_coef(a, g, tid, fitted ? bc[tid] : (status == POLS_GROUP_EMPTY ? 0.0 : fit_nan()));
     if (wv == 0 && a.se) {
-        const double se = fitted ? k13_std_error(A, Li, kt, lane) : k13_nan();
+        const double se = fitted ? k13_std_error(A, Li, kt, lane) : fit_nan();
         if (lane < kt) a.se[(size_t)g * kt + lane] = se;
     }
     if (tid == 0) {
         if (a.status) a.status[g] = status;
-        if (a.deviance) a.deviance[g] = fitted ? D : k13_nan();
+        if (a.deviance) a.deviance[g] = fitted ? D : fit_nan();
         if (a.n_iter) a.n_iter[g] = iters;
     }
 }
@@ -358,16 +301,10 @@ __global__ void __launch_bounds__(256) k13_glm_resident(const GlmArgs a) {
 template <typename T>
 static int k13_resident_launch_t(pols_ctx *ctx, const GlmArgs &a) {
     const int cols = a.k_user + 1 + (a.w ? 1 : 0) + (a.o ? 1 : 0);
-    const size_t lds = k13_resident_lds(a.kt, cols, sizeof(T), (a.ts - 1) / K13_TILE);
-    if (lds > K13_LDS_BUDGET) return fail(POLS_ERR_UNSUPPORTED, "glm: %d columns x %d rows exceed the LDS of a workgroup", a.kt, a.ts);
+    const size_t lds = k13_resident_lds(a.kt, cols, sizeof(T), (a.ts - 1) / FIT_TILE);
+    if (lds > FIT_LDS_BUDGET) return fail(POLS_ERR_UNSUPPORTED, "glm: %d columns x %d rows exceed the LDS of a workgroup", a.kt, a.ts);
     static OncePerDevice once;
-    if (once.needed(ctx->device)) {
-        POLS_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k13_glm_resident<T>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)K13_LDS_BUDGET));
-        once.done(ctx->device);
-    }
-    hipLaunchKernelGGL(k13_glm_resident<T>, dim3((unsigned)a.n_groups), dim3(256), lds, ctx->stream, a);
-    POLS_HIP(hipGetLastError());
-    return POLS_OK;
+    return fit_launch(ctx, &k13_glm_resident<T>, once, a.n_groups, 256, lds, FIT_LDS_BUDGET, a);
 }
 
 int k13_resident_launch(pols_ctx *ctx, int dtype, const GlmArgs &a) {
@@ -377,31 +314,20 @@ int k13_resident_launch(pols_ctx *ctx, int dtype, const GlmArgs &a) {
 }
 
 // ---------------------------------------------------------------- split: the segment pass
-// the item of this workgroup: its group and its rows
-__device__ __forceinline__ void k13_item(const GlmArgs &a, int64_t &g, int64_t &s, int64_t &e) {
-    const int64_t sgi = blockIdx.x;
-    g = a.seg_offs ? (int64_t)a.seg_map[sgi] : sgi;
-    s = a.seg_offs ? a.seg_offs[sgi] : a.offs[g];
-    e = a.seg_offs ? a.seg_offs[sgi + 1] : a.offs[g + 1];
-}
-
 template <typename T>
 __global__ void __launch_bounds__(256) k13_glm_split(const GlmArgs a, const int first) {
     extern __shared__ __attribute__((aligned(16))) double dyn[];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, kt = a.kt, ku = a.k_user, nz = kt + 1, ne = nz * (nz + 1) / 2;
-    int64_t g, s, e;
-    k13_item(a, g, s, e);
+    int64_t g, s, e, base, ntiles;
+    fit_item<T>(a, g, s, e, base, ntiles);
     if (k13_group_tiles<T>(a, g) <= a.res_tiles) return;           // the resident form's group
     const double *st = a.state + (size_t)g * k13_state_stride(kt);
     if (!first && st[0] == 0.0) return;                            // a finished group
-    const int ts = K13_SEG_TS, fam = a.family;
-    double *Wv = dyn, *zv = Wv + K13_TILE, *gp = zv + K13_TILE, *bc = gp + 256, *red = bc + 32;
+    const int ts = FIT_TS, fam = a.family;
+    double *Wv = dyn, *zv = Wv + FIT_TILE, *gp = zv + FIT_TILE, *bc = gp + 256, *red = bc + 32;
     int *cnt = reinterpret_cast<int *>(red + 4);
     T *xs = reinterpret_cast<T *>(red + 6);
-    const int64_t base = s & ~(int64_t)(Vec16<T>::N - 1);
-    const int64_t ntiles = e > s ? (e - base + K13_TILE - 1) / K13_TILE : 0;
-    K13Entries en;
-    k13_entries(kt, tid, en);
+    const TriSpread en = tri_spread(kt + 1, tid);
     double acc[3] = {0.0, 0.0, 0.0};
     if (tid == 0) { cnt[0] = 0; cnt[1] = 0; }
     if (tid < kt) bc[tid] = first ? 0.0 : st[4 + tid];
@@ -409,7 +335,7 @@ __global__ void __launch_bounds__(256) k13_glm_split(const GlmArgs a, const int 
     const double icpt = kt > ku ? bc[ku] : 0.0;
     double dsum = 0.0;
     for (int64_t it = 0; it < ntiles; ++it) {
-        const int64_t t0 = base + it * K13_TILE;
+        const int64_t t0 = base + it * FIT_TILE;
         double yv, w, o;
         bool bad;
         const bool fit = k13_stage<T, false>(a, s, e, t0, xs, ts, yv, w, o, bad);   // (plain loads: the next iteration reads the rows again, from L2 / MALL)
@@ -433,12 +359,12 @@ __global__ void __launch_bounds__(256) k13_glm_split(const GlmArgs a, const int 
         if (lane == 0 && m) atomicAdd(&cnt[0], (int)__popcll(m));
         if (bad) cnt[1] = 1;
         __syncthreads();
-        k13_accumulate<T>(en, acc, xs, ts, Wv, zv, (int)min((int64_t)K13_TILE, e - t0), ku, kt);
+        k13_accumulate<T>(en, acc, xs, ts, Wv, zv, (int)min((int64_t)FIT_TILE, e - t0), ku, kt);
         __syncthreads();                                           // the next tile overwrites xs
     }
     double *out = a.part + (size_t)blockIdx.x * k13_part_stride(kt);
-    k13_reduce(en, acc, gp, out, kt, tid);
-    const double dev = k13_block_sum(dsum, red, lane, wv);
+    tri_reduce(en, acc, gp, out);
+    const double dev = fit_block_sum(dsum, red, lane, wv);
     if (tid == 0) { out[ne] = dev; out[ne + 1] = (double)cnt[0]; out[ne + 2] = (double)cnt[1]; }
 }
 
@@ -458,7 +384,7 @@ __global__ void __launch_bounds__(64) k13_glm_split_group(const GlmArgs a, const
         for (int64_t it = v0; it < v1; ++it) v += a.part[(size_t)it * ps + en];
         Gm[en] = v;
     }
-    k11_wave_sync();
+    fit_wave_sync();
     const double D = 2.0 * Gm[ne];
     int status = -1, iters = first ? 0 : (int)st[2];               // -1: the iteration goes on
     if (first) {
@@ -471,10 +397,10 @@ __global__ void __launch_bounds__(64) k13_glm_split_group(const GlmArgs a, const
         else if (iters >= a.max_iter) status = POLS_GROUP_NOT_CONVERGED;
     }
     if (status < 0) {
-        const bool ok = k11_chol_solve(Gm, A, rhs, d0, kt, lane);
+        const bool ok = fit_chol_solve(Gm, A, rhs, d0, kt, lane);
         if (!ok) status = POLS_GROUP_FALLBACK;
         else {
-            k11_wave_sync();
+            fit_wave_sync();
             const double se = k13_std_error(A, Li, kt, lane);
             if (lane < kt) { st[4 + lane] = rhs[lane]; st[4 + kt + lane] = se; }
             if (lane == 0) { st[0] = 1.0; st[1] = D; st[2] = (double)(iters + 1); }
@@ -484,12 +410,12 @@ __global__ void __launch_bounds__(64) k13_glm_split_group(const GlmArgs a, const
     // ---- finished: outputs
     const bool fitted = status == POLS_GROUP_OK || status == POLS_GROUP_NOT_CONVERGED;
     if (lane < kt) {
-        k13_put_coef(a, g, lane, fitted ? st[4 + lane] : (status == POLS_GROUP_EMPTY ? 0.0 : k13_nan()));
-        if (a.se) a.se[(size_t)g * kt + lane] = fitted ? st[4 + kt + lane] : k13_nan();
+        k13_put_coef(a, g, lane, fitted ? st[4 + lane] : (status == POLS_GROUP_EMPTY ? 0.0 : fit_nan()));
+        if (a.se) a.se[(size_t)g * kt + lane] = fitted ? st[4 + kt + lane] : fit_nan();
     }
     if (lane == 0) {
         if (a.status) a.status[g] = status;
-        if (a.deviance) a.deviance[g] = fitted ? D : k13_nan();
+        if (a.deviance) a.deviance[g] = fitted ? D : fit_nan();
         if (a.n_iter) a.n_iter[g] = iters;
         st[0] = 0.0;
         atomicSub(a.active, 1);
@@ -498,20 +424,15 @@ __global__ void __launch_bounds__(64) k13_glm_split_group(const GlmArgs a, const
 
 static size_t k13_group_lds(int kt) { return sizeof(double) * ((size_t)(kt + 1) * (kt + 2) / 2 + 3 + 2 * (size_t)kt * (kt + 1) + 2 * (size_t)kt); }
 static size_t k13_split_lds(int cols, size_t elem) {
-    return (sizeof(double) * (3 * 256 + 32 + 4 + 2) + elem * (size_t)cols * K13_SEG_TS + 15) & ~(size_t)15;
+    return (sizeof(double) * (3 * 256 + 32 + 4 + 2) + elem * (size_t)cols * FIT_TS + 15) & ~(size_t)15;
 }
 
 template <typename T>
 static int k13_split_launch_t(pols_ctx *ctx, const GlmArgs &a, bool first) {
     const int cols = a.k_user + 1 + (a.w ? 1 : 0) + (a.o ? 1 : 0);
     static OncePerDevice once;
-    if (once.needed(ctx->device)) {
-        POLS_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k13_glm_split<T>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)K13_LDS_BUDGET));
-        once.done(ctx->device);
-    }
-    const int64_t n_items = a.seg_offs ? a.n_seg : a.n_groups;
-    hipLaunchKernelGGL(k13_glm_split<T>, dim3((unsigned)n_items), dim3(256), k13_split_lds(cols, sizeof(T)), ctx->stream, a, first ? 1 : 0);
-    POLS_HIP(hipGetLastError());
+    const int rc = fit_launch(ctx, &k13_glm_split<T>, once, fit_items(a), 256, k13_split_lds(cols, sizeof(T)), FIT_LDS_BUDGET, a, first ? 1 : 0);
+    if (rc) return rc;
     hipLaunchKernelGGL(k13_glm_split_group, dim3((unsigned)a.n_groups), dim3(64), k13_group_lds(a.kt), ctx->stream, a, first ? 1 : 0);
     POLS_HIP(hipGetLastError());
     return POLS_OK;
@@ -526,89 +447,26 @@ int k13_split_launch(pols_ctx *ctx, int dtype, const GlmArgs &a, bool first) {
 // ---------------------------------------------------------------- predict
 template <typename T>
 __global__ void __launch_bounds__(256) k13_glm_predict(const GlmArgs a) {
-    using V = typename Vec16<T>::type;
-    constexpr int VEC = Vec16<T>::N;
-    const int tid = threadIdx.x, ku = a.k_user, kt = a.kt, pol = a.null_policy, fam = a.family;
-    int64_t g, s, e;
-    k13_item(a, g, s, e);
+    const int ku = a.k_user, kt = a.kt, fam = a.family;
+    int64_t g, s, e, base, ntiles;
+    fit_item<T>(a, g, s, e, base, ntiles);
     if (e <= s) return;
-    const int64_t base = s & ~(int64_t)(VEC - 1);
     const double *cg = a.coef64 + (size_t)g * kt;
-    const double icpt = kt > ku ? cg[ku] : 0.0;
-    const T *yp = static_cast<const T *>(a.y), *op = static_cast<const T *>(a.o);
-    T *pred = static_cast<T *>(a.pred), *resid = static_cast<T *>(a.resid), *linp = static_cast<T *>(a.linpred);
-    const int64_t nch = (e - base + VEC - 1) / VEC;
-    for (int64_t c = tid; c < nch; c += 256) {
-        const int64_t row0 = base + c * VEC;
-        const bool whole = row0 + VEC <= a.n_rows;                 // (else: the one chunk across the end of the columns, row by row)
-        const bool full = whole && row0 >= s && row0 + VEC <= e;
-        double p[VEC];
-        bool nullx[VEC];
-#pragma unroll
-        for (int v = 0; v < VEC; ++v) { p[v] = icpt; nullx[v] = false; }
-#pragma unroll
-        for (int j = 0; j <= POLS_MAX_FEATURES; ++j) {             // (the last turn: the offset column)
-            const bool off = j == POLS_MAX_FEATURES;
-            if (off ? op != nullptr : j < ku) {
-                const T *xp = off ? op : static_cast<const T *>(a.x[j < POLS_MAX_FEATURES ? j : 0]);
-                const double cj = off ? 1.0 : cg[j < POLS_MAX_FEATURES ? j : 0];
-                T xv[VEC];
-                if (whole) {
-                    const V ld = load_stream(reinterpret_cast<const V *>(xp + row0));
-#pragma unroll
-                    for (int v = 0; v < VEC; ++v) xv[v] = vget<T>(ld, v);
-                } else {
-#pragma unroll
-                    for (int v = 0; v < VEC; ++v) xv[v] = row0 + v < a.n_rows ? xp[row0 + v] : T(0);
-                }
-#pragma unroll
-                for (int v = 0; v < VEC; ++v) {
-                    nullx[v] = nullx[v] || xv[v] != xv[v];
-                    if (off) p[v] += (double)null_fill<T>(pol, xv[v]);
-                    else p[v] = fma((double)null_fill<T>(pol, xv[v]), cj, p[v]);
-                }
-            }
-        }
-        T pv[VEC], rv[VEC], lv[VEC];
-#pragma unroll
-        for (int v = 0; v < VEC; ++v) {
-            const int64_t r = row0 + v;
-            const bool in = r >= s && r < e;
-            const T yv = in ? yp[r] : T(0);
-            double eta = p[v];
-            if (pol == POLS_NULL_DROP) {                           // the rows that were not part of the fit (ex.rs:409-417)
-                const bool fit = !(a.valid && in && !a.valid[r]) && yv == yv && !nullx[v];
-                if (!fit) eta = k13_nan();
-            }
-            double mu, d;
-            k13_mean(fam, eta, mu, d);
-            lv[v] = (T)eta;
-            pv[v] = (T)mu;
-            rv[v] = (T)((double)yv - mu);
-        }
-        if (full) {
-            if constexpr (VEC == 4) {
-                if (pred) store_stream(reinterpret_cast<V *>(pred + row0), V{pv[0], pv[1], pv[2], pv[3]});
-                if (resid) store_stream(reinterpret_cast<V *>(resid + row0), V{rv[0], rv[1], rv[2], rv[3]});
-                if (linp) store_stream(reinterpret_cast<V *>(linp + row0), V{lv[0], lv[1], lv[2], lv[3]});
-            } else {
-                if (pred) store_stream(reinterpret_cast<V *>(pred + row0), V{pv[0], pv[1]});
-                if (resid) store_stream(reinterpret_cast<V *>(resid + row0), V{rv[0], rv[1]});
-                if (linp) store_stream(reinterpret_cast<V *>(linp + row0), V{lv[0], lv[1]});
-            }
-        } else {
-#pragma unroll
-            for (int v = 0; v < VEC; ++v) {
-                const int64_t r = row0 + v;
-                if (r >= s && r < e) { if (pred) pred[r] = pv[v]; if (resid) resid[r] = rv[v]; if (linp) linp[r] = lv[v]; }
-            }
-        }
-    }
+    T *const out[3] = {static_cast<T *>(a.pred), static_cast<T *>(a.resid), static_cast<T *>(a.linpred)};
+    fit_predict_rows<T>(a, s, e, base, cg, kt > ku ? cg[ku] : 0.0, static_cast<const T *>(a.o), out,
+                        [&](double eta, const double yv, const int64_t, const bool, const bool fit, double (&o)[3]) {
+                            if (!fit) eta = fit_nan();
+                            double mu, d;
+                            k13_mean(fam, eta, mu, d);
+                            o[0] = mu;
+                            o[1] = yv - mu;
+                            o[2] = eta;
+                        });
 }
 
 int k13_predict_launch(pols_ctx *ctx, int dtype, const GlmArgs &a) {
     if (a.n_groups == 0 || a.n_rows == 0 || (!a.pred && !a.resid && !a.linpred)) return POLS_OK;
-    const int64_t n_items = a.seg_offs ? a.n_seg : a.n_groups;
+    const int64_t n_items = fit_items(a);
     if (dtype == POLS_F32) hipLaunchKernelGGL(k13_glm_predict<float>, dim3((unsigned)n_items), dim3(256), 0, ctx->stream, a);
     else hipLaunchKernelGGL(k13_glm_predict<double>, dim3((unsigned)n_items), dim3(256), 0, ctx->stream, a);
     POLS_HIP(hipGetLastError());

@@ -15,27 +15,25 @@
 //   moments  K10's Gram launch (k10_gram_launch) over the concatenated column list [X1 | X2 | Z2 | 1 | y]: the packed upper triangle
 //            of the (T + 1) x (T + 1) cross-moments and the fitted-row count per item.
 //   solve    one wave per group: the partials summed in segment order, A and [C | Z~'y~] gathered from the moments, A factored
-//            (k11_chol_factor), lane c substitutes column c of [Q | r], M and Q'r spread over the lanes, M b = Q'r by k11_chol_solve,
+//            (fit_chol_factor), lane c substitutes column c of [Q | r], M and Q'r spread over the lanes, M b = Q'r by fit_chol_solve,
 //            then the Sargan numerator, the first-stage diagnostics (lane j = endogenous column j), the inverse of M's factor (lane c =
 //            column c), M^-1 and Pi.  b, M^-1 and Pi go to the group's state; coef, status, n_obs, first_stage_f and partial_r2 are final.
 //            Dynamic LDS, sized by T: k14_solve_lds -- 39 440 bytes at kx = 30, L = 31 (T = 31); 2 632 at 3 + 2 + 1 regressors, 4 instruments.
-//   rows     256-row tiles staged by k10_stage (16-byte streaming loads); the thread of a row computes e~_i and adds e~_i^2 to its own
+//   rows     256-row tiles staged by fit_stage (16-byte streaming loads); the thread of a row computes e~_i and adds e~_i^2 to its own
 //            sum, tiles in order; at the end DPP within a wave, the waves as (0 + 1) + (2 + 3).  ROBUST (HC0 / HC1): the thread also
 //            forms x^_i = Pi'z~_i with Pi and b read at one LDS address by every lane (broadcasts), parks u_i = e~_i x^_i beside the
-//            tile, and the kx (kx + 1) / 2 entries of sum u_i u_i' are accumulated with K10's entry-to-thread assignment (k10_entries).
+//            tile, and the kx (kx + 1) / 2 entries of sum u_i u_i' are accumulated with K10's entry-to-thread assignment (tri_spread).
 //            Not launched when no wanted output needs a residual (coefficients and first-stage diagnostics: the frame is read once).
 //            The plain form is given the regressors and y alone (a.k_user = n_feat, a.kt = kx) unless a null instrument drops rows.
 //   finish   one wave per group: the items' partials summed in order, sigma2, V, se / t / p, Sargan and its p-value, cov.
 //   predict  K10's prediction launch from the f64 coefficients (api.hip).
 #include "k14_iv.hpp"
 #include "k10_ridge_path.hpp"
-#include "k10_stage.inl"
-#include "k11_solve.inl"
+#include "fit_launch.hpp"
+#include "fit_solve.inl"
 #include "k7_stats.hpp"
 
 namespace pols {
-
-__device__ __forceinline__ double k14_nan() { return __longlong_as_double(0x7ff8000000000000LL); }
 
 // offsets (doubles) of the solve launch's LDS areas
 struct K14Lds { int Gs, A, d0, B, Gm2, A2, rhs2, d02, Ri, tmp, total; };
@@ -75,15 +73,15 @@ __global__ void __launch_bounds__(64) k14_solve_kernel(const IvArgs a) {
         double v = 0.0;
         for (int64_t it = v0; it < v1; ++it) v += a.gram_part[(size_t)it * gs + en];
         Gs[en] = v;
-        fin = fin && fabs(v) <= 1.79769313486231570815e308;
+        fin = fin && fabs(v) <= FIT_DBL_MAX;
     }
     const bool finite = __ballot(!fin) == 0;
-    k11_wave_sync();
+    fit_wave_sync();
     const double n = Gs[ne];
     // where column i of X and column l of Z (factorisation order [X1 | 1 | Z2]) sit in the staged list [X1 | X2 | Z2 | 1]
     auto xg = [&](int i) { return i < nf ? i : T - 1; };
     auto zg = [&](int l) { return l < k1 ? l : (icpt && l == k1 ? T - 1 : nf + (l - k1 - icpt)); };
-    auto S = [&](int p, int q) { const int i = p < q ? p : q, j = p < q ? q : p; return Gs[i * nz - i * (i - 1) / 2 + (j - i)]; };
+    auto S = [&](int p, int q) { const int i = p < q ? p : q, j = p < q ? q : p; return Gs[tri_index(i, j, nz)]; };
     bool ok = finite && n > (double)L;
     if (ok) {
         for (int p = lane; p < L * L; p += 64) {
@@ -96,8 +94,8 @@ __global__ void __launch_bounds__(64) k14_solve_kernel(const IvArgs a) {
             const int l = p / LDB, c = p - l * LDB;
             B[l * LDB + c] = S(zg(l), c < kx ? xg(c) : T);
         }
-        k11_wave_sync();
-        ok = k11_chol_factor(A, d0, L, lane);
+        fit_wave_sync();
+        ok = fit_chol_factor(A, d0, L, lane);
     }
     if (ok) {
         if (lane < LDB) {                                          // R [Q | r] = [C | Z~'y~]: lane c owns column c
@@ -107,20 +105,19 @@ __global__ void __launch_bounds__(64) k14_solve_kernel(const IvArgs a) {
                 B[j * LDB + lane] = s / A[j * LD + j];
             }
         }
-        k11_wave_sync();
-        for (int en = lane; en < (kx + 1) * (kx + 2) / 2; en += 64) {   // [Q | r]'[Q | r], packed as k11_chol_solve reads it
-            int i = 0, t = en;
-            while (t >= LDB - i) { t -= LDB - i; ++i; }
-            const int j = i + t;
+        fit_wave_sync();
+        for (int en = lane; en < (kx + 1) * (kx + 2) / 2; en += 64) {   // [Q | r]'[Q | r], packed as fit_chol_solve reads it
+            int i, j;
+            tri_unpack(en, LDB, i, j);
             double v = 0.0;
             for (int l = 0; l < L; ++l) v = fma(B[l * LDB + i], B[l * LDB + j], v);
             Gm2[en] = v;
         }
-        k11_wave_sync();
-        ok = k11_chol_solve(Gm2, A2, rhs2, d02, kx, lane);
+        fit_wave_sync();
+        ok = fit_chol_solve(Gm2, A2, rhs2, d02, kx, lane);
     }
     double *st = a.state + (size_t)g * k14_state_stride(kx, L);
-    double fsf = k14_nan(), pr2 = k14_nan();
+    double fsf = fit_nan(), pr2 = fit_nan();
     if (ok) {
         if (lane < L) {                                            // the Sargan terms r - Q b
             double v = B[lane * LDB + kx];
@@ -146,7 +143,7 @@ __global__ void __launch_bounds__(64) k14_solve_kernel(const IvArgs a) {
                 Ri[j * kx + lane] = j < lane ? 0.0 : s / A2[j * LD2 + j];
             }
         }
-        k11_wave_sync();
+        fit_wave_sync();
         if (lane == 0) {
             double v = 0.0;
             for (int l = 0; l < L; ++l) v += tmp[l];
@@ -173,12 +170,12 @@ __global__ void __launch_bounds__(64) k14_solve_kernel(const IvArgs a) {
     if (lane == 0) {
         st[0] = n;
         st[1] = ok ? 1.0 : 0.0;
-        if (!ok) st[2] = k14_nan();
+        if (!ok) st[2] = fit_nan();
         st[3] = 0.0;
         if (a.status) a.status[g] = !(n > 0.0) ? POLS_GROUP_EMPTY : (!(n > (double)L) ? POLS_GROUP_BAD_DOF : (ok ? POLS_GROUP_OK : POLS_GROUP_FALLBACK));
         if (a.n_obs) a.n_obs[g] = (int64_t)n;
     }
-    const double fillv = n > 0.0 ? k14_nan() : 0.0;                // no rows: zeros, as the existing entries
+    const double fillv = n > 0.0 ? fit_nan() : 0.0;                // no rows: zeros, as the existing entries
     if (lane < kx) {
         const double bv = ok ? rhs2[lane] : fillv;
         st[4 + lane] = bv;
@@ -209,31 +206,26 @@ __global__ void __launch_bounds__(256) k14_rows_kernel(const IvArgs a) {
     extern __shared__ __attribute__((aligned(16))) double dyn[];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, TT = a.kt;
     const int nf = a.n_feat, icpt = a.icpt, kx = nf + icpt, k1 = nf - a.n_endog, L = kx - a.n_endog + a.n_inst;
-    constexpr int ts = ROBUST ? K10_GRAM_TS : K10_TILE;            // (robust: the parked columns are read across threads)
+    constexpr int ts = ROBUST ? FIT_TS : FIT_TILE;            // (robust: the parked columns are read across threads)
     double *xs = dyn;                                              // (T + 2) x ts
     double *us = xs + (size_t)(TT + 2) * ts;                       // ROBUST: kx x ts
     double *bs = us + (ROBUST ? (size_t)kx * ts : 0);              // kx
     double *Ps = bs + kx;                                          // ROBUST: L x kx
     double *red = Ps + (ROBUST ? L * kx : 0);                      // 4
     int64_t g, s, e, base, ntiles;
-    k10_item<T>(a, g, s, e, base, ntiles);
+    fit_item<T>(a, g, s, e, base, ntiles);
     const double *st = a.state + (size_t)g * k14_state_stride(kx, L);
     if (st[1] == 0.0) ntiles = 0;                                  // no fit: nothing to sum (workgroup-uniform)
     if (tid < kx) bs[tid] = st[4 + tid];
     if constexpr (ROBUST)
         for (int q = tid; q < L * kx; q += 256) Ps[q] = st[4 + kx + kx * kx + q];
-    const int nme = kx * (kx + 1) / 2;
-    const int parts = nme < 256 ? 256 / nme : 1;
-    const int part = parts > 1 ? tid / nme : 0;
-    int ei[3], ej[3];
-    bool on[3];
-    k10_entries(kx, parts, part, ei, ej, on);
+    const TriSpread sp = tri_spread(kx, tid);                      // the kx (kx + 1) / 2 entries of sum u_i u_i'
     double acc[3] = {0.0, 0.0, 0.0};
     double rss = 0.0;
     __syncthreads();
     for (int64_t it = 0; it < ntiles; ++it) {
-        const int64_t t0 = base + it * K10_TILE;
-        const bool fit = k10_stage<T, true>(a, s, e, t0, xs, ts);
+        const int64_t t0 = base + it * FIT_TILE;
+        const bool fit = fit_stage<T, true>(a, s, e, t0, xs, ts);
         double f = 0.0;
         for (int i = 0; i < nf; ++i) f = fma(xs[(size_t)i * ts + tid], bs[i], f);
         if (icpt) f = fma(xs[(size_t)(TT - 1) * ts + tid], bs[nf], f);
@@ -246,60 +238,27 @@ __global__ void __launch_bounds__(256) k14_rows_kernel(const IvArgs a) {
                 us[(size_t)c * ts + tid] = fit ? ev * xh : 0.0;
             }
             __syncthreads();
-            const int rows_here = (int)min((int64_t)K10_TILE, e - t0);
-#pragma unroll
-            for (int q = 0; q < 3; ++q) {
-                if (!on[q]) continue;
-                const double *ci = us + (size_t)ei[q] * ts, *cj = us + (size_t)ej[q] * ts;
-                double v = acc[q];
-                for (int r = part; r < rows_here; r += parts) v = fma(ci[r], cj[r], v);
-                acc[q] = v;
-            }
+            tri_accumulate(sp, acc, us, ts, 0, (int)min((int64_t)FIT_TILE, e - t0));
         }
         __syncthreads();                                           // the next tile overwrites xs and us
     }
     double *out = a.rows_part + (size_t)blockIdx.x * k14_rows_stride(kx, ROBUST);
-    const double v = wave_sum_row3(rss);
-    if (lane == 63) red[wv] = v;
-    __syncthreads();
-    if (tid == 0) out[0] = (red[0] + red[1]) + (red[2] + red[3]);
-    if constexpr (ROBUST) {
-        if (parts > 1) {
-            if (on[0]) xs[part * nme + (tid - part * nme)] = acc[0];
-            __syncthreads();
-            if (tid < nme) {
-                double t = 0.0;
-                for (int p = 0; p < parts; ++p) t += xs[p * nme + tid];
-                out[1 + tid] = t;
-            }
-        } else {
-#pragma unroll
-            for (int q = 0; q < 3; ++q)
-                if (on[q]) out[1 + tid + 256 * q] = acc[q];
-        }
-    }
+    const double tot = fit_block_sum(rss, red, lane, wv);
+    if (tid == 0) out[0] = tot;
+    if constexpr (ROBUST) tri_reduce(sp, acc, xs, out + 1);
 }
 
 static size_t k14_rows_lds(int T, int kx, int L, bool robust) {
-    return sizeof(double) * ((size_t)(T + 2) * (robust ? K10_GRAM_TS : K10_TILE) + (robust ? (size_t)kx * K10_GRAM_TS + (size_t)L * kx : 0) + kx + 4);
+    return sizeof(double) * ((size_t)(T + 2) * (robust ? FIT_TS : FIT_TILE) + (robust ? (size_t)kx * FIT_TS + (size_t)L * kx : 0) + kx + 4);
 }
-
-constexpr size_t K14_LDS_BUDGET = 160 * 1024 - 256;
 
 template <typename T, bool ROBUST>
 static int k14_rows_launch_t(pols_ctx *ctx, const IvArgs &a) {
     const int kx = a.n_feat + a.icpt, L = kx - a.n_endog + a.n_inst;
     const size_t lds = k14_rows_lds(a.kt, kx, L, ROBUST);
-    if (lds > K14_LDS_BUDGET) return fail(POLS_ERR_UNSUPPORTED, "iv2sls: %d columns exceed the LDS of a workgroup", a.kt);
+    if (lds > FIT_LDS_BUDGET) return fail(POLS_ERR_UNSUPPORTED, "iv2sls: %d columns exceed the LDS of a workgroup", a.kt);
     static OncePerDevice once;
-    if (once.needed(ctx->device)) {
-        POLS_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k14_rows_kernel<T, ROBUST>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)K14_LDS_BUDGET));
-        once.done(ctx->device);
-    }
-    const int64_t n_items = a.seg_offs ? a.n_seg : a.n_groups;
-    hipLaunchKernelGGL((k14_rows_kernel<T, ROBUST>), dim3((unsigned)n_items), dim3(256), lds, ctx->stream, a);
-    POLS_HIP(hipGetLastError());
-    return POLS_OK;
+    return fit_launch(ctx, &k14_rows_kernel<T, ROBUST>, once, fit_items(a), 256, lds, FIT_LDS_BUDGET, a);
 }
 
 int k14_rows_launch(pols_ctx *ctx, int dtype, const IvArgs &a) {
@@ -322,7 +281,7 @@ __global__ void __launch_bounds__(64) k14_finish_kernel(const IvArgs a) {
     const bool ok = st[1] != 0.0;                                  // (wave-uniform)
     double *cov = a.cov ? a.cov + (size_t)g * kx * kx : nullptr;
     if (!ok) {
-        const double q = k14_nan();
+        const double q = fit_nan();
         if (lane < kx) {
             if (a.se) a.se[(size_t)g * kx + lane] = q;
             if (a.t_values) a.t_values[(size_t)g * kx + lane] = q;
@@ -341,9 +300,8 @@ __global__ void __launch_bounds__(64) k14_finish_kernel(const IvArgs a) {
         double v = 0.0;
         for (int64_t it = v0; it < v1; ++it) v += a.rows_part[(size_t)it * rs + en];
         if (en == 0) { rss_s = v; continue; }
-        int i = 0, t = en - 1;
-        while (t >= kx - i) { t -= kx - i; ++i; }
-        const int j = i + t;
+        int i, j;
+        tri_unpack(en - 1, kx, i, j);
         Me[i * kx + j] = v; Me[j * kx + i] = v;
     }
     for (int p = lane; p < kx * kx; p += 64) Mi[p] = st[4 + kx + p];
@@ -379,9 +337,9 @@ __global__ void __launch_bounds__(64) k14_finish_kernel(const IvArgs a) {
     }
     if (lane == 0) {
         if (a.sigma2) a.sigma2[g] = sigma2;
-        const double sg = dof > 0 ? n * st[2] / rss : k14_nan();
+        const double sg = dof > 0 ? n * st[2] / rss : fit_nan();
         if (a.sargan) a.sargan[g] = sg;
-        if (a.sargan_p) a.sargan_p[g] = dof > 0 ? k7_gammaq(0.5 * (double)dof, 0.5 * sg) : k14_nan();
+        if (a.sargan_p) a.sargan_p[g] = dof > 0 ? k7_gammaq(0.5 * (double)dof, 0.5 * sg) : fit_nan();
     }
 }
 

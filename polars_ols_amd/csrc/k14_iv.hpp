@@ -15,7 +15,7 @@ __host__ __device__ inline size_t k14_rows_stride(int kx, bool robust) { return 
 struct IvArgs {
     const void *y;
     const void *w;               // null weights already filled (fill_null_weights), or nullptr
-    const void *x[POLS_MAX_FEATURES];   // the concatenated list [X1 | X2 | Z2]: what K10's Gram launch and k10_stage see as the features
+    const void *x[POLS_MAX_FEATURES];   // the concatenated list [X1 | X2 | Z2]: what K10's Gram launch and fit_stage see as the features
     const int64_t *offs;         // DEVICE offsets of the frame's groups
     int64_t n_groups, n_rows;
     const int64_t *seg_offs;     // long groups cut into segments (ensure_segments) or nullptr: one workgroup per group

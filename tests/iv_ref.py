@@ -200,4 +200,5 @@ SHAPES = {
     "at_cap": (12, 100, 300, 9, 4, 17, True, None),                # T = 9 + 4 + 1 + 17 = 31
     "segmented": (40, 600, 1500, 3, 2, 4, True, 256),              # 3 - 6 segments a group
     "long": (3, 5000, 9000, 2, 1, 3, True, 1024),
+    "two_entries_robust": (12, 100, 300, 21, 1, 2, True, None),    # kx = 23: 276 score-matrix entries, two slots of the spread
 }

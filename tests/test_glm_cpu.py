@@ -19,6 +19,8 @@ SHAPES = {
     "wide": (12, 100, 300, 20, 6),
     "split_forced": (40, 600, 1500, 8, 5),
     "long": (3, 5000, 9000, 6, 5),
+    "two_entries_resident": (20, 300, 500, 23, 5),
+    "three_entries_split": (40, 200, 500, 31, 7),
 }
 
 

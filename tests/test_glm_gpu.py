@@ -27,6 +27,8 @@ SHAPES = {
     "wide": (12, 100, 300, 20, 6, None, None, RESIDENT),
     "split_forced": (40, 600, 1500, 8, 5, "split", 256, SPLIT),        # 3 - 6 segments a group
     "long": (3, 5000, 9000, 6, 5, None, 1024, SPLIT),                  # too long for a workgroup's LDS
+    "two_entries_resident": (20, 300, 500, 23, 5, None, None, RESIDENT),   # 300 Gram entries: two slots of the spread
+    "three_entries_split": (40, 200, 500, 31, 7, "split", 256, SPLIT),     # 528 entries: every slot
 }
 _cache = {}
 

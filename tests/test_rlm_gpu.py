@@ -28,6 +28,8 @@ SHAPES = {
     "several_tiles_streamed": (40, 300, 700, 8, 5, "stream", "k11_rlm_stream"),
     "wide": (12, 60, 200, 20, 6, None, "k11_rlm_resident"),
     "streamed": (6, 1500, 2600, 8, 5, "stream", "k11_rlm_stream"),
+    "three_entries_a_thread": (40, 150, 400, 31, 6, None, "k11_rlm_resident"),   # 528 Gram entries: every slot of the spread
+    "two_entries_streamed": (20, 300, 600, 23, 6, "stream", "k11_rlm_stream"),   # 300 entries
 }
 _cache = {}
 
