@@ -149,6 +149,22 @@ typedef struct {
 } pols_rolling_params;
 void pols_rolling_params_default(pols_rolling_params *p);
 
+/* EXTENTS.  Every pointer below names exactly the extent its comment gives ("n_rows", "n_groups x kt", ...): no entry uses a value in
+ * front of a column's first element or behind its last one -- a load that reaches past an end (the 16-byte chunk that crosses it, a
+ * neighbouring group's rows in a shared chunk, a tile's halo) is clamped into the column or its lanes are SELECTED away, never
+ * multiplied by zero, so what lies next to a column, NaN or not, cannot reach a result -- and no entry writes outside an output's
+ * extent.  Every element of a requested output is written by every successful call; where the text below is silent about an element
+ * (the rows of an empty or failed group, rows before min_periods, a masked row's prediction) it holds what the reference has there: NaN
+ * where the reference has a null / NaN, never what the buffer held before.  A call that returns an error code from its argument
+ * checks has written nothing.  Groups are independent: what one group's rows hold (Inf, NaN, huge values) does not change another
+ * group's results.
+ * ALIGNMENT of DEVICE batches (mem == POLS_MEM_DEVICE; host buffers may sit anywhere).  Every per-row COLUMN, input or output, starts
+ * on a 16-byte boundary: y, every x_cols[j], weights, the further input columns of an entry (pols_glm_params.offset,
+ * pols_iv_params.z_cols, multi-target y_cols) and the per-row outputs pred, resid, multi-target pred_cols, pols_predict's pred_out,
+ * the pols_influence_out row fields, pols_glm_out.linpred and pols_rlm_out.weights; anything else is POLS_ERR_INVALID ("device
+ * columns must be 16-byte aligned").  coef, status, valid, the cluster id columns and the per-group outputs (statistics, the fit
+ * entries' f64 / int32 / int64 tables) need only the alignment of their element type; the dynamic entries take their row-parallel
+ * tile kernels only when coef is 16-byte and valid 4-byte aligned and fall back to the chunk kernels otherwise. */
 typedef struct {
     int32_t dtype;                /* pols_dtype of y / x / weights and of every output */
     int32_t mem;                  /* pols_mem of the data pointers below */
@@ -156,12 +172,12 @@ typedef struct {
     int64_t n_groups;
     const int64_t *group_offsets; /* HOST, n_groups + 1 ascending values, [0] == 0, [n_groups] == n_rows */
     int32_t n_features;           /* user features, excluding the intercept */
-    const void *y;                /* target column, n_rows */
-    const void *const *x_cols;    /* HOST array of n_features column pointers, each n_rows */
+    const void *y;                /* target column, exactly n_rows values; device: 16-byte aligned */
+    const void *const *x_cols;    /* HOST array of n_features column pointers, each exactly n_rows values; device: 16-byte aligned */
     const void *weights;          /* sample_weights column or NULL (polars_ols/least_squares.py:190-196).  A null (NaN) weight acts as
                                      the weight 1e-24 -- sqrt_w = w.sqrt().fill_null(1e-12), least_squares.py:193 -- in every entry:
                                      the fill is a device pass behind this boundary (skipped when null_free is set) */
-    const uint8_t *valid;         /* optional row validity, 1 byte per row (1 = valid), or NULL = all valid */
+    const uint8_t *valid;         /* optional row validity, 1 byte per row (1 = valid), n_rows bytes at any address, or NULL = all valid */
     int32_t add_intercept;        /* append a ones column LAST, named "const" (least_squares.py:184-188) */
     uint64_t offsets_generation;  /* 0: group_offsets is content-checked on every call (hash, then memcmp against the copy the
                                      library keeps of what it last uploaded).  Non-zero: the caller PROMISES that the same
@@ -176,10 +192,10 @@ typedef struct {
 
 typedef struct {
     void *coef;      /* static models: n_groups x kt; dynamic (rls / rolling): n_rows x kt; kt = n_features + add_intercept */
-    void *pred;      /* n_rows, or NULL */
-    void *resid;     /* n_rows: ORIGINAL target - predictions (least_squares.py:239), or NULL */
+    void *pred;      /* n_rows, or NULL; device: 16-byte aligned */
+    void *resid;     /* n_rows: ORIGINAL target - predictions (least_squares.py:239), or NULL; device: 16-byte aligned */
     int32_t *status; /* n_groups pols_group_status values, or NULL */
-} pols_out;
+} pols_out;          /* exact extents, every element written (see EXTENTS above); coef and status: element alignment is enough */
 
 /* ---- compute entries ------------------------------------------------------ */
 
@@ -471,7 +487,7 @@ void pols_rlm_params_default(pols_rlm_params *q);
 typedef struct pols_rlm_out {
     double  *scale;           /* n_groups: the last s computed               */
     int32_t *n_iter;          /* n_groups: updates made                      */
-    void    *weights;         /* n_rows, batch dtype: omega of the last update */
+    void    *weights;         /* n_rows, batch dtype: omega of the last update; device: 16-byte aligned */
 } pols_rlm_out;               /* all live where b->mem says; any may be NULL */
 
 int pols_rlm(pols_ctx *ctx, const pols_batch *b, const pols_ols_params *p, const pols_rlm_params *q, pols_out *out,

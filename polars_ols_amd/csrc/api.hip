@@ -1434,6 +1434,12 @@ int pols_multi_target_least_squares(pols_ctx *ctx, const pols_batch *b, const vo
     std::memset(&o, 0, sizeof(o));
     o.coef = coef; o.status = status;
     if ((rc = check_batch(&bb, &o, K8_KMAX))) return rc;
+    if (b->mem == POLS_MEM_DEVICE) {                                 // (the target and prediction columns are read / written 16 bytes at a time like y / pred)
+        bool ok = aligned16(b->weights);
+        for (int j = 0; j < b->n_features; ++j) ok = ok && aligned16(b->x_cols[j]);
+        for (int t = 0; t < n_targets; ++t) ok = ok && aligned16(y_cols[t]) && (!pred_cols || aligned16(pred_cols[t]));
+        if (!ok) return fail(POLS_ERR_INVALID, "device columns must be 16-byte aligned");
+    }
     // least_squares.py:303-318: unconstrained OLS / ridge only, solve_method in {None, "svd"}
     const double l1 = p->has_l1_ratio ? p->l1_ratio : 0.0;
     if (p->positive || l1 != 0.0)

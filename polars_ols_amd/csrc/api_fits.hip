@@ -238,6 +238,7 @@ int pols_rlm(pols_ctx *ctx, const pols_batch *b, const pols_ols_params *p, const
     if (!(q->tol > 0.0) || !std::isfinite(q->tol)) return fail(POLS_ERR_INVALID, "rlm: tol %g is not positive and finite", q->tol);
     if (b->n_groups == 0) return POLS_OK;
     ro = or_none(ro);
+    if (!fc.host && !aligned16(ro->weights)) return fail(POLS_ERR_INVALID, "device columns must be 16-byte aligned");   // (written 16 bytes at a time)
     const int kt = fc.kt;
     const size_t G = fc.G;
     // which form serves which group: the tiles a group spans from the 16-byte grid point at or below its first row

@@ -301,6 +301,7 @@ class Engine:
     def _fit_entry(self, name, fn, fields, out_cls, q, shapes, want, y, x_cols, offsets, plan_kw, extra=None, keep=()):
         """What ridge_cv / rlm / glm / iv2sls / elastic_net_cv share: the ``want`` check, the plan of the frame, the entry's own
         outputs and the call of the C entry named ``fn`` with (ctx, batch, params, q, out, out_cls(...)); returns the results.
+        ``plan_kw["out"]`` may carry pre-allocated ``coef`` / ``pred`` / ``resid`` / ``status`` buffers, as in ``least_squares``.
         ``shapes(G, N, kt)`` gives {field: (shape, "f64" | "i32" | "i64" | "batch")} for ``fields``.  ``extra(b, like, dev)`` is
         called once the frame is known: it brings along what ``q`` is to point at (a grid, further columns), points ``q`` at it
         and returns it.  ``keep`` and what ``extra`` returns are referenced by this frame until the C entry has returned."""
@@ -325,7 +326,8 @@ class Engine:
         return res
 
     def ridge_cv(self, y, x_cols: Sequence, offsets, alphas, *, want: Sequence[str] = ("coef", "alpha", "alpha_index", "score"),
-                 weights=None, valid=None, add_intercept: bool = False, null_policy: str = "ignore", null_free: bool = False) -> Dict:
+                 weights=None, valid=None, add_intercept: bool = False, null_policy: str = "ignore", null_free: bool = False,
+                 out: Optional[Dict] = None) -> Dict:
         """Ridge regularisation path with leave-one-out selection of alpha for every group in one call (pols_ridge_cv; the
         definitions are in include/pols_mi355x.h).  ``alphas``: the candidates (any order, each >= 0 and finite, at most 64).
         ``want``: any of ``coef pred resid status`` (those of the chosen candidate, as ``least_squares(alpha=chosen)`` returns
@@ -344,11 +346,11 @@ class Engine:
                                lambda G, N, kt: {"alpha": ((G,), "f64"), "alpha_index": ((G,), "i32"), "score": ((G,), "f64"),
                                                  "cv_scores": ((G, A), "f64"), "coef_path": ((G, A, kt), "batch")},
                                want, y, x_cols, offsets, dict(weights=weights, valid=valid, add_intercept=add_intercept,
-                                                              null_policy=null_policy, null_free=null_free), extra=bring_grid)
+                                                              null_policy=null_policy, null_free=null_free, out=out), extra=bring_grid)
 
     def rlm(self, y, x_cols: Sequence, offsets, *, norm: str = "huber", c: Optional[float] = None, max_iter: int = 50, tol: float = 1e-8,
             want: Sequence[str] = ("coef", "status", "scale", "n_iter"), weights=None, valid=None, add_intercept: bool = False,
-            null_policy: str = "ignore") -> Dict:
+            null_policy: str = "ignore", out: Optional[Dict] = None) -> Dict:
         """Huber / bisquare M-estimator for every group in one call: iteratively reweighted least squares with the MAD scale,
         the whole iteration on the device (pols_rlm; the definitions and edge rules are in include/pols_mi355x.h).  ``norm``:
         "huber" or "bisquare"; ``c``: the tuning constant (None: 1.345 / 4.685).  ``want``: any of ``coef pred resid status``
@@ -357,11 +359,11 @@ class Engine:
         q = _rlm_params(self._lib, norm, c, max_iter, tol)
         return self._fit_entry("rlm", "pols_rlm", L.RLM_FIELDS, L.RlmOut, q,
                                lambda G, N, kt: {"scale": ((G,), "f64"), "n_iter": ((G,), "i32"), "weights": ((N,), "batch")},
-                               want, y, x_cols, offsets, dict(weights=weights, valid=valid, add_intercept=add_intercept, null_policy=null_policy))
+                               want, y, x_cols, offsets, dict(weights=weights, valid=valid, add_intercept=add_intercept, null_policy=null_policy, out=out))
 
     def glm(self, y, x_cols: Sequence, offsets, *, family: str = "binomial", offset=None, max_iter: int = 25, tol: float = 1e-8,
             want: Sequence[str] = ("coef", "status", "deviance", "n_iter"), weights=None, valid=None, add_intercept: bool = False,
-            null_policy: str = "ignore") -> Dict:
+            null_policy: str = "ignore", out: Optional[Dict] = None) -> Dict:
         """Logistic / Poisson generalised linear model (canonical link) for every group in one call: iteratively reweighted least
         squares, the whole iteration on the device (pols_glm; the definitions and edge rules are in include/pols_mi355x.h).
         ``family``: "binomial" or "poisson"; ``offset``: optional per-row offset of the linear predictor; ``weights`` are prior
@@ -383,12 +385,12 @@ class Engine:
         return self._fit_entry("glm", "pols_glm", L.GLM_FIELDS, L.GlmOut, q,
                                lambda G, N, kt: {"deviance": ((G,), "f64"), "se": ((G, kt), "f64"), "n_iter": ((G,), "i32"),
                                                  "linpred": ((N,), "batch")},
-                               want, y, x_cols, offsets, dict(weights=weights, valid=valid, add_intercept=add_intercept, null_policy=null_policy),
+                               want, y, x_cols, offsets, dict(weights=weights, valid=valid, add_intercept=add_intercept, null_policy=null_policy, out=out),
                                extra=bring_offset)
 
     def iv2sls(self, y, x_cols: Sequence, z_cols: Sequence, offsets, *, n_endog: int, cov_type: str = "nonrobust", small_sample: bool = True,
                want: Sequence[str] = ("coef", "status", "se", "first_stage_f", "sargan", "sargan_p"), weights=None, valid=None,
-               add_intercept: bool = False, null_policy: str = "ignore") -> Dict:
+               add_intercept: bool = False, null_policy: str = "ignore", out: Optional[Dict] = None) -> Dict:
         """Two-stage least squares (instrumental variables) for every group in one call (pols_iv2sls; the definitions and edge
         rules are in include/pols_mi355x.h).  ``x_cols``: the exogenous regressors first, then the ``n_endog`` endogenous ones;
         ``z_cols``: the excluded instruments (at least ``n_endog``); regressors incl. the intercept plus instruments: at most 31.
@@ -415,13 +417,13 @@ class Engine:
                                                  "cov": ((G, kt, kt), "f64"), "sigma2": ((G,), "f64"), "first_stage_f": ((G, E), "f64"),
                                                  "partial_r2": ((G, E), "f64"), "sargan": ((G,), "f64"), "sargan_p": ((G,), "f64"),
                                                  "n_obs": ((G,), "i64")},
-                               want, y, x_cols, offsets, dict(weights=weights, valid=valid, add_intercept=add_intercept, null_policy=null_policy),
+                               want, y, x_cols, offsets, dict(weights=weights, valid=valid, add_intercept=add_intercept, null_policy=null_policy, out=out),
                                extra=bring_instruments)
 
     def elastic_net_cv(self, y, x_cols: Sequence, offsets, alphas=None, *, n_alphas: int = 100, eps: float = 1e-3, l1_ratio: float = 0.5,
                        n_folds: int = 5, max_iter: int = 1000, tol: float = 1e-5, positive: bool = False,
                        want: Sequence[str] = ("coef", "status", "alpha", "alpha_index", "score"), weights=None, valid=None,
-                       add_intercept: bool = False, null_policy: str = "ignore") -> Dict:
+                       add_intercept: bool = False, null_policy: str = "ignore", out: Optional[Dict] = None) -> Dict:
         """Elastic-net / lasso regularisation path with K-fold selection of alpha for every group in one call
         (pols_elastic_net_cv; the definitions are in include/pols_mi355x.h).  ``alphas``: explicit candidates (any order, each >= 0
         and finite, at most 128), or None for the automatic grid of ``n_alphas`` values from every group's own alpha_max down to
@@ -435,7 +437,7 @@ class Engine:
                                lambda G, N, kt: {"alpha": ((G,), "f64"), "alpha_index": ((G,), "i32"), "score": ((G,), "f64"),
                                                  "cv_scores": ((G, A), "f64"), "alphas_used": ((G, A), "f64"),
                                                  "coef_path": ((G, A, kt), "batch"), "n_iter": ((G, A), "i32")},
-                               want, y, x_cols, offsets, dict(weights=weights, valid=valid, add_intercept=add_intercept, null_policy=null_policy),
+                               want, y, x_cols, offsets, dict(weights=weights, valid=valid, add_intercept=add_intercept, null_policy=null_policy, out=out),
                                keep=grid)
 
     def least_squares(self, y, x_cols: Sequence, offsets, **kwargs) -> Dict:
@@ -1140,20 +1142,27 @@ def default_engine(device: int = 0) -> Engine:
     return _default[device]
 
 
-def _engine_predict(self, x_cols: Sequence, coef, offsets=None, *, add_intercept: bool = False, null_policy: str = "ignore"):
+def _engine_predict(self, x_cols: Sequence, coef, offsets=None, *, add_intercept: bool = False, null_policy: str = "ignore", out=None):
     """``predict`` plugin body (src/expressions.rs:706-741): row-wise sum_j x[t, j] * coef[t, j];
     ``coef`` is n_rows x (k + add_intercept) in the columns' dtype (numpy -> host path, torch CUDA -> device path).  ``null_policy``
-    is the plugin's kwarg: "zero" counts null (NaN) features as 0, "drop" / "ignore" leave the rows with a null anywhere null."""
+    is the plugin's kwarg: "zero" counts null (NaN) features as 0, "drop" / "ignore" leave the rows with a null anywhere null.
+    ``out``: a pre-allocated buffer of n_rows values in the columns' dtype, living where they live (device: 16-byte aligned)."""
     cols = list(x_cols)
     n = cols[0].numel() if _is_torch(cols[0]) else len(cols[0])
     offs = np.asarray([0, n] if offsets is None else offsets, dtype=np.int64)
     b, keep, dev, dt = self._batch(cols[0], cols, offs, None, None, add_intercept)
     if dev:
         coef_k = coef.to(dt).contiguous()
-        out = torch.empty(n, dtype=dt, device=coef_k.device)
+        if out is None:
+            out = torch.empty(n, dtype=dt, device=coef_k.device)
+        elif not (_is_torch(out) and out.is_cuda and out.dtype == dt and tuple(out.shape) == (n,) and out.is_contiguous()):
+            raise ValueError(f"predict: 'out' must be a contiguous CUDA tensor of {n} values of {dt}")
     else:
         coef_k = np.ascontiguousarray(coef, dtype=dt)
-        out = np.empty(n, dtype=dt)
+        if out is None:
+            out = np.empty(n, dtype=dt)
+        elif not (isinstance(out, np.ndarray) and out.dtype == dt and out.shape == (n,) and out.flags.c_contiguous):
+            raise ValueError(f"predict: 'out' must be a contiguous numpy array of {n} values of {np.dtype(dt)}")
     rc = self._lib.pols_predict_policy(self._h, C.byref(b), C.c_void_p(self._ptr(coef_k)), C.c_int64(coef_k.shape[0]),
                                        C.c_int32(L.NULL_POLICIES[null_policy]), C.c_void_p(self._ptr(out)))
     L.check(rc)
