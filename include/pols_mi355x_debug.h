@@ -37,6 +37,15 @@ int pols_stream_probe_ex(pols_ctx *ctx, const pols_batch *b, void *pred_out, int
 long long pols_glm_resident_lds(int kt, int cols, int elem, int tiles);
 int pols_glm_resident_tiles(int kt, int cols, int elem, int per_cu);
 
+/* Which route the static least-squares dispatcher takes for a frame of this shape, without a context or a device: default options with
+ * the (key, value) pairs applied as pols_set_option would (value NULL = default), the offsets scan over shape->group_offsets, the solve
+ * plan of `p` (its POLS_ERR_PANIC / POLS_ERR_INVALID answers are returned as pols_least_squares returns them), then the route picker.
+ * Only dtype, n_rows, n_groups, group_offsets, n_features, add_intercept, null_free and whether weights / valid are non-NULL are read:
+ * no column is touched.  Writes one of "wide", "svd_all", "k2", "k2w", "streamed", "classes_streamed_top", "classes", "k1" ("none": no
+ * groups), in the picker's order (static routes).  The thresholds are those of an MI355X; nothing is asked of a device. */
+int pols_debug_static_route(const pols_batch *shape, const pols_ols_params *p, const char *const *option_keys,
+                            const char *const *option_values, int n_options, char *route_out, int cap);
+
 #ifdef __cplusplus
 }
 #endif

@@ -200,7 +200,7 @@ EXPORTS = [
 ]
 # measurement aids (include/pols_mi355x_debug.h): not part of the reference interface
 DEBUG_EXPORTS = ["pols_timing_enable", "pols_timing_collect", "pols_last_kernel_name", "pols_stream_probe", "pols_stream_probe_ex",
-                 "pols_glm_resident_lds", "pols_glm_resident_tiles"]
+                 "pols_glm_resident_lds", "pols_glm_resident_tiles", "pols_debug_static_route"]
 POLS_COMM_ID_BYTES = 128
 
 
@@ -268,6 +268,8 @@ def lib() -> C.CDLL:
         L.pols_rlm.argtypes = [C.c_void_p, C.POINTER(Batch), C.POINTER(OlsParams), C.POINTER(RlmParams), C.POINTER(Out), C.POINTER(RlmOut)]
         L.pols_glm_resident_lds.argtypes, L.pols_glm_resident_lds.restype = [C.c_int] * 4, C.c_longlong
         L.pols_glm_resident_tiles.argtypes = [C.c_int] * 4
+        L.pols_debug_static_route.argtypes = [C.POINTER(Batch), C.POINTER(OlsParams), C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), C.c_int,
+                                              C.c_char_p, C.c_int]
         L.pols_glm_params_default.argtypes, L.pols_glm_params_default.restype = [C.POINTER(GlmParams)], None
         L.pols_glm.argtypes = [C.c_void_p, C.POINTER(Batch), C.POINTER(OlsParams), C.POINTER(GlmParams), C.POINTER(Out), C.POINTER(GlmOut)]
         L.pols_iv_params_default.argtypes, L.pols_iv_params_default.restype = [C.POINTER(IvParams)], None

@@ -109,6 +109,31 @@ int upload_small(pols_ctx *ctx, void *dst_device, const void *src, size_t bytes)
     return POLS_OK;
 }
 
+// One pass over the host offsets: the statistics the dispatchers read (largest group, alignment, size histogram, overflow rows).
+bool scan_offsets(const int64_t *offs, int64_t n_groups, OffsetsScan *s) {
+    const int64_t cnt = n_groups + 1;
+    *s = OffsetsScan();
+    int64_t mx = 0, ored = 0, mn = 0, mn_pos = INT64_MAX;
+    for (int64_t i = 0; i < cnt; ++i) ored |= offs[i];
+    for (int64_t i = 1; i < cnt; ++i) {
+        const int64_t d = offs[i] - offs[i - 1];
+        mn = d < mn ? d : mn; mx = d > mx ? d : mx;
+        mn_pos = (d > 0 && d < mn_pos) ? d : mn_pos;
+        s->wave_overflow += d > 1021 ? d - 1021 : 0;
+        if (d > 0 && d <= 32) s->small_mask |= d <= 4 ? 1 : (d <= 8 ? 2 : (d <= 16 ? 4 : 8));
+        const int bkt = d <= 1 ? 0 : 64 - __builtin_clzll((unsigned long long)(d - 1));
+        s->hist_cnt[bkt < 47 ? bkt : 47]++; s->hist_rows[bkt < 47 ? bkt : 47] += d;
+    }
+    if (mn < 0) return false;
+    s->max_rows = mx;
+    s->min_rows = mn_pos == INT64_MAX ? 0 : mn_pos;
+    for (int64_t i = n_groups; i >= 1; --i)
+        if (offs[i] > offs[i - 1]) { s->tail_group = i - 1; break; }
+    s->aligned[0] = (ored & 1) == 0;
+    s->aligned[1] = (ored & 3) == 0;
+    return true;
+}
+
 int upload_offsets(pols_ctx *ctx, const int64_t *offs, int64_t n_groups, const int64_t **d_offs, int64_t *max_rows,
                    uint64_t generation) {
     const int64_t cnt = n_groups + 1;
@@ -131,21 +156,8 @@ int upload_offsets(pols_ctx *ctx, const int64_t *offs, int64_t n_groups, const i
         h0 = (h0 ^ u[g]) * P; h1 = (h1 ^ u[g + 1]) * P; h2 = (h2 ^ u[g + 2]) * P; h3 = (h3 ^ u[g + 3]) * P;
     }
     for (; g < cnt; ++g) h0 = (h0 ^ u[g]) * P;
-    int64_t mx = 0, ored = 0, mn = 0, mn_pos = INT64_MAX;
-    for (int64_t i = 0; i < cnt; ++i) ored |= offs[i];
-    int32_t small_mask = 0;                            // which of K6s' team sizes the frame has groups for
-    int64_t hist_cnt[48] = {0}, hist_rows[48] = {0};
-    int64_t over = 0;                                  // rows beyond the 1 021 (+ 3 of chunk-grid slack) a wave-per-group f32 kernel keeps resident
-    for (int64_t i = 1; i < cnt; ++i) {
-        const int64_t d = offs[i] - offs[i - 1];
-        mn = d < mn ? d : mn; mx = d > mx ? d : mx;
-        mn_pos = (d > 0 && d < mn_pos) ? d : mn_pos;
-        over += d > 1021 ? d - 1021 : 0;
-        if (d > 0 && d <= 32) small_mask |= d <= 4 ? 1 : (d <= 8 ? 2 : (d <= 16 ? 4 : 8));
-        const int bkt = d <= 1 ? 0 : 64 - __builtin_clzll((unsigned long long)(d - 1));
-        hist_cnt[bkt < 47 ? bkt : 47]++; hist_rows[bkt < 47 ? bkt : 47] += d;
-    }
-    if (mn < 0) return fail(POLS_ERR_INVALID, "group_offsets must be ascending");
+    OffsetsScan sc;
+    if (!scan_offsets(offs, n_groups, &sc)) return fail(POLS_ERR_INVALID, "group_offsets must be ascending");
     const uint64_t sum = ((h0 * 31 + h1) * 31 + h2) * 31 + h3;
     const bool hit = ctx->offsets.valid && ctx->offs_n == n_groups && ctx->offs_sum == sum &&
                      ctx->offs_copy.size() == (size_t)cnt && std::memcmp(ctx->offs_copy.data(), offs, bytes) == 0;
@@ -163,22 +175,17 @@ int upload_offsets(pols_ctx *ctx, const int64_t *offs, int64_t n_groups, const i
     }
     ctx->offs_host = offs;
     ctx->offs_generation = generation;
-    ctx->offs_max_rows = mx;
-    ctx->offs_min_rows = mn_pos == INT64_MAX ? 0 : mn_pos;
-    ctx->offs_small_mask = small_mask;
-    std::memcpy(ctx->offs_hist_cnt, hist_cnt, sizeof(hist_cnt));
-    std::memcpy(ctx->offs_hist_rows, hist_rows, sizeof(hist_rows));
-    ctx->offs_wave_overflow = over;
-    {
-        int64_t tail = -1;                             // the last group that has rows: its chunk grid may cross the end of the columns
-        for (int64_t i = n_groups; i >= 1; --i)
-            if (offs[i] > offs[i - 1]) { tail = i - 1; break; }
-        ctx->offs_tail_group = tail;
-    }
-    ctx->offs_aligned[0] = (ored & 1) == 0;
-    ctx->offs_aligned[1] = (ored & 3) == 0;
+    ctx->offs_max_rows = sc.max_rows;
+    ctx->offs_min_rows = sc.min_rows;
+    ctx->offs_small_mask = sc.small_mask;
+    std::memcpy(ctx->offs_hist_cnt, sc.hist_cnt, sizeof(sc.hist_cnt));
+    std::memcpy(ctx->offs_hist_rows, sc.hist_rows, sizeof(sc.hist_rows));
+    ctx->offs_wave_overflow = sc.wave_overflow;
+    ctx->offs_tail_group = sc.tail_group;
+    ctx->offs_aligned[0] = sc.aligned[0];
+    ctx->offs_aligned[1] = sc.aligned[1];
     *d_offs = static_cast<const int64_t *>(ctx->offsets.buf.ptr);
-    *max_rows = mx;
+    *max_rows = sc.max_rows;
     return POLS_OK;
 }
 
@@ -403,58 +410,8 @@ int check_batch(const pols_batch *b, const pols_out *o, int max_features) {
     return POLS_OK;
 }
 
-// Shapes the register-resident VALU engine (K1) takes: up to 8 columns whenever the largest group fits its biggest team, and 9-10
-// columns (8 features + intercept, the smoke() shape) while every row stays resident in the wave / two-wave kernels whose Gram
-// is accumulated in passes -- 10 000 x 1 000 x (8 + 1) f32: 77.8 us = 5.1 TB/s against 110 us for the LDS-tile engine (K1m),
-// f64 153.8 against 243.5 us (scripts/bench_k9.py).
-static bool k1_valu_takes(const pols_ctx *ctx, bool f32, int kt, int64_t max_rows, bool has_w = false) {
-    const int vec = f32 ? 4 : 2;
-    if (kt <= 8 && max_rows <= (int64_t)256 * 2 * vec) return true;
-    const int64_t need = max_rows + (ctx->offs_aligned[f32 ? 1 : 0] ? 0 : vec - 1);
-    // round 5: four chunks per lane of the 256-thread team -- up to 4 096 f32 / 2 048 f64 rows stay register-resident at up to 10 columns
-    // (9-10 f32 columns used to leave K1 at 1 024 rows for K1m: 3.2 against 5.3 TB/s on 5 000 x 2 000 x (8 + 1)); POLS_K1_RC2_WIDE=0: the old rule
-    if (kt <= K1_MAX_KT && ctx->opt.static_engine != 2) {
-        // (f64, 10 columns WITH weights: the four-chunk kernel needs 278 registers -- AGPRs, one wave per SIMD -- and stays with K2)
-        if (kt <= 8 || (ctx->opt.k1_rc2_wide && !(!f32 && kt == 10 && has_w))) return need <= (int64_t)256 * 4 * vec;
-        return need <= 1024;
-    }
-    if (kt <= K1_MAX_KT) return need <= 1024;
-    if (kt <= K1W_MAX_KT) return need <= (int64_t)256 * 2 * vec;   // 11-15 columns: up to the 256-thread team's resident rows
-    // 16-31 columns: one chunk per lane.  f64 only where it measured faster than the alternatives (scripts/bench_k16.py, 50 000 x 200
-    // rows): 17-24 columns (867 vs 1 189 us at 20, 1 122 vs 1 418 at 24; at 16 K2 wins 433 vs 506, at 31 the 15-pass kernel is down
-    // to one wave per SIMD and loses 2 686 vs 1 923)
-    if (!f32 && kt == 16 && need <= 16 * vec && !ctx->opt.k1_notiny) return true;   // (round 5: K1t, four groups per wave: 24-row groups 0.7 TB/s in K2)
-    if (!f32 && (kt < 17 || kt > 24)) return false;
-    return kt <= K1X_MAX_KT && need <= (int64_t)256 * 1 * vec;
-}
-// ... and its null-policy family: up to 8 columns like the plain kernels, 9-15 columns (masked three- / four-pass Gram) while resident
-static bool k1_nulls_takes(const pols_ctx *ctx, bool f32, int kt, int64_t max_rows) {
-    const int vec = f32 ? 4 : 2;
-    if (kt <= 8 && max_rows <= (int64_t)256 * 2 * vec) return true;
-    const int64_t need = max_rows + (ctx->offs_aligned[f32 ? 1 : 0] ? 0 : vec - 1);
-    if (kt <= K1_MAX_KT) return need <= 1024;
-    if (kt <= K1W_MAX_KT) return need <= (int64_t)256 * 2 * vec;
-    if (!f32 && (kt < 17 || kt > 24)) return false;                 // 16-31 columns: where the plain kernels run (k1_valu_takes)
-    return kt <= K1X_MAX_KT && need <= (int64_t)256 * 1 * vec;
-}
-
-// handle_nulls (src/expressions.rs:255-296) for the entries that work on FILTERED rows: the batch as the policy leaves it --
-// device columns compacted inside every group (dyn_prep.hip: count pass, host prefix over the per-group counts, scatter pass),
-// new host offsets, nothing null any more (weights included: a null weight is 1e-24, least_squares.py:193).
-struct Compacted {
-    pols_batch bb;
-    std::vector<int64_t> offs;
-    std::vector<const void *> xcols, ycols;    // compacted features / targets (ycols[0] == bb.y)
-    Staged st;                                  // the ORIGINAL rows on the device (for predictions over every row)
-    const int64_t *d_offs = nullptr;            // ... and their offsets
-    const uint8_t *vbytes = nullptr;            // row validity (device)
-    RowCompactArgs ra;                          // the compaction's tables (slab bases: valid until the next compaction)
-};
-
-// `targets` (n_targets >= 1 pointers living where b->mem says) replace b->y as the leading columns: the multi-target mask of
-// ex.rs:539-548 is over every target (and, unless drop_y_zero_x, every feature).  n_targets == 0: the single target b->y.
-static int compact_nulls(pols_ctx *ctx, const pols_batch *b, int policy, Compacted *c, const void *const *targets = nullptr,
-                         int n_targets = 0) {
+// handle_nulls for the entries that work on FILTERED rows (Compacted, api_internal.hpp): slab-parallel compaction inside every group
+int compact_nulls(pols_ctx *ctx, const pols_batch *b, int policy, Compacted *c, const void *const *targets, int n_targets) {
     int rc;
     const int64_t *d_offs = nullptr;
     int64_t max_rows = 0;
@@ -683,157 +640,6 @@ void pols_rolling_params_default(pols_rolling_params *p) {
     p->null_policy = POLS_NULL_DROP_WINDOW;
 }
 
-// ------------------------------------------------------------------ static least squares
-// What the statistics entry needs back from the solve: the staged columns, the device offsets and (when the streamed
-// path ran) the Gram matrices it already produced.  With `info` the outputs are left on the device (no unstage).
-struct LsInfo {
-    Staged st;
-    const int64_t *d_offs = nullptr;
-    int64_t max_rows = 0;
-    double *gram = nullptr;
-    int kt = 0;
-};
-
-// 32 .. 1024 columns (k8_wide.hip): Gram in 64 x 64 MFMA tiles with row splits, workgroup Cholesky / coordinate descent on
-// the Gram matrix in HBM, minimum-norm fallback for flagged groups of at most 32 rows, prediction pass.
-// Multi-target calls (m > 1) pass the target / prediction column tables; the targets share the Gram matrix and one factorisation.
-// With `info` (the statistics entry) the outputs stay on the device and the kernel arguments are handed back.
-struct WideInfo {
-    Staged st;
-    WideArgs a;
-};
-static int wide_static(pols_ctx *ctx, const pols_batch *b, const pols_ols_params *p, pols_out *o, int kt, bool enet,
-                       double ridge_alpha, double enet_l1, bool ols_branch, const void *const *y_cols = nullptr, int m = 1,
-                       void *const *pred_cols = nullptr, WideInfo *info = nullptr) {
-    int rc;
-    const int64_t *d_offs = nullptr;
-    int64_t max_rows = 0;
-    if ((rc = upload_offsets(ctx, b->group_offsets, b->n_groups, &d_offs, &max_rows, b->offsets_generation))) return rc;
-    Staged st;
-    if ((rc = stage_inputs(ctx, b, b->n_groups * m, kt, o, &st))) return rc;
-    if ((rc = fill_null_weights(ctx, b, &st))) return rc;
-    const size_t G = (size_t)b->n_groups;
-    const int NZ = kt + m, nt = (NZ + 63) / 64, npairs = nt * (nt + 1) / 2;
-    // multi-target: device pointers of the m target and m prediction columns (host batches are staged in Work::HostStaged)
-    std::vector<const void *> yptr;
-    std::vector<void *> pptr;
-    const bool host = b->mem == POLS_MEM_HOST;
-    const size_t colb_mt = round256(dtype_size(b->dtype) * (size_t)b->n_rows);
-    if (m > 1) {
-        yptr.assign(y_cols, y_cols + m);
-        if (pred_cols) pptr.assign(pred_cols, pred_cols + m);
-        if (host) {
-            void *mt = nullptr;
-            if ((rc = ensure_scratch(ctx, Work::HostStaged, colb_mt * (size_t)m * (pred_cols ? 2 : 1), &mt))) return rc;
-            char *q = static_cast<char *>(mt);
-            for (int t = 0; t < m; ++t) {
-                POLS_HIP(hipMemcpyAsync(q, y_cols[t], dtype_size(b->dtype) * (size_t)b->n_rows, hipMemcpyHostToDevice, ctx->stream));
-                yptr[t] = q; q += colb_mt;
-            }
-            for (int t = 0; pred_cols && t < m; ++t) { pptr[t] = q; q += colb_mt; }
-        }
-    }
-    const size_t mat = sizeof(double) * (size_t)NZ * NZ;
-    // row splits: enough workgroups to fill the chip when there are few groups, bounded by the partial-Gram memory
-    int64_t splits = std::max<int64_t>(1, (2048 + (int64_t)G * npairs - 1) / ((int64_t)G * npairs));
-    splits = std::min<int64_t>(splits, std::max<int64_t>(1, (max_rows + 255) / 256));
-    while (splits > 1 && (double)splits * (double)G * (double)mat > 2e9) splits /= 2;
-    int64_t rps = (std::max<int64_t>(1, max_rows) + splits - 1) / splits;
-    rps = (rps + 63) / 64 * 64;
-    splits = (std::max<int64_t>(1, max_rows) + rps - 1) / rps;
-
-    void *tab = nullptr, *scr = nullptr;
-    std::vector<const void *> table(st.x.begin(), st.x.end());         // [features][targets][predictions]
-    table.insert(table.end(), yptr.begin(), yptr.end());
-    table.insert(table.end(), pptr.begin(), pptr.end());
-    if ((rc = ensure_scratch(ctx, Work::Tables, sizeof(void *) * table.size(), &tab))) return rc;
-    if ((rc = upload_small(ctx, tab, table.data(), sizeof(void *) * table.size()))) return rc;   // `table` is a local: pinned ring
-    const size_t gram_b = round256(mat * G), part_b = round256(mat * G * (size_t)splits), c64_b = round256(sizeof(double) * G * kt * m);
-    const bool nulls = p->null_policy != POLS_NULL_IGNORE;
-    const size_t mask_b = nulls ? round256((size_t)b->n_rows) + round256(sizeof(double) * G) : 0;
-    if ((rc = ensure_scratch(ctx, Work::Gram, gram_b + part_b + c64_b + mask_b, &scr))) return rc;
-    if (!st.status) {
-        void *sp = nullptr;
-        if ((rc = ensure_scratch(ctx, Work::Status, sizeof(int32_t) * G, &sp))) return rc;
-        st.status = static_cast<int32_t *>(sp);
-    }
-    if (!ctx->fb_flag) {
-        POLS_HIP(hipMalloc(reinterpret_cast<void **>(&ctx->fb_flag), 256));
-        POLS_HIP(hipMemsetAsync(ctx->fb_flag, 0, 256, ctx->stream));
-    }
-    ctx->epoch = (ctx->epoch % 0x0ffffff0) + 1;
-
-    WideArgs a;
-    std::memset(&a, 0, sizeof(a));
-    a.cols = static_cast<const void *const *>(tab);
-    if (m > 1) {
-        a.n_targets = m;
-        a.ycols = a.cols + b->n_features;
-        if (!pptr.empty()) a.pred_cols = static_cast<void *const *>(tab) + b->n_features + m;
-    }
-    a.y = st.y; a.w = st.w; a.offs = d_offs; a.n_groups = b->n_groups; a.n_rows = b->n_rows;
-    a.k_user = b->n_features; a.kt = kt;
-    a.gram = static_cast<double *>(scr);
-    a.partial = reinterpret_cast<double *>(static_cast<char *>(scr) + gram_b);
-    a.coef64 = reinterpret_cast<double *>(static_cast<char *>(scr) + gram_b + part_b);
-    a.splits = (int32_t)splits; a.rows_per_split = rps;
-    a.alpha = enet ? p->alpha : ridge_alpha; a.l1_ratio = enet_l1; a.tol = p->tol; a.max_iter = p->max_iter;
-    a.positive = p->positive ? 1 : 0; a.active_set = (p->solve_method == POLS_SOLVE_CD_ACTIVE_SET) ? 1 : 0;
-    // OLS branch (the reference solves it with a pivoted QR / dgelsd): groups whose pivots say cond(X)^2 would eat the
-    // tolerance go to the Jacobi-SVD pass, exactly like the narrow path; ridge: only a failed factorisation is flagged
-    // (ridge branch: an f32 batch flags what cond * eps_f32 would spoil, an f64 batch only a pivot within rounding noise of 0 -- see ls_core)
-    a.pivot_tol = ols_branch ? (b->dtype == POLS_F32 ? 1e-3 : 1e-10)
-                             : (b->dtype == POLS_F32 && p->solve_method != POLS_SOLVE_SVD ? 1e-3 : 16.0 * (double)kt * 2.220446049250313e-16);
-    // singular-value cut-off of the minimum-norm solver: a caller's rcond (solve_ridge_svd only, ls.rs:143-145), else -1 = "eps * max(fit
-    // rows, columns) of the group" (see prepare_fix in ls_core)
-    a.rc_factor = ols_branch ? 8.0 * 2.220446049250313e-16
-                             : (((p->solve_method == POLS_SOLVE_SVD || m > 1) && p->has_rcond) ? p->rcond : -1.0);   // (m > 1: solve_multi_target -> solve_ridge_svd)
-    a.status = st.status; a.fb_flag = ctx->fb_flag; a.epoch = ctx->epoch;
-    a.coef = st.coef; a.pred = st.pred; a.resid = st.resid;
-    a.null_policy = p->null_policy;
-    if (nulls) {
-        a.valid = st.valid;
-        a.rowmask = reinterpret_cast<uint8_t *>(static_cast<char *>(scr) + gram_b + part_b + c64_b);
-        a.nfit = reinterpret_cast<double *>(static_cast<char *>(scr) + gram_b + part_b + c64_b + round256((size_t)b->n_rows));
-        if ((rc = wide_rowmask_launch(ctx, b->dtype, a))) return rc;
-    }
-    if ((rc = wide_gram_launch(ctx, b->dtype, a))) return rc;
-    if (enet) {
-        if ((rc = wide_cd_launch(ctx, b->dtype, a))) return rc;
-    } else {
-        // (known before the factorisation: wide_chol flags a group with fewer fit rows than columns BY SHAPE under solve_method None / "svd",
-        // where the reference picks the SVD without factoring anything, ls.rs:224-231 -- the last pivots of a rank-deficient Gram matrix can
-        // come out as positive noise above the threshold)
-        {
-            const int sm0 = p->solve_method;
-            a.fix_mode = ols_branch ? (m > 1 ? FIX_MINNORM : sm0 == POLS_SOLVE_AUTO ? FIX_OLS_AUTO : sm0 == POLS_SOLVE_QR ? FIX_OLS_QR : FIX_MINNORM)
-                                    : ((sm0 == POLS_SOLVE_SVD || m > 1) ? FIX_MINNORM : sm0 == POLS_SOLVE_LU ? FIX_LU : FIX_CHOL_LU);
-        }
-        if ((rc = wide_chol_launch(ctx, b->dtype, a))) return rc;
-        int workers = (int)std::min<size_t>(G, 64);
-        void *wk = nullptr;
-        // the solver the fix-up pass runs on a flagged group: the reference's own for this (branch, solve_method), see ls_core
-        const int sm = p->solve_method;
-        a.fix_mode = ols_branch ? (m > 1 ? FIX_MINNORM : sm == POLS_SOLVE_AUTO ? FIX_OLS_AUTO : sm == POLS_SOLVE_QR ? FIX_OLS_QR : FIX_MINNORM)
-                                : ((sm == POLS_SOLVE_SVD || m > 1) ? FIX_MINNORM : sm == POLS_SOLVE_LU ? FIX_LU : FIX_CHOL_LU);
-        const bool lu = fix_uses_lu(a.fix_mode);
-        const int64_t ncmax = lu ? kt : std::min<int64_t>(std::max<int64_t>(1, max_rows), kt);
-        a.work_w_elems = (int64_t)(kt + m) * std::max<int64_t>(1, max_rows);
-        a.work_stride = a.work_w_elems + ncmax * ncmax + 2 * ncmax + (lu ? (int64_t)kt * m : 0);
-        while (workers > 1 && (double)workers * (double)a.work_stride * 8.0 > 1e9) workers /= 2;
-        if ((rc = ensure_scratch(ctx, Work::Fixup, sizeof(double) * (size_t)workers * (size_t)a.work_stride, &wk))) return rc;
-        a.work = static_cast<double *>(wk);
-        if ((rc = wide_minnorm_launch(ctx, b->dtype, a, workers))) return rc;
-    }
-    if (st.pred || st.resid || a.pred_cols)
-        if ((rc = wide_predict_launch(ctx, b->dtype, a))) return rc;
-    if (m > 1 && host && pred_cols)
-        for (int t = 0; t < m; ++t)
-            POLS_HIP(hipMemcpyAsync(pred_cols[t], pptr[t], dtype_size(b->dtype) * (size_t)b->n_rows, hipMemcpyDeviceToHost, ctx->stream));
-    if (info) { info->st = st; info->a = a; return POLS_OK; }
-    return unstage_outputs(ctx, b, b->n_groups * m, kt, o, st);
-}
-
 // Long groups cut into segments: SegTables and what ensure_segments builds are described in api_internal.hpp.  (C++ linkage, as declared
 // there: this definition sits inside the extern "C" block.)
 extern "C++" int ensure_segments(pols_ctx *ctx, const pols_batch *b, int64_t max_rows, size_t extra_per_seg, SegTables *t,
@@ -899,614 +705,6 @@ extern "C++" int ensure_segments(pols_ctx *ctx, const pols_batch *b, int64_t max
     sc.n_seg = n_seg; sc.nz2 = extra_per_seg; sc.nulls = false; sc.max_len = max_len; sc.max_seg = max_seg;
     t->max_len = max_len; t->max_seg = max_seg;
     return POLS_OK;
-}
-
-// Size-class split of the static K1 path (see the launches at the end of ls_core): up to two thresholds t[0] < t[1] (rows), n = how many; 0 = one launch.
-// Cost model: a group costs max(rows, 0.5 x the capacity of the kernel its class gets) row-times (fitted to scripts/bench_spread.py -- 0.3 explains the one-launch numbers, 0.5 also cuts the 50 / 50 frame of 30- and 1 000-row groups, 4.6 -> 5.0 TB/s: log-normal sizes
-// with a 4 000-row tail 1.5 TB/s, 90 % 50-row + 10 % 1 000-row groups 1.9 TB/s in one launch), an extra launch a fixed 6e5.
-static int pick_size_classes(const pols_ctx *ctx, bool f32, int64_t n_groups, int64_t max_rows, int64_t (&t)[2]) {
-    t[0] = t[1] = 0;
-    if (ctx->opt.no_classes || n_groups < 2048) return 0;
-    const double alpha = 0.5, launch_cost = 6.0e5;                    // (an extra launch: ~5 us of a chip that moves ~1.2e5 rows per us)
-    const int b0 = f32 ? 7 : 6;                                       // the smallest kernels hold 128 f32 / 64 f64 rows per group
-                                                                      // (cuts at 32 / 16 rows -- K1t's eight-lane teams -- measured no better: the 6-row groups of the mixed frame
-                                                                      // are minimum-norm problems anyway, and 50-row groups lost 6 % to the 64-row form)
-    int bc = b0;
-    while (((int64_t)1 << bc) < max_rows && bc < 46) ++bc;            // capacity of the kernel the largest group asks for: 2^bc rows
-    // cost with class boundaries at buckets s0 < s1 (-1: unused): bucket q goes to the first boundary >= q, else to the top kernel
-    auto cost = [&](int s0, int s1) {
-        double c = launch_cost * ((s0 >= 0) + (s1 >= 0));
-        for (int q = 0; q < 48; ++q) {
-            if (!ctx->offs_hist_cnt[q]) continue;
-            const double avg = (double)ctx->offs_hist_rows[q] / (double)ctx->offs_hist_cnt[q];
-            const int kb = (s0 >= 0 && q <= s0) ? s0 : ((s1 >= 0 && q <= s1) ? s1 : bc);
-            c += (double)ctx->offs_hist_cnt[q] * std::max(avg, alpha * (double)((int64_t)1 << kb));
-        }
-        return c;
-    };
-    auto count_le = [&](int sb) { int64_t n = 0; for (int q = 0; q <= sb; ++q) n += ctx->offs_hist_cnt[q]; return n; };
-    const double one = cost(-1, -1);
-    double best = one;
-    int bs0 = -1, bs1 = -1;
-    for (int s1 = b0; s1 < bc; ++s1) {
-        const int64_t le1 = count_le(s1);
-        if (le1 == 0 || le1 == n_groups) continue;
-        const double c1 = cost(-1, s1);
-        if (c1 < best) { best = c1; bs0 = -1; bs1 = s1; }
-        for (int s0 = b0; s0 < s1; ++s0) {
-            const int64_t le0 = count_le(s0);
-            if (le0 == 0 || le0 == le1) continue;
-            const double c2 = cost(s0, s1);
-            if (c2 < 0.9 * c1 && c2 < best) { best = c2; bs0 = s0; bs1 = s1; }   // (a third launch has to earn its exiting workgroups)
-        }
-    }
-    if (bs1 < 0 || !(best < 0.75 * one)) return 0;
-    // (a kernel that holds 2^b rows per group takes ragged groups of up to 2^b - (VEC - 1): the chunk grid starts at the 16-byte boundary below the group)
-    const int slack = ctx->offs_aligned[f32 ? 1 : 0] ? 0 : (f32 ? 3 : 1);
-    int n = 0;
-    if (bs0 >= 0) t[n++] = ((int64_t)1 << bs0) - slack;
-    t[n++] = ((int64_t)1 << bs1) - slack;
-    return n;
-}
-
-static int ls_core(pols_ctx *ctx, const pols_batch *b, const pols_ols_params *p, pols_out *o, LsInfo *info) {
-    int rc = check_ctx(ctx);
-    if (rc) return rc;
-    if ((rc = check_batch(b, o, K8_KMAX))) return rc;
-    if (!p) return fail(POLS_ERR_INVALID, "params is NULL");
-    // Null policies (src/expressions.rs:201-296): a null is a NaN; `valid` (optional) additionally drops rows under the
-    // drop family.  They are fused into the streamed path's staging / prediction passes -- no compaction, no copies.
-    if (p->null_policy < POLS_NULL_IGNORE || p->null_policy > POLS_NULL_DROP_WINDOW) return fail(POLS_ERR_INVALID, "unknown null_policy %d", p->null_policy);
-    const int pol = (b->null_free && !b->valid) ? POLS_NULL_IGNORE : p->null_policy;   // nothing null: every policy is the identity
-    const bool nulls = pol != POLS_NULL_IGNORE;
-    if (b->valid && (pol == POLS_NULL_IGNORE || pol == POLS_NULL_ZERO))
-        return fail(POLS_ERR_INVALID, "a validity mask needs a drop-family null_policy");
-
-    // Dispatcher of src/expressions.rs:366-387.
-    const int m = p->solve_method;
-    const double alpha = p->alpha;
-    const bool positive = p->positive != 0;
-    double ridge_alpha = 0.0, enet_l1 = 0.5;
-    bool enet = false;
-    if (alpha == 0.0 && !positive && (m == POLS_SOLVE_AUTO || m == POLS_SOLVE_SVD || m == POLS_SOLVE_QR)) {
-        ridge_alpha = 0.0;  // solve_ols: QR / SVD least squares == normal-equation solution for full column rank
-    } else if (alpha >= 0.0 && (p->has_l1_ratio ? p->l1_ratio : 0.0) == 0.0 && !positive) {
-        if (!(m == POLS_SOLVE_AUTO || m == POLS_SOLVE_CHOL || m == POLS_SOLVE_LU || m == POLS_SOLVE_SVD))
-            return fail(POLS_ERR_PANIC, "Only 'Cholesky', 'LU', & 'SVD' are currently supported solver methods for Ridge.");  // ls.rs:366
-        ridge_alpha = alpha;
-    } else {
-        if (!(m == POLS_SOLVE_AUTO || m == POLS_SOLVE_CD || m == POLS_SOLVE_CD_ACTIVE_SET))
-            return fail(POLS_ERR_PANIC, "Only solve_method 'CD' (coordinate descent) is currently supported for Elastic Net / Lasso problems.");  // ls.rs:404
-        if (!(alpha > 0.0)) return fail(POLS_ERR_PANIC, "'alpha' must be strictly positive");  // ls.rs:409
-        const double l1 = p->has_l1_ratio ? p->l1_ratio : 0.5;
-        if (!(l1 >= 0.0 && l1 <= 1.0)) return fail(POLS_ERR_PANIC, "'l1_ratio' must be strictly between 0. and 1.");  // ls.rs:410
-        enet = true;
-        enet_l1 = l1;
-    }
-
-    const int kt = b->n_features + (b->add_intercept ? 1 : 0);
-    if (b->n_groups == 0) return POLS_OK;
-    if (kt > 31) {
-        // (solve_method "chol" / "lu" with alpha == 0 go through solve_ridge(alpha = 0), ex.rs:366-376: the RIDGE branch)
-        const bool ols_b = !enet && ridge_alpha == 0.0 && alpha == 0.0 && (m == POLS_SOLVE_AUTO || m == POLS_SOLVE_SVD || m == POLS_SOLVE_QR);
-        if (info) return fail(POLS_ERR_INVALID, "internal: the wide statistics path calls wide_static itself");
-        return wide_static(ctx, b, p, o, kt, enet, ridge_alpha, enet_l1, ols_b);
-    }
-    const int64_t *d_offs = nullptr;
-    int64_t max_rows = 0;
-    if ((rc = upload_offsets(ctx, b->group_offsets, b->n_groups, &d_offs, &max_rows, b->offsets_generation))) return rc;
-    Staged st;
-    if ((rc = stage_inputs(ctx, b, b->n_groups, kt, o, &st))) return rc;
-    if ((rc = fill_null_weights(ctx, b, &st))) return rc;
-    auto finish = [&](double *gram) -> int {
-        if (!info) return unstage_outputs(ctx, b, b->n_groups, kt, o, st);
-        info->st = st; info->d_offs = d_offs; info->max_rows = max_rows; info->gram = gram; info->kt = kt;
-        return POLS_OK;
-    };
-    // Every static solve is followed by the SVD fix-up pass over the groups it flags, so a status buffer always exists.
-    if (!enet && !st.status) {
-        void *sp = nullptr;
-        if ((rc = ensure_scratch(ctx, Work::Status, sizeof(int32_t) * (size_t)b->n_groups, &sp))) return rc;
-        st.status = static_cast<int32_t *>(sp);
-    }
-    // OLS branch (the reference solves it with a backward-stable pivoted QR / dgelsd): flag groups whose Cholesky
-    // pivots say cond(X)^2 would exceed the tolerance (1e-6 f64, 1e-4 f32).  Ridge branch: the reference itself
-    // solves the normal equations, so only a failed factorisation is flagged.
-    if (!enet) {
-        if (!ctx->fb_flag) {
-            POLS_HIP(hipMalloc(reinterpret_cast<void **>(&ctx->fb_flag), 256));
-            POLS_HIP(hipMemsetAsync(ctx->fb_flag, 0, 256, ctx->stream));
-        }
-        ctx->epoch = (ctx->epoch % 0x0ffffff0) + 1;
-    }
-    const bool ols_branch = !enet && ridge_alpha == 0.0 && (m == POLS_SOLVE_AUTO || m == POLS_SOLVE_SVD || m == POLS_SOLVE_QR) && alpha == 0.0;
-    // Ridge branch: the reference solves the same normal equations in f64, so an f64 batch flags only a failed factorisation; an f32
-    // batch also flags pivots that say cond(X'X + alpha I) * eps_f32 would exceed the 1e-4 tolerance -- those groups get the
-    // reference's own chain (Cholesky -> LU) in f64 from the fix-up pass.
-    // A pivot within 16 k eps of its diagonal entry is rounding noise around the exact 0 of a singular matrix: it counts as a failed
-    // factorisation ("Cholesky decomposition failed, falling back to LU", demo notebook cell 30) rather than a coin flip.
-    const double chol_noise = 16.0 * (double)kt * 2.220446049250313e-16;
-    const double pivot_tol = ols_branch ? (b->dtype == POLS_F32 ? 1e-3 : 1e-10) : (b->dtype == POLS_F32 && m != POLS_SOLVE_SVD ? 1e-3 : chol_noise);
-    K6Args ka;
-    int fix_workers = 0;
-    // (the pool of fix-up workgroups: 64 for the frames the benchmarks visit -- an empty dispatch -- growing with the number of groups up to
-    //  2 048: a frame of a million 10-row f32 groups has most of them re-solved in f64 here, 64 workgroups were a quarter of the chip)
-    auto prepare_fix = [&](int max_workers = 0) -> int {        // arguments + work area of the fix-up pass
-        if (max_workers <= 0) max_workers = (int)std::max<int64_t>(64, std::min<int64_t>(2048, b->n_groups / 128));
-        const int workers = (int)std::min<int64_t>(b->n_groups, max_workers);
-        const int64_t stride = std::max<int64_t>(1, max_rows) * (kt + 1);
-        void *wk = nullptr;
-        int w_use = workers;
-        while (w_use > 1 && (double)w_use * (double)stride * 8.0 > 4e9) w_use /= 2;
-        int r2;   // Work::Gram holds the Gram matrices / coef64 of the streamed path: the work area gets its own buffer
-        if ((r2 = ensure_scratch(ctx, Work::Fixup, sizeof(double) * (size_t)w_use * (size_t)stride, &wk))) return r2;
-        std::memset(&ka, 0, sizeof(ka));
-        ka.y = st.y; ka.w = st.w;
-        for (int j = 0; j < b->n_features; ++j) ka.x[j] = st.x[j];
-        ka.offs = d_offs; ka.n_groups = b->n_groups; ka.status = st.status;
-        ka.fb_flag = ctx->fb_flag; ka.epoch = ctx->epoch;
-        ka.coef = st.coef; ka.pred = st.pred; ka.resid = st.resid;
-        ka.work = static_cast<double *>(wk); ka.work_stride = stride;
-        ka.alpha = ridge_alpha;
-        // Singular-value cut-off of the minimum-norm solver, relative to s_max.  OLS branch: dgelsd drops s < eps * s_max (rcond
-        // ignored, ls.rs:181-191); the Jacobi rotations leave an exactly dependent column with a norm of a few ulps of s_max rather
-        // than 0, so the cut-off sits 8 ulps up -- enough for that noise at the widths where it can be told from signal, far below the
-        // ~5e-14-relative direction the reference's test_fit_multi_collinear[99-"svd"] expects to be resolved.  (Exact dependence at
-        // tens of columns is a knife edge at this cut-off in LAPACK too; numpy's eps * max(n, k) would settle it and break that
-        // test.)  Ridge branch "svd": the caller's rcond, else -1 = eps * max(fit rows, columns) OF THE GROUP, computed in the kernel
-        // (solve_ridge_svd, ls.rs:143-145).
-        ka.rc_factor = ols_branch ? 8.0 * 2.220446049250313e-16 : ((m == POLS_SOLVE_SVD && p->has_rcond) ? p->rcond : -1.0);
-        // ... and the solver itself is the one the reference runs for this (branch, solve_method): solve_ols None -> pivoted QR when
-        // n > k else SVD (ls.rs:224-231), "qr" -> QR, "svd" -> SVD; solve_ridge None / "chol" -> Cholesky then LU, "lu" -> LU (:352-363)
-        ka.mode = ols_branch ? (m == POLS_SOLVE_AUTO ? FIX_OLS_AUTO : m == POLS_SOLVE_QR ? FIX_OLS_QR : FIX_MINNORM)
-                             : (m == POLS_SOLVE_SVD ? FIX_MINNORM : m == POLS_SOLVE_LU ? FIX_LU : FIX_CHOL_LU);
-        ka.k_user = b->n_features; ka.kt = kt;
-        ka.valid = st.valid; ka.null_policy = pol;
-        fix_workers = w_use;
-        return POLS_OK;
-    };
-    auto svd_fixup = [&]() -> int {
-        if (enet) return POLS_OK;
-        // (measurement aid, an Options switch like the others -- no compute entry reads the environment: what the fix-up dispatch of a
-        // call that flags nothing costs on the stream)
-        if (ctx->opt.debug_skip_fixup) return POLS_OK;
-        int r2 = prepare_fix();
-        if (r2) return r2;
-        return k6_launch(ctx, b->dtype, ka, fix_workers);
-    };
-
-    // solve_ridge_svd with a caller-supplied rcond (ls.rs:143-148): singular values below rcond * s_max are dropped on EVERY
-    // group, full rank or not -- a truncated solve is not the normal-equation solution, so the Jacobi-SVD kernel takes all of
-    // them (one workgroup per group from a pool of up to 2 048 workers; an opt-in, rarely used form of the call).
-    // A whole frame of fewer rows than one 16-byte vector (1-3 f32 / 1 f64 rows) goes the same way: the vector kernels clamp their
-    // loads into the columns and need that much to clamp into; the fix-up solvers are the reference's own for every (branch, method).
-    const bool tiny_frame = !enet && b->n_rows < (b->dtype == POLS_F32 ? 4 : 2);
-    if (!enet && ((!ols_branch && m == POLS_SOLVE_SVD && p->has_rcond) || tiny_frame)) {
-        if ((rc = prepare_fix(2048))) return rc;
-        hipLaunchKernelGGL(mark_fallback_kernel, dim3((unsigned)((b->n_groups + 255) / 256)), dim3(256), 0, ctx->stream, d_offs,
-                           b->n_groups, st.status, ctx->fb_flag, ctx->epoch, 0);
-        POLS_HIP(hipGetLastError());
-        ctx->last_kernel = "k6_small_svd_all_groups";
-        if ((rc = k6_launch(ctx, b->dtype, ka, fix_workers))) return rc;
-        return finish(nullptr);
-    }
-
-    // K2 (k2_resident.hip): rows resident in registers, X'X on the matrix cores, the solver in the same workgroup -- X is read
-    // once whatever the solver.  Elastic net / lasso, explicit LU, and OLS / ridge beyond K1's eight columns or resident rows,
-    // whenever the largest group fits; POLS_STATIC_ENGINE=stream | nok2 go back to the three-launch path / K1m.
-    {
-        const bool f32 = b->dtype == POLS_F32;
-        const int vec = f32 ? 4 : 2;
-        const bool aligned = ctx->offs_aligned[f32 ? 1 : 0];
-        const bool k2_ok = !nulls && kt <= K2_KMAX && k2_fits(b->dtype, kt, max_rows, aligned) && b->n_rows >= vec && ctx->opt.static_engine != 1 &&
-                           ctx->opt.static_engine != 3;
-        const bool k1_resident = nulls ? k1_nulls_takes(ctx, f32, kt, max_rows) : k1_valu_takes(ctx, f32, kt, max_rows, b->weights != nullptr);
-        // (the eight-wave forms are ONE persistent workgroup per CU sized for the largest group: a frame whose groups mostly fill a fraction of it --
-        // log-normal sizes around 300 rows with a 4 000-row tail: 1.07 TB/s in the four-chunk form -- is better off on the streamed path, 2.9;
-        // elastic net keeps K2: its solve needs the rows once)
-        const int64_t k2_cap = max_rows > (int64_t)512 * 2 * vec ? (int64_t)512 * 4 * vec : (int64_t)512 * 2 * vec;
-        const bool k2_sparse = !enet && ctx->opt.static_engine != 2 && max_rows > (int64_t)256 * 2 * vec && b->n_groups >= 2048 &&
-                               (double)b->n_rows < 0.3 * (double)k2_cap * (double)b->n_groups;
-        // POLS_K1_ENGINE=valu | mfma keep the K1 / K1m kernels reachable for the shapes they cover (A/B measurements, tests)
-        const bool legacy_forced = (ctx->opt.k1_engine == 2 && kt <= K1M_MAX_KT) || (ctx->opt.k1_engine == 1 && kt <= K1_MAX_KT);
-        (void)K1W_MAX_KT;
-        // OLS / ridge with 9..15 columns whose tile fits LDS stay with K1m: its solve runs unrolled on wave-uniform values in every
-        // lane (~1.5k cycles), K2's lane-cooperative register Cholesky pays ~40 cycles per cross-lane broadcast (11k cycles at 16
-        // padded columns) -- measured 3.7 against 1.6 TB/s on 10 000 x 1 000 x (8 + intercept) f32.  K2 takes what K1m cannot:
-        // 16 columns, tiles beyond LDS, and every solver that is not a Cholesky.
-        const bool k1m_takes = kt <= K1M_MAX_KT && (f32 ? k1m_fits<float>(b->n_features, b->weights != nullptr, max_rows)
-                                                        : k1m_fits<double>(b->n_features, b->weights != nullptr, max_rows));
-        // Round 3: K2's loop lost its per-column wave-uniform branches and skips the tile stages of chunks a wave has no row of; on the
-        // over-resident shapes (rows beyond K1's registers, tile within LDS) it now beats K1m everywhere measured but f32 with 9-10
-        // columns -- f64 9 / 12 / 15 columns x 1 100 rows: 434 / 447 / 455 us against 468 / 562 / 722; f32 x 2 200 rows: 358 / 364 / 366
-        // against 306 / 371 / 442 (profiles/r03_ab_overresident.txt).
-        // Round 5, re-measured at 8 columns (f32 groups of 2 049..4 096 rows -- ten years of trading days per asset): K2 wins there too, 0.165 /
-        // 0.143 / 0.119 ms against K1m's 0.189 / 0.177 / 0.156 on 4 000 x 2 500, 3 333 x 3 000 and 2 500 x 4 000 rows; K1m keeps 9-10 columns.
-        const bool k1m_wins = k1m_takes && f32 && kt >= 9 && kt <= 10;
-        const bool want = enet || m == POLS_SOLVE_LU || ctx->opt.static_engine == 2 || (!k1_resident && !legacy_forced && !k1m_wins);
-        if (k2_ok && want && !k2_sparse) {
-            K2Args a2;
-            std::memset(&a2, 0, sizeof(a2));
-            a2.y = st.y; a2.w = st.w;
-            for (int j = 0; j < K2_KMAX; ++j) a2.x[j] = j < b->n_features ? st.x[j] : st.y;   // unused slots: any loadable column
-            a2.offs = d_offs; a2.n_groups = b->n_groups; a2.n_rows = b->n_rows;
-            a2.coef = st.coef; a2.pred = st.pred; a2.resid = st.resid; a2.status = st.status;
-            a2.k_user = b->n_features; a2.kt = kt;
-            a2.solver = enet ? (m == POLS_SOLVE_CD_ACTIVE_SET ? K2_CD_ACTIVE_SET : K2_CD) : (m == POLS_SOLVE_LU ? K2_LU : K2_CHOL);
-            // solve_ridge (None / "chol"): Cholesky, and on failure LU (ls.rs:358-363); "svd" and the OLS branch flag for the SVD pass
-            a2.lu_fallback = (!enet && !ols_branch && m != POLS_SOLVE_SVD) ? 1 : 0;
-            a2.alpha = enet ? alpha : ridge_alpha;
-            a2.l1_ratio = enet_l1; a2.tol = p->tol; a2.max_iter = p->max_iter; a2.positive = positive ? 1 : 0;
-            // (an engine that re-solves a flagged group IN the kernel with LU does so on the same Gram matrix: only a genuinely failed
-            // factorisation -- a non-positive or noise pivot -- may take that route.  The f32 ridge branch's conditioning tolerance
-            // (1e-3: those groups get the reference's chain in f64 from the fix-up pass on the K1 / K2w routes) is not applied here,
-            // so that one ill-conditioned group does not get different numerics by the route its shape takes.)
-            a2.pivot_tol = a2.lu_fallback ? chol_noise : pivot_tol;
-            a2.fb_flag = enet ? nullptr : ctx->fb_flag; a2.epoch = ctx->epoch;
-            if ((rc = k2_launch(ctx, b->dtype, a2, max_rows))) return rc;
-            if ((rc = svd_fixup())) return rc;
-            return finish(nullptr);
-        }
-    }
-
-    // K2w (k2w_kernel.inl): OLS / ridge with 17..31 columns, rows resident in registers, Z'Z as three 16 x 16 tiles on the matrix cores,
-    // Cholesky in the same workgroup -- X read ONCE for groups of up to 1 024 f64 / 2 048 f32 rows, which the three-launch streamed
-    // path below reads twice.  Takes what the resident K1 kernels do not (their shapes: k1_valu_takes); POLS_STATIC_ENGINE=k2w takes
-    // every shape it fits (A/B), =stream / =nok2 leave it out.
-    {
-        const bool f32 = b->dtype == POLS_F32;
-        const int vec = f32 ? 4 : 2;
-        const bool fits = !enet && !nulls && m != POLS_SOLVE_LU && k2w_fits(b->dtype, kt, max_rows, ctx->offs_aligned[f32 ? 1 : 0]) && b->n_rows >= vec &&
-                          ctx->opt.static_engine != 1 && ctx->opt.static_engine != 3;
-        const bool k1_resident = k1_valu_takes(ctx, f32, kt, max_rows);
-        // where it measured ahead of the streamed path (scripts/bench_k16.py, 1 000-row groups): f64 from 25 columns (31: 2.45 vs 2.07
-        // TB/s; 20: 1.93 vs 2.10 -- one group per CU, and the serial 32-column solve is 40 % of a group's time whatever kt), f32 always
-        // (2.53 vs 1.75 at 31 columns)
-        // (round 3, solvers padded to 20 / 24 / 28 / 32 and built by independent loads: f64 17 / 20 / 24 columns x 1 000 rows 689 / 722 /
-        // 409 us against 729 / 837 / 492 streamed -- ahead at every width it covers now)
-        // (round 4, two-wave workgroups -- four per CU, four solves in flight: f64 groups of up to 256 rows 24 / 31 columns x 200 rows
-        // 2.03 / 2.10 TB/s against 1.83 (K1) / 1.25 (four waves); at 20 columns K1 stays ahead, 2.02 against 1.87)
-        // (round 5, re-measured over 128 .. 512 rows, scripts/ab_wide_f64.py -> profiles/r05_ab_wide_f64.txt: at 23-24 columns K2w is ahead at every length
-        // K1 would take (256 rows 0.310 vs 0.404 ms, 512 rows 0.263 vs 0.378), at 22 from ~200 rows (0.396 vs 0.419; 512: 0.256 vs 0.333), at 20-21 from
-        // 256 (0.268 vs 0.293; 512: 0.253 vs 0.297); at 17-19 and for groups of ~128 rows K1 stays ahead)
-        // (round 6: groups of 257 .. 512 rows take K1's 256-thread team, which runs three waves per SIMD from 18 columns now -- shorter Gram passes, the
-        // solving wave's rows parked in LDS: 500 rows x 20 / 21 / 22 columns 2.87 / 2.90 / 3.01 TB/s against 2.4-2.8 for K2w; 23 columns 2.88 vs 2.85 at 500 rows, 1.95 vs 1.76 at 300,
-        // profiles/r06_bench_wide_f64_short.txt)
-        const bool short_wide = !f32 && (max_rows > 256 ? kt >= 24 : (kt >= 23 || (kt == 22 && max_rows >= 192) || (kt >= 20 && max_rows >= 224)));
-        if (fits && (!k1_resident || short_wide || ctx->opt.static_engine == 4)) {
-            K2wArgs aw;
-            std::memset(&aw, 0, sizeof(aw));
-            aw.y = st.y; aw.w = st.w;
-            for (int j = 0; j < 32; ++j) aw.x[j] = j < b->n_features ? st.x[j] : st.y;   // unused slots: any loadable column
-            aw.offs = d_offs; aw.n_groups = b->n_groups; aw.n_rows = b->n_rows;
-            aw.coef = st.coef; aw.pred = st.pred; aw.resid = st.resid; aw.status = st.status;
-            aw.k_user = b->n_features; aw.kt = kt;
-            aw.alpha = ridge_alpha; aw.pivot_tol = pivot_tol;
-            aw.fb_flag = ctx->fb_flag; aw.epoch = ctx->epoch;
-            if ((rc = k2w_launch(ctx, b->dtype, aw, max_rows))) return rc;
-            if ((rc = svd_fixup())) return rc;
-            return finish(nullptr);
-        }
-    }
-
-    // Streamed three-launch path: elastic net / 16..31 features when the group does not fit K2's registers; OLS / ridge when
-    // it fits neither the fused kernels nor K1m's LDS tile.  POLS_STATIC_ENGINE=stream forces it.
-    bool stream = enet;
-    if (!enet) {
-        const bool f32 = b->dtype == POLS_F32;
-        const bool fits_lds = f32 ? k1m_fits<float>(b->n_features, b->weights != nullptr, max_rows)
-                                  : k1m_fits<double>(b->n_features, b->weights != nullptr, max_rows);
-        const bool k1_resident = nulls ? k1_nulls_takes(ctx, f32, kt, max_rows) : k1_valu_takes(ctx, f32, kt, max_rows, b->weights != nullptr);
-        // null policies: the register-resident K1 has a NULLS family; everything else goes through the streamed kernels
-        stream = (nulls && !k1_resident) || (!k1_resident && (kt > K1M_MAX_KT || !fits_lds));
-        // Round 5: with the VALU Gram pass (K5v) and the lean prediction kernel the two-pass path runs at 2.7-3.1 TB/s of algorithmic bytes
-        // on frames of up to ten columns without a null policy, K1m's LDS-resident single pass at 1.5-2.2 (profiles/r05_sweep_stream_ab.txt): K1m and K1's
-        // streamed-overflow form stay reachable through POLS_K1_ENGINE=mfma | valu
-        const bool k5v_ok = !nulls && kt <= K5V_MAX_KT && !ctx->opt.kg_single_buffer && ctx->opt.k1_engine == 0;
-        stream = stream || (!k1_resident && k5v_ok);
-        stream = stream || ctx->opt.static_engine == 1;
-        stream = stream || (m == POLS_SOLVE_LU && kt > K1M_MAX_KT);   // explicit LU beyond K2's 16 columns: the streamed solver has one
-    }
-    // The streamed path over the whole frame (ids == nullptr), or over a LIST of its groups (size classes: the groups beyond the K1 family's
-    // registers; segment tables with (start, end) pairs, Gram matrices / coef64 indexed by list position, gram_solve maps back to group ids).
-    double *stream_gram = nullptr;
-    auto run_stream = [&](const std::vector<int32_t> *ids, const int32_t *d_ids, int64_t class_key, int64_t cls_max_rows) -> int {
-        const int64_t ng = ids ? (int64_t)ids->size() : b->n_groups;
-        const int64_t mr = ids ? cls_max_rows : max_rows;
-        // one streaming Gram pass, the small solve (Gram-form CD or Cholesky), then (only if asked for) a prediction pass
-        void *scr = nullptr;
-        const size_t nz = (size_t)kt + 1;
-        const size_t gram_bytes = round256(sizeof(double) * nz * nz * (size_t)ng);
-        const size_t c64_bytes = round256(sizeof(double) * (size_t)kt * (size_t)ng);
-        const size_t nv_bytes = nulls ? round256(sizeof(double) * (size_t)b->n_groups) : 0;
-        // Few long groups (ONE regression over a whole frame is the reference's first README example): a group is one workgroup in
-        // the Gram and the prediction pass, so a 10M-row group used to be one CU's work -- 94 ms.  Long groups are cut into segments
-        // (segment offsets, one workgroup each; the segments' Gram matrices are summed per group in segment order), sized so that the
-        // launch fills the chip about eight deep.
-        SegTables sg;
-        if ((rc = ensure_segments(ctx, b, mr, sizeof(double) * (nz * nz + 1), &sg, ids, class_key))) return rc;
-        const bool split = sg.n_seg > 0;
-        // few groups of hundreds of segments: the segment sums go through 16 slices per group (gram_reduce_launch)
-        const int n_slices = (split && sg.max_seg >= 256 && ng <= 256) ? 16 : 1;
-        const size_t slice_bytes = n_slices > 1 ? round256(sizeof(double) * nz * nz * (size_t)n_slices * (size_t)ng) : 0;
-        if ((rc = ensure_scratch(ctx, Work::Gram, gram_bytes + c64_bytes + nv_bytes + slice_bytes, &scr))) return rc;
-        double *nvalid = nulls ? reinterpret_cast<double *>(static_cast<char *>(scr) + gram_bytes + c64_bytes) : nullptr;
-        const int64_t *seg_offs = split ? sg.offs : d_offs;
-        const int32_t *seg_map = sg.map, *seg_first = sg.first;
-        const int64_t n_seg = split ? sg.n_seg : ng;
-        double *gram_part = reinterpret_cast<double *>(sg.extra);
-        double *nv_part = (split && nulls) ? gram_part + nz * nz * (size_t)n_seg : nullptr;
-        GramArgs ga;
-        std::memset(&ga, 0, sizeof(ga));
-        ga.y = st.y; ga.w = st.w;
-        for (int j = 0; j < b->n_features; ++j) ga.x[j] = st.x[j];
-        ga.offs = seg_offs; ga.n_groups = n_seg; ga.n_rows = b->n_rows; ga.offs_pairs = ids ? 1 : 0;
-        ga.gram = split ? gram_part : static_cast<double *>(scr);
-        ga.k_user = b->n_features; ga.kt = kt;
-        ga.valid = st.valid; ga.null_policy = pol; ga.nvalid = split ? nv_part : nvalid;
-        if ((rc = gram_stream_launch(ctx, b->dtype, ga))) return rc;
-        if (split) {
-            GramReduceArgs ra;
-            std::memset(&ra, 0, sizeof(ra));
-            ra.part = gram_part; ra.nv_part = nv_part; ra.first = seg_first;
-            ra.gram = static_cast<double *>(scr); ra.nvalid = nvalid; ra.n_groups = ng; ra.nz2 = (int32_t)(nz * nz);
-            ra.max_segments = (int32_t)std::min<int64_t>(1 << 30, sg.max_seg);
-            if (n_slices > 1) { ra.slices = reinterpret_cast<double *>(static_cast<char *>(scr) + gram_bytes + c64_bytes + nv_bytes); ra.n_slices = n_slices; }
-            if ((rc = gram_reduce_launch(ctx, ra))) return rc;
-            ga.gram = static_cast<double *>(scr);
-            ctx->last_kernel += "_split";
-        }
-        CdArgs ca;
-        std::memset(&ca, 0, sizeof(ca));
-        ca.gram = ga.gram; ca.offs = d_offs; ca.n_groups = ng; ca.glist = d_ids;
-        ca.coef = st.coef; ca.coef64 = reinterpret_cast<double *>(static_cast<char *>(scr) + gram_bytes);
-        ca.status = st.status;
-        ca.alpha = alpha; ca.l1_ratio = enet_l1; ca.tol = p->tol; ca.max_iter = p->max_iter;
-        ca.positive = positive ? 1 : 0; ca.active_set = (m == POLS_SOLVE_CD_ACTIVE_SET) ? 1 : 0; ca.kt = kt;
-        ca.nvalid = nvalid;
-        if (enet) {
-            if ((rc = gram_cd_launch(ctx, b->dtype, ca))) return rc;
-        } else {
-            ca.alpha = ridge_alpha;
-            ca.solver = (m == POLS_SOLVE_LU) ? 1 : 0;
-            ca.lu_fallback = (!ols_branch && m != POLS_SOLVE_SVD) ? 1 : 0;
-            ca.pivot_tol = ca.lu_fallback ? chol_noise : pivot_tol;   // (see K2 above)
-            ca.fb_flag = ctx->fb_flag; ca.epoch = ctx->epoch;
-            if ((rc = gram_solve_launch(ctx, b->dtype, ca))) return rc;
-        }
-        if (st.pred || st.resid) {
-            PredictArgs pa;
-            std::memset(&pa, 0, sizeof(pa));
-            pa.y = st.y; pa.w = st.w;
-            for (int j = 0; j < b->n_features; ++j) pa.x[j] = st.x[j];
-            pa.offs = seg_offs; pa.n_groups = n_seg; pa.n_rows = b->n_rows; pa.gmap = seg_map; pa.offs_pairs = ids ? 1 : 0;
-            pa.max_item_rows = split ? sg.max_len : mr;
-            pa.coef64 = ca.coef64; pa.pred = st.pred; pa.resid = st.resid;
-            pa.k_user = b->n_features; pa.kt = kt;
-            pa.valid = st.valid; pa.null_policy = pol;
-            if ((rc = predict_launch(ctx, b->dtype, pa))) return rc;
-        }
-        stream_gram = ga.gram;
-        return POLS_OK;
-    };
-
-    K1Args a;
-    std::memset(&a, 0, sizeof(a));
-    a.y = st.y; a.w = st.w; a.valid = st.valid;
-    for (int j = 0; j < b->n_features; ++j) a.x[j] = st.x[j];
-    a.offs = d_offs;
-    a.n_groups = b->n_groups;
-    a.n_rows = b->n_rows;
-    a.coef = st.coef; a.pred = st.pred; a.resid = st.resid; a.status = st.status;
-    a.alpha = ridge_alpha;
-    a.pivot_tol = pivot_tol;
-    a.fb_flag = ctx->fb_flag; a.epoch = ctx->epoch;
-    a.k_user = b->n_features;
-    a.null_policy = pol;
-    // ---- SIZE CLASSES.  The K1 family sizes its workgroup for the LARGEST group of the frame, so on a panel whose group sizes spread widely
-    // (most assets a few hundred rows, a few of them thousands) every small group paid for a team it did not fill -- log-normal sizes around
-    // 300 rows with a 4 000-row tail 1.5 TB/s, 90 % 50-row + 10 % 1 000-row groups 1.9 (scripts/bench_spread.py).  Such frames get one launch per
-    // size class: each walks the list of its own groups with the kernel the dispatcher picks for the class' largest group.  The cuts come
-    // from the size histogram of the offsets scan and a two-parameter cost model (pick_size_classes).  When the largest groups do not fit the
-    // K1 family at all, they form a class of their own on the streamed path (run_stream over their list) and the rest is classed as above.
-    const bool f32b = b->dtype == POLS_F32;
-    auto k1_takes = [&](int64_t rows) { return nulls ? k1_nulls_takes(ctx, f32b, kt, rows) : k1_valu_takes(ctx, f32b, kt, rows, b->weights != nullptr); };
-    const bool classes_allowed = !enet && !ctx->opt.no_classes && !ctx->opt.timeline && ctx->opt.k1_persist <= 0 && ctx->opt.static_engine == 0 &&
-                                 ctx->opt.k1_engine == 0 && b->n_groups >= 2048 && b->n_groups <= 0x7fffffffLL && m != POLS_SOLVE_LU;
-    // the lists of the classes cut[0] < cut[1] < ... (rows): class c holds the groups of cut[c - 1] < rows <= cut[c], the last one the rest
-    auto build_lists = [&](const int64_t *cut, int n_cut) -> int {
-        auto &cc = ctx->class_cache;
-        bool same = cc.valid && cc.offs_id == ctx->offs_id && cc.n_cut == n_cut;
-        for (int c = 0; c < n_cut && same; ++c) same = cc.cut[c] == cut[c];
-        if (same) return POLS_OK;
-        cc.valid = false;
-        std::vector<int32_t> lists[4];
-        for (int64_t g = 0; g < b->n_groups; ++g) {
-            const int64_t n = b->group_offsets[g + 1] - b->group_offsets[g];
-            int c = 0;
-            while (c < n_cut && n > cut[c]) ++c;
-            lists[c].push_back((int32_t)g);
-        }
-        void *d = nullptr;
-        int r2 = grow(cc, sizeof(int32_t) * (size_t)b->n_groups, &d);
-        if (r2) return r2;
-        size_t at = 0;
-        for (int c = 0; c <= n_cut; ++c) {
-            if (!lists[c].empty() && (r2 = upload_small(ctx, static_cast<int32_t *>(d) + at, lists[c].data(), sizeof(int32_t) * lists[c].size()))) return r2;
-            cc.n[c] = (int64_t)lists[c].size();
-            at += lists[c].size();
-        }
-        for (int c = n_cut + 1; c < 4; ++c) cc.n[c] = 0;
-        cc.host_last.swap(lists[n_cut]);
-        cc.valid = true; cc.offs_id = ctx->offs_id; cc.n_cut = n_cut;
-        for (int c = 0; c < n_cut; ++c) cc.cut[c] = cut[c];
-        return POLS_OK;
-    };
-    // K1 launches for the classes [c_lo, c_hi] of the cached lists, longest groups first (their workgroups take longest)
-    // (Tried: every launch over ALL groups, the workgroups of the other classes exiting after reading their offsets -- 18 000 exits per launch on
-    // the log-normal frame cost more than the lists' indirection; and the long groups' launch on a second stream beside the short groups' --
-    // slower by the two events, 0.136 against 0.124 ms.)
-    auto launch_k1_classes = [&](const int64_t *cut, int n_cut, int c_lo, int c_hi, std::string &names) -> int {
-        const auto &cc = ctx->class_cache;
-        int64_t first[4] = {0, cc.n[0], cc.n[0] + cc.n[1], cc.n[0] + cc.n[1] + cc.n[2]};
-        for (int c = c_hi; c >= c_lo; --c) {
-            if (cc.n[c] == 0) continue;
-            K1Args ac = a;
-            ac.glist = static_cast<const int32_t *>(cc.buf.ptr) + first[c];
-            ac.n_groups = cc.n[c];
-            ac.class_max_rows = c < n_cut ? cut[c] : max_rows;
-            int r2 = k1_launch(ctx, b->dtype, kt, ac, ac.class_max_rows, true);
-            if (r2) return r2;
-            names += (names.empty() ? "" : " | ") + ctx->last_kernel;
-        }
-        return POLS_OK;
-    };
-
-    if (stream) {
-        // the largest groups leave the K1 family: do the others fit it, and are they worth their own launches?
-        int64_t k1_top = 0;
-        if (classes_allowed && !k1_takes(max_rows)) {
-            const int slack = ctx->offs_aligned[f32b ? 1 : 0] ? 0 : (f32b ? 3 : 1);
-            for (int bb = 13; bb >= (f32b ? 7 : 6) && k1_top == 0; --bb)
-                if (((int64_t)1 << bb) - slack < max_rows && k1_takes(((int64_t)1 << bb) - slack)) k1_top = ((int64_t)1 << bb) - slack;
-            int64_t rows_low = 0;
-            for (int q = 0; q < 48 && k1_top > 0; ++q)
-                if (((int64_t)1 << q) <= k1_top + 3) rows_low += ctx->offs_hist_rows[q];
-            if ((double)rows_low < 0.3 * (double)b->n_rows) k1_top = 0;      // (mostly long groups: the streamed path for all of them, as before)
-        }
-        if (k1_top > 0) {
-            int64_t cut[3];
-            int64_t low_t[2];
-            const int n_low = pick_size_classes(ctx, f32b, b->n_groups, k1_top, low_t);
-            int n_cut = 0;
-            for (int c = 0; c < n_low; ++c) cut[n_cut++] = low_t[c];
-            cut[n_cut++] = k1_top;
-            if ((rc = build_lists(cut, n_cut))) return rc;
-            if ((rc = prepare_fix())) return rc;
-            std::string names;
-            const auto &cc = ctx->class_cache;
-            if (cc.n[n_cut] > 0) {
-                const int32_t *d_top = static_cast<const int32_t *>(cc.buf.ptr) + (b->n_groups - cc.n[n_cut]);
-                if ((rc = run_stream(&cc.host_last, d_top, k1_top, max_rows))) return rc;
-                names = ctx->last_kernel;
-            }
-            if ((rc = launch_k1_classes(cut, n_cut, 0, n_cut - 1, names))) return rc;
-            ctx->last_kernel = names;
-            if ((rc = k6_launch(ctx, b->dtype, ka, fix_workers))) return rc;
-            return finish(nullptr);
-        }
-        if ((rc = run_stream(nullptr, nullptr, 0, 0))) return rc;
-        if ((rc = svd_fixup())) return rc;
-        return finish(stream_gram);
-    }
-
-    if ((rc = prepare_fix())) return rc;
-    int64_t class_t[2];
-    const int n_cut = (classes_allowed && k1_takes(max_rows)) ? pick_size_classes(ctx, f32b, b->n_groups, max_rows, class_t) : 0;
-    if (n_cut > 0) {
-        if ((rc = build_lists(class_t, n_cut))) return rc;
-        std::string names;
-        if ((rc = launch_k1_classes(class_t, n_cut, 0, n_cut, names))) return rc;
-        ctx->last_kernel = names;
-    } else {
-        if ((rc = k1_launch(ctx, b->dtype, kt, a, max_rows, true))) return rc;
-    }
-    if ((rc = k6_launch(ctx, b->dtype, ka, fix_workers))) return rc;
-    return finish(nullptr);
-}
-
-int pols_least_squares(pols_ctx *ctx, const pols_batch *b, const pols_ols_params *p, pols_out *o) {
-    return ls_core(ctx, b, p, o, nullptr);
-}
-
-// ------------------------------------------------------------------ multi-target
-int pols_multi_target_least_squares(pols_ctx *ctx, const pols_batch *b, const void *const *y_cols, int32_t n_targets,
-                                    const pols_ols_params *p, void *const *pred_cols, void *coef, int32_t *status) {
-    int rc = check_ctx(ctx);
-    if (rc) return rc;
-    if (!b || !p || !y_cols) return fail(POLS_ERR_INVALID, "batch / params / y_cols is NULL");
-    if (n_targets < 1 || n_targets > 256) return fail(POLS_ERR_INVALID, "n_targets must be in 1..256");
-    for (int t = 0; t < n_targets; ++t)
-        if (!y_cols[t] || (pred_cols && !pred_cols[t])) return fail(POLS_ERR_INVALID, "target / prediction column %d is NULL", t);
-    pols_batch bb = *b;
-    bb.y = y_cols[0];
-    pols_out o;
-    std::memset(&o, 0, sizeof(o));
-    o.coef = coef; o.status = status;
-    if ((rc = check_batch(&bb, &o, K8_KMAX))) return rc;
-    if (b->mem == POLS_MEM_DEVICE) {                                 // (the target and prediction columns are read / written 16 bytes at a time like y / pred)
-        bool ok = aligned16(b->weights);
-        for (int j = 0; j < b->n_features; ++j) ok = ok && aligned16(b->x_cols[j]);
-        for (int t = 0; t < n_targets; ++t) ok = ok && aligned16(y_cols[t]) && (!pred_cols || aligned16(pred_cols[t]));
-        if (!ok) return fail(POLS_ERR_INVALID, "device columns must be 16-byte aligned");
-    }
-    // least_squares.py:303-318: unconstrained OLS / ridge only, solve_method in {None, "svd"}
-    const double l1 = p->has_l1_ratio ? p->l1_ratio : 0.0;
-    if (p->positive || l1 != 0.0)
-        return fail(POLS_ERR_PANIC, "Multi-target regression is only supported for unconstrained OLS & Ridge problems.");
-    if (!(p->solve_method == POLS_SOLVE_AUTO || p->solve_method == POLS_SOLVE_SVD))
-        return fail(POLS_ERR_PANIC, "only solve_method='svd' is supported for multi-target regressions");
-    if (!(p->alpha >= 0.0)) return fail(POLS_ERR_PANIC, "alpha must be non-negative");
-    if (p->null_policy < POLS_NULL_IGNORE || p->null_policy > POLS_NULL_DROP_WINDOW) return fail(POLS_ERR_INVALID, "unknown null_policy %d", p->null_policy);
-    if (b->valid && (p->null_policy == POLS_NULL_IGNORE || p->null_policy == POLS_NULL_ZERO))
-        return fail(POLS_ERR_INVALID, "a validity mask needs a drop-family null_policy");
-    const int kt = b->n_features + (b->add_intercept ? 1 : 0);
-    if (kt + n_targets > K8_KMAX) return fail(POLS_ERR_UNSUPPORTED, "%d columns + %d targets > %d", kt, n_targets, K8_KMAX);
-    if (b->n_groups == 0) return POLS_OK;
-    // "ignore" is NOT the identity here: the multi-target body builds both arrays with construct_features_array(.., true)
-    // (src/expressions.rs:546-547), so nulls the policy leaves in place -- targets included -- are zero-filled: "ignore" == "zero".
-    const int policy = p->null_policy == POLS_NULL_IGNORE ? POLS_NULL_ZERO : p->null_policy;
-    if (!b->null_free || b->valid) {
-        // The plugin body under a null policy (src/expressions.rs:521-591): the joint validity mask over every target (and, unless
-        // drop_y_zero_x, every feature), the fit on the rows handle_nulls leaves -- compacted on the device --, then predictions for
-        // EVERY row from the zero-filled features, masked under "drop".
-        Compacted c;
-        if ((rc = compact_nulls(ctx, &bb, policy, &c, y_cols, n_targets))) return rc;
-        const bool host = b->mem == POLS_MEM_HOST;
-        const size_t G = (size_t)b->n_groups, N = (size_t)b->n_rows, sz = dtype_size(b->dtype);
-        const size_t coefb = round256(sz * G * n_targets * kt), statb = round256(sizeof(int32_t) * G), colb = round256(sz * std::max<size_t>(N, 1));
-        const size_t tabb = round256(sizeof(void *) * (size_t)std::max(b->n_features, n_targets));
-        void *d = nullptr;
-        if ((rc = ensure_scratch(ctx, Work::CompactOut, coefb + statb + 2 * tabb + (host && pred_cols ? colb * (size_t)n_targets : 0), &d))) return rc;
-        char *q = static_cast<char *>(d);
-        void *dcoef = (!host && coef) ? coef : static_cast<void *>(q);
-        int32_t *dstat = (!host && status) ? status : reinterpret_cast<int32_t *>(q + coefb);
-        char *tabs = q + coefb + statb, *preds = tabs + 2 * tabb;
-        pols_ols_params pp = *p;
-        pp.null_policy = POLS_NULL_IGNORE;
-        if ((rc = pols_multi_target_least_squares(ctx, &c.bb, c.ycols.data(), n_targets, &pp, nullptr, dcoef, dstat))) return rc;
-        if (pred_cols) {
-            // (the inner call uploaded the COMPACTED offsets in place of the frame's: the original ones again)
-            const int64_t *d_offs = nullptr;
-            int64_t mr = 0;
-            if ((rc = upload_offsets(ctx, b->group_offsets, b->n_groups, &d_offs, &mr, b->offsets_generation))) return rc;
-            std::vector<void *> pt((size_t)n_targets);
-            for (int t = 0; t < n_targets; ++t) pt[(size_t)t] = host ? static_cast<void *>(preds + colb * (size_t)t) : pred_cols[t];
-            if ((rc = upload_small(ctx, tabs, c.st.x.data(), sizeof(void *) * (size_t)b->n_features))) return rc;
-            if ((rc = upload_small(ctx, tabs + tabb, pt.data(), sizeof(void *) * (size_t)n_targets))) return rc;
-            MtPredictArgs ma;
-            std::memset(&ma, 0, sizeof(ma));
-            ma.xtab = reinterpret_cast<const void *const *>(tabs);
-            ma.ptab = reinterpret_cast<void *const *>(tabs + tabb);
-            ma.w = c.st.w; ma.coef = dcoef; ma.vbytes = c.vbytes; ma.offs = d_offs; ma.n_groups = b->n_groups;
-            ma.k_user = b->n_features; ma.kt = kt; ma.m = n_targets;
-            ma.mask_drop = p->null_policy == POLS_NULL_DROP ? 1 : 0;                   // ex.rs:575-583
-            ma.row_blocks = (int32_t)std::min<int64_t>(1024, std::max<int64_t>(1, (int64_t)(N / std::max<size_t>(G, 1)) / 4096));
-            if ((rc = mt_predict_launch(ctx, b->dtype, ma))) return rc;
-            if (host)
-                for (int t = 0; t < n_targets; ++t)
-                    POLS_HIP(hipMemcpyAsync(pred_cols[t], pt[(size_t)t], sz * N, hipMemcpyDeviceToHost, ctx->stream));
-        }
-        if (host) {
-            if (coef) POLS_HIP(hipMemcpyAsync(coef, dcoef, sz * G * n_targets * kt, hipMemcpyDeviceToHost, ctx->stream));
-            if (status) POLS_HIP(hipMemcpyAsync(status, dstat, sizeof(int32_t) * G, hipMemcpyDeviceToHost, ctx->stream));
-            POLS_HIP(hipStreamSynchronize(ctx->stream));
-        }
-        return POLS_OK;
-    }
-    // solve_multi_target (ls.rs:243-260): alpha > 0 -> ridge (SVD form), else minimum-norm least squares: ONE Gram pass over
-    // [X | targets] and ONE factorisation serve every target; flagged groups go through the Jacobi pass once as well.
-    return wide_static(ctx, &bb, p, &o, kt, false, p->alpha, 0.0, p->alpha == 0.0, y_cols, n_targets, pred_cols);
 }
 
 // ------------------------------------------------------------------ mode = "statistics"
@@ -1674,15 +872,8 @@ static int statistics_body(pols_ctx *ctx, const pols_batch *b, const pols_ols_pa
     const size_t G = (size_t)b->n_groups;
     if (kt > 31) {
         // 32 .. 1 024 columns: the K8 kernels solve (same dispatcher), then the wide statistics kernel works from their Gram matrix
-        // the dispatcher's decisions, as in ls_core (src/expressions.rs:366-387)
-        const int m = p->solve_method;
-        const bool positive = p->positive != 0;
-        const double l1 = p->has_l1_ratio ? p->l1_ratio : 0.0;
-        bool enet = false;
-        double ridge_alpha = 0.0, enet_l1 = 0.5;
-        if (p->alpha == 0.0 && !positive && (m == POLS_SOLVE_AUTO || m == POLS_SOLVE_SVD || m == POLS_SOLVE_QR)) ridge_alpha = 0.0;
-        else if (p->alpha >= 0.0 && l1 == 0.0 && !positive) ridge_alpha = p->alpha;
-        else { enet = true; enet_l1 = p->has_l1_ratio ? p->l1_ratio : 0.5; }
+        SolvePlan plan;
+        if ((rc = resolve_solve_plan(p, b->dtype, kt, 1, &plan))) return rc;
         const size_t vecb = round256(sizeof(double) * G), matb = round256(sizeof(double) * G * kt);
         void *scr4 = nullptr;
         if (host && (rc = ensure_scratch(ctx, Work::HostStaged, 3 * vecb + 3 * matb, &scr4))) return rc;
@@ -1690,8 +881,7 @@ static int statistics_body(pols_ctx *ctx, const pols_batch *b, const pols_ols_pa
         pols_out oo = *o;
         char coef_sentinel;
         if (!oo.coef && host) oo.coef = &coef_sentinel;            // host batches stage every non-NULL output
-        const bool ols_b = !enet && ridge_alpha == 0.0 && p->alpha == 0.0;
-        if ((rc = wide_static(ctx, b, p, &oo, kt, enet, ridge_alpha, enet_l1, ols_b, nullptr, 1, nullptr, &wi))) return rc;
+        if ((rc = wide_static(ctx, b, p, &oo, kt, plan, nullptr, 1, nullptr, &wi))) return rc;
         WideStatsOut so;
         double *const user[6] = {s->r2, s->mae, s->mse, s->std_err, s->t_values, s->p_values};
         double *dev[6];
@@ -1702,7 +892,7 @@ static int statistics_body(pols_ctx *ctx, const pols_batch *b, const pols_ols_pa
         }
         so.r2 = dev[0]; so.mae = dev[1]; so.mse = dev[2]; so.se = dev[3]; so.tv = dev[4]; so.pv = dev[5];
         so.lambda = p->alpha;
-        so.factored = !enet && kt + 1 > 128;                       // wide_chol ran on the Gram matrix in place (k8_wide.hip)
+        so.factored = !plan.enet() && kt + 1 > 128;                       // wide_chol ran on the Gram matrix in place (k8_wide.hip)
         if ((rc = wide_stats_launch(ctx, b->dtype, wi.a, so))) return rc;
         if (!host) return POLS_OK;
         for (int i = 0; i < 6; ++i)
@@ -2952,7 +2142,7 @@ int k1_launch(pols_ctx *ctx, int dtype, int kt, const K1Args &a, int64_t max_gro
     // kernel with the same access pattern reaches whenever a group's rows stay register-resident (k <= 8:
     // <= 2048 rows f32, <= 1024 rows f64); K1m reads HBM once for any group whose tile fits LDS and carries up
     // to 15 features, at ~65 % of that bandwidth (LDS caps it at 4 groups in flight per CU).
-    const bool k1_ok = k1_valu_takes(ctx, f32, kt, max_group_rows, a.w != nullptr);
+    const bool k1_ok = k1_valu_takes(ctx->opt, ctx->offs_aligned[f32 ? 1 : 0], f32, kt, max_group_rows, a.w != nullptr);
     bool use_mfma = fits && !k1_ok && (max_group_rows > 64 * 2 * vec || kt > K1_MAX_KT);
     if (ctx->opt.k1_engine == 1 && kt <= K1_MAX_KT) use_mfma = false;
     if (ctx->opt.k1_engine == 2 && fits) use_mfma = true;
