@@ -78,7 +78,11 @@ typedef enum {
 typedef enum {
     POLS_GROUP_OK = 0,
     POLS_GROUP_FALLBACK = 1, /* Cholesky failed, the reference's fallback solver was taken (ls.rs:299-327); also every group with FEWER rows
-                              * than columns under solve_method None / "svd": the reference picks the SVD for it by shape (ls.rs:224-231) */
+                              * than columns under solve_method None / "svd": the reference picks the SVD for it by shape (ls.rs:224-231).
+                              * "Failed" includes the conditioning rule of the OLS branch and of f32 ridge: a pivot d_j <= pivot_tol (G_jj + alpha)
+                              * with pivot_tol = 10^-1.5 for f32 batches and 1e-6 for f64 ones, the measured ratios below which a normal-equation
+                              * solve leaves the parity tolerance (1e-4 / 1e-6).  Such a group is re-solved in f64 by the reference's own solver
+                              * for the call: its values are the reference's, only the status tells. */
     POLS_GROUP_EMPTY = 2,    /* no rows: coefficients are zeros (src/expressions.rs:357-359) */
     POLS_GROUP_NOT_CONVERGED = 3, /* coordinate descent hit max_iter (result still returned, like the reference) */
     POLS_GROUP_BAD_DOF = 4   /* statistics only: degrees of freedom <= 0; the reference panics the whole query here

@@ -67,16 +67,17 @@ struct SolvePlan {
     SolveBranch branch = SolveBranch::Ols;
     double ridge_alpha = 0.0, enet_l1 = 0.5;
     double chol_noise = 0.0;     // a pivot within this (relative) of its diagonal entry is rounding noise around an exact 0
-    double pivot_tol = 0.0;      // groups with a pivot d_j <= pivot_tol * G_jj are flagged for the fix-up pass
+    double pivot_tol = 0.0;      // groups with a pivot d_j <= pivot_tol * (G_jj + alpha) are flagged for the fix-up pass: the measured conditioning
+                                 // threshold (10^-1.5 f32 / 1e-6 f64 batches, DESIGN.md "K6 fix_up") on the OLS branch and f32 ridge, else chol_noise
     double rc_factor = -1.0;     // singular-value cut-off of the minimum-norm solver (< 0: eps * max(fit rows, columns) of the group)
     int fix_mode = 0;            // FixMode: the solver the fix-up pass runs on a flagged group
-    int lu_fallback = 0;         // engines with an in-kernel LU: a failed Cholesky is retried there (solve_ridge, ls.rs:358-363)
+    int lu_fallback = 0;         // engines with an in-kernel LU: a failed Cholesky is retried there (solve_ridge, ls.rs:358-363) -- set for f64 batches only
     bool enet() const { return branch == SolveBranch::Enet; }
     bool ols() const { return branch == SolveBranch::Ols; }
     // (an engine that re-solves a flagged group IN the kernel with LU does so on the same Gram matrix: only a genuinely failed
-    // factorisation -- a non-positive or noise pivot -- may take that route.  The f32 ridge branch's conditioning tolerance
-    // (1e-3: those groups get the reference's chain in f64 from the fix-up pass on the K1 / K2w routes) is not applied there,
-    // so that one ill-conditioned group does not get different numerics by the route its shape takes.)
+    // factorisation -- a non-positive or noise pivot -- may take that route.  lu_fallback is set for f64 batches only: under solve_method
+    // None / "chol" an f32 batch's ill-conditioned ridge groups get the reference's chain in f64 from the fix-up pass on every route, at
+    // pivot_tol.  An explicit "lu" still runs the in-kernel LU of K2 / the streamed solve, which consults no pivot_tol.)
     double in_kernel_pivot_tol() const { return lu_fallback ? chol_noise : pivot_tol; }
 };
 // POLS_OK, or the POLS_ERR_PANIC of the reference's own argument checks.  n_targets > 1: solve_multi_target (minimum-norm fix-up, rcond honoured).

@@ -42,15 +42,23 @@ int resolve_solve_plan(const pols_ols_params *p, int dtype, int kt, int n_target
         s.branch = SolveBranch::Enet;
         s.enet_l1 = l1;
     }
-    // OLS branch (the reference solves it with a backward-stable pivoted QR / dgelsd): flag groups whose Cholesky pivots say cond(X)^2
-    // would exceed the tolerance (1e-6 f64, 1e-4 f32); they go to the fix-up pass.
+    // OLS branch (the reference solves it with a backward-stable pivoted QR / dgelsd): flag groups whose Cholesky pivots say the
+    // normal equations cannot deliver the parity tolerance (1e-6 f64, 1e-4 f32); they go to the fix-up pass.  The thresholds are
+    // MEASURED (scripts/cond_ladder.py -> profiles/cond_ladder.txt, DESIGN.md "K6 fix_up"): the smallest half-decade T such that every
+    // raw solve of a group with exact pivot ratio >= T / sqrt(10) was within the tolerance on every route -- 10^-1.5 for f32 batches,
+    // 1e-6 for f64.  (1e-3 / 1e-10 until then: unflagged groups up to 19 x / 2e4 x outside the tolerance in the one to four decades above them.)
     // Ridge branch: the reference solves the same normal equations in f64, so an f64 batch flags only a failed factorisation; an f32
     // batch also flags pivots that say cond(X'X + alpha I) * eps_f32 would exceed the 1e-4 tolerance -- those groups get the
-    // reference's own chain (Cholesky -> LU) in f64 from the fix-up pass.
+    // reference's own chain (Cholesky -> LU) in f64 from the fix-up pass, on every route under solve_method None / "chol": the in-kernel
+    // LU retry of K2 and of the streamed solve would factor the same f32-born Gram matrix again (measured up to 480 x the tolerance), so
+    // f32 batches do not use it.  (An explicit solve_method "lu" on those two routes is still solved in the kernel and flags only what
+    // its LU cannot solve: not measured, not covered by the ladder tests.)
     // A pivot within 16 k eps of its diagonal entry is rounding noise around the exact 0 of a singular matrix: it counts as a failed
     // factorisation ("Cholesky decomposition failed, falling back to LU", demo notebook cell 30) rather than a coin flip.
     s.chol_noise = 16.0 * (double)kt * 2.220446049250313e-16;
-    s.pivot_tol = s.ols() ? (dtype == POLS_F32 ? 1e-3 : 1e-10) : (dtype == POLS_F32 && m != POLS_SOLVE_SVD ? 1e-3 : s.chol_noise);
+    const bool f32 = dtype == POLS_F32;
+    const double cond_tol = f32 ? 0.03162277660168379 : 1e-6;
+    s.pivot_tol = s.ols() ? cond_tol : (f32 && m != POLS_SOLVE_SVD ? cond_tol : s.chol_noise);
     // Singular-value cut-off of the minimum-norm solver, relative to s_max.  OLS branch: dgelsd drops s < eps * s_max (rcond
     // ignored, ls.rs:181-191); the Jacobi rotations leave an exactly dependent column with a norm of a few ulps of s_max rather
     // than 0, so the cut-off sits 8 ulps up -- enough for that noise at the widths where it can be told from signal, far below the
@@ -64,8 +72,9 @@ int resolve_solve_plan(const pols_ols_params *p, int dtype, int kt, int n_target
     // solve_multi_target (ls.rs:243-260): the SVD forms
     s.fix_mode = s.ols() ? (multi ? FIX_MINNORM : m == POLS_SOLVE_AUTO ? FIX_OLS_AUTO : m == POLS_SOLVE_QR ? FIX_OLS_QR : FIX_MINNORM)
                          : ((m == POLS_SOLVE_SVD || multi) ? FIX_MINNORM : m == POLS_SOLVE_LU ? FIX_LU : FIX_CHOL_LU);
-    // solve_ridge (None / "chol"): Cholesky, and on failure LU (ls.rs:358-363); "svd" and the OLS branch flag for the SVD pass
-    s.lu_fallback = (s.branch == SolveBranch::Ridge && m != POLS_SOLVE_SVD) ? 1 : 0;
+    // solve_ridge (None / "chol"): Cholesky, and on failure LU (ls.rs:358-363), in the kernel for f64 batches; "svd", the OLS branch
+    // and f32 batches flag for the fix-up pass
+    s.lu_fallback = (s.branch == SolveBranch::Ridge && m != POLS_SOLVE_SVD && !f32) ? 1 : 0;
     *out = s;
     return POLS_OK;
 }
@@ -587,6 +596,7 @@ static int route_classes_streamed_top(StaticCall &c, const RoutePick &r) {
     if ((rc = launch_k1_classes(c, r.cut, r.n_cut, 0, r.n_cut - 1, names))) return rc;
     ctx->last_kernel = names;
     c.stream_gram = nullptr;                     // (of the top class only: not the frame's)
+    if (ctx->opt.debug_skip_fixup) return POLS_OK;   // (measurement switch, like svd_fixup)
     return k6_launch(ctx, c.b->dtype, c.ka, c.fix_workers);
 }
 
@@ -604,6 +614,7 @@ static int route_k1(StaticCall &c, const RoutePick &r) {
         k1_args(a, c);
         if ((rc = k1_launch(ctx, c.b->dtype, c.kt, a, c.max_rows, true))) return rc;
     }
+    if (ctx->opt.debug_skip_fixup) return POLS_OK;   // (measurement switch, like svd_fixup)
     return k6_launch(ctx, c.b->dtype, c.ka, c.fix_workers);
 }
 

@@ -41,7 +41,7 @@ struct K1Args {
     double alpha;                        // ridge penalty added to diag(X^T X) (ls.rs:355-356)
     int32_t *fb_flag;                    // device word stamped with `epoch` when any group is flagged (lets K6 exit at once otherwise)
     int32_t epoch;
-    double pivot_tol;                    // flag the group for the SVD fallback when a Cholesky pivot d_j <= pivot_tol * G_jj
+    double pivot_tol;                    // flag the group for the fix-up pass when a Cholesky pivot d_j <= pivot_tol * (G_jj + alpha)
     int32_t k_user;                      // KT - add_intercept
     int64_t skip_group;                  // K1p: the group a single wave handles after the persistent loop (or -1)
     unsigned long long *dbg;             // POLS_TIMELINE=1: 8 s_memtime stamps per group (debug only)
