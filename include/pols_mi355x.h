@@ -689,6 +689,64 @@ typedef struct pols_iv_out {
 int pols_iv2sls(pols_ctx *ctx, const pols_batch *b, const pols_ols_params *p, const pols_iv_params *q, pols_out *out,
                 const pols_iv_out *r);
 
+/* Regression that absorbs one categorical effect inside every group -- the "within" estimator (no reference counterpart; Stata's
+ * areg / xtreg, fe and linearmodels' PanelOLS(entity_effects=True) for every group of the frame in one call, without a dummy column
+ * per category).  Everything below is per group g.
+ * Fitted rows.  F_g are the rows pols_least_squares fits under the policy -- the same null rules, validity-mask rule and null-weight
+ * rule (1e-24); n = |F_g|.  q->ids holds one 64-bit id per row in the batch's row order, living where b->mem says; ids follow their
+ * rows through the policy and carry no nulls.
+ * Categories.  The distinct ids among F_g; C is their number.  A category with one fitted row counts in C and contributes a zero row.
+ * Within transform, over the k = n_features user columns only (the ones column is never part of the fit): W_c = sum_{i in c} w_i
+ * (w = 1 without weights), xbar_c = sum w_i x_i / W_c, ybar_c likewise; x~_i = sqrt(w_i) (x_i - xbar_c(i)), y~_i likewise.  The means
+ * are computed first and the moments are those of the demeaned rows (never raw moments minus a per-category correction).
+ * Solve.  A = X~'X~ = L L' by Cholesky; pivot j fails when d_j <= 16 k eps T_jj with T_jj = sum w_i x_ij^2, the RAW second moment: a
+ * column that is constant inside every category up to rounding is flagged.  b = A^-1 X~'y~; e~_i = y~_i - x~_i'b; RSS = sum e~_i^2,
+ * summed over the rows and not taken from the moments.
+ * Effects.  a_c = ybar_c - xbar_c'b.  With add_intercept coef[kt - 1] = c0 = sum_c W_c a_c / sum_c W_c and fe_i = a_c(i) - c0;
+ * without it fe_i = a_c(i).  out->pred = x_i'b + a_c(i), out->resid = y - pred, every row predicted or masked exactly as
+ * pols_least_squares does for the policy; a row outside F_g whose id has no fitted row in its group gets NaN in pred, resid and fe.
+ * Inference.  df = n - k - C, sigma2 = RSS / df.  POLS_COV_NONROBUST: V = sigma2 A^-1, p two-sided Student-t(df).
+ * POLS_COV_CLUSTER (clustered on the ids): s_c = sum_{i in c} e~_i x~_i, V = q A^-1 (sum_c s_c s_c') A^-1 with
+ * q = C / (C - 1) (n - 1) / (n - k - 1) -- the nested-cluster convention: the absorbed effects are not charged again --, p two-sided
+ * Student-t(C - 1); NaN when C < 2 or n - k - 1 <= 0.  se_j = sqrt(V_jj), t_j = b_j / se_j; the intercept's se / t / p are NaN.
+ * r2_within = 1 - RSS / sum y~_i^2; r2 = 1 - RSS / sum w_i (y_i - ybar_w)^2 (the total sum of squares is formed as the within sum
+ * plus sum_c W_c (ybar_c - ybar_w)^2).
+ * out->status: POLS_GROUP_EMPTY for n = 0 (zero coefficients, everything else NaN); POLS_GROUP_BAD_DOF for df <= 0 (everything NaN);
+ * POLS_GROUP_FALLBACK with everything NaN when a pivot fails or a moment is not finite; otherwise POLS_GROUP_OK.  n_obs and
+ * n_categories are written in every case.
+ * All arithmetic is f64 on the inputs' values, for f32 batches too; coef / pred / resid / fe are in the batch dtype, everything else
+ * is f64.  No floating-point atomics; every sum runs in a fixed order -- a group's categories by ascending id, a category's rows by
+ * position (frame order inside an id) in batches of 64 whose terms meet in a fixed tree, segments of a long group in segment order --
+ * so two runs are bit-identical and HOST and DEVICE batches agree bit for bit.  Groups may have any length.  The call synchronises
+ * the stream twice (the order probe, the number of categories).  When none of se / t_values / p_values / sigma2 / r2_within / r2 is
+ * asked for, the residual pass is skipped.
+ * From pols_ols_params only null_policy is read.  POLS_ERR_INVALID: NULL ids; n_features < 1; alpha != 0, positive, or has_l1_ratio
+ * with l1_ratio > 0; a cov_type other than the two named; a validity mask without a drop-family policy; on the device, a pred / resid
+ * / fe that is not 16-byte aligned.  POLS_ERR_UNSUPPORTED: kt > 31 or n_rows >= 2^31.  There is no Arrow twin and no sharded entry.
+ * Not built: a second absorbed id; HC0-HC3 / HAC covariance on absorbed fits; penalised fits; rolling / recursive forms. */
+typedef struct pols_absorb_params {
+    const int64_t *ids;         /* one id per row, in the batch's row order, where b->mem says */
+    int32_t cov_type;           /* POLS_COV_NONROBUST or POLS_COV_CLUSTER (clustered on ids)    */
+} pols_absorb_params;
+
+/* ids = NULL, cov_type = POLS_COV_NONROBUST */
+void pols_absorb_params_default(pols_absorb_params *q);
+
+typedef struct pols_absorb_out {
+    double  *se;                /* n_groups x kt                                 */
+    double  *t_values;          /* n_groups x kt                                 */
+    double  *p_values;          /* n_groups x kt                                 */
+    double  *sigma2;            /* n_groups: RSS / df                            */
+    double  *r2_within;         /* n_groups                                      */
+    double  *r2;                /* n_groups                                      */
+    void    *fe;                /* n_rows, batch dtype: the row's effect         */
+    int64_t *n_obs;             /* n_groups: fitted rows                         */
+    int64_t *n_categories;      /* n_groups: C                                   */
+} pols_absorb_out;              /* all live where b->mem says; any may be NULL */
+
+int pols_least_squares_absorb(pols_ctx *ctx, const pols_batch *b, const pols_ols_params *p, const pols_absorb_params *q,
+                              pols_out *out, const pols_absorb_out *r);
+
 /* ---- group-key ingestion: `.over(key)` / `group_by(key)` ------------------------------------------------------------
  * The reference's plugin functions never see a key column: Polars partitions the frame on the host and calls them once per
  * group (README.md:19, README.md:57 and :91 `.over("group")`, tests/test_ols.py:110, :384, :860).  The batched entries

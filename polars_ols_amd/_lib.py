@@ -175,6 +175,20 @@ class IvOut(C.Structure):             # pols_iv_out
     _fields_ = [(n, C.c_void_p) for n in IV_FIELDS]
 
 
+class AbsorbParams(C.Structure):      # pols_absorb_params
+    _fields_ = [("ids", C.c_void_p), ("cov_type", C.c_int32)]
+
+
+# pols_absorb_out, in the struct's order; the covariance estimators of the entry (a subset of COV_TYPES)
+ABSORB_FIELDS = ("se", "t_values", "p_values", "sigma2", "r2_within", "r2", "fe", "n_obs", "n_categories")
+ABSORB_COV_TYPES = ("nonrobust", "cluster")
+ABSORB_MAX_COLUMNS = 31
+
+
+class AbsorbOut(C.Structure):         # pols_absorb_out
+    _fields_ = [(n, C.c_void_p) for n in ABSORB_FIELDS]
+
+
 EXPORTS = [
     "pols_device_count", "pols_version", "pols_last_error", "pols_create", "pols_destroy", "pols_set_stream",
     "pols_use_private_stream",
@@ -197,6 +211,7 @@ EXPORTS = [
     "pols_enet_cv_params_default", "pols_elastic_net_cv",
     "pols_glm_params_default", "pols_glm",
     "pols_iv_params_default", "pols_iv2sls",
+    "pols_absorb_params_default", "pols_least_squares_absorb",
 ]
 # measurement aids (include/pols_mi355x_debug.h): not part of the reference interface
 DEBUG_EXPORTS = ["pols_timing_enable", "pols_timing_collect", "pols_last_kernel_name", "pols_stream_probe", "pols_stream_probe_ex",
@@ -274,6 +289,9 @@ def lib() -> C.CDLL:
         L.pols_glm.argtypes = [C.c_void_p, C.POINTER(Batch), C.POINTER(OlsParams), C.POINTER(GlmParams), C.POINTER(Out), C.POINTER(GlmOut)]
         L.pols_iv_params_default.argtypes, L.pols_iv_params_default.restype = [C.POINTER(IvParams)], None
         L.pols_iv2sls.argtypes = [C.c_void_p, C.POINTER(Batch), C.POINTER(OlsParams), C.POINTER(IvParams), C.POINTER(Out), C.POINTER(IvOut)]
+        L.pols_absorb_params_default.argtypes, L.pols_absorb_params_default.restype = [C.POINTER(AbsorbParams)], None
+        L.pols_least_squares_absorb.argtypes = [C.c_void_p, C.POINTER(Batch), C.POINTER(OlsParams), C.POINTER(AbsorbParams), C.POINTER(Out),
+                                                C.POINTER(AbsorbOut)]
         L.pols_enet_cv_params_default.argtypes, L.pols_enet_cv_params_default.restype = [C.POINTER(EnetCvParams)], None
         L.pols_elastic_net_cv.argtypes = [C.c_void_p, C.POINTER(Batch), C.POINTER(OlsParams), C.POINTER(EnetCvParams), C.POINTER(Out),
                                           C.POINTER(EnetCvOut)]

@@ -1,5 +1,5 @@
 // api_fits.hip -- the per-group fit entries of the C-ABI: pols_ridge_cv (K10), pols_rlm (K11), pols_elastic_net_cv (K12), pols_glm
-// (K13), pols_iv2sls (K14).  Host code only.  What they share is written once, up front: the opening checks and the staging
+// (K13), pols_iv2sls (K14), pols_least_squares_absorb (K16).  Host code only.  What they share is written once, up front: the opening checks and the staging
 // (FitCall), the common fields of the kernel argument structs (fit_frame, fit_segments), the entry's own outputs (ExtraOut), K10's
 // prediction pass (fit_predict) and extra input columns (stage_extra_columns).  DESIGN.md, "Adding a per-group fit entry".
 #include <algorithm>
@@ -12,6 +12,8 @@
 #include "k12_enet_cv.hpp"
 #include "k13_glm.hpp"
 #include "k14_iv.hpp"
+#include "k16_absorb.hpp"
+#include "k7c_cluster.hpp"
 
 using namespace pols;
 
@@ -457,6 +459,97 @@ int pols_iv2sls(pols_ctx *ctx, const pols_batch *b, const pols_ols_params *p, co
     }
     // the prediction pass: the regressors alone, or -- "drop" -- the whole list with zero coefficients for the instruments, whose nulls mask rows
     if ((rc = fit_predict(ctx, b, fc, &sg, a.x, pred_all ? nf + m : nf, pred_all ? T : kx, a.coefp))) return rc;
+    return xo.home(ctx, b, o, fc);
+}
+
+void pols_absorb_params_default(pols_absorb_params *q) {
+    if (!q) return;
+    q->ids = nullptr;
+    q->cov_type = POLS_COV_NONROBUST;
+}
+
+// K16 (k16_absorb.hip): K7c's order builder on the id column, the categories (run starts, their prefix, the index of every row), the
+// means per category, the moments of the demeaned rows, the per-group solve, the residual pass per category and the per-group finish
+// (only when a wanted output needs a residual), then the prediction pass.
+int pols_least_squares_absorb(pols_ctx *ctx, const pols_batch *b, const pols_ols_params *p, const pols_absorb_params *q, pols_out *o,
+                              const pols_absorb_out *ro) {
+    FitCall fc;
+    int rc = fit_check(ctx, b, p, q, o, "absorb", K16_KMAX, &fc);
+    if (rc) return rc;
+    if (p->alpha != 0.0 || p->positive || (p->has_l1_ratio && p->l1_ratio > 0.0))
+        return fail(POLS_ERR_INVALID, "absorb: alpha / positive / l1_ratio do not apply (penalised absorbed fits are not built)");
+    if (b->n_features < 1) return fail(POLS_ERR_INVALID, "absorb: no feature column");
+    if (!q->ids) return fail(POLS_ERR_INVALID, "absorb: ids is NULL");
+    if (q->cov_type != POLS_COV_NONROBUST && q->cov_type != POLS_COV_CLUSTER)
+        return fail(POLS_ERR_INVALID, "absorb: cov_type %d is not NONROBUST / CLUSTER", q->cov_type);
+    if (b->n_rows >= ((int64_t)1 << 31)) return fail(POLS_ERR_UNSUPPORTED, "absorb: %lld rows >= 2^31", (long long)b->n_rows);
+    if (b->n_groups == 0) return POLS_OK;
+    ro = or_none(ro);
+    if (!fc.host && !(aligned16(ro->fe) && aligned16(o->pred) && aligned16(o->resid)))   // (written 16 bytes at a time)
+        return fail(POLS_ERR_INVALID, "device columns must be 16-byte aligned");
+    const int k = b->n_features, kc = fc.kt;
+    const size_t G = fc.G, N = (size_t)b->n_rows;
+    const bool cluster = q->cov_type == POLS_COV_CLUSTER;
+    const bool need_rows = ro->se || ro->t_values || ro->p_values || ro->sigma2 || ro->r2_within || ro->r2;
+    if ((rc = fit_stage(ctx, b, o, &fc))) return rc;
+    AbsorbArgs a = {};
+    fit_frame(a, b, fc);
+    a.kt = k + 1; a.icpt = b->add_intercept ? 1 : 0; a.cluster = cluster ? 1 : 0;
+    a.pred = fc.st.pred; a.resid = fc.st.resid;
+    const int64_t *d_ids = q->ids;
+    if (fc.host) {
+        void *wi = nullptr;
+        if ((rc = ensure_scratch(ctx, Work::AbsorbIds, round256(sizeof(int64_t) * N + 8), &wi))) return rc;
+        if (N > 0) POLS_HIP(hipMemcpyAsync(wi, q->ids, sizeof(int64_t) * N, hipMemcpyHostToDevice, ctx->stream));
+        d_ids = static_cast<const int64_t *>(wi);
+    }
+    a.ids = d_ids;
+    SegTables sg;
+    if ((rc = ensure_segments(ctx, b, fc.max_rows, 0, &sg))) return rc;
+    fit_segments(a, sg);
+    const size_t items = sg.n_seg > 0 ? (size_t)sg.n_seg : G;
+    if ((rc = k7c_order_launch(ctx, d_ids, fc.d_offs, b->n_groups, b->n_rows, &a.order))) return rc;
+    const size_t cntb = round256(sizeof(int32_t) * items), firstb = round256(sizeof(int64_t) * (items + 1)), idxb = round256(sizeof(int32_t) * N + 4);
+    void *wx = nullptr, *wc = nullptr, *wm = nullptr;
+    if ((rc = ensure_scratch(ctx, Work::AbsorbIndex, cntb + firstb + idxb, &wx))) return rc;
+    a.item_cnt = static_cast<int32_t *>(wx);
+    a.item_first = reinterpret_cast<int64_t *>(static_cast<char *>(wx) + cntb);
+    a.catidx = reinterpret_cast<int32_t *>(static_cast<char *>(wx) + cntb + firstb);
+    if ((rc = k16_count_launch(ctx, a))) return rc;
+    POLS_HIP(hipMemcpyAsync(&a.n_cats, a.item_first + items, sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
+    POLS_HIP(hipStreamSynchronize(ctx->stream));                   // the number of categories sizes the table
+    const size_t nc = (size_t)a.n_cats;
+    const size_t startb = round256(sizeof(int64_t) * (nc + 1)), catb = round256(sizeof(double) * nc * k16_cat_stride(k) + 8),
+                 residb = round256(sizeof(double) * nc * k16_resid_stride(k, cluster) + 8);
+    const size_t gramb = round256(sizeof(double) * items * k16_gram_stride(k)), stateb = round256(sizeof(double) * G * k16_state_stride(k));
+    if ((rc = ensure_scratch(ctx, Work::AbsorbCats, startb + catb + residb, &wc))) return rc;
+    if ((rc = ensure_scratch(ctx, Work::AbsorbMoments, gramb + stateb, &wm))) return rc;
+    a.cat_start = static_cast<int64_t *>(wc);
+    a.cat = reinterpret_cast<double *>(static_cast<char *>(wc) + startb);
+    a.resid_part = reinterpret_cast<double *>(static_cast<char *>(wc) + startb + catb);
+    a.gram_part = static_cast<double *>(wm);
+    a.state = reinterpret_cast<double *>(static_cast<char *>(wm) + gramb);
+    ExtraOut xo;
+    xo.add(ro->se, a.se, sizeof(double) * G * kc);
+    xo.add(ro->t_values, a.t_values, sizeof(double) * G * kc);
+    xo.add(ro->p_values, a.p_values, sizeof(double) * G * kc);
+    xo.add(ro->sigma2, a.sigma2, sizeof(double) * G);
+    xo.add(ro->r2_within, a.r2_within, sizeof(double) * G);
+    xo.add(ro->r2, a.r2, sizeof(double) * G);
+    xo.add(ro->fe, a.fe, fc.sz * N);
+    xo.add(ro->n_obs, a.n_obs, sizeof(int64_t) * G);
+    xo.add(ro->n_categories, a.n_categories, sizeof(int64_t) * G);
+    if ((rc = xo.place(ctx, fc, Work::AbsorbOut))) return rc;
+    ctx->last_kernel = a.order ? "k16_absorb_ordered" : "k16_absorb_sorted";
+    if ((rc = k16_index_launch(ctx, a))) return rc;
+    if ((rc = k16_means_launch(ctx, b->dtype, a))) return rc;
+    if ((rc = k16_gram_launch(ctx, b->dtype, a))) return rc;
+    if ((rc = k16_solve_launch(ctx, a))) return rc;
+    if (need_rows) {
+        if ((rc = k16_resid_launch(ctx, b->dtype, a))) return rc;
+        if ((rc = k16_finish_launch(ctx, a))) return rc;
+    }
+    if ((rc = k16_predict_launch(ctx, b->dtype, a))) return rc;
     return xo.home(ctx, b, o, fc);
 }
 

@@ -3,7 +3,7 @@
 //                   prediction, dynamic (rolling / recursive), layout and Arrow entries
 //   api_static.hip  the static least-squares path: resolve_solve_plan, ensure_fallback_epoch, k1_valu_takes, pick_static_route, ls_core,
 //                   wide_static, pols_least_squares, pols_multi_target_least_squares, pols_debug_static_route
-//   api_fits.hip    the K10-K14 fit entries
+//   api_fits.hip    the K10-K14 and K16 fit entries
 #pragma once
 
 #include <vector>

@@ -94,6 +94,11 @@ enum class Work : int {
     IvState,        // 2SLS (K14): n, usable, Sargan numerator, b, M^-1 and Pi per group (f64), then the coefficients for the prediction pass
     IvInputs,       // 2SLS (K14): the instrument columns of a HOST batch
     IvOut,          // 2SLS (K14): the pols_iv_out fields of a HOST batch before they go home
+    AbsorbIds,      // absorbed effect (K16): the id column of a HOST batch
+    AbsorbIndex,    // absorbed effect (K16): run starts per segment / group and their prefix, the category index of every row (int32)
+    AbsorbCats,     // absorbed effect (K16): first position of every category, the table (n_c -> a_c, W_c, means), RSS / z^2 per category
+    AbsorbMoments,  // absorbed effect (K16): demeaned cross-moment partials per segment / group, then n, C, df, c0, b, A^-1 per group
+    AbsorbOut,      // absorbed effect (K16): the pols_absorb_out fields of a HOST batch before they go home
     Count
 };
 

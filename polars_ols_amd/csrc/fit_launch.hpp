@@ -1,4 +1,4 @@
-// fit_launch.hpp -- the host side of a launch of the per-group fit kernels K10 .. K14 (the device side: fit_tile.inl, fit_solve.inl).
+// fit_launch.hpp -- the host side of a launch of the per-group fit kernels K10 .. K14 and K16 (the device side: fit_tile.inl, fit_solve.inl).
 #pragma once
 #include "common.hpp"
 

@@ -1,6 +1,6 @@
 // fit_solve.inl -- the one-wave Cholesky solve of K11 (k11_rlm.hip), K13 (k13_glm.hip) and K14 (k14_iv.hip): a packed Gram matrix in
 // LDS goes to the coefficients by a right-looking factorisation (the trailing update spread over the lanes) and the two
-// substitutions; K14 also takes the factorisation alone.
+// substitutions; K14 also takes the factorisation alone, and K16 (k16_absorb.hip) takes it with pivots held against another diagonal.
 #pragma once
 #include "fit_tile.inl"
 

@@ -1,5 +1,5 @@
-// fit_tile.inl -- the device primitives shared by the per-group fit kernels K10 .. K14 (k10_ridge_path.hip, k11_rlm.hip, k12_enet_cv.hip,
-// k13_glm.hip, k14_iv.hip): the workgroup's item and its 256-row tile grid, the tile load and K10's staging policy, the packed upper
+// fit_tile.inl -- the device primitives shared by the per-group fit kernels K10 .. K14 and K16 (k10_ridge_path.hip, k11_rlm.hip,
+// k12_enet_cv.hip, k13_glm.hip, k14_iv.hip, k16_absorb.hip): the workgroup's item and its 256-row tile grid, the tile load and K10's staging policy, the packed upper
 // triangle of a Gram matrix spread over 256 threads with its accumulate and reduce steps, a block sum and the walk of a prediction
 // pass.  Everything sums in a fixed order and uses no floating-point atomics.  The one-wave Cholesky solve is in fit_solve.inl, the
 // host side of a launch in fit_launch.hpp.
@@ -117,7 +117,7 @@ __device__ __forceinline__ double fit_block_sum(double v, double *red, const int
 // rows [t0, t0 + 256) of the item [s, e) into xs (column stride ts) as f64: 16-byte loads on the columns' 16-byte grid (column q of the
 // tile is one wave's work, every load of a lane issued before the first use), then the thread of a row applies the null policy and
 // sqrt(w).  Features 0 .. ku - 1, the ones column at ku (kt > ku), y~ at kt; column kt + 1 holds the raw weights in between.  Args:
-// RidgeCvArgs, RlmArgs, EnetCvArgs or IvArgs -- y, w, x, n_rows, valid, null_policy, k_user, kt.  Returns whether this thread's row
+// RidgeCvArgs, RlmArgs, EnetCvArgs, IvArgs or AbsorbArgs -- y, w, x, n_rows, valid, null_policy, k_user, kt.  Returns whether this thread's row
 // (t0 + tid) is a fitted row.  Ends on a barrier.
 template <typename T, bool STREAM, typename Args>
 __device__ __forceinline__ bool fit_stage(const Args &a, const int64_t s, const int64_t e, const int64_t t0, double *xs, const int ts) {

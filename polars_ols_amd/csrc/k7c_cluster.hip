@@ -356,7 +356,97 @@ int k7c_sort_pass(pols_ctx *ctx, const SortBufs &sb, const S *col, int64_t mn, i
     return k9_radix_sort_pairs<uint64_t>(ctx, sb.tmp, &t, static_cast<const uint64_t *>(sb.keys_in), static_cast<uint64_t *>(sb.keys_out),
                                          vin, perm_out, sb.n, bits);
 }
+
+// The order builder of one call: the work areas of every clustering at once (growing one later would free memory a queued kernel
+// still reads), then one probe for the ranges of both ids and the order of A, B and AB inside every group.
+struct OrderPlan {
+    SortBufs sb;
+    uint32_t *order;
+    ClusterProbe h;
+};
+
+// idb: the second id column, or nullptr
+int k7c_order_prepare(pols_ctx *ctx, const int64_t *ida, const int64_t *idb, const int64_t *offs, int64_t G, int64_t n, OrderPlan *pl) {
+    SortBufs &sb = pl->sb;
+    ClusterProbe &h = pl->h;
+    std::memset(&sb, 0, sizeof(sb));
+    sb.n = n;
+    pl->order = nullptr;
+    std::memset(&h, 0, sizeof(h));
+    if (n > 0) {
+        size_t t32 = 0, t64 = 0;
+        int rc = k9_radix_sort_pairs<uint32_t>(ctx, nullptr, &t32, nullptr, nullptr, nullptr, nullptr, n, 32);
+        if (!rc) rc = k9_radix_sort_pairs<uint64_t>(ctx, nullptr, &t64, nullptr, nullptr, nullptr, nullptr, n, 64);
+        if (rc) return rc;
+        sb.tmp_bytes = round256(std::max(t32, t64));
+        const unsigned nblk = std::min<unsigned>(k7c_blocks(n), (unsigned)std::max(ctx->num_cus, 1) * 8);
+        const size_t kb = round256(sizeof(uint64_t) * (size_t)n), ib = round256(sizeof(uint32_t) * (size_t)n),
+                     pb = round256(sizeof(ClusterProbe) * nblk);
+        void *base = nullptr, *ob = nullptr;
+        if ((rc = ensure_scratch(ctx, Work::ClusterSort, 2 * kb + 3 * ib + pb + sb.tmp_bytes, &base))) return rc;
+        if ((rc = ensure_scratch(ctx, Work::ClusterOrder, ib, &ob))) return rc;
+        char *p = static_cast<char *>(base);
+        sb.keys_in = p; p += kb;
+        sb.keys_out = p; p += kb;
+        sb.vals[0] = reinterpret_cast<uint32_t *>(p); p += ib;
+        sb.vals[1] = reinterpret_cast<uint32_t *>(p); p += ib;
+        sb.rowgroup = reinterpret_cast<uint32_t *>(p); p += ib;
+        ClusterProbe *dprobe = reinterpret_cast<ClusterProbe *>(p); p += pb;
+        sb.tmp = p;
+        pl->order = static_cast<uint32_t *>(ob);
+        std::vector<ClusterProbe> part(nblk);
+        hipLaunchKernelGGL(k7c_probe_kernel, dim3(nblk), dim3(256), 0, ctx->stream, ida, idb, offs, G, n, dprobe);
+        POLS_HIP(hipGetLastError());
+        POLS_HIP(hipMemcpyAsync(part.data(), dprobe, sizeof(ClusterProbe) * nblk, hipMemcpyDeviceToHost, ctx->stream));
+        POLS_HIP(hipStreamSynchronize(ctx->stream));
+        h = part[0];
+        for (unsigned q = 1; q < nblk; ++q) {
+            for (int w = 0; w < 2; ++w) { h.mn[w] = std::min(h.mn[w], part[q].mn[w]); h.mx[w] = std::max(h.mx[w], part[q].mx[w]); }
+            for (int w = 0; w < 3; ++w) h.uns[w] |= part[q].uns[w];
+        }
+        if ((h.uns[0] || h.uns[1] || h.uns[2]) && G > 1) {
+            hipLaunchKernelGGL(k7c_rowgroup_kernel, dim3(k7c_blocks(n)), dim3(256), 0, ctx->stream, offs, G, n, sb.rowgroup);
+            POLS_HIP(hipGetLastError());
+        }
+    }
+    return POLS_OK;
+}
+
+// the order of clustering wi (0: ids[0], 1: ids[1], 2: the pairs); *out = nullptr where the probe found its ids in order already
+int k7c_order_way(pols_ctx *ctx, const OrderPlan &pl, const int64_t *const *ids, int wi, int64_t G, const uint32_t **out) {
+    const SortBufs &sb = pl.sb;
+    const ClusterProbe &h = pl.h;
+    *out = nullptr;
+    if (sb.n > 0 && h.uns[wi]) {
+        // LSD: the least significant key first; every pass is stable, so ties keep the order of the passes before
+        struct Pass { const int64_t *col; int64_t mn; int bits; };
+        Pass passes[2];
+        int np = 0;
+        const int ia = wi == 1 ? 1 : 0;
+        if (wi == 2) passes[np++] = {ids[1], h.mn[1], k7c_bits((uint64_t)h.mx[1] - (uint64_t)h.mn[1])};
+        passes[np++] = {ids[ia], h.mn[ia], k7c_bits((uint64_t)h.mx[ia] - (uint64_t)h.mn[ia])};
+        const int total = np + (G > 1 ? 1 : 0);
+        const uint32_t *cur = nullptr;
+        for (int q = 0; q < total; ++q) {
+            uint32_t *dst = q == total - 1 ? pl.order : (cur == sb.vals[1] ? sb.vals[0] : sb.vals[1]);
+            int rc = q < np ? k7c_sort_pass<int64_t>(ctx, sb, passes[q].col, passes[q].mn, passes[q].bits, cur, dst)
+                            : k7c_sort_pass<uint32_t>(ctx, sb, sb.rowgroup, 0, k7c_bits((uint64_t)(G - 1)), cur, dst);
+            if (rc) return rc;
+            cur = dst;
+        }
+        *out = pl.order;
+    }
+    return POLS_OK;
+}
 }  // namespace
+
+int k7c_order_launch(pols_ctx *ctx, const int64_t *ids, const int64_t *offs, int64_t n_groups, int64_t n_rows, const uint32_t **order) {
+    OrderPlan pl;
+    int rc = k7c_order_prepare(ctx, ids, nullptr, offs, n_groups, n_rows, &pl);
+    if (rc) return rc;
+    const int64_t *cols[2] = {ids, nullptr};
+    return k7c_order_way(ctx, pl, cols, 0, n_groups, order);
+}
 
 constexpr size_t K7C_LDS_BUDGET = 160 * 1024 - 2048;   // dynamic LDS of the scores kernel (its static piece table aside)
 
@@ -383,50 +473,9 @@ static int k7c_launch_t(pols_ctx *ctx, const ClusterArgs &c) {
         int rc = k7r_prepare_launch(ctx, sizeof(T) == 4 ? POLS_F32 : POLS_F64, ra);
         if (rc) return rc;
     }
-    // the work areas of every clustering at once (growing one later would free memory a queued kernel still reads)
-    SortBufs sb;
-    std::memset(&sb, 0, sizeof(sb));
-    sb.n = n;
-    uint32_t *order = nullptr;
-    ClusterProbe h;
-    std::memset(&h, 0, sizeof(h));
-    if (n > 0) {
-        size_t t32 = 0, t64 = 0;
-        int rc = k9_radix_sort_pairs<uint32_t>(ctx, nullptr, &t32, nullptr, nullptr, nullptr, nullptr, n, 32);
-        if (!rc) rc = k9_radix_sort_pairs<uint64_t>(ctx, nullptr, &t64, nullptr, nullptr, nullptr, nullptr, n, 64);
-        if (rc) return rc;
-        sb.tmp_bytes = round256(std::max(t32, t64));
-        const unsigned nblk = std::min<unsigned>(k7c_blocks(n), (unsigned)std::max(ctx->num_cus, 1) * 8);
-        const size_t kb = round256(sizeof(uint64_t) * (size_t)n), ib = round256(sizeof(uint32_t) * (size_t)n),
-                     pb = round256(sizeof(ClusterProbe) * nblk);
-        void *base = nullptr, *ob = nullptr;
-        if ((rc = ensure_scratch(ctx, Work::ClusterSort, 2 * kb + 3 * ib + pb + sb.tmp_bytes, &base))) return rc;
-        if ((rc = ensure_scratch(ctx, Work::ClusterOrder, ib, &ob))) return rc;
-        char *p = static_cast<char *>(base);
-        sb.keys_in = p; p += kb;
-        sb.keys_out = p; p += kb;
-        sb.vals[0] = reinterpret_cast<uint32_t *>(p); p += ib;
-        sb.vals[1] = reinterpret_cast<uint32_t *>(p); p += ib;
-        sb.rowgroup = reinterpret_cast<uint32_t *>(p); p += ib;
-        ClusterProbe *dprobe = reinterpret_cast<ClusterProbe *>(p); p += pb;
-        sb.tmp = p;
-        order = static_cast<uint32_t *>(ob);
-        // one probe for the ranges of both ids and the order of A, B and AB inside every group
-        std::vector<ClusterProbe> part(nblk);
-        hipLaunchKernelGGL(k7c_probe_kernel, dim3(nblk), dim3(256), 0, ctx->stream, c.ids[0], c.ways > 1 ? c.ids[1] : nullptr, a.offs, G, n, dprobe);
-        POLS_HIP(hipGetLastError());
-        POLS_HIP(hipMemcpyAsync(part.data(), dprobe, sizeof(ClusterProbe) * nblk, hipMemcpyDeviceToHost, ctx->stream));
-        POLS_HIP(hipStreamSynchronize(ctx->stream));
-        h = part[0];
-        for (unsigned q = 1; q < nblk; ++q) {
-            for (int w = 0; w < 2; ++w) { h.mn[w] = std::min(h.mn[w], part[q].mn[w]); h.mx[w] = std::max(h.mx[w], part[q].mx[w]); }
-            for (int w = 0; w < 3; ++w) h.uns[w] |= part[q].uns[w];
-        }
-        if ((h.uns[0] || h.uns[1] || h.uns[2]) && G > 1) {
-            hipLaunchKernelGGL(k7c_rowgroup_kernel, dim3(k7c_blocks(n)), dim3(256), 0, ctx->stream, a.offs, G, n, sb.rowgroup);
-            POLS_HIP(hipGetLastError());
-        }
-    }
+    OrderPlan pl;
+    int rc = k7c_order_prepare(ctx, c.ids[0], c.ways > 1 ? c.ids[1] : nullptr, a.offs, G, n, &pl);
+    if (rc) return rc;
     double *sums = c.part + (size_t)n_items * k7c_part_stride(kt);
     const int n_ways = c.ways == 2 ? 3 : 1;
     for (int wi = 0; wi < n_ways; ++wi) {
@@ -435,26 +484,7 @@ static int k7c_launch_t(pols_ctx *ctx, const ClusterArgs &c) {
         w.k2 = wi == 2 ? c.ids[1] : nullptr;
         w.part = c.part;
         w.sums = sums + (size_t)wi * G * (kt + 1);
-        w.order = nullptr;
-        if (n > 0 && h.uns[wi]) {
-            // LSD: the least significant key first; every pass is stable, so ties keep the order of the passes before
-            struct Pass { const int64_t *col; int64_t mn; int bits; };
-            Pass passes[2];
-            int np = 0;
-            const int ia = wi == 1 ? 1 : 0;
-            if (wi == 2) passes[np++] = {c.ids[1], h.mn[1], k7c_bits((uint64_t)h.mx[1] - (uint64_t)h.mn[1])};
-            passes[np++] = {c.ids[ia], h.mn[ia], k7c_bits((uint64_t)h.mx[ia] - (uint64_t)h.mn[ia])};
-            const int total = np + (G > 1 ? 1 : 0);
-            const uint32_t *cur = nullptr;
-            for (int q = 0; q < total; ++q) {
-                uint32_t *dst = q == total - 1 ? order : (cur == sb.vals[1] ? sb.vals[0] : sb.vals[1]);
-                int rc = q < np ? k7c_sort_pass<int64_t>(ctx, sb, passes[q].col, passes[q].mn, passes[q].bits, cur, dst)
-                                : k7c_sort_pass<uint32_t>(ctx, sb, sb.rowgroup, 0, k7c_bits((uint64_t)(G - 1)), cur, dst);
-                if (rc) return rc;
-                cur = dst;
-            }
-            w.order = order;
-        }
+        if ((rc = k7c_order_way(ctx, pl, c.ids, wi, G, &w.order))) return rc;
         hipLaunchKernelGGL(k7c_scores_kernel<T>, dim3((unsigned)n_items), dim3(256), lds, ctx->stream, c, w);
         hipLaunchKernelGGL(k7c_finish_kernel, dim3((unsigned)G), dim3(256), 0, ctx->stream, c, w);
         POLS_HIP(hipGetLastError());

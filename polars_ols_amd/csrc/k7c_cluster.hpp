@@ -32,6 +32,11 @@ __host__ __device__ inline size_t k7c_part_stride(int kt) { return 3 * (size_t)k
 // prepare (K7r's) / per clustering: runs, scores, finish / se, t, p on the stream; r2 / mae / mse come from K7 unchanged
 int k7c_cluster_launch(pols_ctx *ctx, int dtype, const ClusterArgs &c);
 
+// the runs step alone, for one id column (device, one id per row): *order = position -> row with every group's positions in ascending
+// id order and frame order within an id (Work::ClusterSort / ClusterOrder, valid until the next call that orders), or nullptr when
+// the probe found the ids non-decreasing inside every group already.  Synchronises the stream once (the probe's result).
+int k7c_order_launch(pols_ctx *ctx, const int64_t *ids, const int64_t *offs, int64_t n_groups, int64_t n_rows, const uint32_t **order);
+
 // out[w][i] = in[w][src[i]] for the ways id columns: the ids of the rows a null policy keeps (src: row_compact_srcmap_launch)
 int k7c_gather_ids_launch(pols_ctx *ctx, const int32_t *src, int64_t n, const int64_t *const *in, int64_t *const *out, int ways);
 

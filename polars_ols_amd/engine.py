@@ -420,6 +420,41 @@ class Engine:
                                want, y, x_cols, offsets, dict(weights=weights, valid=valid, add_intercept=add_intercept, null_policy=null_policy, out=out),
                                extra=bring_instruments)
 
+    def absorb(self, y, x_cols: Sequence, ids, offsets, *, cov_type: str = "nonrobust",
+               want: Sequence[str] = ("coef", "status", "se", "n_obs", "n_categories"), weights=None, valid=None,
+               add_intercept: bool = False, null_policy: str = "ignore", out: Optional[Dict] = None) -> Dict:
+        """Regression that absorbs one categorical effect inside every group -- the "within" estimator, ``areg`` / ``xtreg, fe`` --
+        for every group in one call, without a dummy column per category (pols_least_squares_absorb; the definitions and edge
+        rules are in include/pols_mi355x.h).  ``ids``: one integer id per row, in the rows' order.  ``cov_type``: "nonrobust" or
+        "cluster" (clustered on ``ids``).  ``want``: any of ``coef`` (the slopes, then the mean effect c0 with ``add_intercept``)
+        ``pred resid status`` (status 4 = no degrees of freedom), ``se t_values p_values`` [n_groups, k, f64], ``sigma2 r2_within
+        r2`` [n_groups, f64], ``fe`` [n_rows, batch dtype, the row's effect], ``n_obs n_categories`` [n_groups, int64].  Arrays are
+        numpy or torch and live where the inputs live.  Without any of ``se t_values p_values sigma2 r2_within r2`` the residual
+        pass is skipped."""
+        x_cols = list(x_cols)
+        q = _absorb_params(self._lib, len(x_cols), cov_type, add_intercept)
+
+        def bring_ids(b, like, dev):
+            if ids is None:
+                raise ValueError("absorb: 'ids' is required")
+            if dev:
+                col = torch.as_tensor(ids, device=like.device).to(torch.int64).contiguous()
+            elif _is_torch(ids):
+                col = np.ascontiguousarray(ids.cpu().numpy(), dtype=np.int64)
+            else:
+                col = np.ascontiguousarray(ids, dtype=np.int64)
+            if tuple(col.shape) != (b.n_rows,):
+                raise ValueError(f"absorb: {tuple(col.shape)} ids for {b.n_rows} rows")
+            q.ids = self._ptr(col)
+            return col
+
+        return self._fit_entry("absorb", "pols_least_squares_absorb", L.ABSORB_FIELDS, L.AbsorbOut, q,
+                               lambda G, N, kt: {"se": ((G, kt), "f64"), "t_values": ((G, kt), "f64"), "p_values": ((G, kt), "f64"),
+                                                 "sigma2": ((G,), "f64"), "r2_within": ((G,), "f64"), "r2": ((G,), "f64"),
+                                                 "fe": ((N,), "batch"), "n_obs": ((G,), "i64"), "n_categories": ((G,), "i64")},
+                               want, y, x_cols, offsets, dict(weights=weights, valid=valid, add_intercept=add_intercept, null_policy=null_policy, out=out),
+                               extra=bring_ids)
+
     def elastic_net_cv(self, y, x_cols: Sequence, offsets, alphas=None, *, n_alphas: int = 100, eps: float = 1e-3, l1_ratio: float = 0.5,
                        n_folds: int = 5, max_iter: int = 1000, tol: float = 1e-5, positive: bool = False,
                        want: Sequence[str] = ("coef", "status", "alpha", "alpha_index", "score"), weights=None, valid=None,
@@ -738,6 +773,22 @@ def _iv_params(lib, n_features, n_instruments, n_endog, cov_type, small_sample, 
     if lib is not None:
         lib.pols_iv_params_default(C.byref(q))
     q.n_endog, q.n_instruments, q.cov_type, q.small_sample = int(n_endog), int(n_instruments), L.COV_TYPES[cov_type], int(bool(small_sample))
+    return q
+
+
+def _absorb_params(lib, n_features, cov_type, add_intercept) -> "L.AbsorbParams":
+    """the argument checks of Engine.absorb / compute_absorbed_least_squares (``lib`` None: check only, no device needed)"""
+    if n_features < 1:
+        raise ValueError("absorb: at least one feature is required")
+    if cov_type not in L.ABSORB_COV_TYPES:
+        raise ValueError(f"absorb: 'cov_type' must be one of {list(L.ABSORB_COV_TYPES)}, got {cov_type!r}")
+    total = n_features + int(bool(add_intercept))
+    if total > L.ABSORB_MAX_COLUMNS:
+        raise ValueError(f"absorb: {total} features (incl. intercept) > {L.ABSORB_MAX_COLUMNS}")
+    q = L.AbsorbParams()
+    if lib is not None:
+        lib.pols_absorb_params_default(C.byref(q))
+    q.ids, q.cov_type = None, L.COV_TYPES[cov_type]
     return q
 
 

@@ -26,7 +26,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import PolsPanic
-from .engine import Engine, Layout, _enet_cv_params, _is_torch, _glm_params, _iv_params, _ridge_cv_grid, _rlm_params, default_engine
+from .engine import Engine, Layout, _absorb_params, _enet_cv_params, _is_torch, _glm_params, _iv_params, _ridge_cv_grid, _rlm_params, default_engine
 
 try:
     import torch
@@ -45,6 +45,7 @@ __all__ = [
     "compute_rlm", "RLM",
     "compute_glm", "GLM",
     "compute_iv2sls", "IV2SLS",
+    "compute_absorbed_least_squares", "AbsorbedOLS",
 ]
 
 # ---- polars_ols/least_squares.py:47-63 --------------------------------------------------------------------------
@@ -596,6 +597,41 @@ def _apply_iv2sls(frame: Frame, over, eng: Optional[Engine], target: Expr, exog:
     return target.output_name, grp.untake(out["pred"] if mode == "predictions" else out["resid"])
 
 
+class AbsorbedOLS(dict):
+    """mode="statistics" of an absorbed-effect fit (pols_least_squares_absorb; the definitions are in include/pols_mi355x.h): per
+    group ``coefficients standard_errors t_values p_values`` [G, k] (``feature_names``; with an intercept the last coefficient is the
+    mean effect c0 and its standard error / t / p are NaN), ``sigma2 r2_within r2 n_obs n_categories status`` [G]; ``keys`` holds the
+    group keys of an ``.over`` (None for a whole-frame fit, where G == 1)."""
+
+    def __init__(self, names, out, keys, cov_type):
+        super().__init__(feature_names=list(names), coefficients=out["coef"], standard_errors=out["se"], t_values=out["t_values"],
+                         p_values=out["p_values"], sigma2=out["sigma2"], r2_within=out["r2_within"], r2=out["r2"], n_obs=out["n_obs"],
+                         n_categories=out["n_categories"], status=out["status"], keys=keys, cov_type=cov_type)
+        self.keys_ = keys
+
+
+_VALID_ABSORB_MODES = ("predictions", "residuals", "coefficients", "statistics", "effects")
+
+
+def _apply_absorb(frame: Frame, over, eng: Optional[Engine], target: Expr, features: Sequence[Expr], absorb, sample_weights,
+                  add_intercept: bool, mode: str, cov_type: str, null_policy: str):
+    """compute_absorbed_least_squares body: the group layout of _apply_static around Engine.absorb; the id column moves with its rows."""
+    y, xs, names, icpt, w = _pre_process_data(frame, target, features, sample_weights, add_intercept)
+    ids = _cluster_ids(frame, [absorb], y)
+    eng = eng or default_engine(y.device.index or 0 if _is_torch(y) else 0)
+    grp = _Groups(eng, None if over is None else (frame[over] if isinstance(over, str) else over), y.shape[0])
+    moved = grp.take([y, w] + list(xs) + ids)
+    want = {"predictions": ("pred",), "residuals": ("resid",), "coefficients": ("coef",), "effects": ("fe",),
+            "statistics": ("coef", "status") + tuple(f for f in _lib.ABSORB_FIELDS if f != "fe")}[mode]
+    out = eng.absorb(moved[0], moved[2:2 + len(xs)], moved[2 + len(xs)], grp.offsets, cov_type=cov_type, want=want, weights=moved[1],
+                     add_intercept=icpt, null_policy=null_policy)
+    if mode == "statistics":
+        return "statistics", AbsorbedOLS(names, out, grp.keys, cov_type)
+    if mode == "coefficients":
+        return "coefficients", Coefficients(names, out["coef"], grp.keys, grp.gid_frame(out["coef"]))
+    return target.output_name, grp.untake(out[{"predictions": "pred", "residuals": "resid", "effects": "fe"}[mode]])
+
+
 def _apply_dynamic(frame: Frame, over, eng: Optional[Engine], target: Expr, features: Sequence[Expr], sample_weights,
                    add_intercept: bool, mode: str, kind: str, kw):
     """compute_recursive_least_squares / compute_rolling_least_squares bodies (ls.py:332-409 around
@@ -788,6 +824,27 @@ def compute_iv2sls(target, *exog, endog, instruments, cov_type: str = "nonrobust
     _iv_params(None, len(ex) + len(en), len(zs), len(en), cov_type, small_sample, icpt)
     return Expr(t._name, fn=lambda frame, over, eng: _apply_iv2sls(frame, over, eng, t, ex, en, zs, sample_weights, add_intercept, mode,
                                                                    cov_type, small_sample, null_policy))
+
+
+def compute_absorbed_least_squares(target, *features, absorb, cov_type: str = "nonrobust", sample_weights=None,
+                                   add_intercept: bool = False, mode: str = "predictions", null_policy: str = "ignore") -> Expr:
+    """Regression per group that absorbs one categorical effect (the "within" estimator: ``areg``, ``xtreg, fe``,
+    ``PanelOLS(entity_effects=True)``) without a dummy column per category.  ``absorb``: the id column (a name, an expression or an
+    array; under ``.over(key)`` it moves with its rows).  Modes "predictions" (x'b plus the row's effect), "residuals",
+    "coefficients" (the slopes; with ``add_intercept`` the mean effect last) and "effects" (the row's effect, centred on the mean
+    effect with ``add_intercept``); mode="statistics" returns an ``AbsorbedOLS`` with standard errors (``cov_type`` "nonrobust" or
+    "cluster", clustered on the absorbed id), t and p values, sigma2, the within and overall R2 and the category counts."""
+    if mode not in _VALID_ABSORB_MODES:
+        raise ValueError(f"'mode' must be one of {_VALID_ABSORB_MODES}, got {mode!r}")
+    if null_policy not in _VALID_NULL_POLICIES:
+        raise ValueError(f"'null_policy' must be one of {sorted(_VALID_NULL_POLICIES)}, got {null_policy!r}")
+    if absorb is None:
+        raise ValueError("'absorb' names the id column whose effect is absorbed")
+    t, fs = parse_into_expr(target), [parse_into_expr(f) for f in features]
+    icpt = add_intercept and not any(f.output_name == "const" for f in fs)
+    _absorb_params(None, len(fs), cov_type, icpt)
+    return Expr(t._name, fn=lambda frame, over, eng: _apply_absorb(frame, over, eng, t, fs, absorb, sample_weights, add_intercept, mode,
+                                                                   cov_type, null_policy))
 
 
 def compute_multi_target_least_squares(targets, *features, sample_weights=None, add_intercept: bool = False,
@@ -1063,6 +1120,11 @@ class LeastSquares:
                add_intercept: bool = False, mode: str = "predictions", null_policy: str = "ignore") -> Expr:
         return compute_iv2sls(self._expr, *exog, endog=endog, instruments=instruments, cov_type=cov_type, small_sample=small_sample,
                               sample_weights=sample_weights, add_intercept=add_intercept, mode=mode, null_policy=null_policy)
+
+    def absorb(self, *features, absorb, cov_type: str = "nonrobust", sample_weights=None, add_intercept: bool = False,
+               mode: str = "predictions", null_policy: str = "ignore") -> Expr:
+        return compute_absorbed_least_squares(self._expr, *features, absorb=absorb, cov_type=cov_type, sample_weights=sample_weights,
+                                              add_intercept=add_intercept, mode=mode, null_policy=null_policy)
 
     def lasso(self, *features, alpha: float, **kwargs) -> Expr:
         return self.least_squares(*features, alpha=alpha, l1_ratio=1.0, **kwargs)
