@@ -13,7 +13,6 @@
 #include "k1_gram_chol.hpp"
 #include "k2_resident.hpp"
 #include "k2w_resident.hpp"
-#include "k3_rls.hpp"
 #include "k4_rolling.hpp"
 #include "k5_enet.hpp"
 #include "k6_svd.hpp"
@@ -229,12 +228,15 @@ bool options_set(Options &o, const char *key, const char *v) {
     else if (ieq(key, "K1_PERSIST_SUB")) o.k1_persist_sub = on ? std::atoi(v) : d.k1_persist_sub;
     else if (ieq(key, "K1T_SUB32")) o.k1t_sub32 = on ? (std::atoi(v) != 0) : d.k1t_sub32;
     else if (ieq(key, "STATIC_ENGINE")) o.static_engine = !on ? 0 : ieq(v, "stream") ? 1 : ieq(v, "k2") ? 2 : ieq(v, "nok2") ? 3 : ieq(v, "k2w") ? 4 : 0;
-    else if (ieq(key, "RLS_ENGINE")) o.rls_engine = !on ? 0 : ieq(v, "seq") ? 1 : ieq(v, "scan") ? 2 : ieq(v, "chunk") ? 3 : ieq(v, "halo") ? 4 : 0;
+    else if (ieq(key, "RLS_ENGINE")) o.rls_engine = !on ? RlsEngine::Auto : ieq(v, "seq") ? RlsEngine::Seq : ieq(v, "scan") ? RlsEngine::Scan : ieq(v, "chunk") ? RlsEngine::Chunk : ieq(v, "halo") ? RlsEngine::Halo : RlsEngine::Auto;
     else if (ieq(key, "RLM_ENGINE")) o.rlm_engine = !on ? 0 : ieq(v, "stream") ? 1 : 0;
     else if (ieq(key, "GLM_ENGINE")) o.glm_engine = !on ? 0 : ieq(v, "split") ? 1 : 0;
     else if (ieq(key, "RLS_SPINS")) o.rls_spin_limit = on ? std::atoi(v) : d.rls_spin_limit;
     else if (ieq(key, "RLS_EARLY")) o.rls_early = on ? std::atoi(v) : d.rls_early;
-    else if (ieq(key, "ROLLING_ENGINE")) o.rolling_engine = !on ? 0 : ieq(v, "chunk") ? 1 : ieq(v, "halo") ? 2 : ieq(v, "nocompact") ? 3 : ieq(v, "halowave") ? 4 : ieq(v, "scatter") ? 5 : 0;
+    else if (ieq(key, "ROLLING_ENGINE")) {
+        using E = RollingEngine;
+        o.rolling_engine = !on ? E::Auto : ieq(v, "chunk") ? E::Chunk : ieq(v, "halo") ? E::Halo : ieq(v, "nocompact") ? E::NoCompact : ieq(v, "halowave") ? E::HaloWave : ieq(v, "scatter") ? E::Scatter : E::Auto;
+    }
     else if (ieq(key, "K1_ENGINE")) o.k1_engine = !on ? 0 : ieq(v, "valu") ? 1 : ieq(v, "mfma") ? 2 : 0;
     else if (ieq(key, "K9_TAKE")) o.k9_take = !on ? 0 : ieq(v, "gather") ? 1 : ieq(v, "scatter") ? 2 : 0;
     else return false;
@@ -610,7 +612,7 @@ int pols_timing_collect(pols_ctx *ctx, float *ms_out, int max) {
 
 const char *pols_last_kernel_name(pols_ctx *ctx) { return ctx ? ctx->last_kernel.c_str() : ""; }
 
-// ------------------------------------------------------------------ defaults (ls.py:101-107, 137-140, 156-160)
+// ------------------------------------------------------------------ defaults (ls.py:101-107; the dynamic entries': api_dynamic.hip)
 void pols_ols_params_default(pols_ols_params *p) {
     std::memset(p, 0, sizeof(*p));
     p->alpha = 0.0;
@@ -621,23 +623,6 @@ void pols_ols_params_default(pols_ols_params *p) {
     p->solve_method = POLS_SOLVE_AUTO;
     p->has_rcond = 0;
     p->null_policy = POLS_NULL_IGNORE;
-}
-
-void pols_rls_params_default(pols_rls_params *p) {
-    std::memset(p, 0, sizeof(*p));
-    p->has_half_life = 0;
-    p->initial_state_covariance = 10.0;
-    p->initial_state_mean = nullptr;
-    p->null_policy = POLS_NULL_DROP;
-}
-
-void pols_rolling_params_default(pols_rolling_params *p) {
-    std::memset(p, 0, sizeof(*p));
-    p->window_size = 1000000;
-    p->min_periods = -1;
-    p->use_woodbury = -1;
-    p->alpha = 0.0;
-    p->null_policy = POLS_NULL_DROP_WINDOW;
 }
 
 // Long groups cut into segments: SegTables and what ensure_segments builds are described in api_internal.hpp.  (C++ linkage, as declared
@@ -1126,749 +1111,6 @@ int pols_least_squares_statistics_cluster(pols_ctx *ctx, const pols_batch *b, co
         if (!cl->ids[w] && b->n_rows > 0) return fail(POLS_ERR_INVALID, "cluster statistics: ids[%d] is NULL", w);
     if (b->n_rows >= ((int64_t)1 << 31)) return fail(POLS_ERR_UNSUPPORTED, "cluster statistics: %lld rows (row indices are 31-bit)", (long long)b->n_rows);
     return statistics_body(ctx, b, p, nullptr, cl, o, s);
-}
-
-// Dynamic models share the staging of a batch whose coefficient output has one row per input row, and the pre-processing the
-// reference's Python layer / plugin bodies do around the solver (dyn_prep.hpp): validity from the null policy, sqrt(w) scaling, the
-// ones column, nulls -> 0 -- on the device, behind the boundary.
-struct DynState {
-    int k = 0;                       // columns the kernels see: n_features + add_intercept
-    bool post = false;               // predictions need the 1 / sqrt(w) un-scaling and / or the validity mask
-    DynPrepArgs pa;
-    pols_batch tables;               // the batch as build_chunk_tables should see it (validity bytes may now live on the device)
-    bool deferred = false;           // the zero-filling rewrite of the columns has been left out (see dynamic_prologue's may_defer)
-    std::vector<void *> outp;        // ... and these are the columns it would write
-};
-
-// may_defer: the caller has a kernel that masks invalid rows itself (the masked tile kernel of the rolling entry): the zero-filling rewrite
-// of the columns -- a read and a write of the whole frame -- is skipped and left to dynamic_rewrite_deferred() should that kernel not be taken.
-static int dynamic_prologue(pols_ctx *ctx, const pols_batch *b, int null_policy, pols_out *o, const int64_t **d_offs, int64_t *max_rows,
-                            Staged *st, DynState *ds, bool may_defer = false) {
-    int rc = check_ctx(ctx);
-    if (rc) return rc;
-    if ((rc = check_batch(b, o, K4Y_KMAX))) return rc;
-    if (null_policy < POLS_NULL_IGNORE || null_policy > POLS_NULL_DROP_WINDOW) return fail(POLS_ERR_INVALID, "unknown null_policy %d", null_policy);
-    const int k = b->n_features + (b->add_intercept ? 1 : 0);
-    ds->k = k;
-    ds->tables = *b;
-    std::memset(&ds->pa, 0, sizeof(ds->pa));
-    if ((rc = upload_offsets(ctx, b->group_offsets, b->n_groups, d_offs, max_rows, b->offsets_generation))) return rc;
-    if ((rc = stage_inputs(ctx, b, b->n_rows, k, o, st))) return rc;
-    if (b->n_groups == 0 || b->n_rows == 0) return POLS_OK;
-    const bool scan = st->valid == nullptr && !b->null_free;   // no validity bytes from the caller: a null is a NaN, the policy decides
-    const bool has_w = st->w != nullptr, icpt = b->add_intercept != 0;
-    bool some_invalid = !scan, some_null = false;
-    const size_t sz = dtype_size(b->dtype), colb = round256(sz * (size_t)b->n_rows), vb = round256((size_t)b->n_rows);
-    char *base = nullptr;
-    DynPrepArgs &pa = ds->pa;
-    // (a caller's validity bytes without weights / intercept: the columns may still hold NaNs on the masked rows -- they are
-    //  zero-filled like everywhere else, so that no prefix sum ever meets a NaN; null_free says there is nothing to fill)
-    if (scan || has_w || icpt || (st->valid != nullptr && !b->null_free)) {
-        // Work::DynPrep: [flags][validity bytes][feature pointers in][column pointers out][sqrt(w)][target][k columns]
-        void *d = nullptr;
-        const size_t tabb = round256(sizeof(void *) * (size_t)std::max(k, 1));
-        if ((rc = ensure_scratch(ctx, Work::DynPrep, 256 + vb + 2 * tabb + colb * (size_t)(k + 2), &d))) return rc;
-        base = static_cast<char *>(d);
-        char *cols = base + 256 + vb + 2 * tabb;
-        std::vector<void *> outp((size_t)k);
-        for (int j = 0; j < k; ++j) outp[(size_t)j] = cols + colb * (size_t)(2 + j);
-        if ((rc = upload_small(ctx, base + 256 + vb, st->x.data(), sizeof(void *) * (size_t)b->n_features))) return rc;
-        if ((rc = upload_small(ctx, base + 256 + vb + tabb, outp.data(), sizeof(void *) * (size_t)k))) return rc;
-        pa.y = st->y; pa.w = st->w;
-        pa.xtab = reinterpret_cast<const void *const *>(base + 256 + vb);
-        pa.k_user = b->n_features; pa.add_intercept = icpt ? 1 : 0; pa.null_policy = null_policy; pa.n_rows = b->n_rows;
-        pa.valid_out = reinterpret_cast<uint8_t *>(base + 256);
-        pa.flags = reinterpret_cast<int32_t *>(base);
-        pa.sw_out = has_w ? cols : nullptr;
-        pa.y_out = cols + colb;
-        pa.xout = reinterpret_cast<void *const *>(base + 256 + vb + tabb);
-        if (scan) {
-            POLS_HIP(hipMemsetAsync(base, 0, 256, ctx->stream));
-            if ((rc = dyn_scan_launch(ctx, b->dtype, pa))) return rc;
-            int32_t flags[2] = {0, 0};
-            POLS_HIP(hipMemcpyAsync(flags, base, sizeof(flags), hipMemcpyDeviceToHost, ctx->stream));
-            POLS_HIP(hipStreamSynchronize(ctx->stream));   // the host decides which path runs (mask-free tables are cached)
-            some_invalid = flags[0] > 0;
-            some_null = flags[1] > 0;
-            if (some_invalid) {
-                st->valid = pa.valid_out;
-                ds->tables.valid = pa.valid_out;
-                ds->tables.mem = POLS_MEM_DEVICE;
-            }
-        }
-        if (has_w || icpt || some_invalid || some_null) {
-            // (rows left out of the fit hold the nulls that put them there: zero-filled too, so that no kernel ever multiplies a NaN by 0)
-            if (may_defer && !has_w && !icpt && st->valid != nullptr && !some_null) {    // (a null INSIDE a kept row has to be filled: no deferral)
-                ds->deferred = true;                          // the columns stay the caller's; dynamic_rewrite_deferred() does this later if needed
-                ds->outp.assign(outp.begin(), outp.end());
-            } else {
-                if ((rc = dyn_rewrite_launch(ctx, b->dtype, pa))) return rc;
-                st->y = pa.y_out;
-                st->x.assign(outp.begin(), outp.end());
-            }
-        }
-    }
-    ds->post = (has_w || st->valid != nullptr) && st->pred != nullptr;
-    pa.pred = st->pred;
-    pa.valid_post = st->valid;
-    if (!has_w) pa.sw_out = nullptr;
-    return POLS_OK;
-}
-
-static int dynamic_rewrite_deferred(pols_ctx *ctx, const pols_batch *b, Staged *st, DynState *ds) {
-    if (!ds->deferred) return POLS_OK;
-    int rc = dyn_rewrite_launch(ctx, b->dtype, ds->pa);
-    if (rc) return rc;
-    st->y = ds->pa.y_out;
-    st->x.assign(ds->outp.begin(), ds->outp.end());
-    ds->deferred = false;
-    return POLS_OK;
-}
-
-static int build_chunk_tables(pols_ctx *ctx, const pols_batch *b, int64_t mp, int slots, K4Args *a, int64_t min_chunk = 64, int64_t max_chunk = 512);
-// beyond 128 features a chunk carries a k x k state and a k x k total in HBM (16 MB at k = 1 024) and its workgroup an O(k^3)
-// inversion: a few hundred long chunks instead of thousands of 64-row ones
-static int64_t hbm_state_chunk(int64_t n_rows) { return std::max<int64_t>(64, (n_rows + 383) / 384); }
-
-// Work::Tables of the dynamic entries: [128 doubles: RLS prior mean][column pointer table for more than 32 features]
-static int dynamic_tables(pols_ctx *ctx, void **base) {
-    return ensure_scratch(ctx, Work::Tables, sizeof(double) * K4Y_KMAX + sizeof(void *) * K4Y_KMAX, base);
-}
-static int upload_column_table(pols_ctx *ctx, const Staged &st, int k, K4Args *a) {
-    for (int j = 0; j < std::min(k, (int)POLS_MAX_FEATURES); ++j) a->x[j] = st.x[j];
-    if (k <= POLS_MAX_FEATURES) return POLS_OK;
-    void *d = nullptr;
-    int rc = dynamic_tables(ctx, &d);
-    if (rc) return rc;
-    char *tab = static_cast<char *>(d) + sizeof(double) * K4Y_KMAX;
-    if ((rc = upload_small(ctx, tab, st.x.data(), sizeof(void *) * (size_t)k))) return rc;
-    a->xtab = reinterpret_cast<const void *const *>(tab);
-    return POLS_OK;
-}
-
-// Sequence-start bytes of the row-parallel dynamic kernels, cached per uploaded offsets.
-static int ensure_start_flags(pols_ctx *ctx, const int64_t *d_offs, int64_t n_groups, int64_t n_rows, const uint8_t **flags) {
-    auto &fc = ctx->start_flags;
-    void *d = nullptr;
-    int rc = grow(fc, round256((size_t)n_rows + 4), &d);
-    if (rc) return rc;
-    if (!fc.valid || fc.offs_id != ctx->offs_id || fc.n_groups != n_groups || fc.n_rows != n_rows) {
-        fc.valid = false;
-        if ((rc = k3c_start_flags(ctx, d_offs, n_groups, n_rows, static_cast<uint8_t *>(d)))) return rc;
-        fc.valid = true; fc.offs_id = ctx->offs_id; fc.n_groups = n_groups; fc.n_rows = n_rows;
-    }
-    *flags = static_cast<const uint8_t *>(d);
-    return POLS_OK;
-}
-
-// first rows of the packed tiles of a frame (whole sequences per tile, first fit in frame order; N appended) -- see ensure_packed_tiles
-static void packed_tile_starts(const int64_t *offs, int64_t n_groups, int64_t N, int64_t tile_rows, std::vector<int64_t> *first) {
-    first->clear();
-    int64_t base = -1;
-    for (int64_t g = 0; g < n_groups; ++g) {
-        if (offs[g + 1] == offs[g]) continue;
-        if (base < 0 || offs[g + 1] - base > tile_rows) { first->push_back(offs[g]); base = offs[g] & ~(int64_t)3; }
-    }
-    first->push_back(N);
-}
-
-// Packed tiles of the row-parallel dynamic kernels (K3c / K4c): no sequence longer than a tile (less the three rows a tile may start
-// before its first sequence) -> tiles are cut at sequence starts, whole sequences, first fit in frame order; tile t owns rows
-// [map[t], map[t + 1]).  Taken when the tiles come out at least 70 % full; *n_tiles = 0 otherwise.  Cached per frame (ctx->k3c).
-static int ensure_packed_tiles(pols_ctx *ctx, const pols_batch *b, int64_t tile_rows, int64_t max_rows, const int64_t **map, int64_t *n_tiles) {
-    *map = nullptr; *n_tiles = 0;
-    if (max_rows > tile_rows - 3) return POLS_OK;
-    const int64_t N = b->n_rows;
-    auto &tc = ctx->k3c;
-    void *dmap = nullptr;
-    int rc = grow(tc, round256(sizeof(int64_t) * (size_t)(b->n_groups + 2)), &dmap);
-    if (rc) return rc;
-    if (!tc.valid || tc.offs_id != ctx->offs_id || tc.n_groups != b->n_groups || tc.n_rows != N || tc.tile_rows != tile_rows) {
-        tc.valid = false;
-        std::vector<int64_t> first;
-        packed_tile_starts(b->group_offsets, b->n_groups, N, tile_rows, &first);
-        const int64_t nt = (int64_t)first.size() - 1;
-        tc.n_tiles = nt * tile_rows * 7 <= N * 10 ? nt : 0;
-        if (tc.n_tiles && (rc = upload_small(ctx, dmap, first.data(), sizeof(int64_t) * first.size()))) return rc;
-        tc.valid = true; tc.offs_id = ctx->offs_id; tc.n_groups = b->n_groups; tc.n_rows = N; tc.tile_rows = tile_rows;
-    }
-    *n_tiles = tc.n_tiles;
-    if (tc.n_tiles) *map = static_cast<const int64_t *>(dmap);
-    return POLS_OK;
-}
-
-// K3c's halo form: per tile of tile_rows rows the first row of the sequence that holds the row in front of the tile (tile 0: 0) -- the
-// prior's decay up to the tile is then exact.  Cached per frame (ctx->k3h).
-static int ensure_tile_seq0(pols_ctx *ctx, const pols_batch *b, int64_t tile_rows, int64_t n_tiles, const int64_t **map) {
-    *map = nullptr;
-    const int64_t N = b->n_rows;
-    auto &tc = ctx->k3h;
-    void *dmap = nullptr;
-    int rc = grow(tc, round256(sizeof(int64_t) * (size_t)(n_tiles + 1)), &dmap);
-    if (rc) return rc;
-    if (!tc.valid || tc.offs_id != ctx->offs_id || tc.n_groups != b->n_groups || tc.n_rows != N || tc.tile_rows != tile_rows) {
-        tc.valid = false;
-        std::vector<int64_t> first((size_t)n_tiles, 0);
-        const int64_t *offs = b->group_offsets;
-        int64_t g = 0;
-        for (int64_t t = 1; t < n_tiles; ++t) {
-            const int64_t row = t * tile_rows - 1;
-            while (g + 1 < b->n_groups && offs[g + 1] <= row) ++g;            // the (non-empty) group that holds `row`
-            first[(size_t)t] = offs[g];
-        }
-        if ((rc = upload_small(ctx, dmap, first.data(), sizeof(int64_t) * first.size()))) return rc;
-        tc.valid = true; tc.offs_id = ctx->offs_id; tc.n_groups = b->n_groups; tc.n_rows = N; tc.tile_rows = tile_rows;
-    }
-    *map = static_cast<const int64_t *>(dmap);
-    return POLS_OK;
-}
-
-int pols_recursive_least_squares(pols_ctx *ctx, const pols_batch *b, const pols_rls_params *p, pols_out *o) {
-    if (!p) return fail(POLS_ERR_INVALID, "params is NULL");
-    const int64_t *d_offs = nullptr;
-    int64_t max_rows = 0;
-    Staged st;
-    DynState ds;
-    // (may_defer: the row-parallel kernel K3c masks invalid rows itself -- their values are SELECTED to zero, their decay is 1 -- so the zero-filling
-    //  rewrite of the frame, a read and a write of every column, is left out on frames it takes: 10 000 x 1 000 x 6 with 3 % nulls 0.49 -> 0.31 ms)
-    int rc = dynamic_prologue(ctx, b, p->null_policy, o, &d_offs, &max_rows, &st, &ds, true);
-    if (rc) return rc;
-    if (b->n_groups == 0 || b->n_rows == 0) return POLS_OK;
-    if (o->resid) return fail(POLS_ERR_INVALID, "rls: residuals are target - predictions in the caller (least_squares.py:239)");
-    const int kf = ds.k;                                  // features the kernels see (the intercept column included)
-    // Up to 10 features (8 + intercept and beyond): the row-parallel, read-once kernel (K3c, k3c_scan.hip) whatever the sequence lengths -- every
-    // access a 16-byte one down the row axis, so it needs 16-byte aligned columns / outputs (anything else: the chunk kernels below).
-    // POLS_RLS_ENGINE=seq|chunk go back to K3 / the lane-per-chunk K3s.
-    auto rowpar_ok = [&]() {
-        bool ok = kf <= K3C_KMAX && ctx->opt.rls_engine != 1 && ctx->opt.rls_engine != 3 && aligned16(st.y) && (!st.coef || aligned16(st.coef)) &&
-                  (!st.pred || aligned16(st.pred)) && (!st.valid || (reinterpret_cast<uintptr_t>(st.valid) & 3) == 0);
-        for (int j = 0; j < kf && ok; ++j) ok = aligned16(st.x[j]);
-        return ok;
-    };
-    bool rowpar = rowpar_ok();
-    if (!rowpar && ds.deferred) {                         // every other kernel wants zero-filled columns (and the rewritten ones are aligned)
-        if ((rc = dynamic_rewrite_deferred(ctx, b, &st, &ds))) return rc;
-        rowpar = rowpar_ok();
-    }
-    K3Args a;
-    std::memset(&a, 0, sizeof(a));
-    a.y = st.y; a.valid = st.valid;
-    for (int j = 0; j < std::min<int>(kf, POLS_MAX_FEATURES); ++j) a.x[j] = st.x[j];
-    a.offs = d_offs;
-    a.n_groups = b->n_groups;
-    a.coef = st.coef; a.pred = st.pred;
-    a.k = kf;
-    a.forgetting_factor = p->has_half_life ? std::exp(std::log(0.5) / p->half_life) : 1.0;   // ls.rs:513-517
-    a.initial_state_covariance = p->initial_state_covariance;
-    if (p->initial_state_mean) {
-        void *d = nullptr;
-        if ((rc = dynamic_tables(ctx, &d))) return rc;
-        if ((rc = upload_small(ctx, d, p->initial_state_mean, sizeof(double) * kf))) return rc;   // the host array belongs to the caller (kf values)
-        a.mean0 = static_cast<const double *>(d);
-    }
-    // Long sequences: the chunk-parallel information-form scan (K3s); short ones: the wave-per-sequence P-form
-    // recursion (K3).  POLS_RLS_ENGINE=seq|scan forces one.
-    // More than 8 features: the wave-per-chunk scan (k4w_wide.hip), whatever the length; more than 32: the workgroup-per-chunk
-    // kernels that propagate the inverse (k4x_inverse.hip).
-    const bool wide = kf > K4_KMAX, xwide = kf > POLS_MAX_FEATURES;
-    bool scan = max_rows > 4096 || wide;
-    if (ctx->opt.rls_engine == 1 && !wide) scan = false;
-    if (ctx->opt.rls_engine == 2 || ctx->opt.rls_engine == 3) scan = true;
-    if (rowpar) {
-        const int64_t N = b->n_rows, tile_rows = k3c_tile_rows(kf), n_tiles = (N + tile_rows - 1) / tile_rows;
-        const int64_t n_blocks = (n_tiles + 63) / 64;
-        const size_t b_rec = round256(sizeof(double) * K3C_NCP * (size_t)n_tiles), b_int = round256(sizeof(int32_t) * (size_t)n_tiles),
-                     b_brec = round256(sizeof(double) * K3C_NCP * (size_t)n_blocks), b_bint = round256(sizeof(int32_t) * (size_t)n_blocks),
-                     total = 2 * b_rec + 2 * b_int + 2 * b_brec + b_bint;
-        void *d = nullptr;
-        if ((rc = ensure_scratch(ctx, Work::K3cRecords, total, &d))) return rc;
-        char *base = static_cast<char *>(d);
-        const uint8_t *flags = nullptr;
-        if ((rc = ensure_start_flags(ctx, d_offs, b->n_groups, N, &flags))) return rc;
-        K3cArgs c;
-        std::memset(&c, 0, sizeof(c));
-        // No sequence longer than a tile (less the three rows a tile may start before its first sequence): tiles are cut at sequence
-        // starts -- whole sequences, first fit in frame order -- and need no carry-in, so ONE launch reads and writes the frame once.
-        // Taken when the packed tiles are at least 70 % full (the two-pass form costs about 1.5 launches of full tiles).
-        int64_t n_packed = 0;
-        if (ctx->opt.rls_engine != 2 && (rc = ensure_packed_tiles(ctx, b, tile_rows, max_rows, &c.tile_row0, &n_packed))) return rc;
-        c.y = st.y; c.valid = st.valid; c.start = flags;
-        for (int j = 0; j < kf; ++j) c.x[j] = st.x[j];
-        c.n_rows = N; c.coef = st.coef; c.pred = st.pred; c.mean0 = a.mean0;
-        c.ff = a.forgetting_factor; c.p0 = a.initial_state_covariance;
-        c.rec = reinterpret_cast<double *>(base); c.carry = reinterpret_cast<double *>(base + b_rec);
-        c.rec_closed = reinterpret_cast<int32_t *>(base + 2 * b_rec); c.carry_open = reinterpret_cast<int32_t *>(base + 2 * b_rec + b_int);
-        c.brec = reinterpret_cast<double *>(base + 2 * b_rec + 2 * b_int); c.bcarry = reinterpret_cast<double *>(base + 2 * b_rec + 2 * b_int + b_brec);
-        c.brec_closed = reinterpret_cast<int32_t *>(base + 2 * b_rec + 2 * b_int + 2 * b_brec);
-        c.n_tiles = n_packed ? n_packed : n_tiles; c.k = kf;
-        c.all_closed = n_packed || max_rows <= tile_rows ? 1 : 0;   // (any tile_rows consecutive rows then hold a sequence start)
-        // A finite half-life bounds how far back a row's state reaches: with ff^H <= 2^-36 for H = 256 .. 2 048 rows (half_life <= 56.9) a tile
-        // re-accumulates its carry-in from the H rows in front of it -- one launch, no records, no scan over the tiles (k3c_scan.hip, step H).
-        // Null-free frames only (a masked row does not decay the state, so the distance to the tile is not the row distance);
-        // POLS_RLS_ENGINE=scan keeps the exact scan, which also serves half_life = None and the longer half-lives.
-        const int32_t halo = n_packed || st.valid || ctx->opt.rls_engine == 2 || kf > K3C_HALO_KMAX ? 0 : k3c_halo_batches(c.ff);
-        if (halo) {
-            if ((rc = ensure_tile_seq0(ctx, b, tile_rows, n_tiles, &c.tile_seq0))) return rc;
-            c.halo_batches = halo; c.log2ff = std::log2(c.ff); c.ffstep = std::pow(c.ff, (double)(tile_rows - 4));
-            c.fresh_need = (int32_t)std::min<double>(std::ceil(-32.0 / c.log2ff), 256.0 * halo - 4.0);
-            // ... and when the rows that matter all lie in the ONE tile in front (H <= 1 024 = a four-wave tile, up to 6 features), that tile's own
-            // aggregate is all the carry-in needs: the look-back-one form (k3c_scan.hip MODE 3) -- every tile publishes its aggregate early, picks up
-            // its predecessor's behind its own scan, and re-reads nothing.  POLS_RLS_ENGINE=halo keeps the halo form.
-            const size_t gbytes = (size_t)n_tiles * 32 * 16;
-            if (kf <= 6 && halo <= 4 && tile_rows == 1024 && n_tiles > 1 && gbytes < ((size_t)1 << 31) && ctx->opt.rls_engine != 4) {
-                void *g = nullptr;
-                bool fresh = false;
-                if ((rc = grow(ctx->k3c_gran, gbytes, &g, &fresh))) return rc;
-                if (fresh) POLS_HIP(hipMemsetAsync(g, 0, ctx->k3c_gran.cap, ctx->stream));       // no stale tag may survive
-                c.gran = g; c.gran_bytes = (int64_t)gbytes; c.epoch = ++ctx->k3c_epoch;
-                c.spin_limit = ctx->opt.rls_spin_limit >= 0 ? ctx->opt.rls_spin_limit : 64;
-                c.early_publish = ctx->opt.rls_early;
-            }
-        }
-        if ((rc = k3c_launch(ctx, b->dtype, c))) return rc;
-    } else if (scan) {
-        const int k = kf;
-        K4Args s4;
-        std::memset(&s4, 0, sizeof(s4));
-        // 9..32 features: one wave per chunk with the covariance distributed over its registers (K3p, k4p_wide.hip).  A sequence of up to
-        // 1 024 rows is one chunk (the recursion starts from the prior: no totals, no scan); POLS_RLS_ENGINE=chunk keeps k4w_wide.hip.
-        const bool wave_p = wide && !xwide && ctx->opt.rls_engine != 3;
-        // (thousands of sequences are parallelism enough: only the few beyond 1 024 rows are cut then, and only they pay the totals pass and the scan)
-        const int64_t pchunk = (max_rows <= 1024 || b->n_groups >= 4096) ? 1024 : std::min<int64_t>(1024, std::max<int64_t>(256, b->n_rows / 16384));
-        const int64_t minc = wave_p ? pchunk : (k > 128 ? hbm_state_chunk(b->n_rows) : 64);
-        if ((rc = build_chunk_tables(ctx, &ds.tables, 1, wide ? k * k + k + 1 : k * (k + 1) / 2 + k + 1, &s4, minc, wave_p ? pchunk : std::max<int64_t>(512, minc)))) return rc;
-        s4.y = st.y; s4.valid = st.valid;
-        if ((rc = upload_column_table(ctx, st, k, &s4))) return rc;
-        s4.coef = st.coef; s4.pred = st.pred;
-        s4.k = k;
-        s4.ff = a.forgetting_factor; s4.p0 = a.initial_state_covariance; s4.mean0 = a.mean0;
-        if (wide) { s4.tot_cs = k * k + k + 1; s4.tot_qs = 1; }            // chunk-major for the wave / workgroup-per-chunk kernels
-        else { s4.tot_cs = 1; s4.tot_qs = s4.n_chunks; }                   // component-major for the lane-per-chunk kernels
-        if (wave_p) rc = k4p_launch(ctx, b->dtype, s4, true, max_rows <= pchunk);
-        else rc = k > K4X_KMAX ? k3y_launch(ctx, b->dtype, s4) : xwide ? k3x_launch(ctx, b->dtype, s4) : (wide ? k3sw_launch(ctx, b->dtype, s4) : k3s_launch(ctx, b->dtype, s4));
-        if (rc) return rc;
-    } else {
-        if ((rc = k3_launch(ctx, b->dtype, a))) return rc;
-    }
-    // (the row-parallel kernel writes the null predictions of the rows left out itself: the post pass is only its 1 / sqrt(w) un-scaling there)
-    if (ds.post && (!rowpar || ds.pa.sw_out) && (rc = dyn_post_launch(ctx, b->dtype, ds.pa))) return rc;
-    return unstage_outputs(ctx, b, b->n_rows, kf, o, st);
-}
-
-// Host-side tables shared by the chunk-parallel dynamic kernels (K4 rolling, K3s RLS scan): validity prefix
-// (cnt / vidx), per-group warm-up constants of solve_rolling_ols (ls.rs:881-900) and the chunk list; uploaded to
-// ctx->chunk_cache's table, the per-chunk totals live in Work::Gram (`slots` doubles per chunk).  Only the tables of a mask-free batch on
-// the uploaded offsets are kept for the next call: other offsets (a compacted frame) can share every key the cache compares.
-static int build_chunk_tables(pols_ctx *ctx, const pols_batch *b, int64_t mp, int slots, K4Args *a, int64_t min_chunk, int64_t max_chunk) {
-    int rc;
-    const int64_t N = b->n_rows;
-    std::vector<uint8_t> hvalid;
-    const uint8_t *hv = nullptr;
-    // validity bytes that live on the device: the prefix tables are built there too (dyn_prep.hip valid_tables_launch) -- copying the
-    // bytes home, walking every row and uploading two int32 tables was 40+ ms of a 10 M-row call whose kernels take 3-5
-    const bool uploaded = ctx->offsets.valid && b->group_offsets == ctx->offs_host;
-    const bool dev_tables = b->valid && b->mem == POLS_MEM_DEVICE && uploaded && b->n_groups > 0 && N > 0;
-    if (b->valid && !dev_tables) {
-        if (b->mem == POLS_MEM_DEVICE) {
-            hvalid.resize((size_t)N);
-            POLS_HIP(hipMemcpyAsync(hvalid.data(), b->valid, (size_t)N, hipMemcpyDeviceToHost, ctx->stream));
-            POLS_HIP(hipStreamSynchronize(ctx->stream));
-            hv = hvalid.data();
-        } else {
-            hv = b->valid;
-        }
-    }
-    // one lane (or wave / workgroup) per chunk: short chunks = more parallelism in the walk, longer chunk list for the scan
-    // (measured on the 1M-row sequence: 64-row chunks = 15 625 lanes beat 32- and 16-row chunks -- the per-lane row loads are
-    // uncoalesced and more concurrent lanes cost more in the memory system than they win in parallelism)
-    const int64_t chunk_len = std::min<int64_t>(std::max(max_chunk, min_chunk), std::max<int64_t>(min_chunk, N / 16384));
-    auto &cc = ctx->chunk_cache;
-    const bool cacheable = !hv && !dev_tables && uploaded;
-    if (cacheable && cc.valid && cc.offs_id == ctx->offs_id && cc.n_groups == b->n_groups &&
-        cc.n_rows == N && cc.mp == mp && cc.chunk_len == (int32_t)chunk_len) {      // same frame as the last call
-        void *tot = nullptr;
-        if ((rc = ensure_scratch(ctx, Work::Gram, sizeof(double) * (size_t)slots * std::max<size_t>(1, (size_t)cc.n_chunks), &tot))) return rc;
-        const char *tp = static_cast<const char *>(cc.buf.ptr);
-        a->groups = reinterpret_cast<const K4Group *>(tp);
-        a->chunks = reinterpret_cast<const K4Chunk *>(tp + cc.b_groups);
-        a->order = reinterpret_cast<const int32_t *>(tp + cc.b_groups + round256(sizeof(K4Chunk) * (size_t)cc.n_chunks));
-        a->cnt = nullptr; a->vidx = nullptr;
-        a->n_chunks = cc.n_chunks; a->n_groups = (int32_t)b->n_groups;
-        a->totals = static_cast<double *>(tot);
-        a->chunk_len = (int32_t)chunk_len;
-        return POLS_OK;
-    }
-    std::vector<K4Group> groups((size_t)b->n_groups);
-    std::vector<K4Chunk> chunks;
-    std::vector<int32_t> cnt, vidx;
-    if (hv) { cnt.resize((size_t)N); vidx.assign((size_t)N, -1); }
-    for (int64_t g = 0; g < b->n_groups; ++g) {
-        const int64_t s = b->group_offsets[g], e = b->group_offsets[g + 1], n = e - s;
-        if (n > 0x7fffffffLL) return fail(POLS_ERR_UNSUPPORTED, "group longer than 2^31 rows");
-        K4Group G;
-        G.start = s; G.end = e; G.first_chunk = (int32_t)chunks.size();
-        int64_t mpv = mp, n_valid = 0;                                                           // ls.rs:881-891
-        bool reached = false;
-        if (hv) {
-            int32_t c = 0;
-            for (int64_t i = 0; i < n; ++i) {
-                if (hv[s + i]) { vidx[(size_t)(s + c)] = (int32_t)i; ++c; }
-                cnt[(size_t)(s + i)] = c;
-                if (!reached) {
-                    n_valid = c;
-                    if (c == mp) { mpv = i + 1; reached = true; }
-                }
-            }
-        } else {
-            n_valid = std::min(n, mp);
-            if (n >= mp) { mpv = mp; reached = true; }
-        }
-        G.mpv = mpv;
-        G.gate_n = n_valid;
-        G.all_nan = (n < std::max(n_valid, mp)) ? 1 : 0;                                         // ls.rs:893-900
-        groups[(size_t)g] = G;
-        for (int64_t t = s, ci = 0; t < e; t += chunk_len, ++ci)
-            chunks.push_back(K4Chunk{t, std::min(e, t + chunk_len), (int32_t)g, (int32_t)ci});
-    }
-    const size_t b_groups = round256(sizeof(K4Group) * groups.size());
-    const size_t b_chunks = round256(sizeof(K4Chunk) * chunks.size());
-    const size_t b_cnt = (hv || dev_tables) ? round256(sizeof(int32_t) * (size_t)N) : 0;
-    const int64_t n_slabs = (N + 255) / 256;
-    const size_t b_sc = dev_tables ? round256(sizeof(uint32_t) * (size_t)n_slabs) : 0, b_sb = dev_tables ? round256(sizeof(int64_t) * (size_t)(n_slabs + 1)) : 0,
-                 b_co = dev_tables ? round256(sizeof(int64_t) * (size_t)(b->n_groups + 1)) : 0;
-    // work order of the wave-per-chunk kernels (K4Args::order): chunk ids sorted by length, longest first (stable: equal chunks keep their order) --
-    // sequences of 5 .. 4 000 rows cut at ~500 gave waves whose four chunks were 30 and 480 rows long: RLS at 12 features 2.9 ms on a log-normal
-    // frame against 0.9 ms on equal sequences (scripts/bench_dyn_spread.py)
-    std::vector<int32_t> order(chunks.size());
-    for (size_t i = 0; i < order.size(); ++i) order[i] = (int32_t)i;
-    if (chunks.size() < 0x7fffffffULL)
-        std::stable_sort(order.begin(), order.end(), [&](int32_t x, int32_t y) { return chunks[(size_t)x].t1 - chunks[(size_t)x].t0 > chunks[(size_t)y].t1 - chunks[(size_t)y].t0; });
-    const size_t b_order = round256(sizeof(int32_t) * order.size());
-    void *tab = nullptr, *tot = nullptr;
-    cc.valid = false;                                  // the table is about to be rewritten
-    if ((rc = grow(cc, b_groups + b_chunks + b_order + 2 * b_cnt + b_sc + b_sb + b_co + 256, &tab))) return rc;
-    if ((rc = ensure_scratch(ctx, Work::Gram, sizeof(double) * (size_t)slots * std::max<size_t>(1, chunks.size()), &tot))) return rc;
-    char *tp = static_cast<char *>(tab);
-    if ((rc = upload_small(ctx, tp, groups.data(), sizeof(K4Group) * groups.size()))) return rc;   // locals: through the pinned ring
-    if ((rc = upload_small(ctx, tp + b_groups, chunks.data(), sizeof(K4Chunk) * chunks.size()))) return rc;
-    if ((rc = upload_small(ctx, tp + b_groups + b_chunks, order.data(), sizeof(int32_t) * order.size()))) return rc;
-    if (hv) {
-        if ((rc = upload_small(ctx, tp + b_groups + b_chunks + b_order, cnt.data(), sizeof(int32_t) * (size_t)N))) return rc;
-        if ((rc = upload_small(ctx, tp + b_groups + b_chunks + b_order + b_cnt, vidx.data(), sizeof(int32_t) * (size_t)N))) return rc;
-    }
-    a->groups = reinterpret_cast<const K4Group *>(tp);
-    a->chunks = reinterpret_cast<const K4Chunk *>(tp + b_groups);
-    a->order = reinterpret_cast<const int32_t *>(tp + b_groups + b_chunks);
-    a->cnt = (hv || dev_tables) ? reinterpret_cast<const int32_t *>(tp + b_groups + b_chunks + b_order) : nullptr;
-    a->vidx = (hv || dev_tables) ? reinterpret_cast<const int32_t *>(tp + b_groups + b_chunks + b_order + b_cnt) : nullptr;
-    if (dev_tables) {
-        // (the groups were uploaded with the null-free constants -- mpv = min_periods, gate_n = min(rows, min_periods); the device pass
-        // patches both from the validity bytes.  all_nan only depends on the group's length: n_valid never exceeds min_periods)
-        char *xb = tp + b_groups + b_chunks + b_order + 2 * b_cnt;
-        RowCompactArgs ra;
-        std::memset(&ra, 0, sizeof(ra));
-        ra.valid = b->valid; ra.offs = static_cast<const int64_t *>(ctx->offsets.buf.ptr);
-        ra.n_rows = N; ra.n_groups = b->n_groups; ra.n_slabs = n_slabs;
-        ra.slab_cnt = reinterpret_cast<uint32_t *>(xb);
-        ra.slab_base = reinterpret_cast<int64_t *>(xb + b_sc);
-        ra.c_offs = reinterpret_cast<int64_t *>(xb + b_sc + b_sb);
-        ra.slab_gfirst = nullptr;
-        if ((rc = row_compact_offsets_launch(ctx, ra))) return rc;
-        ValidTablesArgs va;
-        std::memset(&va, 0, sizeof(va));
-        va.valid = b->valid; va.offs = ra.offs; va.n_rows = N; va.n_groups = b->n_groups; va.n_slabs = n_slabs;
-        va.slab_base = ra.slab_base; va.c_offs = ra.c_offs;
-        va.cnt = reinterpret_cast<int32_t *>(tp + b_groups + b_chunks + b_order);
-        va.vidx = reinterpret_cast<int32_t *>(tp + b_groups + b_chunks + b_order + b_cnt);
-        va.groups = tp; va.min_periods = mp;
-        if ((rc = valid_tables_launch(ctx, va))) return rc;
-    }
-    a->n_chunks = (int64_t)chunks.size();
-    a->n_groups = (int32_t)b->n_groups;
-    a->totals = static_cast<double *>(tot);
-    a->chunk_len = (int32_t)chunk_len;
-    if (cacheable) {
-        cc.offs_id = ctx->offs_id; cc.n_groups = b->n_groups; cc.n_rows = N; cc.mp = mp; cc.n_chunks = a->n_chunks;
-        cc.chunk_len = (int32_t)chunk_len; cc.valid = true; cc.b_groups = b_groups;
-    }
-    return POLS_OK;
-}
-
-int pols_rolling_least_squares(pols_ctx *ctx, const pols_batch *b, const pols_rolling_params *p, pols_out *o) {
-    if (!p) return fail(POLS_ERR_INVALID, "params is NULL");
-    const int64_t *d_offs = nullptr;
-    int64_t max_rows = 0;
-    Staged st;
-    DynState ds;
-    // ("drop_window" without weights / intercept on up to 10 features: the masked tile kernel reads the caller's columns as they are)
-    // ("drop": the compaction in front of the tile kernel copies the VALID rows, which hold no null under that policy, out of the caller's columns)
-    const bool may_defer = (p->null_policy == POLS_NULL_DROP_WINDOW || p->null_policy == POLS_NULL_DROP) && b->n_features <= K4C_KMAX &&
-                           ctx->opt.rolling_engine != 1 && ctx->opt.rolling_engine != 3;
-    int rc = dynamic_prologue(ctx, b, p->null_policy, o, &d_offs, &max_rows, &st, &ds, may_defer);
-    if (rc) return rc;
-    if (b->n_groups == 0 || b->n_rows == 0) return POLS_OK;
-    if (o->resid) return fail(POLS_ERR_INVALID, "rolling: residuals are target - predictions in the caller (least_squares.py:239)");
-    const int k = ds.k;                                   // features the kernels see (the intercept column included)
-    const bool wide = k > K4_KMAX, xwide = k > POLS_MAX_FEATURES;                               // k4w_wide.hip / k4x_inverse.hip
-    if (p->window_size < 1) return fail(POLS_ERR_INVALID, "window_size must be >= 1");
-    const int64_t w = p->window_size;
-    const int64_t mp = p->min_periods >= 0 ? p->min_periods : std::min<int64_t>(k, w);          // ls.rs:860
-    if (mp < 1) return fail(POLS_ERR_INVALID, "min_periods must be >= 1 (the reference indexes row min_periods - 1, ls.rs:941-943)");
-    const bool drop = p->null_policy == POLS_NULL_DROP || p->null_policy == POLS_NULL_DROP_ZERO ||
-                      p->null_policy == POLS_NULL_DROP_Y_ZERO_X;                                // ls.rs:947-950
-
-    // Null-free frames, up to 6 features, min_periods <= window <= 508: the row-parallel tile kernel (K4c, k4c_rolling.hip) -- with
-    // every row valid the "drop" deque and the fixed window are the same sums.  POLS_ROLLING_ENGINE=chunk goes back to the
-    // lane-per-chunk kernel.
-    bool tiles = k <= K4C_KMAX && st.valid == nullptr && mp <= w && ctx->opt.rolling_engine != 1 && aligned16(st.y) &&
-                 (!st.coef || aligned16(st.coef)) && (!st.pred || aligned16(st.pred));
-    for (int j = 0; j < k && tiles; ++j) tiles = aligned16(st.x[j]);
-    // whole sequences per tile when none is longer than one: no window reaches outside its tile, no halo, any window
-    // (POLS_ROLLING_ENGINE=halo: off); otherwise the halo waves cover windows up to 508 rows (252 at 7 / 8 features)
-    const int64_t *packed_map = nullptr;
-    int64_t n_packed = 0;
-    if (tiles && ctx->opt.rolling_engine != 2 && (rc = ensure_packed_tiles(ctx, b, K4C_PACKED_ROWS, max_rows, &packed_map, &n_packed))) return rc;
-    if (tiles && !packed_map && w > k4c_max_window(k)) tiles = false;
-    // The drop family on a frame WITH nulls (the reference's default policy for rolling_ols, ls.rs:947-986): its deque of valid rows is
-    // the null-free window over the VALID rows, and a row left out repeats the last coefficients -- so the valid rows are compacted
-    // (dyn_prep.hip: slab counts, scan, scatter), the tile kernel runs on them, and an expansion pass forward-fills the coefficients
-    // onto the original rows and predicts them.  Not taken when a non-empty group holds fewer valid rows than min_periods (the
-    // reference then solves a window it never filled, :881-900 -- the lane-per-chunk kernels below reproduce that).
-    // (11..32 features, and 9 / 10 where the tile kernel's window / alignment conditions fail: the same compaction in front of the
-    // wave-per-chunk kernel K4p, k4p_wide.hip)
-    const bool c_tiles_ok = k <= K4C_KMAX && (w <= k4c_max_window(k) || max_rows <= K4C_PACKED_ROWS - 3);
-    const bool c_wave_ok = k > K4_KMAX && k <= POLS_MAX_FEATURES;
-    bool tiles_c = !tiles && drop && st.valid != nullptr && mp <= w && (c_tiles_ok || c_wave_ok) &&
-                   ctx->opt.rolling_engine != 1 && ctx->opt.rolling_engine != 3 && b->n_rows >= 8;
-    if (tiles_c) {
-        const int64_t N = b->n_rows, G = b->n_groups, n_slabs = (N + 255) / 256;
-        const size_t sz = dtype_size(b->dtype), colb = round256(sz * (size_t)N);
-        const size_t b_cnt = round256(sizeof(uint32_t) * (size_t)n_slabs), b_base = round256(sizeof(int64_t) * (size_t)(n_slabs + 1)),
-                     b_offs = round256(sizeof(int64_t) * (size_t)(G + 1)), b_gf = round256(sizeof(int64_t) * (size_t)n_slabs),
-                     b_tab = round256(sizeof(void *) * (size_t)(k + 1));
-        // Up to 10 features the tile kernel GATHERS the valid rows through a source map and writes the frame's rows itself (k4c_kernel.inl GATHER,
-        // dyn_out_gather.inl): no compacted copy of the columns, no expansion pass.  POLS_ROLLING_ENGINE=scatter keeps the three-pass form (and
-        // K4p, 11..32 features, still runs on compacted columns).
-        const bool gather = c_tiles_ok && N < ((int64_t)1 << 31) && ctx->opt.rolling_engine != 5;
-        void *d = nullptr;
-        if ((rc = ensure_scratch(ctx, Work::RowCompact, b_cnt + b_base + b_offs + b_gf + 2 * b_tab + (gather ? 0 : colb * (size_t)(k + 1)), &d))) return rc;
-        char *base = static_cast<char *>(d);
-        char *cols = base + b_cnt + b_base + b_offs + b_gf + 2 * b_tab;
-        std::vector<const void *> inp((size_t)k + 1);
-        std::vector<void *> outp((size_t)k + 1);
-        inp[0] = st.y;
-        for (int j = 0; j < k; ++j) inp[(size_t)j + 1] = st.x[(size_t)j];
-        for (int j = 0; j <= k; ++j) outp[(size_t)j] = gather ? nullptr : cols + colb * (size_t)j;
-        if ((rc = upload_small(ctx, base + b_cnt + b_base + b_offs + b_gf, inp.data(), sizeof(void *) * (size_t)(k + 1)))) return rc;
-        if ((rc = upload_small(ctx, base + b_cnt + b_base + b_offs + b_gf + b_tab, outp.data(), sizeof(void *) * (size_t)(k + 1)))) return rc;
-        RowCompactArgs ra;
-        std::memset(&ra, 0, sizeof(ra));
-        ra.valid = st.valid;
-        if ((rc = ensure_start_flags(ctx, d_offs, G, N, &ra.start))) return rc;
-        ra.offs = d_offs; ra.n_rows = N; ra.n_groups = G; ra.n_slabs = n_slabs;
-        ra.slab_cnt = reinterpret_cast<uint32_t *>(base);
-        ra.slab_base = reinterpret_cast<int64_t *>(base + b_cnt);
-        ra.c_offs = reinterpret_cast<int64_t *>(base + b_cnt + b_base);
-        ra.slab_gfirst = reinterpret_cast<int64_t *>(base + b_cnt + b_base + b_offs);
-        ra.in = reinterpret_cast<const void *const *>(base + b_cnt + b_base + b_offs + b_gf);
-        ra.out = reinterpret_cast<void *const *>(base + b_cnt + b_base + b_offs + b_gf + b_tab);
-        ra.n_cols = k + 1; ra.k = k;
-        if ((rc = row_compact_offsets_launch(ctx, ra))) return rc;
-        std::vector<int64_t> c_offs((size_t)G + 1);
-        POLS_HIP(hipMemcpyAsync(c_offs.data(), ra.c_offs, sizeof(int64_t) * (size_t)(G + 1), hipMemcpyDeviceToHost, ctx->stream));
-        POLS_HIP(hipStreamSynchronize(ctx->stream));       // the host cuts the compacted frame into tiles and checks the warm-up quirk
-        const int64_t Nc = c_offs[(size_t)G];
-        int64_t max_c = 0;
-        for (int64_t g = 0; g < G && tiles_c; ++g) {
-            const int64_t nc = c_offs[(size_t)g + 1] - c_offs[(size_t)g];
-            if (b->group_offsets[g + 1] > b->group_offsets[g] && nc < mp) tiles_c = false;
-            max_c = std::max(max_c, nc);
-        }
-        if (Nc < 8) tiles_c = false;
-        if (tiles_c) {
-            void *dc = nullptr, *df = nullptr, *dm = nullptr;
-            if (gather) {
-                void *dsrc = nullptr;
-                if ((rc = ensure_scratch(ctx, Work::GatherMap, round256(sizeof(int32_t) * (size_t)(Nc + 4)), &dsrc))) return rc;
-                ra.src = static_cast<int32_t *>(dsrc);
-                if ((rc = row_compact_srcmap_launch(ctx, ra))) return rc;
-            } else {
-                if ((rc = row_compact_scatter_launch(ctx, b->dtype, ra))) return rc;
-                if ((rc = ensure_scratch(ctx, Work::CompactCoef, round256(sz * (size_t)Nc * (size_t)k), &dc))) return rc;
-            }
-            if (!c_tiles_ok) {
-                // the compacted frame through K4p: chunk tables of the COMPACTED offsets (build_chunk_tables does not cache them)
-                pols_batch cb = *b;
-                cb.group_offsets = c_offs.data(); cb.n_rows = Nc; cb.valid = nullptr;
-                const int64_t pchunk = max_c <= 1024 ? 1024 : std::min<int64_t>(1024, std::max<int64_t>(256, Nc / 16384));
-                K4Args a;
-                std::memset(&a, 0, sizeof(a));
-                if ((rc = build_chunk_tables(ctx, &cb, mp, k * k + k, &a, pchunk, pchunk))) return rc;
-                a.y = outp[0];
-                for (int j = 0; j < k; ++j) a.x[j] = outp[(size_t)j + 1];
-                a.coef = dc; a.pred = nullptr;
-                a.window = w; a.alpha = p->alpha > 0.0 ? p->alpha : 0.0; a.k = k; a.drop_mode = 1;
-                a.tot_cs = k * k + k; a.tot_qs = 1;
-                a.use_totals = (max_c > pchunk && w > 1024) ? 1 : 0;
-                a.groups_end_row = Nc;
-                if ((rc = k4p_launch(ctx, b->dtype, a, false, max_c <= pchunk))) return rc;
-                ra.coef_c = dc; ra.coef = st.coef; ra.pred = st.pred;
-                if ((rc = row_compact_expand_launch(ctx, b->dtype, ra))) return rc;
-                ctx->last_kernel += "_compacted";
-                if (ds.post && (rc = dyn_post_launch(ctx, b->dtype, ds.pa))) return rc;
-                return unstage_outputs(ctx, b, b->n_rows, k, o, st);
-            }
-            if ((rc = ensure_scratch(ctx, Work::CompactStarts, round256((size_t)Nc + 4), &df))) return rc;
-            if ((rc = k3c_start_flags(ctx, ra.c_offs, G, Nc, static_cast<uint8_t *>(df)))) return rc;
-            K4cArgs c;
-            std::memset(&c, 0, sizeof(c));
-            c.start = static_cast<const uint8_t *>(df);
-            if (gather) {
-                c.y = st.y;
-                for (int j = 0; j < k; ++j) c.x[j] = st.x[(size_t)j];
-                c.src = ra.src; c.n_frame = N; c.fvalid = st.valid; c.fstart = ra.start;
-                c.n_rows = Nc; c.coef = st.coef; c.pred = st.pred;
-            } else {
-                c.y = outp[0];
-                for (int j = 0; j < k; ++j) c.x[j] = outp[(size_t)j + 1];
-                c.n_rows = Nc; c.coef = dc; c.pred = nullptr;
-            }
-            c.window = w; c.min_periods = mp; c.alpha = p->alpha > 0.0 ? p->alpha : 0.0; c.k = k;
-            if (max_c <= K4C_PACKED_ROWS - 3 && (ctx->opt.rolling_engine != 2 || w > k4c_max_window(k))) {
-                std::vector<int64_t> first;
-                packed_tile_starts(c_offs.data(), G, Nc, K4C_PACKED_ROWS, &first);
-                const int64_t nt = (int64_t)first.size() - 1;
-                if (nt * K4C_PACKED_ROWS * 7 <= Nc * 10 || w > k4c_max_window(k)) {    // (a window beyond the halo forms: packed whatever the fill)
-                    c.window = std::min<int64_t>(w, 2 * K4C_PACKED_ROWS);
-                    c.min_periods = std::min<int64_t>(mp, c.window);     // (see the null-free route below)
-                    if ((rc = ensure_scratch(ctx, Work::CompactTiles, round256(sizeof(int64_t) * first.size()), &dm))) return rc;
-                    if ((rc = upload_small(ctx, dm, first.data(), sizeof(int64_t) * first.size()))) return rc;
-                    c.tile_row0 = static_cast<const int64_t *>(dm); c.n_packed = nt;
-                }
-            }
-            if ((rc = k4c_launch(ctx, b->dtype, c))) return rc;
-            if (gather) {
-                // (the kernel wrote NaN predictions on the rows left out: the post pass is only needed for the 1 / sqrt(w) un-scaling)
-                if (ds.post && ds.pa.sw_out && (rc = dyn_post_launch(ctx, b->dtype, ds.pa))) return rc;
-                return unstage_outputs(ctx, b, b->n_rows, k, o, st);
-            }
-            ra.coef_c = dc; ra.coef = st.coef; ra.pred = st.pred;
-            if ((rc = row_compact_expand_launch(ctx, b->dtype, ra))) return rc;
-            ctx->last_kernel += "_compacted";
-            if (ds.post && (rc = dyn_post_launch(ctx, b->dtype, ds.pa))) return rc;
-            return unstage_outputs(ctx, b, b->n_rows, k, o, st);
-        }
-    }
-    if (tiles) {
-        K4cArgs c;
-        std::memset(&c, 0, sizeof(c));
-        if ((rc = ensure_start_flags(ctx, d_offs, b->n_groups, b->n_rows, &c.start))) return rc;
-        c.y = st.y;
-        for (int j = 0; j < k; ++j) c.x[j] = st.x[j];
-        c.n_rows = b->n_rows; c.coef = st.coef; c.pred = st.pred;
-        c.window = packed_map ? std::min<int64_t>(w, 2 * K4C_PACKED_ROWS) : w;   // (a window longer than a tile never fills: any such is the same)
-        // min_periods follows the clamp: on packed tiles no sequence has more than 1 021 rows, so a min_periods beyond the clamped
-        // window (2 048 < min_periods <= window_size) is "never enough rows" either way -- all NaN, what the reference returns for a
-        // sequence shorter than min_periods (ls.rs:893-900) -- and the launch check (min_periods <= window) must not reject it
-        c.min_periods = std::min<int64_t>(mp, c.window); c.alpha = p->alpha > 0.0 ? p->alpha : 0.0; c.k = k;
-        c.tile_row0 = packed_map; c.n_packed = n_packed;
-        if ((rc = k4c_launch(ctx, b->dtype, c))) return rc;
-        if (ds.post && (rc = dyn_post_launch(ctx, b->dtype, ds.pa))) return rc;
-        return unstage_outputs(ctx, b, b->n_rows, k, o, st);
-    }
-    // The FIXED window over rows ("drop_window", the RollingKwargs default, ls.rs:987-1029) on a frame WITH nulls, up to 10 features: the
-    // tile kernel with every invalid row a zero row (k4c_kernel.inl, MASKED) -- all rows solved from S_i = E(i) - E(i - window) -- behind a
-    // per-row table of which rows the reference solves (dyn_prep.hip: NaN before the warm-up row, the last solved row's coefficients where the
-    // n_valid_window gate is closed), applied by a fill pass.  One case stays with the chunk kernels: a sequence in which a valid row is
-    // older than the window when its warm-up ends is never subtracted by the reference (:989) -- the device flags it, the host reads the flag.
-    bool tiles_m = !drop && st.valid != nullptr && ds.tables.valid != nullptr && ds.tables.mem == POLS_MEM_DEVICE && k <= K4C_KMAX && mp <= w &&
-                   ctx->opt.rolling_engine != 1 && ctx->opt.rolling_engine != 3 && b->n_rows >= 8 && aligned16(st.y) && (!st.coef || aligned16(st.coef)) &&
-                   (!st.pred || aligned16(st.pred)) && (reinterpret_cast<uintptr_t>(st.valid) & 3) == 0;
-    for (int j = 0; j < k && tiles_m; ++j) tiles_m = aligned16(st.x[j]);
-    if (tiles_m) {
-        const int64_t *pmap = nullptr;
-        int64_t n_pk = 0;
-        if (ctx->opt.rolling_engine != 2 && (rc = ensure_packed_tiles(ctx, b, K4C_PACKED_ROWS, max_rows, &pmap, &n_pk))) return rc;
-        if (!pmap && w > k4c_max_window(k)) tiles_m = false;
-        if (tiles_m) {
-            const int64_t N = b->n_rows, G = b->n_groups, n_slabs = (N + 255) / 256;
-            const size_t b_r2 = round256(sizeof(uint16_t) * (size_t)N), b_sol = round256((size_t)N + 4), b_sc = round256(sizeof(uint32_t) * (size_t)n_slabs),
-                         b_s8 = round256(sizeof(int64_t) * (size_t)(n_slabs + 1)), b_g8 = round256(sizeof(int64_t) * (size_t)(G + 1)),
-                         b_g4 = round256(sizeof(int32_t) * (size_t)G);
-            void *d = nullptr;
-            const int64_t n_blk = (n_slabs + 1023) / 1024;
-            const size_t b_blk = round256(sizeof(unsigned long long) * 2 * (size_t)n_blk);
-            if ((rc = ensure_scratch(ctx, Work::RowCompact, 256 + b_blk + 2 * b_r2 + b_sol + b_sc + 3 * b_s8 + 2 * b_g8 + b_g4, &d))) return rc;   // (Work::RowCompact: the compaction's, never live here)
-            char *q = static_cast<char *>(d);
-            RollMaskArgs ma;
-            std::memset(&ma, 0, sizeof(ma));
-            ma.flag = reinterpret_cast<int32_t *>(q); q += 256;
-            ma.blk_cnt = reinterpret_cast<unsigned long long *>(q); ma.blk_last = ma.blk_cnt + n_blk; q += b_blk;
-            ma.incl = reinterpret_cast<uint16_t *>(q); q += b_r2;
-            ma.code = reinterpret_cast<uint16_t *>(q); q += b_r2;
-            ma.solved = reinterpret_cast<uint8_t *>(q); q += b_sol;
-            ma.slab_cnt = reinterpret_cast<uint32_t *>(q); q += b_sc;
-            ma.slab_base = reinterpret_cast<int64_t *>(q); q += b_s8;
-            ma.slab_last = reinterpret_cast<int64_t *>(q); q += b_s8;
-            ma.slab_carry = reinterpret_cast<int64_t *>(q); q += b_s8;
-            ma.c_offs = reinterpret_cast<int64_t *>(q); q += b_g8;
-            ma.g_mpv = reinterpret_cast<int64_t *>(q); q += b_g8;
-            ma.g_gate = reinterpret_cast<int32_t *>(q); q += b_g4;
-            ma.valid = st.valid; ma.offs = d_offs; ma.n_rows = N; ma.n_groups = G; ma.n_slabs = n_slabs;
-            ma.window = w; ma.min_periods = mp;
-            if ((rc = roll_mask_tables_launch(ctx, ma))) return rc;
-            int32_t flag = 0;
-            POLS_HIP(hipMemcpyAsync(&flag, ma.flag, sizeof(flag), hipMemcpyDeviceToHost, ctx->stream));
-            POLS_HIP(hipStreamSynchronize(ctx->stream));       // the host decides which kernel runs
-            if (flag == 0) {
-                if ((rc = roll_mask_rows_launch(ctx, ma))) return rc;
-                K4cArgs c;
-                std::memset(&c, 0, sizeof(c));
-                if ((rc = ensure_start_flags(ctx, d_offs, b->n_groups, b->n_rows, &c.start))) return rc;
-                c.y = st.y; c.valid = st.valid; c.solved = ma.solved;
-                for (int j = 0; j < k; ++j) { c.x[j] = st.x[j]; ma.x[j] = st.x[j]; }
-                c.n_rows = N; c.coef = st.coef; c.pred = st.pred;
-                c.window = pmap ? std::min<int64_t>(w, 2 * K4C_PACKED_ROWS) : w;
-                c.min_periods = std::min<int64_t>(mp, c.window); c.alpha = p->alpha > 0.0 ? p->alpha : 0.0; c.k = k;
-                c.tile_row0 = pmap; c.n_packed = n_pk;
-                if ((rc = k4c_launch(ctx, b->dtype, c))) return rc;
-                ma.coef = st.coef; ma.pred = st.pred; ma.k = k;
-                if ((rc = roll_mask_fill_launch(ctx, b->dtype, ma))) return rc;
-                // (the kernel and the fill pass null the predictions of masked rows themselves: the post pass only un-scales by 1 / sqrt(w))
-                if (ds.post && ds.pa.sw_out && (rc = dyn_post_launch(ctx, b->dtype, ds.pa))) return rc;
-                return unstage_outputs(ctx, b, b->n_rows, k, o, st);
-            }
-        }
-    }
-    if ((rc = dynamic_rewrite_deferred(ctx, b, &st, &ds))) return rc;   // the masked tile kernel did not take the frame: the chunk kernels want zero-filled columns
-    K4Args a;
-    std::memset(&a, 0, sizeof(a));
-    // 9..32 features on a null-free frame, min_periods <= window: one wave per chunk, the inverse distributed over its registers and the
-    // sums kept beside it (K4p, k4p_wide.hip).  A sequence of up to 1 024 rows is one chunk; a chunk of a longer one re-sums the rows of the
-    // window in front of it, so cut sequences need a window of at most 1 024 rows.  POLS_ROLLING_ENGINE=chunk keeps k4w_wide.hip.
-    const int64_t pchunk = (max_rows <= 1024 || b->n_groups >= 4096) ? 1024 : std::min<int64_t>(1024, std::max<int64_t>(256, b->n_rows / 16384));
-    // ... and the FIXED window over rows ("drop_window") on frames with validity bytes on the device: the same kernel with the rows masked
-    // and the solves gated (the validity prefix is built on the device, dyn_prep.hip)
-    const bool wave_p = wide && !xwide && mp <= w && ctx->opt.rolling_engine != 1 &&
-                        (st.valid == nullptr || (!drop && ds.tables.valid != nullptr && ds.tables.mem == POLS_MEM_DEVICE));
-    const int64_t minc = wave_p ? pchunk : (k > 128 ? hbm_state_chunk(b->n_rows) : 64);
-    if ((rc = build_chunk_tables(ctx, &ds.tables, mp, wide ? k * k + k : k * (k + 1) / 2 + k, &a, minc, wave_p ? pchunk : std::max<int64_t>(512, minc)))) return rc;
-    a.y = st.y; a.valid = st.valid;
-    if ((rc = upload_column_table(ctx, st, k, &a))) return rc;
-    a.coef = st.coef; a.pred = st.pred;
-    a.window = w; a.alpha = p->alpha > 0.0 ? p->alpha : 0.0;                                    // ls.rs:865, 924-926
-    a.k = k; a.drop_mode = drop ? 1 : 0;
-    if (wide) { a.tot_cs = k * k + k; a.tot_qs = 1; }
-    else { a.tot_cs = 1; a.tot_qs = a.n_chunks; }
-    if (wave_p) {
-        a.use_totals = (max_rows > pchunk && w > 1024) ? 1 : 0;    // cut sequences, a window too long to re-sum at every chunk start
-        a.groups_end_row = b->n_rows;
-        rc = k4p_launch(ctx, b->dtype, a, false, max_rows <= pchunk);
-    }
-    else rc = k > K4X_KMAX ? k4y_launch(ctx, b->dtype, a) : xwide ? k4x_launch(ctx, b->dtype, a) : (wide ? k4w_launch(ctx, b->dtype, a) : k4_launch(ctx, b->dtype, a));
-    if (rc) return rc;
-    if (ds.post && (rc = dyn_post_launch(ctx, b->dtype, ds.pa))) return rc;
-    return unstage_outputs(ctx, b, b->n_rows, k, o, st);
 }
 
 int pols_predict(pols_ctx *ctx, const pols_batch *b, const void *coef, int64_t coef_rows, void *pred_out) {

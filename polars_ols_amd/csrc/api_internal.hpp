@@ -1,8 +1,12 @@
 // api_internal.hpp -- what the entry translation units share beyond common.hpp.  Who defines what:
 //   api.hip         contexts, options, offsets upload (+ scan_offsets), staging, segments, k1_launch, mark_fallback_kernel; the statistics,
-//                   prediction, dynamic (rolling / recursive), layout and Arrow entries
+//                   prediction, sharded, layout and Arrow entries
 //   api_static.hip  the static least-squares path: resolve_solve_plan, ensure_fallback_epoch, k1_valu_takes, pick_static_route, ls_core,
 //                   wide_static, pols_least_squares, pols_multi_target_least_squares, pols_debug_static_route
+//   api_dynamic.hip the dynamic entries: the prologue (DynState), the cached per-frame tables, pick_rls_route / pick_rolling_route and one
+//                   function per route, pols_recursive_least_squares, pols_rolling_least_squares and their parameter defaults.  Nothing of it
+//                   is declared here: no other translation unit calls into it (it uses check_ctx / check_batch / Staged / stage_inputs /
+//                   unstage_outputs / aligned16 from below and fail / grow / ensure_scratch / upload_small / upload_offsets from common.hpp)
 //   api_fits.hip    the K10-K14 and K16 fit entries
 #pragma once
 

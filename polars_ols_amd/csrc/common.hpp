@@ -106,6 +106,23 @@ struct TimedLaunch {
     hipEvent_t start, stop;
 };
 
+// POLS_ROLLING_ENGINE / POLS_RLS_ENGINE: which family of dynamic kernels the entries of api_dynamic.hip may take (DESIGN.md "Dynamic routes").
+enum class RollingEngine {
+    Auto,        // K4c tiles where they apply
+    Chunk,       // "chunk": the lane-per-chunk K4 (and K4w instead of K4p)
+    Halo,        // "halo": no packed tiles
+    NoCompact,   // "nocompact": the drop family with nulls stays with the chunk kernels
+    HaloWave,    // "halowave": K4c keeps its halo wave (A/B of the own-halo form)
+    Scatter,     // "scatter": the drop family with nulls through compacted columns + an expansion pass instead of the source map
+};
+enum class RlsEngine {
+    Auto,
+    Seq,         // "seq": K3, the wave-per-sequence recursion
+    Scan,        // "scan": K3c's exact scan (no packed tiles, no halo) up to 10 features, else the chunk kernels
+    Chunk,       // "chunk": the lane-per-chunk K3s (K3sw instead of K3p)
+    Halo,        // "halo": K3c's halo form where the look-back form would run
+};
+
 // Tuning / diagnostic knobs.  Parsed ONCE from the POLS_* environment variables in pols_create() (a launch path never calls
 // getenv) and changeable afterwards through pols_set_option(); every field's default is the shipped behaviour.
 struct Options {
@@ -125,10 +142,10 @@ struct Options {
     int k1t_rc4 = -1;             // POLS_K1T_RC4        -1: default rule
     int k1t_sub8 = -1;            // POLS_K1T_SUB8       eight-lane K1t teams: -1 default rule (frames that fit 16 chunk slots), 0 never, 1 only frames that fit 8
     int static_engine = 0;        // POLS_STATIC_ENGINE  0 auto, 1 "stream" (three launches), 2 "k2" (wherever it fits), 3 "nok2"
-    int rls_engine = 0;           // POLS_RLS_ENGINE     0 auto, 1 "seq" (K3), 2 "scan" (K3c up to 8 features, else the chunk kernels), 3 "chunk" (lane-per-chunk K3s), 4 "halo" (K3c: the halo form where the look-back form would run)
+    RlsEngine rls_engine = RlsEngine::Auto;             // POLS_RLS_ENGINE
     int rls_early = 0;            // POLS_RLS_EARLY      K3c look-back form: 0 = the tile's record falls out of its scan (default), 1 = computed and published before it (step E; A/B: 34.6 vs 31.2 us on cfg4)
     int rls_spin_limit = -1;      // POLS_RLS_SPINS      K3c look-back form: polls before a wave falls back to the halo (-1: default 64; 0: always fall back -- the test of that path)
-    int rolling_engine = 0;       // POLS_ROLLING_ENGINE 0 auto (K4c tiles where they apply), 1 "chunk" (lane-per-chunk K4), 2 "halo" (no packed tiles), 3 "nocompact" (the drop family with nulls stays with the chunk kernels), 4 "halowave" (K4c keeps its halo wave: A/B of the own-halo form), 5 "scatter" (the drop family with nulls: compacted columns + expansion pass instead of the source map)
+    RollingEngine rolling_engine = RollingEngine::Auto; // POLS_ROLLING_ENGINE
     int k1_engine = 0;            // POLS_K1_ENGINE      0 auto, 1 "valu", 2 "mfma"
     int k9_take = 0;              // POLS_K9_TAKE        0 auto, 1 "gather", 2 "scatter"
     int k1_nt_loads = -1;         // POLS_K1_NT_LOADS    -1: default rule, 0 / 1

@@ -630,7 +630,7 @@ static int k4c_launch_k(pols_ctx *ctx, const K4cArgs &a) {
     // no halo wave: the tile's first wave reaches in front of the tile itself (windows up to 256 rows; at 10 features the table and the parked sums
     // are more than a CU's LDS).  POLS_ROLLING_ENGINE=halowave keeps the halo wave (A/B).
     if constexpr (K <= 9) {
-        if (a.window <= 256 && ctx->opt.rolling_engine != 4) return k4c_launch_h<T, K, 0, MASKED, true, GATHER>(ctx, a);
+        if (a.window <= 256 && ctx->opt.rolling_engine != RollingEngine::HaloWave) return k4c_launch_h<T, K, 0, MASKED, true, GATHER>(ctx, a);
     }
     if (a.window <= 252) return k4c_launch_h<T, K, 1, MASKED, false, GATHER>(ctx, a);            // 256 HW >= 4 ceil(window / 4) + 1
     if constexpr (K <= 6) return k4c_launch_h<T, K, 2, MASKED, false, GATHER>(ctx, a);

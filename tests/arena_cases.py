@@ -290,7 +290,7 @@ def halo_batches(half_life) -> int:
 
 
 def rls_kernel(k: int, half_life, offs, dtype, engine: Optional[str] = None, nulls: bool = False, aligned: bool = True) -> str:
-    """the kernel the RLS dispatcher takes (csrc/api.hip, pols_recursive_least_squares)"""
+    """the kernel the RLS dispatcher takes (csrc/api_dynamic.hip, pick_rls_route)"""
     dt = dt_name(dtype)
     max_rows, n = int(np.diff(offs).max()), int(offs[-1])
     if k > 128:
@@ -312,7 +312,7 @@ def rls_kernel(k: int, half_life, offs, dtype, engine: Optional[str] = None, nul
 
 
 def rolling_kernel(k: int, window: int, policy: str, offs, dtype, valid=None, engine: Optional[str] = None, aligned: bool = True) -> str:
-    """the kernel (family) the rolling dispatcher takes (csrc/api.hip, pols_rolling_least_squares); K4p's names carry a lane suffix,
+    """the kernel (family) the rolling dispatcher takes (csrc/api_dynamic.hip, pick_rolling_route); K4p's names carry a lane suffix,
     so its entry is a prefix"""
     from test_k4_gpu import _keeps_a_never_dropped_row
 

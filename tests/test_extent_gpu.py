@@ -673,7 +673,7 @@ def test_multi_target_off_the_grid_is_rejected(eng, dtype):
 #   coef    static entries and the fit entries store coefficients value by value (the only 16-byte stores are to per-row columns:
 #           pred / resid, the influence fields, glm's linpred, rlm's weights -- all checked on the host); the dynamic entries' tile
 #           kernels (K3c, K4c, K4cm) store n_rows x k tables 16 bytes at a time and are NOT taken for a table off the grid
-#           (api.hip rowpar_ok / tiles / tiles_m): the chunk kernels K3 / K3s / K4 / K4p and the gathered K4cg store value by value;
+#           (api_dynamic.hip rowpar_aligned): the chunk kernels K3 / K3s / K4 / K4p and the gathered K4cg store value by value;
 #   status  one int32 store per group everywhere;
 #   valid   read four bytes at a time by K3c, K4cm and the compaction's group pass only, each behind a 4-byte alignment test.
 
@@ -764,7 +764,7 @@ def test_rlm_weights_output_off_the_grid_is_rejected(eng):
 @pytest.mark.parametrize("what", ["coef", "valid"])
 @pytest.mark.parametrize("k,kind", [(3, "c"), (6, "b"), (10, "c"), (12, "c")])
 def test_rls_coef_or_valid_one_element_off_the_grid(eng, what, k, kind):
-    """the row-parallel kernel is not taken (api.hip rowpar_ok): K3 up to 4 096 rows a sequence, K3s beyond, K3p from 9 features on"""
+    """the row-parallel kernel is not taken (api_dynamic.hip pick_rls_route): K3 up to 4 096 rows a sequence, K3s beyond, K3p from 9 features on"""
     from oracle import orc
 
     dtype, half_life = np.float64, 21
@@ -799,7 +799,7 @@ def test_rls_coef_or_valid_one_element_off_the_grid(eng, what, k, kind):
 @pytest.mark.parametrize("what,policy", [("coef", "drop"), ("coef+nan", "drop"), ("coef+nan", "drop_window"), ("valid", "drop"), ("valid", "drop_window")])
 @pytest.mark.parametrize("k", [6, 9, 12])
 def test_rolling_coef_or_valid_one_element_off_the_grid(eng, what, policy, k):
-    """no tile kernel with 16-byte stores (api.hip tiles / tiles_m): the chunk walk K4 up to 8 features, K4p beyond, and under "drop"
+    """no tile kernel with 16-byte stores (api_dynamic.hip pick_rolling_route): the chunk walk K4 up to 8 features, K4p beyond, and under "drop"
     with nulls the gathered tile kernel, whose copy-out stores value by value (dyn_out_gather.inl)"""
     from oracle import orc
 
