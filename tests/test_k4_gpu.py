@@ -3,6 +3,8 @@ src/least_squares.rs:848-1032), the brute-force per-window golden fixtures and t
 import numpy as np
 import pytest
 
+from dyn_ladder import window_matrix as _window_matrix      # the rows a window holds under a policy (shared with the dynamic ladders)
+
 pytestmark = pytest.mark.gpu
 
 
@@ -48,19 +50,6 @@ def _window_obs(offs, valid, window, policy):
             lag = np.concatenate([np.zeros(min(window, e - s), dtype=np.int64), c[: max(0, e - s - window)]])
             out[s:e] = c - lag
     return out
-
-
-def _window_matrix(offs, valid, X, i, window, policy):
-    """the feature rows whose outer products make up row i's window state (the rows the reference's deque / fixed window holds)"""
-    g = int(np.searchsorted(offs, i, side="right") - 1)
-    s = int(offs[g])
-    v = np.ones(i + 1 - s, dtype=bool) if valid is None else np.asarray(valid[s:i + 1]).astype(bool)
-    idx = s + np.flatnonzero(v)
-    if policy == "drop":
-        idx = idx[-window:]                            # the last `window` VALID rows
-    else:
-        idx = idx[idx > i - window]                    # the valid rows among the last `window` rows
-    return X[idx]
 
 
 def _keeps_a_never_dropped_row(offs, valid, window, min_periods):
