@@ -16,10 +16,6 @@
 #include "k4_rolling.hpp"
 #include "k5_enet.hpp"
 #include "k6_svd.hpp"
-#include "k7_stats.hpp"
-#include "k7r_robust.hpp"
-#include "k7c_cluster.hpp"
-#include "k7i_influence.hpp"
 #include "k8_wide.hpp"
 #include "k10_ridge_path.hpp"
 #include "k11_rlm.hpp"
@@ -500,6 +496,72 @@ int compact_nulls(pols_ctx *ctx, const pols_batch *b, int policy, Compacted *c, 
 
 using namespace pols;
 
+// Long groups cut into segments: SegTables and what ensure_segments builds are described in api_internal.hpp.
+int ensure_segments(pols_ctx *ctx, const pols_batch *b, int64_t max_rows, size_t extra_per_seg, SegTables *t,
+                    const std::vector<int32_t> *ids, int64_t class_key) {
+    *t = SegTables();
+    const int64_t seg_target = ctx->opt.seg_target > 0 ? std::max<int64_t>(256, ctx->opt.seg_target)
+                                                      : std::max<int64_t>(4096, ((b->n_rows / std::max<int64_t>(1, 8 * (int64_t)ctx->num_cus) + 1023) / 1024) * 1024);
+    if (!ids && (!(max_rows > 2 * seg_target) || ctx->opt.no_split)) return POLS_OK;
+    const int64_t n_items = ids ? (int64_t)ids->size() : b->n_groups;
+    auto &sc = ctx->seg_cache[ids ? 1 : 0];               // (class tables have their own: they do not evict the whole-frame tables)
+    int rc;
+    // (the key is the frame; the per-segment extra area only has to be large enough -- its users differ in what they keep there: the Gram
+    // partials of ls_core, the moments of the statistics entry, nothing for pols_predict -- and it is kept at the largest size asked for,
+    // so that alternating users of one frame stop rebuilding and re-uploading the tables)
+    const bool same_frame = sc.valid && sc.offs_id == ctx->offs_id && sc.n_groups == b->n_groups && sc.n_rows == b->n_rows &&
+                            sc.seg_target == seg_target && sc.class_key == class_key && sc.n_items == n_items;
+    const bool hit = same_frame && sc.nz2 >= extra_per_seg;
+    auto lay = [&](char *sb, int64_t n_seg) {
+        const size_t b_so = round256(sizeof(int64_t) * (size_t)(ids ? 2 * n_seg : n_seg + 1)), b_sm = round256(sizeof(int32_t) * (size_t)n_seg),
+                     b_sf = round256(sizeof(int32_t) * (size_t)(n_items + 1));
+        t->offs = reinterpret_cast<const int64_t *>(sb);
+        t->map = reinterpret_cast<const int32_t *>(sb + b_so);
+        t->first = reinterpret_cast<const int32_t *>(sb + b_so + b_sm);
+        t->extra = sb + b_so + b_sm + b_sf;
+        t->n_seg = n_seg;
+        return b_so + b_sm + b_sf;
+    };
+    if (hit) { lay(static_cast<char *>(sc.buf.ptr), sc.n_seg); t->max_len = sc.max_len; t->max_seg = sc.max_seg; return POLS_OK; }
+    if (same_frame) extra_per_seg = std::max<size_t>(extra_per_seg, sc.nz2);
+    sc.valid = false;
+    std::vector<int64_t> so;
+    std::vector<int32_t> sm, sf((size_t)n_items + 1);
+    if (!ids) so.push_back(0);
+    int64_t max_len = 0, max_seg = 0;
+    for (int64_t i = 0; i < n_items; ++i) {
+        const int64_t g = ids ? (int64_t)(*ids)[(size_t)i] : i;
+        if (i > 0) max_seg = std::max<int64_t>(max_seg, (int64_t)sm.size() - sf[(size_t)i - 1]);
+        sf[(size_t)i] = (int32_t)sm.size();
+        const int64_t s0 = b->group_offsets[g], e0 = b->group_offsets[g + 1];
+        const int64_t pieces = std::max<int64_t>(1, (e0 - s0 + seg_target - 1) / seg_target);
+        const int64_t len = std::max<int64_t>(1, ((e0 - s0 + pieces - 1) / pieces + 255) / 256 * 256);   // (256-row multiples: whole staging chunks)
+        max_len = std::max(max_len, std::min(len, e0 - s0));
+        for (int64_t r = s0; r < e0 || r == s0; r += len) {
+            if (ids) so.push_back(r);
+            so.push_back(std::min(e0, r + len));
+            sm.push_back((int32_t)i);
+            if (e0 == s0) break;
+        }
+    }
+    sf[(size_t)n_items] = (int32_t)sm.size();
+    if (n_items > 0) max_seg = std::max<int64_t>(max_seg, (int64_t)sm.size() - sf[(size_t)n_items - 1]);
+    const int64_t n_seg = (int64_t)sm.size();
+    const size_t tabs = round256(sizeof(int64_t) * so.size()) + round256(sizeof(int32_t) * sm.size()) + round256(sizeof(int32_t) * sf.size());
+    void *ds = nullptr;
+    if ((rc = grow(sc, tabs + round256(extra_per_seg * (size_t)n_seg), &ds))) return rc;
+    char *sb = static_cast<char *>(ds);
+    lay(sb, n_seg);
+    if ((rc = upload_small(ctx, const_cast<int64_t *>(t->offs), so.data(), sizeof(int64_t) * so.size()))) return rc;
+    if ((rc = upload_small(ctx, const_cast<int32_t *>(t->map), sm.data(), sizeof(int32_t) * sm.size()))) return rc;
+    if ((rc = upload_small(ctx, const_cast<int32_t *>(t->first), sf.data(), sizeof(int32_t) * sf.size()))) return rc;
+    sc.valid = true; sc.offs_id = ctx->offs_id; sc.n_groups = b->n_groups; sc.n_rows = b->n_rows; sc.seg_target = seg_target;
+    sc.class_key = class_key; sc.n_items = n_items;
+    sc.n_seg = n_seg; sc.nz2 = extra_per_seg; sc.nulls = false; sc.max_len = max_len; sc.max_seg = max_seg;
+    t->max_len = max_len; t->max_seg = max_seg;
+    return POLS_OK;
+}
+
 // ------------------------------------------------------------------ context
 extern "C" {
 
@@ -623,494 +685,6 @@ void pols_ols_params_default(pols_ols_params *p) {
     p->solve_method = POLS_SOLVE_AUTO;
     p->has_rcond = 0;
     p->null_policy = POLS_NULL_IGNORE;
-}
-
-// Long groups cut into segments: SegTables and what ensure_segments builds are described in api_internal.hpp.  (C++ linkage, as declared
-// there: this definition sits inside the extern "C" block.)
-extern "C++" int ensure_segments(pols_ctx *ctx, const pols_batch *b, int64_t max_rows, size_t extra_per_seg, SegTables *t,
-                                 const std::vector<int32_t> *ids, int64_t class_key) {
-    *t = SegTables();
-    const int64_t seg_target = ctx->opt.seg_target > 0 ? std::max<int64_t>(256, ctx->opt.seg_target)
-                                                      : std::max<int64_t>(4096, ((b->n_rows / std::max<int64_t>(1, 8 * (int64_t)ctx->num_cus) + 1023) / 1024) * 1024);
-    if (!ids && (!(max_rows > 2 * seg_target) || ctx->opt.no_split)) return POLS_OK;
-    const int64_t n_items = ids ? (int64_t)ids->size() : b->n_groups;
-    auto &sc = ctx->seg_cache[ids ? 1 : 0];               // (class tables have their own: they do not evict the whole-frame tables)
-    int rc;
-    // (the key is the frame; the per-segment extra area only has to be large enough -- its users differ in what they keep there: the Gram
-    // partials of ls_core, the moments of the statistics entry, nothing for pols_predict -- and it is kept at the largest size asked for,
-    // so that alternating users of one frame stop rebuilding and re-uploading the tables)
-    const bool same_frame = sc.valid && sc.offs_id == ctx->offs_id && sc.n_groups == b->n_groups && sc.n_rows == b->n_rows &&
-                            sc.seg_target == seg_target && sc.class_key == class_key && sc.n_items == n_items;
-    const bool hit = same_frame && sc.nz2 >= extra_per_seg;
-    auto lay = [&](char *sb, int64_t n_seg) {
-        const size_t b_so = round256(sizeof(int64_t) * (size_t)(ids ? 2 * n_seg : n_seg + 1)), b_sm = round256(sizeof(int32_t) * (size_t)n_seg),
-                     b_sf = round256(sizeof(int32_t) * (size_t)(n_items + 1));
-        t->offs = reinterpret_cast<const int64_t *>(sb);
-        t->map = reinterpret_cast<const int32_t *>(sb + b_so);
-        t->first = reinterpret_cast<const int32_t *>(sb + b_so + b_sm);
-        t->extra = sb + b_so + b_sm + b_sf;
-        t->n_seg = n_seg;
-        return b_so + b_sm + b_sf;
-    };
-    if (hit) { lay(static_cast<char *>(sc.buf.ptr), sc.n_seg); t->max_len = sc.max_len; t->max_seg = sc.max_seg; return POLS_OK; }
-    if (same_frame) extra_per_seg = std::max<size_t>(extra_per_seg, sc.nz2);
-    sc.valid = false;
-    std::vector<int64_t> so;
-    std::vector<int32_t> sm, sf((size_t)n_items + 1);
-    if (!ids) so.push_back(0);
-    int64_t max_len = 0, max_seg = 0;
-    for (int64_t i = 0; i < n_items; ++i) {
-        const int64_t g = ids ? (int64_t)(*ids)[(size_t)i] : i;
-        if (i > 0) max_seg = std::max<int64_t>(max_seg, (int64_t)sm.size() - sf[(size_t)i - 1]);
-        sf[(size_t)i] = (int32_t)sm.size();
-        const int64_t s0 = b->group_offsets[g], e0 = b->group_offsets[g + 1];
-        const int64_t pieces = std::max<int64_t>(1, (e0 - s0 + seg_target - 1) / seg_target);
-        const int64_t len = std::max<int64_t>(1, ((e0 - s0 + pieces - 1) / pieces + 255) / 256 * 256);   // (256-row multiples: whole staging chunks)
-        max_len = std::max(max_len, std::min(len, e0 - s0));
-        for (int64_t r = s0; r < e0 || r == s0; r += len) {
-            if (ids) so.push_back(r);
-            so.push_back(std::min(e0, r + len));
-            sm.push_back((int32_t)i);
-            if (e0 == s0) break;
-        }
-    }
-    sf[(size_t)n_items] = (int32_t)sm.size();
-    if (n_items > 0) max_seg = std::max<int64_t>(max_seg, (int64_t)sm.size() - sf[(size_t)n_items - 1]);
-    const int64_t n_seg = (int64_t)sm.size();
-    const size_t tabs = round256(sizeof(int64_t) * so.size()) + round256(sizeof(int32_t) * sm.size()) + round256(sizeof(int32_t) * sf.size());
-    void *ds = nullptr;
-    if ((rc = grow(sc, tabs + round256(extra_per_seg * (size_t)n_seg), &ds))) return rc;
-    char *sb = static_cast<char *>(ds);
-    lay(sb, n_seg);
-    if ((rc = upload_small(ctx, const_cast<int64_t *>(t->offs), so.data(), sizeof(int64_t) * so.size()))) return rc;
-    if ((rc = upload_small(ctx, const_cast<int32_t *>(t->map), sm.data(), sizeof(int32_t) * sm.size()))) return rc;
-    if ((rc = upload_small(ctx, const_cast<int32_t *>(t->first), sf.data(), sizeof(int32_t) * sf.size()))) return rc;
-    sc.valid = true; sc.offs_id = ctx->offs_id; sc.n_groups = b->n_groups; sc.n_rows = b->n_rows; sc.seg_target = seg_target;
-    sc.class_key = class_key; sc.n_items = n_items;
-    sc.n_seg = n_seg; sc.nz2 = extra_per_seg; sc.nulls = false; sc.max_len = max_len; sc.max_seg = max_seg;
-    t->max_len = max_len; t->max_seg = max_seg;
-    return POLS_OK;
-}
-
-// ------------------------------------------------------------------ mode = "statistics"
-// The ids of a batch's rows on the device: the caller's own for a device batch, staged into Work::ClusterIds for a host batch.
-static int cluster_device_ids(pols_ctx *ctx, const pols_batch *b, const pols_cluster_params *cl, int ways, const int64_t **dev) {
-    if (b->mem == POLS_MEM_DEVICE) {
-        for (int w = 0; w < ways; ++w) dev[w] = cl->ids[w];
-        return POLS_OK;
-    }
-    const size_t colb = round256(sizeof(int64_t) * (size_t)std::max<int64_t>(b->n_rows, 1));
-    void *d = nullptr;
-    int rc = ensure_scratch(ctx, Work::ClusterIds, colb * (size_t)ways, &d);
-    if (rc) return rc;
-    for (int w = 0; w < ways; ++w) {
-        char *dst = static_cast<char *>(d) + colb * (size_t)w;
-        if (b->n_rows) POLS_HIP(hipMemcpyAsync(dst, cl->ids[w], sizeof(int64_t) * (size_t)b->n_rows, hipMemcpyHostToDevice, ctx->stream));
-        dev[w] = reinterpret_cast<const int64_t *>(dst);
-    }
-    return POLS_OK;
-}
-
-// What pols_least_squares_influence adds to a statistics call (K7i, k7i_influence.hip).  The group stage runs where the fit runs (on the
-// compacted frame under a null policy), the row pass where the ORIGINAL rows are: the level of statistics_body that compacted them.
-struct InflCall {
-    const pols_influence_params *q;
-    const pols_influence_out *io;
-    bool rows_by_caller = false;            // set by the compaction level: it runs the row pass itself, with the validity bytes
-    double *prep = nullptr, *grp = nullptr; // the group stage's tables (Work::InflPrep; Work::InflGroup behind the RSS)
-};
-
-// The row pass of K7i over the rows of `b` as staged in `st`, then the per-group outputs; valid == nullptr: every row was fitted.
-static int influence_rows(pols_ctx *ctx, const pols_batch *b, const Staged &st, const int64_t *d_offs, const SegTables &sg, const uint8_t *valid,
-                          int zero_fill, const InflCall &ic) {
-    const bool host = b->mem == POLS_MEM_HOST;
-    const size_t G = (size_t)b->n_groups, N = (size_t)b->n_rows, sz = dtype_size(b->dtype), colb = round256(sz * std::max<size_t>(N, 1));
-    const pols_influence_out *io = ic.io;
-    void *const user[K7I_NOUT] = {io->leverage, io->student_internal, io->student_external, io->cooks_d, io->dffits, io->se_mean,
-                                  io->se_obs, io->mean_lo, io->mean_hi, io->obs_lo, io->obs_hi};
-    int rc, n_out = 0;
-    for (int i = 0; i < K7I_NOUT; ++i) n_out += user[i] ? 1 : 0;
-    InflArgs a;
-    std::memset(&a, 0, sizeof(a));
-    a.y = st.y; a.w = st.w;
-    for (int j = 0; j < b->n_features; ++j) a.x[j] = st.x[(size_t)j];
-    a.offs = d_offs; a.n_groups = b->n_groups; a.n_rows = b->n_rows;
-    if (sg.n_seg > 0) { a.seg_offs = sg.offs; a.seg_map = sg.map; a.n_seg = sg.n_seg; }
-    a.valid = valid; a.zero_fill = zero_fill;
-    a.k_user = b->n_features; a.kt = b->n_features + (b->add_intercept ? 1 : 0);
-    a.prep = ic.prep; a.grp = ic.grp;
-    void *rows = nullptr;
-    if (host && n_out && (rc = ensure_scratch(ctx, Work::InflRows, colb * (size_t)n_out, &rows))) return rc;
-    char *q = static_cast<char *>(rows);
-    for (int i = 0; i < K7I_NOUT; ++i) {
-        if (!user[i]) continue;
-        if (!host && !aligned16(user[i])) return fail(POLS_ERR_INVALID, "device columns must be 16-byte aligned");
-        a.out[i] = host ? static_cast<void *>(q) : user[i];
-        q += host ? colb : 0;
-    }
-    if ((rc = k7i_rows_launch(ctx, b->dtype, a))) return rc;
-    if (host && N)
-        for (int i = 0; i < K7I_NOUT; ++i)
-            if (user[i]) POLS_HIP(hipMemcpyAsync(user[i], a.out[i], sz * N, hipMemcpyDeviceToHost, ctx->stream));
-    double *const gu[3] = {io->sigma2, io->df, io->t_crit};
-    for (int i = 0; i < 3; ++i)
-        if (gu[i]) POLS_HIP(hipMemcpyAsync(gu[i], ic.grp + (size_t)i * G, sizeof(double) * G, host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, ctx->stream));
-    return POLS_OK;
-}
-
-// The body of pols_least_squares_statistics and of its robust and cluster twins: cov == cl == nullptr is the non-robust entry; with
-// cov (HC0 .. HAC, validated by pols_least_squares_statistics_robust, at most K7_KMAX columns) K7 still writes r2 / mae / mse and the
-// status words and K7r (k7r_robust.hip) the standard errors, t- and p-values; with cl (validated by
-// pols_least_squares_statistics_cluster) K7c (k7c_cluster.hip) writes them.  With infl (pols_least_squares_influence: cov == cl == nullptr,
-// at most K7_KMAX columns) K7 also leaves the side-car RSS, and K7i (k7i_influence.hip) writes the per-row diagnostics.
-static int statistics_body(pols_ctx *ctx, const pols_batch *b, const pols_ols_params *p, const pols_cov_params *cov,
-                           const pols_cluster_params *cl, pols_out *o, const pols_stats_out *s, InflCall *infl = nullptr) {
-    int rc = check_ctx(ctx);
-    if (rc) return rc;
-    if ((rc = check_batch(b, o, K8_KMAX))) return rc;
-    if (!p || !s) return fail(POLS_ERR_INVALID, "params / stats is NULL");
-    if (p->null_policy < POLS_NULL_IGNORE || p->null_policy > POLS_NULL_DROP_WINDOW) return fail(POLS_ERR_INVALID, "unknown null_policy %d", p->null_policy);
-    if (b->valid && (p->null_policy == POLS_NULL_IGNORE || p->null_policy == POLS_NULL_ZERO))
-        return fail(POLS_ERR_INVALID, "a validity mask needs a drop-family null_policy");
-    if (b->n_groups == 0) return POLS_OK;
-    if ((p->null_policy != POLS_NULL_IGNORE && !b->null_free) || b->valid) {
-        // The statistics are those of the rows handle_nulls leaves (src/expressions.rs:469-471): filter / zero-fill on the device,
-        // then this very entry on the filtered batch.  Outputs are per group, so they land where the caller wants them.
-        Compacted c;
-        if ((rc = compact_nulls(ctx, b, p->null_policy, &c))) return rc;
-        pols_ols_params pp = *p;
-        pp.null_policy = POLS_NULL_IGNORE;
-        const size_t G = (size_t)b->n_groups, sz = dtype_size(b->dtype);
-        pols_cluster_params cc;
-        if (cl) {
-            // the ids follow their rows: the source row of every kept row (the compaction's own slab bases), then a gather
-            cc = *cl;
-            const int ways = cl->cov_type == POLS_COV_CLUSTER2 ? 2 : 1;
-            const int64_t *src[2] = {nullptr, nullptr};
-            if ((rc = cluster_device_ids(ctx, b, cl, ways, src))) return rc;
-            const int64_t nv = c.offs[G];
-            const size_t mapb = round256(sizeof(int32_t) * (size_t)std::max<int64_t>(nv, 1)), colb = round256(sizeof(int64_t) * (size_t)std::max<int64_t>(nv, 1));
-            void *d = nullptr;
-            if ((rc = ensure_scratch(ctx, Work::ClusterCompact, mapb + colb * (size_t)ways, &d))) return rc;
-            int64_t *dst[2] = {nullptr, nullptr};
-            for (int w = 0; w < ways; ++w) dst[w] = reinterpret_cast<int64_t *>(static_cast<char *>(d) + mapb + colb * (size_t)w);
-            if (nv > 0) {
-                RowCompactArgs ra = c.ra;
-                ra.src = static_cast<int32_t *>(d);
-                if ((rc = row_compact_srcmap_launch(ctx, ra))) return rc;
-                if ((rc = k7c_gather_ids_launch(ctx, ra.src, nv, src, dst, ways))) return rc;
-            }
-            for (int w = 0; w < ways; ++w) cc.ids[w] = dst[w];
-            if (b->mem == POLS_MEM_HOST && cl->n_clusters) {
-                void *nc = nullptr;
-                if ((rc = ensure_scratch(ctx, Work::ClusterCounts, round256(sizeof(int64_t) * G * (size_t)ways), &nc))) return rc;
-                cc.n_clusters = static_cast<int64_t *>(nc);
-            }
-        }
-        const pols_cluster_params *clc = cl ? &cc : nullptr;
-        if (infl) infl->rows_by_caller = true;
-        // the influence row pass: over the ORIGINAL rows (c.st), the compaction's validity bytes telling the fitted rows from the others
-        auto rows_of_frame = [&]() -> int {
-            const int64_t *d_offs = nullptr;
-            int64_t mr = 0;
-            int rc2 = upload_offsets(ctx, b->group_offsets, b->n_groups, &d_offs, &mr, b->offsets_generation);   // (the fit uploaded the compacted ones)
-            if (rc2) return rc2;
-            SegTables sgf;
-            if ((rc2 = ensure_segments(ctx, b, mr, 0, &sgf))) return rc2;
-            return influence_rows(ctx, b, c.st, d_offs, sgf, c.vbytes, c.ra.zero_fill, *infl);
-        };
-        if (b->mem == POLS_MEM_DEVICE) {
-            if ((rc = statistics_body(ctx, &c.bb, &pp, cov, clc, o, s, infl))) return rc;
-            return infl ? rows_of_frame() : POLS_OK;
-        }
-        const int kt = b->n_features + (b->add_intercept ? 1 : 0);
-        const size_t coefb = round256(sz * G * kt), statb = round256(sizeof(int32_t) * G), vecb = round256(sizeof(double) * G),
-                     matb = round256(sizeof(double) * G * kt);
-        void *d = nullptr;
-        if ((rc = ensure_scratch(ctx, Work::CompactOut, coefb + statb + 3 * vecb + 3 * matb, &d))) return rc;
-        char *q = static_cast<char *>(d);
-        pols_out od;
-        std::memset(&od, 0, sizeof(od));
-        if (o->coef) od.coef = q;
-        if (o->status) od.status = reinterpret_cast<int32_t *>(q + coefb);
-        q += coefb + statb;
-        double *const user[6] = {s->r2, s->mae, s->mse, s->std_err, s->t_values, s->p_values};
-        double *dev[6];
-        for (int i = 0; i < 6; ++i) { dev[i] = user[i] ? reinterpret_cast<double *>(q) : nullptr; q += i < 3 ? vecb : matb; }
-        pols_stats_out sd;
-        sd.r2 = dev[0]; sd.mae = dev[1]; sd.mse = dev[2]; sd.std_err = dev[3]; sd.t_values = dev[4]; sd.p_values = dev[5];
-        if ((rc = statistics_body(ctx, &c.bb, &pp, cov, clc, &od, &sd, infl))) return rc;
-        if (infl && (rc = rows_of_frame())) return rc;
-        if (cl && cl->n_clusters)
-            POLS_HIP(hipMemcpyAsync(cl->n_clusters, cc.n_clusters, sizeof(int64_t) * G * (cl->cov_type == POLS_COV_CLUSTER2 ? 2 : 1),
-                                    hipMemcpyDeviceToHost, ctx->stream));
-        if (o->coef) POLS_HIP(hipMemcpyAsync(o->coef, od.coef, sz * G * kt, hipMemcpyDeviceToHost, ctx->stream));
-        if (o->status) POLS_HIP(hipMemcpyAsync(o->status, od.status, sizeof(int32_t) * G, hipMemcpyDeviceToHost, ctx->stream));
-        for (int i = 0; i < 6; ++i)
-            if (user[i]) POLS_HIP(hipMemcpyAsync(user[i], dev[i], sizeof(double) * G * (i < 3 ? 1 : kt), hipMemcpyDeviceToHost, ctx->stream));
-        POLS_HIP(hipStreamSynchronize(ctx->stream));
-        return POLS_OK;
-    }
-    const int kt = b->n_features + (b->add_intercept ? 1 : 0);
-    const size_t sz = dtype_size(b->dtype);
-    const bool host = b->mem == POLS_MEM_HOST;
-    const size_t G = (size_t)b->n_groups;
-    if (kt > 31) {
-        // 32 .. 1 024 columns: the K8 kernels solve (same dispatcher), then the wide statistics kernel works from their Gram matrix
-        SolvePlan plan;
-        if ((rc = resolve_solve_plan(p, b->dtype, kt, 1, &plan))) return rc;
-        const size_t vecb = round256(sizeof(double) * G), matb = round256(sizeof(double) * G * kt);
-        void *scr4 = nullptr;
-        if (host && (rc = ensure_scratch(ctx, Work::HostStaged, 3 * vecb + 3 * matb, &scr4))) return rc;
-        WideInfo wi;
-        pols_out oo = *o;
-        char coef_sentinel;
-        if (!oo.coef && host) oo.coef = &coef_sentinel;            // host batches stage every non-NULL output
-        if ((rc = wide_static(ctx, b, p, &oo, kt, plan, nullptr, 1, nullptr, &wi))) return rc;
-        WideStatsOut so;
-        double *const user[6] = {s->r2, s->mae, s->mse, s->std_err, s->t_values, s->p_values};
-        double *dev[6];
-        char *q = static_cast<char *>(scr4);
-        for (int i = 0; i < 6; ++i) {
-            dev[i] = !user[i] ? nullptr : (host ? reinterpret_cast<double *>(q) : user[i]);
-            if (host) q += (i < 3) ? vecb : matb;
-        }
-        so.r2 = dev[0]; so.mae = dev[1]; so.mse = dev[2]; so.se = dev[3]; so.tv = dev[4]; so.pv = dev[5];
-        so.lambda = p->alpha;
-        so.factored = !plan.enet() && kt + 1 > 128;                       // wide_chol ran on the Gram matrix in place (k8_wide.hip)
-        if ((rc = wide_stats_launch(ctx, b->dtype, wi.a, so))) return rc;
-        if (!host) return POLS_OK;
-        for (int i = 0; i < 6; ++i)
-            if (user[i])
-                POLS_HIP(hipMemcpyAsync(user[i], dev[i], sizeof(double) * G * (i < 3 ? 1 : kt), hipMemcpyDeviceToHost, ctx->stream));
-        if (!o->coef) oo.coef = nullptr;
-        return unstage_outputs(ctx, b, b->n_groups, kt, &oo, wi.st);
-    }
-    // Work::Tables: [coefficients when the caller did not ask for them (device batches)] [statistic arrays of a host batch]
-    const size_t coefb = round256(sz * G * kt), vecb = round256(sizeof(double) * G), matb = round256(sizeof(double) * G * kt);
-    void *scr = nullptr;
-    if ((rc = ensure_scratch(ctx, Work::Tables, coefb + 3 * vecb + 3 * matb, &scr))) return rc;
-    char *q = static_cast<char *>(scr);
-    pols_out oo = *o;
-    char coef_sentinel;   // host batches stage every non-NULL output: ask for the coefficients, throw the copy away below
-    if (!oo.coef) oo.coef = host ? static_cast<void *>(&coef_sentinel) : static_cast<void *>(q);
-    q += coefb;
-    LsInfo info;
-    if ((rc = ls_core(ctx, b, p, &oo, &info))) return rc;
-
-    double *gram = info.gram;
-    if (!gram) {
-        void *gs = nullptr;
-        const size_t nz = (size_t)kt + 1;
-        if ((rc = ensure_scratch(ctx, Work::Gram, round256(sizeof(double) * nz * nz * G), &gs))) return rc;
-        GramArgs ga;
-        std::memset(&ga, 0, sizeof(ga));
-        ga.y = info.st.y; ga.w = info.st.w;
-        for (int j = 0; j < b->n_features; ++j) ga.x[j] = info.st.x[j];
-        ga.offs = info.d_offs; ga.n_groups = b->n_groups; ga.n_rows = b->n_rows;
-        ga.gram = static_cast<double *>(gs);
-        ga.k_user = b->n_features; ga.kt = kt;
-        // long groups (the size-class + streamed route of ls_core keeps no per-group Gram matrices): the segment split of the streamed path
-        // here too -- an unsplit launch is one workgroup per group, i.e. ONE CU for a multi-million-row group
-        SegTables sgg;
-        if ((rc = ensure_segments(ctx, b, ctx->offs_max_rows, sizeof(double) * (nz * nz + 1), &sgg))) return rc;
-        if (sgg.n_seg > 0) {
-            const int n_slices = (sgg.max_seg >= 256 && G <= 256) ? 16 : 1;
-            void *sl = nullptr;
-            if (n_slices > 1 && (rc = ensure_scratch(ctx, Work::Fixup, round256(sizeof(double) * nz * nz * (size_t)n_slices * G), &sl))) return rc;   // (the fix-up work area, idle here)
-            ga.offs = sgg.offs; ga.n_groups = sgg.n_seg; ga.gram = reinterpret_cast<double *>(sgg.extra);
-            if ((rc = gram_stream_launch(ctx, b->dtype, ga))) return rc;
-            GramReduceArgs ra;
-            std::memset(&ra, 0, sizeof(ra));
-            ra.part = ga.gram; ra.first = sgg.first; ra.gram = static_cast<double *>(gs); ra.n_groups = b->n_groups; ra.nz2 = (int32_t)(nz * nz);
-            ra.max_segments = (int32_t)std::min<int64_t>(1 << 30, sgg.max_seg);
-            if (n_slices > 1) { ra.slices = static_cast<double *>(sl); ra.n_slices = n_slices; }
-            if ((rc = gram_reduce_launch(ctx, ra))) return rc;
-            ga.gram = static_cast<double *>(gs);
-        } else if ((rc = gram_stream_launch(ctx, b->dtype, ga))) return rc;
-        gram = ga.gram;
-    }
-    StatsArgs sa;
-    std::memset(&sa, 0, sizeof(sa));
-    sa.y = info.st.y; sa.w = info.st.w;
-    for (int j = 0; j < b->n_features; ++j) sa.x[j] = info.st.x[j];
-    sa.offs = info.d_offs; sa.n_groups = b->n_groups; sa.gram = gram;
-    sa.coef = info.st.coef; sa.lambda = p->alpha; sa.status = info.st.status;
-    sa.k_user = b->n_features; sa.kt = kt;
-    {   // long groups (ONE model summary over a whole frame): the row passes run per segment
-        const int64_t mr = ctx->offs_max_rows;                 // (of the offsets ls_core just uploaded: no O(groups) host loop per call)
-        SegTables sg;
-        const size_t per_seg = sizeof(double) * 5;
-        if ((rc = ensure_segments(ctx, b, mr, per_seg, &sg))) return rc;
-        if (sg.n_seg > 0) {
-            void *pp = nullptr;
-            if ((rc = ensure_scratch(ctx, Work::RowCompact, round256(sizeof(double) * G * (3 * (size_t)kt + 1)), &pp))) return rc;   // (Work::RowCompact: the rolling entry's, never live here)
-            sa.seg_offs = sg.offs; sa.seg_map = sg.map; sa.seg_first = sg.first; sa.n_seg = sg.n_seg;
-            sa.seg_part = reinterpret_cast<double *>(sg.extra);
-            sa.prep = static_cast<double *>(pp);
-        }
-    }
-    double *dev[6];
-    double *const user[6] = {s->r2, s->mae, s->mse, s->std_err, s->t_values, s->p_values};
-    for (int i = 0; i < 6; ++i) {
-        dev[i] = !user[i] ? nullptr : (host ? reinterpret_cast<double *>(q) : user[i]);
-        q += (i < 3) ? vecb : matb;
-    }
-    sa.r2 = dev[0]; sa.mae = dev[1]; sa.mse = dev[2]; sa.se = dev[3]; sa.tv = dev[4]; sa.pv = dev[5];
-    if (infl) {
-        // K7 leaves the side-car RSS of every group (StatsArgs::rss), K7r's prepare launch A^-1 / b / trace / ok in K7i's own table
-        void *ip = nullptr, *ig = nullptr;
-        if ((rc = ensure_scratch(ctx, Work::InflPrep, round256(sizeof(double) * G * k7r_prep_stride(kt)), &ip))) return rc;
-        const size_t n_items = sa.seg_offs ? (size_t)sa.n_seg : G;   // (f32 batches: the refinement's X~'e~ per segment / group behind the rest)
-        if ((rc = ensure_scratch(ctx, Work::InflGroup, round256(sizeof(double) * (G * 5 + (b->dtype == POLS_F32 ? n_items * (size_t)kt : 0))), &ig))) return rc;
-        sa.rss = static_cast<double *>(ig);
-        infl->prep = static_cast<double *>(ip);
-        infl->grp = static_cast<double *>(ig) + G;
-    }
-    if (cov) {
-        // robust: K7 keeps r2 / mae / mse / status, K7r writes the standard errors, t- and p-values (its own buffers: sa's segment
-        // tables are the frame's cached ones, the partial sums of K7 and K7r live apart)
-        RobustArgs ra;
-        std::memset(&ra, 0, sizeof(ra));
-        ra.s = sa;
-        sa.se = sa.tv = sa.pv = nullptr;
-        ra.cov_type = cov->cov_type;
-        ra.maxlags = cov->cov_type == POLS_COV_HAC ? cov->maxlags : 0;
-        const int64_t n_items = sa.seg_offs ? sa.n_seg : (int64_t)G;
-        void *rp = nullptr, *rm = nullptr;
-        if ((rc = ensure_scratch(ctx, Work::RobustPrep, round256(sizeof(double) * G * k7r_prep_stride(kt)), &rp))) return rc;
-        if ((rc = ensure_scratch(ctx, Work::RobustMeat, round256(sizeof(double) * (size_t)n_items * k7r_part_stride(kt)), &rm))) return rc;
-        ra.prep = static_cast<double *>(rp);
-        ra.part = static_cast<double *>(rm);
-        if ((rc = k7_stats_launch(ctx, b->dtype, sa))) return rc;
-        if ((rc = k7r_robust_launch(ctx, b->dtype, ra))) return rc;
-    } else if (cl) {
-        // cluster-robust: K7 keeps r2 / mae / mse / status, K7c writes the standard errors, t- and p-values and the cluster counts
-        ClusterArgs ca;
-        std::memset(&ca, 0, sizeof(ca));
-        ca.s = sa;
-        sa.se = sa.tv = sa.pv = nullptr;
-        ca.n_rows = b->n_rows;
-        ca.ways = cl->cov_type == POLS_COV_CLUSTER2 ? 2 : 1;
-        ca.use_correction = cl->use_correction ? 1 : 0;
-        if ((rc = cluster_device_ids(ctx, b, cl, ca.ways, ca.ids))) return rc;
-        const int64_t n_items = sa.seg_offs ? sa.n_seg : (int64_t)G;
-        void *cp = nullptr, *cq = nullptr, *nc = nullptr;
-        if ((rc = ensure_scratch(ctx, Work::ClusterPrep, round256(sizeof(double) * G * k7r_prep_stride(kt)), &cp))) return rc;
-        if ((rc = ensure_scratch(ctx, Work::ClusterPart, round256(sizeof(double) * ((size_t)n_items * k7c_part_stride(kt) + 3 * G * ((size_t)kt + 1))), &cq)))
-            return rc;
-        if (cl->n_clusters && host && (rc = ensure_scratch(ctx, Work::ClusterCounts, round256(sizeof(int64_t) * G * (size_t)ca.ways), &nc))) return rc;
-        ca.n_clusters = host ? static_cast<int64_t *>(nc) : cl->n_clusters;
-        ca.prep = static_cast<double *>(cp);
-        ca.part = static_cast<double *>(cq);
-        if ((rc = k7_stats_launch(ctx, b->dtype, sa))) return rc;
-        if ((rc = k7c_cluster_launch(ctx, b->dtype, ca))) return rc;
-        if (host && cl->n_clusters)
-            POLS_HIP(hipMemcpyAsync(cl->n_clusters, ca.n_clusters, sizeof(int64_t) * G * (size_t)ca.ways, hipMemcpyDeviceToHost, ctx->stream));
-    } else if ((rc = k7_stats_launch(ctx, b->dtype, sa))) return rc;
-    if (infl) {
-        RobustArgs ra;
-        std::memset(&ra, 0, sizeof(ra));
-        ra.s = sa;
-        ra.prep = infl->prep;
-        if ((rc = k7r_prepare_launch(ctx, b->dtype, ra))) return rc;
-        InflGroupArgs ga;
-        std::memset(&ga, 0, sizeof(ga));
-        if (b->dtype == POLS_F32) {
-            // the Gram matrix of an f32 batch carries f32-sized errors: one step of iterative refinement of b in f64 (k7i_influence.hip)
-            ra.part = infl->grp + 4 * G;
-            if ((rc = k7i_refine_launch(ctx, b->dtype, ra))) return rc;
-            ga.xe = ra.part;
-            ga.seg_first = sa.seg_offs ? sa.seg_first : nullptr;
-        }
-        ga.offs = info.d_offs; ga.n_groups = b->n_groups; ga.kt = kt;
-        ga.lambda = p->alpha; ga.level = infl->q->level;
-        ga.prep = infl->prep; ga.rss = sa.rss; ga.grp = infl->grp;
-        if ((rc = k7i_group_launch(ctx, ga))) return rc;
-        if (!infl->rows_by_caller) {
-            SegTables sgi;
-            sgi.offs = sa.seg_offs; sgi.map = sa.seg_map; sgi.first = sa.seg_first; sgi.n_seg = sa.n_seg;
-            if ((rc = influence_rows(ctx, b, info.st, info.d_offs, sgi, nullptr, 0, *infl))) return rc;
-        }
-    }
-    if (!host) return POLS_OK;
-    for (int i = 0; i < 6; ++i)
-        if (user[i])
-            POLS_HIP(hipMemcpyAsync(user[i], dev[i], sizeof(double) * G * (i < 3 ? 1 : kt), hipMemcpyDeviceToHost, ctx->stream));
-    if (!o->coef) oo.coef = nullptr;
-    return unstage_outputs(ctx, b, b->n_groups, kt, &oo, info.st);
-}
-
-int pols_least_squares_statistics(pols_ctx *ctx, const pols_batch *b, const pols_ols_params *p, pols_out *o,
-                                  const pols_stats_out *s) {
-    return statistics_body(ctx, b, p, nullptr, nullptr, o, s);
-}
-
-void pols_cov_params_default(pols_cov_params *c) {
-    if (!c) return;
-    c->cov_type = POLS_COV_NONROBUST;
-    c->maxlags = 0;
-}
-
-int pols_least_squares_statistics_robust(pols_ctx *ctx, const pols_batch *b, const pols_ols_params *p, const pols_cov_params *cov,
-                                         pols_out *o, const pols_stats_out *s) {
-    if (!cov) return fail(POLS_ERR_INVALID, "cov is NULL");
-    if (cov->cov_type == POLS_COV_CLUSTER || cov->cov_type == POLS_COV_CLUSTER2)
-        return fail(POLS_ERR_INVALID, "cov_type %d: cluster-robust standard errors go through pols_least_squares_statistics_cluster", cov->cov_type);
-    if (cov->cov_type < POLS_COV_NONROBUST || cov->cov_type > POLS_COV_HAC) return fail(POLS_ERR_INVALID, "unknown cov_type %d", cov->cov_type);
-    if (cov->cov_type == POLS_COV_NONROBUST) return pols_least_squares_statistics(ctx, b, p, o, s);
-    if (cov->cov_type == POLS_COV_HAC) {
-        if (cov->maxlags < 0) return fail(POLS_ERR_INVALID, "HAC: maxlags %d < 0", cov->maxlags);
-        if (cov->maxlags > K7R_MAXLAGS) return fail(POLS_ERR_UNSUPPORTED, "HAC: maxlags %d > %d", cov->maxlags, K7R_MAXLAGS);
-    }
-    if (!b) return fail(POLS_ERR_INVALID, "batch is NULL");
-    const int kt = b->n_features + (b->add_intercept ? 1 : 0);
-    if (kt > K7_KMAX)
-        return fail(POLS_ERR_UNSUPPORTED, "robust statistics: %d features (incl. intercept) > %d; wider frames have only the non-robust form", kt, K7_KMAX);
-    return statistics_body(ctx, b, p, cov, nullptr, o, s);
-}
-
-void pols_influence_params_default(pols_influence_params *q) {
-    if (!q) return;
-    q->level = 0.95;
-}
-
-int pols_least_squares_influence(pols_ctx *ctx, const pols_batch *b, const pols_ols_params *p, const pols_influence_params *q,
-                                 pols_out *o, const pols_influence_out *infl) {
-    if (!q || !infl) return fail(POLS_ERR_INVALID, "influence params / outputs are NULL");
-    if (!(q->level > 0.0 && q->level < 1.0)) return fail(POLS_ERR_INVALID, "influence: level %g outside (0, 1)", q->level);
-    if (!b) return fail(POLS_ERR_INVALID, "batch is NULL");
-    const int kt = b->n_features + (b->add_intercept ? 1 : 0);
-    if (kt > K7_KMAX)
-        return fail(POLS_ERR_UNSUPPORTED, "influence: %d features (incl. intercept) > %d; wider frames have only the statistics", kt, K7_KMAX);
-    pols_stats_out none;
-    std::memset(&none, 0, sizeof(none));
-    InflCall ic{q, infl};
-    return statistics_body(ctx, b, p, nullptr, nullptr, o, &none, &ic);
-}
-
-void pols_cluster_params_default(pols_cluster_params *c) {
-    if (!c) return;
-    c->cov_type = POLS_COV_CLUSTER;
-    c->use_correction = 1;
-    c->ids[0] = c->ids[1] = nullptr;
-    c->n_clusters = nullptr;
-}
-
-int pols_least_squares_statistics_cluster(pols_ctx *ctx, const pols_batch *b, const pols_ols_params *p, const pols_cluster_params *cl,
-                                          pols_out *o, const pols_stats_out *s) {
-    if (!cl) return fail(POLS_ERR_INVALID, "cluster params are NULL");
-    if (cl->cov_type != POLS_COV_CLUSTER && cl->cov_type != POLS_COV_CLUSTER2)
-        return fail(POLS_ERR_INVALID, "cluster statistics: cov_type %d is neither POLS_COV_CLUSTER nor POLS_COV_CLUSTER2", cl->cov_type);
-    if (!b) return fail(POLS_ERR_INVALID, "batch is NULL");
-    const int kt = b->n_features + (b->add_intercept ? 1 : 0);
-    if (kt > K7_KMAX)
-        return fail(POLS_ERR_UNSUPPORTED, "cluster statistics: %d features (incl. intercept) > %d; wider frames have only the non-robust form", kt, K7_KMAX);
-    const int ways = cl->cov_type == POLS_COV_CLUSTER2 ? 2 : 1;
-    for (int w = 0; w < ways; ++w)
-        if (!cl->ids[w] && b->n_rows > 0) return fail(POLS_ERR_INVALID, "cluster statistics: ids[%d] is NULL", w);
-    if (b->n_rows >= ((int64_t)1 << 31)) return fail(POLS_ERR_UNSUPPORTED, "cluster statistics: %lld rows (row indices are 31-bit)", (long long)b->n_rows);
-    return statistics_body(ctx, b, p, nullptr, cl, o, s);
 }
 
 int pols_predict(pols_ctx *ctx, const pols_batch *b, const void *coef, int64_t coef_rows, void *pred_out) {

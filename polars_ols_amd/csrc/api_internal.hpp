@@ -1,6 +1,9 @@
 // api_internal.hpp -- what the entry translation units share beyond common.hpp.  Who defines what:
-//   api.hip         contexts, options, offsets upload (+ scan_offsets), staging, segments, k1_launch, mark_fallback_kernel; the statistics,
-//                   prediction, sharded, layout and Arrow entries
+//   api.hip         contexts, options, offsets upload (+ scan_offsets), staging, compact_nulls, segments (ensure_segments), k1_launch,
+//                   mark_fallback_kernel; the prediction, sharded, layout and Arrow entries
+//   api_stats.hip   statistics mode: pols_least_squares_statistics, its robust and cluster twins, pols_least_squares_influence and their
+//                   parameter defaults -- the null-policy level, the fit level and its stages.  Nothing of it is declared here (it uses
+//                   check_ctx / check_batch / Staged / unstage_outputs / compact_nulls / ls_core / wide_static / ensure_segments from below)
 //   api_static.hip  the static least-squares path: resolve_solve_plan, ensure_fallback_epoch, k1_valu_takes, pick_static_route, ls_core,
 //                   wide_static, pols_least_squares, pols_multi_target_least_squares, pols_debug_static_route
 //   api_dynamic.hip the dynamic entries: the prologue (DynState), the cached per-frame tables, pick_rls_route / pick_rolling_route and one
