@@ -723,7 +723,7 @@ int pols_iv2sls(pols_ctx *ctx, const pols_batch *b, const pols_ols_params *p, co
  * From pols_ols_params only null_policy is read.  POLS_ERR_INVALID: NULL ids; n_features < 1; alpha != 0, positive, or has_l1_ratio
  * with l1_ratio > 0; a cov_type other than the two named; a validity mask without a drop-family policy; on the device, a pred / resid
  * / fe that is not 16-byte aligned.  POLS_ERR_UNSUPPORTED: kt > 31 or n_rows >= 2^31.  There is no Arrow twin and no sharded entry.
- * Not built: a second absorbed id; HC0-HC3 / HAC covariance on absorbed fits; penalised fits; rolling / recursive forms. */
+ * Not built: HC0-HC3 / HAC covariance on absorbed fits; penalised fits; rolling / recursive forms. */
 typedef struct pols_absorb_params {
     const int64_t *ids;         /* one id per row, in the batch's row order, where b->mem says */
     int32_t cov_type;           /* POLS_COV_NONROBUST or POLS_COV_CLUSTER (clustered on ids)    */
@@ -746,6 +746,84 @@ typedef struct pols_absorb_out {
 
 int pols_least_squares_absorb(pols_ctx *ctx, const pols_batch *b, const pols_ols_params *p, const pols_absorb_params *q,
                               pols_out *out, const pols_absorb_out *r);
+
+/* Regression that absorbs TWO categorical effects inside every group -- two-way fixed effects (no reference counterpart; Stata's
+ * reghdfe y x, absorb(firm year) and linearmodels' PanelOLS(entity_effects=True, time_effects=True) for every group of the frame in
+ * one call, without a dummy column per category).  Everything below is per group g.  F_g, n, the weights (a null weight acts as 1e-24),
+ * the null-policy rules and the validity-mask rule are exactly those of pols_least_squares_absorb above.  q->ids and q->ids2 hold one
+ * 64-bit id per row each, in the batch's row order, living where b->mem says; they carry no nulls.  All arithmetic is f64 on the
+ * inputs' values, for f32 batches too.
+ * Categories and components.  C1 and C2 are the numbers of distinct ids of each column among F_g (a category with one fitted row
+ * counts).  M is the number of connected components of the bipartite graph whose vertices are the categories and whose edges are the
+ * fitted rows.  M is exact: the labels are propagated until nothing changes, whatever max_iter says.
+ * Demeaning one column v (y and each of the k = n_features user columns, each on its own; never a ones column).  Start from v0, the
+ * values the fit sees under the policy.  One sweep does two steps: m1_c = sum_{i in c} w_i v_i / W1_c for every id-1 category, then
+ * v_i -= m1_c1(i); on the updated v, m2_d = sum_{i in d} w_i v_i / W2_d for every id-2 category, then v_i -= m2_c2(i).  The iteration
+ * stops after the first sweep with max(max_c |m1_c|, max_d |m2_d|) <= tol s, where s = sqrt(sum w_i v0_i^2 / sum w_i); otherwise after
+ * max_iter sweeps.  At least one sweep is made.  The column's accumulated means are a1_c(v) = the sum of m1_c over the sweeps, a2_d(v)
+ * likewise.  x~_i = sqrt(w_i) v_i(final), y~ likewise.
+ * Solve.  A = X~'X~ = L L' by Cholesky with the pivot rule of pols_least_squares_absorb unchanged: pivot j fails when
+ * d_j <= 16 k eps T_jj, T_jj = sum w_i x_ij^2 the RAW second moment.  b = A^-1 X~'y~; e~ = y~ - X~ b; RSS = sum e~_i^2 over the rows.
+ * Inference.  df = n - k - (C1 + C2 - M), sigma2 = RSS / df.  POLS_COV_NONROBUST: V = sigma2 A^-1, p two-sided Student-t(df).
+ * POLS_COV_CLUSTER (clustered on ids, the first column): s_c = sum_{i in c} e~_i x~_i over the id-1 categories,
+ * V = q A^-1 (sum_c s_c s_c') A^-1 with q = C1 / (C1 - 1) (n - 1) / (n - k - 1 - (C2 - M)) -- the nested convention of
+ * pols_least_squares_absorb with the second effect charged like regressors --, p two-sided Student-t(C1 - 1); NaN when C1 < 2 or the
+ * denominator is <= 0.  The intercept's se / t / p are NaN.  r2_within = 1 - RSS / sum y~_i^2, r2 = 1 - RSS / sum w_i (y_i - ybar_w)^2.
+ * Effects and rows.  a1_c = a1_c(y) - sum_j b_j a1_c(x_j), a2_d likewise.  pred_i = x_i'b + a1_c1(i) + a2_c2(i) for every row,
+ * resid = y - pred.  With add_intercept coef[kt - 1] = c0 = sum_{F_g} w_i (a1 + a2)_i / sum w_i, and fe1_i, fe2_i are each centred on
+ * their own weighted mean over F_g, so that c0 + fe1 + fe2 = a1 + a2; without it fe1 = a1 and fe2 = a2.  Only the sum a1 + a2 is
+ * identified: the split between the two is whatever the iteration started from zero gives (inside every component a constant can move
+ * from one effect to the other).  A row outside F_g gets NaN in pred / resid / fe1 / fe2 when either of its ids has no fitted row in
+ * the group, or when its two categories lie in different components; otherwise it is predicted.
+ * out->status, in this precedence: POLS_GROUP_EMPTY for n = 0 (zero coefficients, everything else NaN); POLS_GROUP_BAD_DOF for
+ * df <= 0 (everything NaN); POLS_GROUP_FALLBACK with everything NaN when a pivot fails or a moment is not finite;
+ * POLS_GROUP_NOT_CONVERGED when a column made max_iter sweeps without the stop rule firing (the result is still returned, as pols_rlm
+ * and pols_glm do); otherwise POLS_GROUP_OK.  n_iter[g] is the largest sweep count among the k + 1 columns.  n_obs, n_categories,
+ * n_categories2, n_components and n_iter are written in every case.  At the default tol a column that is an exact sum
+ * f(id1) + g(id2) is demeaned to rounding noise and flagged by the pivot rule; with a loose tol what the iteration leaves may pass it.
+ * Determinism as pols_least_squares_absorb: no floating-point atomics; a category's rows are summed by position (frame order inside an
+ * id) in batches of 64 whose terms meet in a fixed tree, the batches in position order; reruns are bit-identical, and HOST and DEVICE
+ * batches agree bit for bit.  A group's result depends on nothing outside the group.  Groups may have any length: one workgroup per
+ * (group, column) iterates with its column in LDS when the group has at most 11 684 rows (7 435 when the store carries weights: a
+ * weights column, or a policy that can take rows out of the fit) -- 14 n + 4 | 22 n + 4 bytes of the 163 584 a launch may ask for --
+ * and on a global f64 scratch of (k + 1) x n_rows otherwise, with the same bits on a group that fits both.  The option
+ * POLS_ABSORB2_ROUTE=global sends every group to the scratch form (resident / unset: LDS wherever the group fits).  The call
+ * synchronises the stream three times (the two order probes, the category counts).
+ * From pols_ols_params only null_policy is read.  POLS_ERR_INVALID: NULL ids or ids2; max_iter < 1; a tol that is not positive and
+ * finite; n_features < 1; alpha != 0, positive, or has_l1_ratio with l1_ratio > 0; a cov_type other than the two named; a validity
+ * mask without a drop-family policy; on the device, a pred / resid / fe1 / fe2 that is not 16-byte aligned.  POLS_ERR_UNSUPPORTED:
+ * kt > 31 or n_rows >= 2^31.  There is no Arrow twin and no sharded entry.
+ * Not built: three or more absorbed ids; acceleration of the iteration (conjugate gradient, symmetric Kaczmarz); a multi-workgroup
+ * form for one very long column; HC / HAC and two-way cluster covariance on absorbed fits; Arrow and sharded twins. */
+typedef struct pols_absorb2_params {
+    const int64_t *ids;         /* first id per row (the clustering of POLS_COV_CLUSTER), where b->mem says */
+    const int64_t *ids2;        /* second id per row                                                         */
+    int32_t cov_type;           /* POLS_COV_NONROBUST or POLS_COV_CLUSTER                                    */
+    int32_t max_iter;           /* sweeps per column at the most, >= 1                                       */
+    double  tol;                /* stop rule, relative to the column's root mean square; positive and finite */
+} pols_absorb2_params;
+
+/* ids = NULL, ids2 = NULL, cov_type = POLS_COV_NONROBUST, max_iter = 10000, tol = 1e-10 */
+void pols_absorb2_params_default(pols_absorb2_params *q);
+
+typedef struct pols_absorb2_out {
+    double  *se;                /* n_groups x kt                                 */
+    double  *t_values;          /* n_groups x kt                                 */
+    double  *p_values;          /* n_groups x kt                                 */
+    double  *sigma2;            /* n_groups: RSS / df                            */
+    double  *r2_within;         /* n_groups                                      */
+    double  *r2;                /* n_groups                                      */
+    void    *fe1;               /* n_rows, batch dtype: the row's first effect   */
+    void    *fe2;               /* n_rows, batch dtype: the row's second effect  */
+    int64_t *n_obs;             /* n_groups: fitted rows                         */
+    int64_t *n_categories;      /* n_groups: C1                                  */
+    int64_t *n_categories2;     /* n_groups: C2                                  */
+    int64_t *n_components;      /* n_groups: M                                   */
+    int32_t *n_iter;            /* n_groups: most sweeps among the k + 1 columns */
+} pols_absorb2_out;             /* all live where b->mem says; any may be NULL */
+
+int pols_least_squares_absorb2(pols_ctx *ctx, const pols_batch *b, const pols_ols_params *p, const pols_absorb2_params *q,
+                               pols_out *out, const pols_absorb2_out *r);
 
 /* ---- group-key ingestion: `.over(key)` / `group_by(key)` ------------------------------------------------------------
  * The reference's plugin functions never see a key column: Polars partitions the frame on the host and calls them once per

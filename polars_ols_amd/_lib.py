@@ -189,6 +189,19 @@ class AbsorbOut(C.Structure):         # pols_absorb_out
     _fields_ = [(n, C.c_void_p) for n in ABSORB_FIELDS]
 
 
+class Absorb2Params(C.Structure):     # pols_absorb2_params
+    _fields_ = [("ids", C.c_void_p), ("ids2", C.c_void_p), ("cov_type", C.c_int32), ("max_iter", C.c_int32), ("tol", C.c_double)]
+
+
+# pols_absorb2_out, in the struct's order
+ABSORB2_FIELDS = ("se", "t_values", "p_values", "sigma2", "r2_within", "r2", "fe1", "fe2", "n_obs", "n_categories", "n_categories2",
+                  "n_components", "n_iter")
+
+
+class Absorb2Out(C.Structure):        # pols_absorb2_out
+    _fields_ = [(n, C.c_void_p) for n in ABSORB2_FIELDS]
+
+
 EXPORTS = [
     "pols_device_count", "pols_version", "pols_last_error", "pols_create", "pols_destroy", "pols_set_stream",
     "pols_use_private_stream",
@@ -212,6 +225,7 @@ EXPORTS = [
     "pols_glm_params_default", "pols_glm",
     "pols_iv_params_default", "pols_iv2sls",
     "pols_absorb_params_default", "pols_least_squares_absorb",
+    "pols_absorb2_params_default", "pols_least_squares_absorb2",
 ]
 # measurement aids (include/pols_mi355x_debug.h): not part of the reference interface
 DEBUG_EXPORTS = ["pols_timing_enable", "pols_timing_collect", "pols_last_kernel_name", "pols_stream_probe", "pols_stream_probe_ex",
@@ -292,6 +306,9 @@ def lib() -> C.CDLL:
         L.pols_absorb_params_default.argtypes, L.pols_absorb_params_default.restype = [C.POINTER(AbsorbParams)], None
         L.pols_least_squares_absorb.argtypes = [C.c_void_p, C.POINTER(Batch), C.POINTER(OlsParams), C.POINTER(AbsorbParams), C.POINTER(Out),
                                                 C.POINTER(AbsorbOut)]
+        L.pols_absorb2_params_default.argtypes, L.pols_absorb2_params_default.restype = [C.POINTER(Absorb2Params)], None
+        L.pols_least_squares_absorb2.argtypes = [C.c_void_p, C.POINTER(Batch), C.POINTER(OlsParams), C.POINTER(Absorb2Params), C.POINTER(Out),
+                                                 C.POINTER(Absorb2Out)]
         L.pols_enet_cv_params_default.argtypes, L.pols_enet_cv_params_default.restype = [C.POINTER(EnetCvParams)], None
         L.pols_elastic_net_cv.argtypes = [C.c_void_p, C.POINTER(Batch), C.POINTER(OlsParams), C.POINTER(EnetCvParams), C.POINTER(Out),
                                           C.POINTER(EnetCvOut)]

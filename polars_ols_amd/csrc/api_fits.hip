@@ -1,5 +1,5 @@
 // api_fits.hip -- the per-group fit entries of the C-ABI: pols_ridge_cv (K10), pols_rlm (K11), pols_elastic_net_cv (K12), pols_glm
-// (K13), pols_iv2sls (K14), pols_least_squares_absorb (K16).  Host code only.  What they share is written once, up front: the opening checks and the staging
+// (K13), pols_iv2sls (K14), pols_least_squares_absorb (K16), pols_least_squares_absorb2 (K17).  Host code only.  What they share is written once, up front: the opening checks and the staging
 // (FitCall), the common fields of the kernel argument structs (fit_frame, fit_segments), the entry's own outputs (ExtraOut), K10's
 // prediction pass (fit_predict) and extra input columns (stage_extra_columns).  DESIGN.md, "Adding a per-group fit entry".
 #include <algorithm>
@@ -13,6 +13,7 @@
 #include "k13_glm.hpp"
 #include "k14_iv.hpp"
 #include "k16_absorb.hpp"
+#include "k17_absorb2.hpp"
 #include "k7c_cluster.hpp"
 
 using namespace pols;
@@ -550,6 +551,189 @@ int pols_least_squares_absorb(pols_ctx *ctx, const pols_batch *b, const pols_ols
         if ((rc = k16_finish_launch(ctx, a))) return rc;
     }
     if ((rc = k16_predict_launch(ctx, b->dtype, a))) return rc;
+    return xo.home(ctx, b, o, fc);
+}
+
+void pols_absorb2_params_default(pols_absorb2_params *q) {
+    if (!q) return;
+    q->ids = nullptr;
+    q->ids2 = nullptr;
+    q->cov_type = POLS_COV_NONROBUST;
+    q->max_iter = 10000;
+    q->tol = 1e-10;
+}
+
+// K17 (k17_absorb2.hip): K7c's order builder and K16's category launches on each id column, the stage launch (the rows in id-1 order,
+// perm2), the demean launch -- resident, global, or one of each over a group list when the frame has groups on both sides of the
+// resident capacity --, the moments of the demeaned columns, the per-group solve, the residual pass per id-1 category and the per-group
+// finish (only when a wanted output needs a residual), then the prediction pass.
+int pols_least_squares_absorb2(pols_ctx *ctx, const pols_batch *b, const pols_ols_params *p, const pols_absorb2_params *q, pols_out *o,
+                               const pols_absorb2_out *ro) {
+    FitCall fc;
+    int rc = fit_check(ctx, b, p, q, o, "absorb2", K17_KMAX, &fc);
+    if (rc) return rc;
+    if (p->alpha != 0.0 || p->positive || (p->has_l1_ratio && p->l1_ratio > 0.0))
+        return fail(POLS_ERR_INVALID, "absorb2: alpha / positive / l1_ratio do not apply (penalised absorbed fits are not built)");
+    if (b->n_features < 1) return fail(POLS_ERR_INVALID, "absorb2: no feature column");
+    if (!q->ids || !q->ids2) return fail(POLS_ERR_INVALID, "absorb2: ids / ids2 is NULL");
+    if (q->cov_type != POLS_COV_NONROBUST && q->cov_type != POLS_COV_CLUSTER)
+        return fail(POLS_ERR_INVALID, "absorb2: cov_type %d is not NONROBUST / CLUSTER", q->cov_type);
+    if (q->max_iter < 1) return fail(POLS_ERR_INVALID, "absorb2: max_iter %d < 1", q->max_iter);
+    if (!(q->tol > 0.0) || !std::isfinite(q->tol)) return fail(POLS_ERR_INVALID, "absorb2: tol %g is not positive and finite", q->tol);
+    if (b->n_rows >= ((int64_t)1 << 31)) return fail(POLS_ERR_UNSUPPORTED, "absorb2: %lld rows >= 2^31", (long long)b->n_rows);
+    if (b->n_groups == 0) return POLS_OK;
+    ro = or_none(ro);
+    // (pred / resid / fe1 are written 16 bytes at a time; fe2 goes out row by row and is held to the same rule as its sibling)
+    if (!fc.host && !(aligned16(ro->fe1) && aligned16(ro->fe2) && aligned16(o->pred) && aligned16(o->resid)))
+        return fail(POLS_ERR_INVALID, "device columns must be 16-byte aligned");
+    const int k = b->n_features, kc = fc.kt;
+    const size_t G = fc.G, N = (size_t)b->n_rows;
+    const bool cluster = q->cov_type == POLS_COV_CLUSTER;
+    const bool need_rows = ro->se || ro->t_values || ro->p_values || ro->sigma2 || ro->r2_within || ro->r2;
+    if ((rc = fit_stage(ctx, b, o, &fc))) return rc;
+    Absorb2Args a = {};
+    fit_frame(a, b, fc);
+    a.kt = k + 1; a.icpt = b->add_intercept ? 1 : 0; a.cluster = cluster ? 1 : 0;
+    a.has_w = (fc.st.w || (fc.pol != POLS_NULL_IGNORE && fc.pol != POLS_NULL_ZERO)) ? 1 : 0;
+    a.max_iter = q->max_iter; a.tol = q->tol;
+    a.pred = fc.st.pred; a.resid = fc.st.resid;
+    const int64_t *d_ids[2] = {q->ids, q->ids2};
+    const size_t idb = round256(sizeof(int64_t) * N + 8);
+    if (fc.host) {
+        void *wi = nullptr;
+        if ((rc = ensure_scratch(ctx, Work::Absorb2Ids, 2 * idb, &wi))) return rc;
+        for (int w = 0; w < 2; ++w) {
+            char *dst = static_cast<char *>(wi) + idb * (size_t)w;
+            if (N > 0) POLS_HIP(hipMemcpyAsync(dst, w ? q->ids2 : q->ids, sizeof(int64_t) * N, hipMemcpyHostToDevice, ctx->stream));
+            d_ids[w] = reinterpret_cast<const int64_t *>(dst);
+        }
+    }
+    SegTables sg;
+    if ((rc = ensure_segments(ctx, b, fc.max_rows, 0, &sg))) return rc;
+    fit_segments(a, sg);
+    const size_t items = sg.n_seg > 0 ? (size_t)sg.n_seg : G;
+    // which groups the resident store takes: by their rows alone (k17_resident_bytes lays the start tables out for C = n)
+    const int64_t cap = ctx->opt.absorb2_route == 1 ? -1 : k17_resident_rows(a.has_w != 0);
+    std::vector<int32_t> lists;                                    // the resident groups, then the others
+    int64_t n_res = 0, max_res = 0, max_glb = 0;
+    for (size_t g = 0; g < G; ++g) {
+        const int64_t rows = b->group_offsets[g + 1] - b->group_offsets[g];
+        if (rows <= cap) { ++n_res; max_res = std::max(max_res, rows); } else max_glb = std::max(max_glb, rows);
+    }
+    const bool mixed = n_res > 0 && (size_t)n_res < G;
+    if (mixed) {
+        lists.resize(G);
+        size_t ir = 0, ig = (size_t)n_res;
+        for (size_t g = 0; g < G; ++g)
+            lists[(b->group_offsets[g + 1] - b->group_offsets[g] <= cap) ? ir++ : ig++] = (int32_t)g;
+    }
+    // the orders: K7c's builder keeps one order at a time, so the first is copied before the builder runs again
+    const size_t ib = round256(sizeof(uint32_t) * N + 4), listb = mixed ? round256(sizeof(int32_t) * G) : 0;
+    void *wo = nullptr;
+    if ((rc = ensure_scratch(ctx, Work::Absorb2Order, 3 * ib + listb, &wo))) return rc;
+    uint32_t *ord1 = static_cast<uint32_t *>(wo);
+    a.pos1 = reinterpret_cast<uint32_t *>(static_cast<char *>(wo) + ib);
+    a.perm2 = reinterpret_cast<uint32_t *>(static_cast<char *>(wo) + 2 * ib);
+    int32_t *d_list = reinterpret_cast<int32_t *>(static_cast<char *>(wo) + 3 * ib);
+    if (mixed && (rc = upload_small(ctx, d_list, lists.data(), sizeof(int32_t) * G))) return rc;
+    if ((rc = k7c_order_launch(ctx, d_ids[0], fc.d_offs, b->n_groups, b->n_rows, &a.order1))) return rc;
+    if (a.order1) {
+        POLS_HIP(hipMemcpyAsync(ord1, a.order1, sizeof(uint32_t) * N, hipMemcpyDeviceToDevice, ctx->stream));
+        a.order1 = ord1;
+    }
+    if ((rc = k7c_order_launch(ctx, d_ids[1], fc.d_offs, b->n_groups, b->n_rows, &a.order2))) return rc;
+    // the categories of each id column: K16's launches on an AbsorbArgs that names the column, its order and its tables
+    const size_t cntb = round256(sizeof(int32_t) * items), firstb = round256(sizeof(int64_t) * (items + 1)), idxb = round256(sizeof(int32_t) * N + 4);
+    void *wx = nullptr, *wc = nullptr, *wm = nullptr, *wl = nullptr;
+    if ((rc = ensure_scratch(ctx, Work::Absorb2Index, 2 * (cntb + firstb + idxb), &wx))) return rc;
+    AbsorbArgs way[2] = {};
+    for (int w = 0; w < 2; ++w) {
+        AbsorbArgs &c = way[w];
+        char *base = static_cast<char *>(wx) + (cntb + firstb + idxb) * (size_t)w;
+        c.offs = fc.d_offs; c.n_groups = b->n_groups; c.n_rows = b->n_rows;
+        fit_segments(c, sg);
+        c.ids = d_ids[w]; c.order = w ? a.order2 : a.order1;
+        c.item_cnt = reinterpret_cast<int32_t *>(base);
+        c.item_first = reinterpret_cast<int64_t *>(base + cntb);
+        c.catidx = reinterpret_cast<int32_t *>(base + cntb + firstb);
+        if ((rc = k16_count_launch(ctx, c))) return rc;
+        POLS_HIP(hipMemcpyAsync(&c.n_cats, c.item_first + items, sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
+    }
+    POLS_HIP(hipStreamSynchronize(ctx->stream));                   // the numbers of categories size the tables
+    const size_t nc1 = (size_t)way[0].n_cats, nc2 = (size_t)way[1].n_cats, kz = (size_t)k + 1;
+    const size_t st1b = round256(sizeof(int64_t) * (nc1 + 1)), st2b = round256(sizeof(int64_t) * (nc2 + 1)),
+                 am1b = round256(sizeof(double) * kz * nc1 + 8), am2b = round256(sizeof(double) * kz * nc2 + 8),
+                 d1b = round256(sizeof(double) * nc1 + 8), d2b = round256(sizeof(double) * nc2 + 8),
+                 l1b = round256(sizeof(int32_t) * nc1 + 4), l2b = round256(sizeof(int32_t) * nc2 + 4),
+                 residb = round256(sizeof(double) * nc1 * k17_resid_stride(k, cluster) + 8);
+    if ((rc = ensure_scratch(ctx, Work::Absorb2Cats, st1b + st2b + 2 * (am1b + am2b) + 2 * d1b + 2 * d2b + l1b + l2b + residb, &wc))) return rc;
+    {
+        char *c = static_cast<char *>(wc);
+        way[0].cat_start = reinterpret_cast<int64_t *>(c); c += st1b;
+        way[1].cat_start = reinterpret_cast<int64_t *>(c); c += st2b;
+        a.am1 = reinterpret_cast<double *>(c); c += am1b;
+        a.am2 = reinterpret_cast<double *>(c); c += am2b;
+        a.aw1 = reinterpret_cast<double *>(c); c += am1b;
+        a.aw2 = reinterpret_cast<double *>(c); c += am2b;
+        a.wc1 = reinterpret_cast<double *>(c); c += d1b;
+        a.eff1 = reinterpret_cast<double *>(c); c += d1b;
+        a.wc2 = reinterpret_cast<double *>(c); c += d2b;
+        a.eff2 = reinterpret_cast<double *>(c); c += d2b;
+        a.lab1 = reinterpret_cast<int32_t *>(c); c += l1b;
+        a.lab2 = reinterpret_cast<int32_t *>(c); c += l2b;
+        a.resid_part = reinterpret_cast<double *>(c);
+    }
+    const size_t colsb = round256(sizeof(double) * kz * N + 8), wfb = round256(sizeof(double) * N + 8), labb = round256(sizeof(int32_t) * N + 4),
+                 fitbb = round256(N + 1);
+    if ((rc = ensure_scratch(ctx, Work::Absorb2Cols, colsb + wfb + labb + fitbb, &wl))) return rc;
+    a.cols = static_cast<double *>(wl);
+    a.wfit = reinterpret_cast<double *>(static_cast<char *>(wl) + colsb);
+    a.rowlab = reinterpret_cast<int32_t *>(static_cast<char *>(wl) + colsb + wfb);
+    a.fitb = reinterpret_cast<uint8_t *>(static_cast<char *>(wl) + colsb + wfb + labb);
+    const size_t gramb = round256(sizeof(double) * items * k17_gram_stride(k)), stateb = round256(sizeof(double) * G * k17_state_stride(k)),
+                 colstb = round256(sizeof(double) * G * kz * K17_COLSTAT), grpstb = round256(sizeof(double) * G * K17_GRPSTAT);
+    if ((rc = ensure_scratch(ctx, Work::Absorb2Moments, gramb + stateb + colstb + grpstb, &wm))) return rc;
+    a.gram_part = static_cast<double *>(wm);
+    a.state = reinterpret_cast<double *>(static_cast<char *>(wm) + gramb);
+    a.colstat = reinterpret_cast<double *>(static_cast<char *>(wm) + gramb + stateb);
+    a.grpstat = reinterpret_cast<double *>(static_cast<char *>(wm) + gramb + stateb + colstb);
+    for (int w = 0; w < 2; ++w)
+        if ((rc = k16_index_launch(ctx, way[w]))) return rc;
+    a.first1 = way[0].item_first; a.first2 = way[1].item_first;
+    a.catidx1 = way[0].catidx; a.catidx2 = way[1].catidx;
+    a.start1 = way[0].cat_start; a.start2 = way[1].cat_start;
+    a.n_cats1 = way[0].n_cats; a.n_cats2 = way[1].n_cats;
+    ExtraOut xo;
+    xo.add(ro->se, a.se, sizeof(double) * G * kc);
+    xo.add(ro->t_values, a.t_values, sizeof(double) * G * kc);
+    xo.add(ro->p_values, a.p_values, sizeof(double) * G * kc);
+    xo.add(ro->sigma2, a.sigma2, sizeof(double) * G);
+    xo.add(ro->r2_within, a.r2_within, sizeof(double) * G);
+    xo.add(ro->r2, a.r2, sizeof(double) * G);
+    xo.add(ro->fe1, a.fe1, fc.sz * N);
+    xo.add(ro->fe2, a.fe2, fc.sz * N);
+    xo.add(ro->n_obs, a.n_obs, sizeof(int64_t) * G);
+    xo.add(ro->n_categories, a.n_categories, sizeof(int64_t) * G);
+    xo.add(ro->n_categories2, a.n_categories2, sizeof(int64_t) * G);
+    xo.add(ro->n_components, a.n_components, sizeof(int64_t) * G);
+    xo.add(ro->n_iter, a.n_iter, sizeof(int32_t) * G);
+    if ((rc = xo.place(ctx, fc, Work::Absorb2Out))) return rc;
+    ctx->last_kernel = mixed ? "k17_absorb2_mixed" : (n_res > 0 ? "k17_absorb2_resident" : "k17_absorb2_global");
+    if ((rc = k17_stage_launch(ctx, b->dtype, a))) return rc;
+    if (mixed) {
+        Absorb2Args part = a;
+        part.list = d_list; part.n_list = n_res;
+        if ((rc = k17_demean_launch(ctx, part, true, max_res))) return rc;
+        part.list = d_list + n_res; part.n_list = (int64_t)G - n_res;
+        if ((rc = k17_demean_launch(ctx, part, false, max_glb))) return rc;
+    } else if ((rc = k17_demean_launch(ctx, a, n_res > 0, n_res > 0 ? max_res : max_glb))) return rc;
+    if ((rc = k17_gram_launch(ctx, a))) return rc;
+    if ((rc = k17_solve_launch(ctx, a))) return rc;
+    if (need_rows) {
+        if ((rc = k17_resid_launch(ctx, a))) return rc;
+        if ((rc = k17_finish_launch(ctx, a))) return rc;
+    }
+    if ((rc = k17_predict_launch(ctx, b->dtype, a))) return rc;
     return xo.home(ctx, b, o, fc);
 }
 

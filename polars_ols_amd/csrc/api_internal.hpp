@@ -10,7 +10,7 @@
 //                   function per route, pols_recursive_least_squares, pols_rolling_least_squares and their parameter defaults.  Nothing of it
 //                   is declared here: no other translation unit calls into it (it uses check_ctx / check_batch / Staged / stage_inputs /
 //                   unstage_outputs / aligned16 from below and fail / grow / ensure_scratch / upload_small / upload_offsets from common.hpp)
-//   api_fits.hip    the K10-K14 and K16 fit entries
+//   api_fits.hip    the K10-K14, K16 and K17 fit entries
 #pragma once
 
 #include <vector>

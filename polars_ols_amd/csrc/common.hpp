@@ -99,6 +99,13 @@ enum class Work : int {
     AbsorbCats,     // absorbed effect (K16): first position of every category, the table (n_c -> a_c, W_c, means), RSS / z^2 per category
     AbsorbMoments,  // absorbed effect (K16): demeaned cross-moment partials per segment / group, then n, C, df, c0, b, A^-1 per group
     AbsorbOut,      // absorbed effect (K16): the pols_absorb_out fields of a HOST batch before they go home
+    Absorb2Ids,     // two absorbed effects (K17): the two id columns of a HOST batch
+    Absorb2Order,   // two absorbed effects (K17): the id-1 order (a copy: K7c's builder runs again for id 2), row -> id-1 position, perm2, the group list of a mixed frame
+    Absorb2Index,   // two absorbed effects (K17): K16's run starts / prefix / category index of every row, once per id column
+    Absorb2Cats,    // two absorbed effects (K17): per id column the first positions, accumulated means, W_c, effects, component labels; RSS / z^2 per id-1 category
+    Absorb2Cols,    // two absorbed effects (K17): the column scratch (k + 1) x n_rows in id-1 order (f64), the rows' weights, labels and fit bytes
+    Absorb2Moments, // two absorbed effects (K17): Gram partials per segment / group, the groups' state, the per-column and per-group records of the demean launch
+    Absorb2Out,     // two absorbed effects (K17): the pols_absorb2_out fields of a HOST batch before they go home
     Count
 };
 
@@ -162,7 +169,8 @@ struct Options {
     int k1_wg = 0;                // POLS_K1_WG          8-column team kernels: 2 / 4 = 512- / 1 024-thread workgroups (2 / 4 times the groups per workgroup, A/B)
     int rlm_engine = 0;           // POLS_RLM_ENGINE     0 auto (groups that fit the LDS stay resident), 1 "stream" (K11's streamed form for every group)
     int glm_engine = 0;           // POLS_GLM_ENGINE     0 auto (groups that fit the LDS stay resident), 1 "split" (K13's split form for every group)
-    int k1_xcd = 0;               // POLS_K1_XCD         resident K1 kernels: 1 = XCD-contiguous workgroup -> group map (each XCD walks one eighth of the frame)
+    int absorb2_route = 0;        // POLS_ABSORB2_ROUTE  0 auto / "resident" (groups that fit the LDS store stay resident), 1 "global" (K17's scratch form for every group)
+    int k1_xcd = 0;               // POLS_K1_XCD      resident K1 kernels: 1 = XCD-contiguous workgroup -> group map (each XCD walks one eighth of the frame)
 };
 void options_from_env(Options &o);
 // key: the variable's name with or without the POLS_ prefix (case-insensitive); value NULL = back to the default.  False = unknown key.

@@ -30,8 +30,7 @@
 //   predict  per item, fit_predict_rows: pred = x_i'b + a_c, resid = y - pred, fe = a_c - c0 for every row of the frame.
 #include "k16_absorb.hpp"
 #include "fit_launch.hpp"
-#include "fit_solve.inl"
-#include "k7_stats.hpp"
+#include "k16_absorb.inl"
 
 #include <algorithm>
 
@@ -43,8 +42,6 @@ __device__ __forceinline__ bool k16_starts(const AbsorbArgs &a, int64_t gs, int6
     if (i == gs) return true;
     return a.ids[k16_row(a, i)] != a.ids[k16_row(a, i - 1)];
 }
-// the sum over the wave in every lane, in the fixed order of the DPP steps; all 64 lanes active
-__device__ __forceinline__ double k16_wave_sum(double v) { return readlane63(wave_sum_row3(v)); }
 // the item of a workgroup of the count / index launches (no tile grid)
 __device__ __forceinline__ void k16_item(const AbsorbArgs &a, int64_t &g, int64_t &gs, int64_t &s, int64_t &e) {
     const int64_t sgi = blockIdx.x;
@@ -53,22 +50,6 @@ __device__ __forceinline__ void k16_item(const AbsorbArgs &a, int64_t &g, int64_
     s = a.seg_offs ? a.seg_offs[sgi] : gs;
     e = a.seg_offs ? a.seg_offs[sgi + 1] : a.offs[g + 1];
 }
-// the column pointers into LDS (a run-time index into the kernel arguments would put them in scratch)
-__device__ __forceinline__ void k16_columns(const AbsorbArgs &a, const void **xp, const int tid) {
-#pragma unroll
-    for (int j = 0; j < POLS_MAX_FEATURES; ++j)
-        if (tid == j && j < a.k_user) xp[j] = a.x[j];
-}
-// the group of position p: the last g with offs[g] <= p (the groups before it that start there are empty)
-__device__ __forceinline__ int64_t k16_group_of(const int64_t *offs, int64_t n_groups, int64_t p) {
-    int64_t lo = 0, hi = n_groups;
-    while (hi - lo > 1) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (offs[mid] <= p) lo = mid; else hi = mid;
-    }
-    return lo;
-}
-
 // ---------------------------------------------------------------- count, scan, index
 __global__ void __launch_bounds__(256) k16_count_kernel(const AbsorbArgs a) {
     __shared__ int red[4];
@@ -291,53 +272,8 @@ __global__ void __launch_bounds__(64) k16_solve_kernel(const AbsorbArgs a) {
     const double yy = Gs[tri_index(k, k, nz)], tss = yy + k16_wave_sum(lB);
     const double df = n - (double)k - C;
     bool ok = finite && n > 0.0 && df > 0.0;
-    if (ok) {
-        for (int en = lane; en < ne; en += 64) {
-            int i, j;
-            tri_unpack(en, nz, i, j);
-            const double v = Gs[en];
-            if (j == k) { if (i < k) rhs[i] = v; }
-            else { A[i * LD + j] = v; A[j * LD + i] = v; }
-        }
-        if (lane < k) d0[lane] = Gs[ne + lane];                    // the pivots are held against the RAW second moments
-        fit_wave_sync();
-        ok = fit_chol_factor(A, d0, k, lane);
-    }
-    if (ok) {
-        for (int j = 0; j < k; ++j) {                              // L z = g
-            const double z = rhs[j] / A[j * LD + j];
-            fit_wave_sync();
-            if (lane == j) rhs[j] = z;
-            else if (lane > j && lane < k) rhs[lane] -= A[lane * LD + j] * z;
-            fit_wave_sync();
-        }
-        for (int j = k - 1; j >= 0; --j) {                         // L'b = z
-            const double z = rhs[j] / A[j * LD + j];
-            fit_wave_sync();
-            if (lane == j) rhs[j] = z;
-            else if (lane < j) rhs[lane] -= A[j * LD + lane] * z;
-            fit_wave_sync();
-        }
-        const double v = lane < k ? rhs[lane] : 0.0;
-        ok = __ballot(!(fabs(v) <= FIT_DBL_MAX)) == 0;
-    }
     double *st = a.state + (size_t)g * k16_state_stride(k);
-    if (ok) {
-        if (lane < k) {                                            // column `lane` of the inverse of the factor
-            for (int j = 0; j < k; ++j) {
-                double s = j == lane ? 1.0 : 0.0;
-                for (int i = lane; i < j; ++i) s = fma(-A[j * LD + i], Ri[i * k + lane], s);
-                Ri[j * k + lane] = j < lane ? 0.0 : s / A[j * LD + j];
-            }
-        }
-        fit_wave_sync();
-        for (int p = lane; p < k * k; p += 64) {                   // A^-1
-            const int i = p / k, j = p - i * k;
-            double v = 0.0;
-            for (int l = i > j ? i : j; l < k; ++l) v = fma(Ri[l * k + i], Ri[l * k + j], v);
-            st[8 + k + p] = v;
-        }
-    }
+    ok = k16_solve_core(ok, Gs, Gs + ne, A, d0, rhs, Ri, st + 8 + k, k, lane);
     // the effects a_c = ybar_c - xbar_c'b into the table (NaN for a category without a fitted row, and for a group without a fit)
     double lA = 0.0;
     for (int64_t c = c0i + lane; c < c1i; c += 64) {
@@ -479,11 +415,7 @@ __global__ void __launch_bounds__(64) k16_finish_kernel(const AbsorbArgs a) {
         } else if (lane < k) {
             v = sigma2 * st[8 + k + lane * k + lane];
         }
-        if (lane < k && v >= 0.0) {
-            se = sqrt(v);
-            tv = st[8 + lane] / se;
-            pv = (tv != tv) ? q : k7_betai(0.5 * dfp, 0.5, dfp / (dfp + tv * tv));
-        }
+        if (lane < k) k16_se_t_p(v, st[8 + lane], dfp, se, tv, pv);
     }
     if (lane < kc) {                                               // (the intercept's entries stay NaN)
         if (a.se) a.se[(size_t)g * kc + lane] = se;

@@ -455,6 +455,47 @@ class Engine:
                                want, y, x_cols, offsets, dict(weights=weights, valid=valid, add_intercept=add_intercept, null_policy=null_policy, out=out),
                                extra=bring_ids)
 
+    def absorb2(self, y, x_cols: Sequence, ids, ids2, offsets, *, cov_type: str = "nonrobust", max_iter: int = 10_000, tol: float = 1e-10,
+                want: Sequence[str] = ("coef", "status", "se", "n_obs", "n_categories", "n_categories2", "n_components", "n_iter"),
+                weights=None, valid=None, add_intercept: bool = False, null_policy: str = "ignore", out: Optional[Dict] = None) -> Dict:
+        """Regression that absorbs two categorical effects inside every group -- two-way fixed effects, ``reghdfe y x, absorb(firm
+        year)`` -- for every group in one call, by alternating projections on the device (pols_least_squares_absorb2; the definitions
+        and edge rules are in include/pols_mi355x.h).  ``ids`` / ``ids2``: one integer id per row each, in the rows' order.
+        ``cov_type``: "nonrobust" or "cluster" (clustered on ``ids``).  ``max_iter`` / ``tol``: the sweeps per column at the most and
+        the stop rule (status 3 = a column made ``max_iter`` sweeps; the result is still returned).  ``want``: any of ``coef`` (the
+        slopes, then the mean effect c0 with ``add_intercept``) ``pred resid status``, ``se t_values p_values`` [n_groups, k, f64],
+        ``sigma2 r2_within r2`` [n_groups, f64], ``fe1 fe2`` [n_rows, batch dtype, the row's two effects], ``n_obs n_categories
+        n_categories2 n_components`` [n_groups, int64] and ``n_iter`` [n_groups, int32].  Arrays are numpy or torch and live where
+        the inputs live."""
+        x_cols = list(x_cols)
+        q = _absorb2_params(self._lib, len(x_cols), cov_type, add_intercept, max_iter, tol)
+
+        def bring_ids(b, like, dev):
+            cols = []
+            for name, col in (("ids", ids), ("ids2", ids2)):
+                if col is None:
+                    raise ValueError(f"absorb2: '{name}' is required")
+                if dev:
+                    col = torch.as_tensor(col, device=like.device).to(torch.int64).contiguous()
+                elif _is_torch(col):
+                    col = np.ascontiguousarray(col.cpu().numpy(), dtype=np.int64)
+                else:
+                    col = np.ascontiguousarray(col, dtype=np.int64)
+                if tuple(col.shape) != (b.n_rows,):
+                    raise ValueError(f"absorb2: {tuple(col.shape)} {name} for {b.n_rows} rows")
+                cols.append(col)
+            q.ids, q.ids2 = self._ptr(cols[0]), self._ptr(cols[1])
+            return cols
+
+        return self._fit_entry("absorb2", "pols_least_squares_absorb2", L.ABSORB2_FIELDS, L.Absorb2Out, q,
+                               lambda G, N, kt: {"se": ((G, kt), "f64"), "t_values": ((G, kt), "f64"), "p_values": ((G, kt), "f64"),
+                                                 "sigma2": ((G,), "f64"), "r2_within": ((G,), "f64"), "r2": ((G,), "f64"),
+                                                 "fe1": ((N,), "batch"), "fe2": ((N,), "batch"), "n_obs": ((G,), "i64"),
+                                                 "n_categories": ((G,), "i64"), "n_categories2": ((G,), "i64"),
+                                                 "n_components": ((G,), "i64"), "n_iter": ((G,), "i32")},
+                               want, y, x_cols, offsets, dict(weights=weights, valid=valid, add_intercept=add_intercept, null_policy=null_policy, out=out),
+                               extra=bring_ids)
+
     def elastic_net_cv(self, y, x_cols: Sequence, offsets, alphas=None, *, n_alphas: int = 100, eps: float = 1e-3, l1_ratio: float = 0.5,
                        n_folds: int = 5, max_iter: int = 1000, tol: float = 1e-5, positive: bool = False,
                        want: Sequence[str] = ("coef", "status", "alpha", "alpha_index", "score"), weights=None, valid=None,
@@ -789,6 +830,20 @@ def _absorb_params(lib, n_features, cov_type, add_intercept) -> "L.AbsorbParams"
     if lib is not None:
         lib.pols_absorb_params_default(C.byref(q))
     q.ids, q.cov_type = None, L.COV_TYPES[cov_type]
+    return q
+
+
+def _absorb2_params(lib, n_features, cov_type, add_intercept, max_iter, tol) -> "L.Absorb2Params":
+    """the argument checks of Engine.absorb2 / the two-way path of compute_absorbed_least_squares (``lib`` None: check only)"""
+    _absorb_params(None, n_features, cov_type, add_intercept)
+    if isinstance(max_iter, bool) or int(max_iter) != max_iter or max_iter < 1:
+        raise ValueError(f"absorb: 'max_iter' must be an integer >= 1, got {max_iter!r}")
+    if not (isinstance(tol, (int, float)) and not isinstance(tol, bool) and 0.0 < float(tol) < float("inf")):
+        raise ValueError(f"absorb: 'tol' must be positive and finite, got {tol!r}")
+    q = L.Absorb2Params()
+    if lib is not None:
+        lib.pols_absorb2_params_default(C.byref(q))
+    q.ids, q.ids2, q.cov_type, q.max_iter, q.tol = None, None, L.COV_TYPES[cov_type], int(max_iter), float(tol)
     return q
 
 

@@ -26,7 +26,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import PolsPanic
-from .engine import Engine, Layout, _absorb_params, _enet_cv_params, _is_torch, _glm_params, _iv_params, _ridge_cv_grid, _rlm_params, default_engine
+from .engine import Engine, Layout, _absorb_params, _absorb2_params, _enet_cv_params, _is_torch, _glm_params, _iv_params, _ridge_cv_grid, _rlm_params, default_engine
 
 try:
     import torch
@@ -601,12 +601,16 @@ class AbsorbedOLS(dict):
     """mode="statistics" of an absorbed-effect fit (pols_least_squares_absorb; the definitions are in include/pols_mi355x.h): per
     group ``coefficients standard_errors t_values p_values`` [G, k] (``feature_names``; with an intercept the last coefficient is the
     mean effect c0 and its standard error / t / p are NaN), ``sigma2 r2_within r2 n_obs n_categories status`` [G]; ``keys`` holds the
-    group keys of an ``.over`` (None for a whole-frame fit, where G == 1)."""
+    group keys of an ``.over`` (None for a whole-frame fit, where G == 1).  A two-way fit (pols_least_squares_absorb2) also carries
+    ``n_categories2 n_components n_iter`` [G]; a one-way fit has no such keys."""
 
     def __init__(self, names, out, keys, cov_type):
         super().__init__(feature_names=list(names), coefficients=out["coef"], standard_errors=out["se"], t_values=out["t_values"],
                          p_values=out["p_values"], sigma2=out["sigma2"], r2_within=out["r2_within"], r2=out["r2"], n_obs=out["n_obs"],
                          n_categories=out["n_categories"], status=out["status"], keys=keys, cov_type=cov_type)
+        for key in ("n_categories2", "n_components", "n_iter"):    # (a two-way fit only: the one-way object keeps its keys)
+            if key in out:
+                self[key] = out[key]
         self.keys_ = keys
 
 
@@ -614,13 +618,27 @@ _VALID_ABSORB_MODES = ("predictions", "residuals", "coefficients", "statistics",
 
 
 def _apply_absorb(frame: Frame, over, eng: Optional[Engine], target: Expr, features: Sequence[Expr], absorb, sample_weights,
-                  add_intercept: bool, mode: str, cov_type: str, null_policy: str):
-    """compute_absorbed_least_squares body: the group layout of _apply_static around Engine.absorb; the id column moves with its rows."""
+                  add_intercept: bool, mode: str, cov_type: str, null_policy: str, two_way=None):
+    """compute_absorbed_least_squares body: the group layout of _apply_static around Engine.absorb (``two_way``: the max_iter / tol of
+    Engine.absorb2, ``absorb`` then holds two columns); the id columns move with their rows."""
     y, xs, names, icpt, w = _pre_process_data(frame, target, features, sample_weights, add_intercept)
-    ids = _cluster_ids(frame, [absorb], y)
+    ids = _cluster_ids(frame, list(absorb) if two_way is not None else [absorb], y)
     eng = eng or default_engine(y.device.index or 0 if _is_torch(y) else 0)
     grp = _Groups(eng, None if over is None else (frame[over] if isinstance(over, str) else over), y.shape[0])
     moved = grp.take([y, w] + list(xs) + ids)
+    if two_way is not None:
+        want = {"predictions": ("pred",), "residuals": ("resid",), "coefficients": ("coef",), "effects": ("fe1", "fe2"),
+                "statistics": ("coef", "status") + tuple(f for f in _lib.ABSORB2_FIELDS if f not in ("fe1", "fe2"))}[mode]
+        out = eng.absorb2(moved[0], moved[2:2 + len(xs)], moved[2 + len(xs)], moved[3 + len(xs)], grp.offsets, cov_type=cov_type,
+                          max_iter=two_way[0], tol=two_way[1], want=want, weights=moved[1], add_intercept=icpt, null_policy=null_policy)
+        if mode == "statistics":
+            return "statistics", AbsorbedOLS(names, out, grp.keys, cov_type)
+        if mode == "coefficients":
+            return "coefficients", Coefficients(names, out["coef"], grp.keys, grp.gid_frame(out["coef"]))
+        if mode == "effects":                                      # both effects, keyed by the absorbed columns (in their order)
+            keys = [c if isinstance(c, str) else f"effect_{j + 1}" for j, c in enumerate(absorb)]
+            return target.output_name, {keys[0]: grp.untake(out["fe1"]), keys[1]: grp.untake(out["fe2"])}
+        return target.output_name, grp.untake(out["pred" if mode == "predictions" else "resid"])
     want = {"predictions": ("pred",), "residuals": ("resid",), "coefficients": ("coef",), "effects": ("fe",),
             "statistics": ("coef", "status") + tuple(f for f in _lib.ABSORB_FIELDS if f != "fe")}[mode]
     out = eng.absorb(moved[0], moved[2:2 + len(xs)], moved[2 + len(xs)], grp.offsets, cov_type=cov_type, want=want, weights=moved[1],
@@ -827,13 +845,18 @@ def compute_iv2sls(target, *exog, endog, instruments, cov_type: str = "nonrobust
 
 
 def compute_absorbed_least_squares(target, *features, absorb, cov_type: str = "nonrobust", sample_weights=None,
-                                   add_intercept: bool = False, mode: str = "predictions", null_policy: str = "ignore") -> Expr:
+                                   add_intercept: bool = False, mode: str = "predictions", null_policy: str = "ignore",
+                                   max_iter: Optional[int] = None, tol: Optional[float] = None) -> Expr:
     """Regression per group that absorbs one categorical effect (the "within" estimator: ``areg``, ``xtreg, fe``,
     ``PanelOLS(entity_effects=True)``) without a dummy column per category.  ``absorb``: the id column (a name, an expression or an
     array; under ``.over(key)`` it moves with its rows).  Modes "predictions" (x'b plus the row's effect), "residuals",
     "coefficients" (the slopes; with ``add_intercept`` the mean effect last) and "effects" (the row's effect, centred on the mean
     effect with ``add_intercept``); mode="statistics" returns an ``AbsorbedOLS`` with standard errors (``cov_type`` "nonrobust" or
-    "cluster", clustered on the absorbed id), t and p values, sigma2, the within and overall R2 and the category counts."""
+    "cluster", clustered on the absorbed id), t and p values, sigma2, the within and overall R2 and the category counts.
+    ``absorb`` may also be a list or tuple of TWO columns: two-way fixed effects (``reghdfe y x, absorb(firm year)``) by alternating
+    projections, ``max_iter`` sweeps per column at the most (default 10 000) with stop rule ``tol`` (default 1e-10); "cluster" then
+    clusters on the first column, mode "effects" returns a dict of both effects keyed by the two columns, and the statistics also
+    carry ``n_categories2 n_components n_iter``.  ``max_iter`` / ``tol`` do not apply to a single column."""
     if mode not in _VALID_ABSORB_MODES:
         raise ValueError(f"'mode' must be one of {_VALID_ABSORB_MODES}, got {mode!r}")
     if null_policy not in _VALID_NULL_POLICIES:
@@ -842,9 +865,22 @@ def compute_absorbed_least_squares(target, *features, absorb, cov_type: str = "n
         raise ValueError("'absorb' names the id column whose effect is absorbed")
     t, fs = parse_into_expr(target), [parse_into_expr(f) for f in features]
     icpt = add_intercept and not any(f.output_name == "const" for f in fs)
-    _absorb_params(None, len(fs), cov_type, icpt)
+    two_way = None
+    if isinstance(absorb, (list, tuple)):
+        if len(absorb) == 1:
+            absorb = absorb[0]
+        elif len(absorb) == 2:
+            two_way = (10_000 if max_iter is None else max_iter, 1e-10 if tol is None else tol)
+        else:
+            raise ValueError(f"'absorb' takes one id column or two, got {len(absorb)} (three or more absorbed effects are not built)")
+    if two_way is None:
+        if max_iter is not None or tol is not None:
+            raise ValueError("'max_iter' / 'tol' belong to the two-way iteration: a single absorbed column has a closed form")
+        _absorb_params(None, len(fs), cov_type, icpt)
+    else:
+        _absorb2_params(None, len(fs), cov_type, icpt, *two_way)
     return Expr(t._name, fn=lambda frame, over, eng: _apply_absorb(frame, over, eng, t, fs, absorb, sample_weights, add_intercept, mode,
-                                                                   cov_type, null_policy))
+                                                                   cov_type, null_policy, two_way))
 
 
 def compute_multi_target_least_squares(targets, *features, sample_weights=None, add_intercept: bool = False,
@@ -1122,9 +1158,10 @@ class LeastSquares:
                               sample_weights=sample_weights, add_intercept=add_intercept, mode=mode, null_policy=null_policy)
 
     def absorb(self, *features, absorb, cov_type: str = "nonrobust", sample_weights=None, add_intercept: bool = False,
-               mode: str = "predictions", null_policy: str = "ignore") -> Expr:
+               mode: str = "predictions", null_policy: str = "ignore", max_iter: Optional[int] = None,
+               tol: Optional[float] = None) -> Expr:
         return compute_absorbed_least_squares(self._expr, *features, absorb=absorb, cov_type=cov_type, sample_weights=sample_weights,
-                                              add_intercept=add_intercept, mode=mode, null_policy=null_policy)
+                                              add_intercept=add_intercept, mode=mode, null_policy=null_policy, max_iter=max_iter, tol=tol)
 
     def lasso(self, *features, alpha: float, **kwargs) -> Expr:
         return self.least_squares(*features, alpha=alpha, l1_ratio=1.0, **kwargs)
