@@ -1,7 +1,8 @@
 // api_fits.hip -- the per-group fit entries of the C-ABI: pols_ridge_cv (K10), pols_rlm (K11), pols_elastic_net_cv (K12), pols_glm
 // (K13), pols_iv2sls (K14), pols_least_squares_absorb (K16), pols_least_squares_absorb2 (K17).  Host code only.  What they share is written once, up front: the opening checks and the staging
-// (FitCall), the common fields of the kernel argument structs (fit_frame, fit_segments), the entry's own outputs (ExtraOut), K10's
-// prediction pass (fit_predict) and extra input columns (stage_extra_columns).  DESIGN.md, "Adding a per-group fit entry".
+// (FitCall), the common fields of the kernel argument structs (fit_frame, fit_segments), the work buffers (Carve, carve), the entry's own
+// outputs (ExtraOut), K10's prediction pass (fit_predict), extra input columns (stage_extra_columns), the tile count rlm and glm route by
+// (group_tiles) and the stages of the absorb pair.  DESIGN.md, "Adding a per-group fit entry".
 #include <algorithm>
 #include <cassert>
 #include <cmath>
@@ -15,6 +16,10 @@
 #include "k16_absorb.hpp"
 #include "k17_absorb2.hpp"
 #include "k7c_cluster.hpp"
+#pragma GCC visibility push(hidden)     // host helpers of this file alone: nothing of them is exported
+#include "k17_split.hpp"
+#include "scratch_carve.hpp"
+#pragma GCC visibility pop
 
 using namespace pols;
 
@@ -77,8 +82,16 @@ template <typename A> void fit_segments(A &a, const SegTables &sg) {
     if (sg.n_seg > 0) { a.seg_offs = sg.offs; a.seg_map = sg.map; a.seg_first = sg.first; a.n_seg = sg.n_seg; }
 }
 
+// One work buffer for the regions declared on `cv`: the allocation of their total, then every slot points into it.
+int carve(pols_ctx *ctx, Work w, const Carve &cv) {
+    void *base = nullptr;
+    int rc = ensure_scratch(ctx, w, cv.total(), &base);
+    if (!rc) cv.place(base);
+    return rc;
+}
+
 // The entry's own outputs, each registered once: the caller's pointer, the slot of the argument struct, the bytes.  place(): the
-// slot of a DEVICE batch is the caller's pointer; the wanted fields of a HOST batch are carved out of `w` at 256-byte steps and
+// slot of a DEVICE batch is the caller's pointer; the wanted fields of a HOST batch are carved out of `w` (one region each) and
 // an unwanted one's slot stays nullptr.  home(): the wanted fields of a HOST batch go home, then the pols_out ones (unstage_outputs).
 struct ExtraOut {
     struct Field {
@@ -95,22 +108,16 @@ struct ExtraOut {
         f[n++] = Field{home, &slot, nullptr, bytes, [](void *s, void *p) { *static_cast<T **>(s) = static_cast<T *>(p); }};
     }
     int place(pols_ctx *ctx, const FitCall &fc, Work w) {
-        size_t total = 0;
-        void *buf = nullptr;
-        for (int i = 0; i < n; ++i)
-            if (f[i].home && fc.host) total += round256(f[i].bytes);
-        if (total > 0) {
-            int rc = ensure_scratch(ctx, w, total, &buf);
-            if (rc) return rc;
-        }
-        char *c = static_cast<char *>(buf);
+        Carve cv;
         for (int i = 0; i < n; ++i) {
             if (!f[i].home) continue;
-            f[i].dev = fc.host ? c : f[i].home;
-            f[i].set(f[i].slot, f[i].dev);
-            if (fc.host) c += round256(f[i].bytes);
+            f[i].dev = f[i].home;
+            if (fc.host) cv.add(f[i].dev, f[i].bytes, &f[i].home);   // (a wanted field of 0 bytes keeps a non-null slot: the kernels tell by it)
         }
-        return POLS_OK;
+        int rc = cv.total() > 0 ? carve(ctx, w, cv) : POLS_OK;
+        for (int i = 0; i < n && !rc; ++i)
+            if (f[i].home) f[i].set(f[i].slot, f[i].dev);
+        return rc;
     }
     int home(pols_ctx *ctx, const pols_batch *b, const pols_out *o, const FitCall &fc) const {
         if (!fc.host) return POLS_OK;
@@ -142,19 +149,154 @@ int fit_predict(pols_ctx *ctx, const pols_batch *b, const FitCall &fc, const Seg
 // n further columns of n_rows batch-dtype values (the GLM offset, the instruments): a HOST batch's are copied into `w`, a DEVICE
 // batch's are taken where they are.
 int stage_extra_columns(pols_ctx *ctx, const pols_batch *b, Work w, const void *const *src, int n, const void **dst) {
-    const size_t bytes = dtype_size(b->dtype) * (size_t)b->n_rows, colb = round256(bytes);
+    const size_t bytes = dtype_size(b->dtype) * (size_t)b->n_rows;
     const bool copy = b->mem == POLS_MEM_HOST && bytes > 0 && n > 0;
-    void *buf = nullptr;
-    if (copy) {
-        int rc = ensure_scratch(ctx, w, colb * (size_t)n, &buf);
-        if (rc) return rc;
-    }
+    Carve cv;
     for (int j = 0; j < n; ++j) {
-        dst[j] = copy ? static_cast<char *>(buf) + colb * (size_t)j : src[j];
+        dst[j] = src[j];
+        if (copy) cv.add(dst[j], bytes);
+    }
+    int rc = copy ? carve(ctx, w, cv) : POLS_OK;
+    if (rc) return rc;
+    for (int j = 0; j < n; ++j) {
         if (copy) POLS_HIP(hipMemcpyAsync(const_cast<void *>(dst[j]), src[j], bytes, hipMemcpyHostToDevice, ctx->stream));
         else if (b->mem == POLS_MEM_DEVICE && !aligned16(src[j])) return fail(POLS_ERR_INVALID, "device columns must be 16-byte aligned");
     }
     return POLS_OK;
+}
+
+// What rlm and glm route by: the tiles group g spans from the 16-byte grid point at or below its first row.
+int group_tiles(const pols_batch *b, int64_t g, int64_t *tiles) {
+    const int64_t s = b->group_offsets[g], e = b->group_offsets[g + 1], vec = b->dtype == POLS_F32 ? 4 : 2;
+    if (e < s) return fail(POLS_ERR_INVALID, "group_offsets must not decrease");
+    *tiles = e > s ? (e - (s & ~(vec - 1)) + 255) / 256 : 0;
+    return POLS_OK;
+}
+
+// ---------------------------------------------------------------- the stages of the absorb pair (K16, K17)
+// The checks behind fit_check, in the order they fire.  `name` words the messages; `iter`: K17's stop rule (K16: nullptr); fe / fe2: the
+// entry's effect columns (a frame without groups is not held to the alignment rule: the entry returns before any work).
+int absorb_check(const pols_batch *b, const pols_ols_params *p, const pols_out *o, const FitCall &fc, const char *name,
+                 const int64_t *const *ids, int n_ids, int cov_type, const pols_absorb2_params *iter, const void *fe, const void *fe2) {
+    if (p->alpha != 0.0 || p->positive || (p->has_l1_ratio && p->l1_ratio > 0.0))
+        return fail(POLS_ERR_INVALID, "%s: alpha / positive / l1_ratio do not apply (penalised absorbed fits are not built)", name);
+    if (b->n_features < 1) return fail(POLS_ERR_INVALID, "%s: no feature column", name);
+    for (int w = 0; w < n_ids; ++w)
+        if (!ids[w]) return fail(POLS_ERR_INVALID, "%s: %s is NULL", name, n_ids == 2 ? "ids / ids2" : "ids");
+    if (cov_type != POLS_COV_NONROBUST && cov_type != POLS_COV_CLUSTER)
+        return fail(POLS_ERR_INVALID, "%s: cov_type %d is not NONROBUST / CLUSTER", name, cov_type);
+    if (iter && iter->max_iter < 1) return fail(POLS_ERR_INVALID, "%s: max_iter %d < 1", name, iter->max_iter);
+    if (iter && (!(iter->tol > 0.0) || !std::isfinite(iter->tol))) return fail(POLS_ERR_INVALID, "%s: tol %g is not positive and finite", name, iter->tol);
+    if (b->n_rows >= ((int64_t)1 << 31)) return fail(POLS_ERR_UNSUPPORTED, "%s: %lld rows >= 2^31", name, (long long)b->n_rows);
+    // (pred / resid / fe / fe1 are written 16 bytes at a time; fe2 goes out row by row and is held to the same rule as its sibling)
+    if (b->n_groups > 0 && !fc.host && !(aligned16(fe) && aligned16(fe2) && aligned16(o->pred) && aligned16(o->resid)))
+        return fail(POLS_ERR_INVALID, "device columns must be 16-byte aligned");
+    return POLS_OK;
+}
+
+// The id columns on the device: a HOST batch's are copied into `w` (one region each), a DEVICE batch's are taken in place.
+int stage_ids(pols_ctx *ctx, const FitCall &fc, Work w, const int64_t *const *ids, int n, size_t N, const int64_t **d_ids) {
+    Carve cv;
+    for (int j = 0; j < n; ++j) {
+        d_ids[j] = ids[j];
+        if (fc.host) cv.add(d_ids[j], sizeof(int64_t) * N + 8);
+    }
+    int rc = fc.host ? carve(ctx, w, cv) : POLS_OK;
+    if (rc) return rc;
+    for (int j = 0; j < n; ++j)
+        if (fc.host && N > 0) POLS_HIP(hipMemcpyAsync(const_cast<int64_t *>(d_ids[j]), ids[j], sizeof(int64_t) * N, hipMemcpyHostToDevice, ctx->stream));
+    return POLS_OK;
+}
+
+// The categories of n id columns (c[j]: the frame, .ids and .order are set): the count / first / index tables of each in `w`, K16's count
+// launch and the copy of the number of categories into c[j].n_cats -- which holds once the CALLER has synchronised the stream.
+int categories(pols_ctx *ctx, Work w, AbsorbArgs *c, int n, size_t items, size_t N) {
+    Carve cv;
+    for (int j = 0; j < n; ++j) {
+        cv.add(c[j].item_cnt, sizeof(int32_t) * items); cv.add(c[j].item_first, sizeof(int64_t) * (items + 1));
+        cv.add(c[j].catidx, sizeof(int32_t) * N + 4);
+    }
+    int rc = carve(ctx, w, cv);
+    if (rc) return rc;
+    for (int j = 0; j < n; ++j) {
+        if ((rc = k16_count_launch(ctx, c[j]))) return rc;
+        POLS_HIP(hipMemcpyAsync(&c[j].n_cats, c[j].item_first + items, sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
+    }
+    return POLS_OK;
+}
+
+// The statistics both entries return, and whether any is wanted: only then the residual pass and the finish run.  (The entry's own
+// fields follow in the order of its struct: the order of registration is the order of a HOST batch's carve.)
+template <typename A, typename O> bool absorb_stats_out(ExtraOut &xo, A &a, const O *ro, size_t G, int kc) {
+    xo.add(ro->se, a.se, sizeof(double) * G * kc); xo.add(ro->t_values, a.t_values, sizeof(double) * G * kc);
+    xo.add(ro->p_values, a.p_values, sizeof(double) * G * kc); xo.add(ro->sigma2, a.sigma2, sizeof(double) * G);
+    xo.add(ro->r2_within, a.r2_within, sizeof(double) * G); xo.add(ro->r2, a.r2, sizeof(double) * G);
+    return ro->se || ro->t_values || ro->p_values || ro->sigma2 || ro->r2_within || ro->r2;
+}
+
+// K17: the two orders (K7c's builder keeps one at a time, so the first is copied before the builder runs again) and, behind them, the
+// group list of a mixed frame.
+int absorb2_orders(pols_ctx *ctx, const pols_batch *b, const FitCall &fc, const int64_t *const *d_ids, const K17Split &sp, Absorb2Args &a,
+                   const int32_t **d_list) {
+    const size_t N = (size_t)b->n_rows, ib = sizeof(uint32_t) * N + 4;
+    uint32_t *ord1 = nullptr;
+    int32_t *list = nullptr;
+    Carve cv;
+    cv.add(ord1, ib); cv.add(a.pos1, ib); cv.add(a.perm2, ib);
+    cv.add(list, sp.mixed() ? sizeof(int32_t) * fc.G : 0);
+    int rc = carve(ctx, Work::Absorb2Order, cv);
+    if (rc) return rc;
+    if (sp.mixed() && (rc = upload_small(ctx, list, sp.list.data(), sizeof(int32_t) * fc.G))) return rc;
+    *d_list = list;
+    if ((rc = k7c_order_launch(ctx, d_ids[0], fc.d_offs, b->n_groups, b->n_rows, &a.order1))) return rc;
+    if (a.order1) {
+        POLS_HIP(hipMemcpyAsync(ord1, a.order1, sizeof(uint32_t) * N, hipMemcpyDeviceToDevice, ctx->stream));
+        a.order1 = ord1;
+    }
+    return k7c_order_launch(ctx, d_ids[1], fc.d_offs, b->n_groups, b->n_rows, &a.order2);
+}
+
+// K17: what the numbers of categories size (per id column: the starts, the means and their weight sums -- the same bytes twice --, the
+// weights, effects and labels), the staged columns and the moments.
+int absorb2_tables(pols_ctx *ctx, Absorb2Args &a, AbsorbArgs *way, size_t items, size_t G, size_t N, int k, bool cluster) {
+    const size_t nc1 = (size_t)way[0].n_cats, nc2 = (size_t)way[1].n_cats, kz = (size_t)k + 1;
+    const size_t am1b = sizeof(double) * kz * nc1 + 8, am2b = sizeof(double) * kz * nc2 + 8, d1b = sizeof(double) * nc1 + 8, d2b = sizeof(double) * nc2 + 8;
+    Carve cats, cols, moments;
+    cats.add(way[0].cat_start, sizeof(int64_t) * (nc1 + 1)); cats.add(way[1].cat_start, sizeof(int64_t) * (nc2 + 1));
+    cats.add(a.am1, am1b); cats.add(a.am2, am2b);
+    cats.add(a.aw1, am1b); cats.add(a.aw2, am2b);
+    cats.add(a.wc1, d1b); cats.add(a.eff1, d1b);
+    cats.add(a.wc2, d2b); cats.add(a.eff2, d2b);
+    cats.add(a.lab1, sizeof(int32_t) * nc1 + 4); cats.add(a.lab2, sizeof(int32_t) * nc2 + 4);
+    cats.add(a.resid_part, sizeof(double) * nc1 * k17_resid_stride(k, cluster) + 8);
+    cols.add(a.cols, sizeof(double) * kz * N + 8); cols.add(a.wfit, sizeof(double) * N + 8);
+    cols.add(a.rowlab, sizeof(int32_t) * N + 4); cols.add(a.fitb, N + 1);
+    moments.add(a.gram_part, sizeof(double) * items * k17_gram_stride(k)); moments.add(a.state, sizeof(double) * G * k17_state_stride(k));
+    moments.add(a.colstat, sizeof(double) * G * kz * K17_COLSTAT); moments.add(a.grpstat, sizeof(double) * G * K17_GRPSTAT);
+    int rc = carve(ctx, Work::Absorb2Cats, cats);
+    if (!rc) rc = carve(ctx, Work::Absorb2Cols, cols);
+    return rc ? rc : carve(ctx, Work::Absorb2Moments, moments);
+}
+
+// K17: the launches behind the tables -- stage, demean (resident, global, or one of each over the two halves of a mixed frame's list),
+// moments, solve, the residual pass and the finish when a wanted output needs a residual, the prediction pass.
+int absorb2_launches(pols_ctx *ctx, int dtype, const Absorb2Args &a, const K17Split &sp, const int32_t *d_list, bool need_rows) {
+    int rc = k17_stage_launch(ctx, dtype, a);
+    if (rc) return rc;
+    if (sp.mixed()) {
+        Absorb2Args part = a;
+        part.list = d_list; part.n_list = sp.n_res;
+        if ((rc = k17_demean_launch(ctx, part, true, sp.max_res))) return rc;
+        part.list = d_list + sp.n_res; part.n_list = a.n_groups - sp.n_res;
+        if ((rc = k17_demean_launch(ctx, part, false, sp.max_glb))) return rc;
+    } else if ((rc = k17_demean_launch(ctx, a, sp.n_res > 0, sp.n_res > 0 ? sp.max_res : sp.max_glb))) return rc;
+    if ((rc = k17_gram_launch(ctx, a))) return rc;
+    if ((rc = k17_solve_launch(ctx, a))) return rc;
+    if (need_rows) {
+        if ((rc = k17_resid_launch(ctx, a))) return rc;
+        if ((rc = k17_finish_launch(ctx, a))) return rc;
+    }
+    return k17_predict_launch(ctx, dtype, a);
 }
 
 }  // namespace
@@ -188,20 +330,17 @@ int pols_ridge_cv(pols_ctx *ctx, const pols_batch *b, const pols_ols_params *p, 
     SegTables sg;
     if ((rc = ensure_segments(ctx, b, fc.max_rows, 0, &sg))) return rc;
     const size_t items = sg.n_seg > 0 ? (size_t)sg.n_seg : G;
-    const size_t gramb = round256(sizeof(double) * items * k10_gram_stride(kt)), eigb = round256(sizeof(double) * G * k10_eig_stride(kt));
-    const size_t alb = round256(sizeof(double) * (size_t)na), partb = round256(sizeof(double) * items * (size_t)na);
-    void *wg = nullptr, *ws = nullptr;
-    if ((rc = ensure_scratch(ctx, Work::RidgeCvGram, gramb + eigb, &wg))) return rc;
-    if ((rc = ensure_scratch(ctx, Work::RidgeCvScores, alb + partb + round256(sizeof(double) * G * kt), &ws))) return rc;
-    if ((rc = upload_small(ctx, ws, q->alphas, sizeof(double) * (size_t)na))) return rc;
     RidgeCvArgs a = {};
     fit_frame(a, b, fc);
     fit_segments(a, sg);
-    a.alphas = static_cast<const double *>(ws); a.n_alphas = na;
-    a.gram_part = static_cast<double *>(wg);
-    a.eig = reinterpret_cast<double *>(static_cast<char *>(wg) + gramb);
-    a.score_part = reinterpret_cast<double *>(static_cast<char *>(ws) + alb);
-    a.coef64 = reinterpret_cast<double *>(static_cast<char *>(ws) + alb + partb);
+    a.n_alphas = na;
+    Carve gram, scores;
+    gram.add(a.gram_part, sizeof(double) * items * k10_gram_stride(kt)); gram.add(a.eig, sizeof(double) * G * k10_eig_stride(kt));
+    scores.add(a.alphas, sizeof(double) * (size_t)na); scores.add(a.score_part, sizeof(double) * items * (size_t)na);
+    scores.add(a.coef64, sizeof(double) * G * kt);
+    if ((rc = carve(ctx, Work::RidgeCvGram, gram))) return rc;
+    if ((rc = carve(ctx, Work::RidgeCvScores, scores))) return rc;
+    if ((rc = upload_small(ctx, const_cast<double *>(a.alphas), q->alphas, sizeof(double) * (size_t)na))) return rc;
     ExtraOut xo;
     xo.add(ro->alpha, a.alpha, sizeof(double) * G);
     xo.add(ro->score, a.score, sizeof(double) * G);
@@ -244,31 +383,28 @@ int pols_rlm(pols_ctx *ctx, const pols_batch *b, const pols_ols_params *p, const
     if (!fc.host && !aligned16(ro->weights)) return fail(POLS_ERR_INVALID, "device columns must be 16-byte aligned");   // (written 16 bytes at a time)
     const int kt = fc.kt;
     const size_t G = fc.G;
-    // which form serves which group: the tiles a group spans from the 16-byte grid point at or below its first row
-    const int vec = b->dtype == POLS_F32 ? 4 : 2;
+    // which form serves which group
     const int cap = ctx->opt.rlm_engine == 1 ? -1 : k11_resident_tiles(kt);
-    int64_t n_res = 0, n_str = 0, res_tiles = 0, str_rows = 0;
+    int64_t n_res = 0, n_str = 0, res_tiles = 0, str_rows = 0, tiles = 0;
     for (int64_t g = 0; g < b->n_groups; ++g) {
-        const int64_t s = b->group_offsets[g], e = b->group_offsets[g + 1];
-        if (e < s) return fail(POLS_ERR_INVALID, "group_offsets must not decrease");
-        const int64_t tiles = e > s ? (e - (s & ~(int64_t)(vec - 1)) + 255) / 256 : 0;
+        if ((rc = group_tiles(b, g, &tiles))) return rc;
         if (tiles <= cap) { ++n_res; res_tiles = std::max(res_tiles, tiles); }
-        else { ++n_str; str_rows = std::max(str_rows, e - s); }
+        else { ++n_str; str_rows = std::max(str_rows, b->group_offsets[g + 1] - b->group_offsets[g]); }
     }
     if (str_rows > K11_STREAM_MAX_ROWS)
         return fail(POLS_ERR_UNSUPPORTED, "rlm: a group of %lld rows > %lld (one workgroup walks a streamed group; the split form is not built)",
                     (long long)str_rows, (long long)K11_STREAM_MAX_ROWS);
     if ((rc = fit_stage(ctx, b, o, &fc))) return rc;
-    void *wc = nullptr, *wr = nullptr;
-    if ((rc = ensure_scratch(ctx, Work::RlmCoef, round256(sizeof(double) * G * kt), &wc))) return rc;
-    if (n_str > 0 && (rc = ensure_scratch(ctx, Work::RlmRows, round256(sizeof(double) * (size_t)b->n_rows), &wr))) return rc;
     RlmArgs a = {};
     fit_frame(a, b, fc);
     a.norm = q->norm; a.max_iter = q->max_iter; a.tol = q->tol;
     a.c = q->c > 0.0 ? q->c : (q->norm == POLS_RLM_HUBER ? 1.345 : 4.685);
     a.res_tiles = cap; a.ts = (int32_t)res_tiles * 256 + 1;
-    a.rows = static_cast<double *>(wr);
-    a.coef64 = static_cast<double *>(wc);
+    Carve coef, rows;
+    coef.add(a.coef64, sizeof(double) * G * kt);
+    rows.add(a.rows, sizeof(double) * (size_t)b->n_rows);          // (stays nullptr unless a group is streamed)
+    if ((rc = carve(ctx, Work::RlmCoef, coef))) return rc;
+    if (n_str > 0 && (rc = carve(ctx, Work::RlmRows, rows))) return rc;
     ExtraOut xo;
     xo.add(ro->scale, a.scale, sizeof(double) * G);
     xo.add(ro->n_iter, a.n_iter, sizeof(int32_t) * G);
@@ -308,18 +444,15 @@ int pols_glm(pols_ctx *ctx, const pols_batch *b, const pols_ols_params *p, const
     ro = or_none(ro);
     const int kt = fc.kt;
     const size_t G = fc.G, sz = fc.sz;
-    // which form serves which group: the tiles a group spans from the 16-byte grid point at or below its first row
-    const int vec = b->dtype == POLS_F32 ? 4 : 2;
+    // which form serves which group
     const int cols = b->n_features + 1 + (b->weights ? 1 : 0) + (q->offset ? 1 : 0);
     // (two resident launches: the groups whose LDS request leaves room for a second workgroup on a CU, and the longer ones -- one long
     //  group must not size the request of a whole frame of short ones)
     const int cap = ctx->opt.glm_engine == 1 ? -1 : k13_resident_tiles(kt, cols, sz, 1);
     const int cap2 = std::min(cap, k13_resident_tiles(kt, cols, sz, 2));
-    int64_t n_res = 0, n_spl = 0, res_tiles = 0, res2_tiles = 0, n_res1 = 0;
+    int64_t n_res = 0, n_spl = 0, res_tiles = 0, res2_tiles = 0, n_res1 = 0, tiles = 0;
     for (int64_t g = 0; g < b->n_groups; ++g) {
-        const int64_t s = b->group_offsets[g], e = b->group_offsets[g + 1];
-        if (e < s) return fail(POLS_ERR_INVALID, "group_offsets must not decrease");
-        const int64_t tiles = e > s ? (e - (s & ~(int64_t)(vec - 1)) + 255) / 256 : 0;
+        if ((rc = group_tiles(b, g, &tiles))) return rc;
         if (tiles <= cap2) { ++n_res; res2_tiles = std::max(res2_tiles, tiles); }
         else if (tiles <= cap) { ++n_res; ++n_res1; res_tiles = std::max(res_tiles, tiles); }
         else ++n_spl;
@@ -330,23 +463,19 @@ int pols_glm(pols_ctx *ctx, const pols_batch *b, const pols_ols_params *p, const
     if (!fc.host && !aligned16(ro->linpred)) return fail(POLS_ERR_INVALID, "device columns must be 16-byte aligned");
     SegTables sg;
     if (n_spl > 0 && (rc = ensure_segments(ctx, b, fc.max_rows, sizeof(double) * k13_part_stride(kt), &sg))) return rc;
-    void *wc = nullptr, *ws = nullptr;
-    if ((rc = ensure_scratch(ctx, Work::GlmCoef, round256(sizeof(double) * G * kt), &wc))) return rc;
-    const size_t stateb = round256(sizeof(double) * G * k13_state_stride(kt)), partb = sg.n_seg > 0 ? 0 : round256(sizeof(double) * G * k13_part_stride(kt));
-    if (n_spl > 0 && (rc = ensure_scratch(ctx, Work::GlmState, 256 + stateb + partb, &ws))) return rc;
     GlmArgs a = {};
     fit_frame(a, b, fc);
     fit_segments(a, sg);
     a.o = d_off;
     a.family = q->family; a.max_iter = q->max_iter; a.tol = q->tol;
     a.res_tiles = cap;
-    if (n_spl > 0) {
-        char *c = static_cast<char *>(ws);
-        a.active = reinterpret_cast<int32_t *>(c);
-        a.state = reinterpret_cast<double *>(c + 256);
-        a.part = sg.n_seg > 0 ? reinterpret_cast<double *>(sg.extra) : reinterpret_cast<double *>(c + 256 + stateb);
-    }
-    a.coef64 = static_cast<double *>(wc);
+    double *seg_part = reinterpret_cast<double *>(sg.extra);       // (the partial sums of a split frame lie behind its segment tables)
+    Carve coef, state;
+    coef.add(a.coef64, sizeof(double) * G * kt);
+    state.add(a.active, 256); state.add(a.state, sizeof(double) * G * k13_state_stride(kt));
+    state.add(a.part, sg.n_seg > 0 ? 0 : sizeof(double) * G * k13_part_stride(kt), &seg_part);
+    if ((rc = carve(ctx, Work::GlmCoef, coef))) return rc;
+    if (n_spl > 0 && (rc = carve(ctx, Work::GlmState, state))) return rc;
     ExtraOut xo;
     xo.add(ro->deviance, a.deviance, sizeof(double) * G);
     xo.add(ro->se, a.se, sizeof(double) * G * kt);
@@ -421,18 +550,14 @@ int pols_iv2sls(pols_ctx *ctx, const pols_batch *b, const pols_ols_params *p, co
     fit_segments(a, sg);
     const size_t items = sg.n_seg > 0 ? (size_t)sg.n_seg : G;
     const bool pred_all = pol == POLS_NULL_DROP && (fc.st.pred || fc.st.resid);   // the one policy whose prediction pass masks rows
-    const size_t gramb = round256(sizeof(double) * items * k10_gram_stride(T)), rowsb = round256(sizeof(double) * items * k14_rows_stride(kx, robust));
-    const size_t stateb = round256(sizeof(double) * G * k14_state_stride(kx, L)), coefb = round256(sizeof(double) * G * (size_t)(pred_all ? T : kx));
-    void *wm = nullptr, *ws = nullptr;
-    if ((rc = ensure_scratch(ctx, Work::IvMoments, gramb + rowsb, &wm))) return rc;
-    if ((rc = ensure_scratch(ctx, Work::IvState, stateb + coefb, &ws))) return rc;
+    Carve moments, state;
+    moments.add(a.gram_part, sizeof(double) * items * k10_gram_stride(T)); moments.add(a.rows_part, sizeof(double) * items * k14_rows_stride(kx, robust));
+    state.add(a.state, sizeof(double) * G * k14_state_stride(kx, L)); state.add(a.coefp, sizeof(double) * G * (size_t)(pred_all ? T : kx));
+    if ((rc = carve(ctx, Work::IvMoments, moments))) return rc;
+    if ((rc = carve(ctx, Work::IvState, state))) return rc;
     a.k_user = nf + m; a.kt = T;                               // of the staged list [X1 | X2 | Z2]
     a.n_feat = nf; a.n_endog = q->n_endog; a.n_inst = m; a.icpt = icpt;
     a.cov_type = q->cov_type; a.small_sample = q->small_sample ? 1 : 0; a.pred_all = pred_all ? 1 : 0;
-    a.gram_part = static_cast<double *>(wm);
-    a.rows_part = reinterpret_cast<double *>(static_cast<char *>(wm) + gramb);
-    a.state = static_cast<double *>(ws);
-    a.coefp = reinterpret_cast<double *>(static_cast<char *>(ws) + stateb);
     ExtraOut xo;
     xo.add(ro->se, a.se, sizeof(double) * G * kx);
     xo.add(ro->t_values, a.t_values, sizeof(double) * G * kx);
@@ -447,7 +572,7 @@ int pols_iv2sls(pols_ctx *ctx, const pols_batch *b, const pols_ols_params *p, co
     if ((rc = xo.place(ctx, fc, Work::IvOut))) return rc;
     ctx->last_kernel = sg.n_seg > 0 ? "k14_iv2sls_split" : "k14_iv2sls";
     RidgeCvArgs ga = k10_frame(b, fc, &sg, a.x, nf + m, T);    // K10's Gram launch over the whole list
-    ga.gram_part = static_cast<double *>(wm);
+    ga.gram_part = const_cast<double *>(a.gram_part);
     if ((rc = k10_gram_launch(ctx, b->dtype, ga))) return rc;
     if ((rc = k14_solve_launch(ctx, a))) return rc;
     if (need_rows) {
@@ -477,69 +602,36 @@ int pols_least_squares_absorb(pols_ctx *ctx, const pols_batch *b, const pols_ols
     FitCall fc;
     int rc = fit_check(ctx, b, p, q, o, "absorb", K16_KMAX, &fc);
     if (rc) return rc;
-    if (p->alpha != 0.0 || p->positive || (p->has_l1_ratio && p->l1_ratio > 0.0))
-        return fail(POLS_ERR_INVALID, "absorb: alpha / positive / l1_ratio do not apply (penalised absorbed fits are not built)");
-    if (b->n_features < 1) return fail(POLS_ERR_INVALID, "absorb: no feature column");
-    if (!q->ids) return fail(POLS_ERR_INVALID, "absorb: ids is NULL");
-    if (q->cov_type != POLS_COV_NONROBUST && q->cov_type != POLS_COV_CLUSTER)
-        return fail(POLS_ERR_INVALID, "absorb: cov_type %d is not NONROBUST / CLUSTER", q->cov_type);
-    if (b->n_rows >= ((int64_t)1 << 31)) return fail(POLS_ERR_UNSUPPORTED, "absorb: %lld rows >= 2^31", (long long)b->n_rows);
-    if (b->n_groups == 0) return POLS_OK;
     ro = or_none(ro);
-    if (!fc.host && !(aligned16(ro->fe) && aligned16(o->pred) && aligned16(o->resid)))   // (written 16 bytes at a time)
-        return fail(POLS_ERR_INVALID, "device columns must be 16-byte aligned");
-    const int k = b->n_features, kc = fc.kt;
+    if ((rc = absorb_check(b, p, o, fc, "absorb", &q->ids, 1, q->cov_type, nullptr, ro->fe, nullptr))) return rc;
+    if (b->n_groups == 0) return POLS_OK;
+    const int k = b->n_features;
     const size_t G = fc.G, N = (size_t)b->n_rows;
     const bool cluster = q->cov_type == POLS_COV_CLUSTER;
-    const bool need_rows = ro->se || ro->t_values || ro->p_values || ro->sigma2 || ro->r2_within || ro->r2;
     if ((rc = fit_stage(ctx, b, o, &fc))) return rc;
     AbsorbArgs a = {};
     fit_frame(a, b, fc);
     a.kt = k + 1; a.icpt = b->add_intercept ? 1 : 0; a.cluster = cluster ? 1 : 0;
     a.pred = fc.st.pred; a.resid = fc.st.resid;
-    const int64_t *d_ids = q->ids;
-    if (fc.host) {
-        void *wi = nullptr;
-        if ((rc = ensure_scratch(ctx, Work::AbsorbIds, round256(sizeof(int64_t) * N + 8), &wi))) return rc;
-        if (N > 0) POLS_HIP(hipMemcpyAsync(wi, q->ids, sizeof(int64_t) * N, hipMemcpyHostToDevice, ctx->stream));
-        d_ids = static_cast<const int64_t *>(wi);
-    }
-    a.ids = d_ids;
+    if ((rc = stage_ids(ctx, fc, Work::AbsorbIds, &q->ids, 1, N, &a.ids))) return rc;
     SegTables sg;
     if ((rc = ensure_segments(ctx, b, fc.max_rows, 0, &sg))) return rc;
     fit_segments(a, sg);
     const size_t items = sg.n_seg > 0 ? (size_t)sg.n_seg : G;
-    if ((rc = k7c_order_launch(ctx, d_ids, fc.d_offs, b->n_groups, b->n_rows, &a.order))) return rc;
-    const size_t cntb = round256(sizeof(int32_t) * items), firstb = round256(sizeof(int64_t) * (items + 1)), idxb = round256(sizeof(int32_t) * N + 4);
-    void *wx = nullptr, *wc = nullptr, *wm = nullptr;
-    if ((rc = ensure_scratch(ctx, Work::AbsorbIndex, cntb + firstb + idxb, &wx))) return rc;
-    a.item_cnt = static_cast<int32_t *>(wx);
-    a.item_first = reinterpret_cast<int64_t *>(static_cast<char *>(wx) + cntb);
-    a.catidx = reinterpret_cast<int32_t *>(static_cast<char *>(wx) + cntb + firstb);
-    if ((rc = k16_count_launch(ctx, a))) return rc;
-    POLS_HIP(hipMemcpyAsync(&a.n_cats, a.item_first + items, sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
+    if ((rc = k7c_order_launch(ctx, a.ids, fc.d_offs, b->n_groups, b->n_rows, &a.order))) return rc;
+    if ((rc = categories(ctx, Work::AbsorbIndex, &a, 1, items, N))) return rc;
     POLS_HIP(hipStreamSynchronize(ctx->stream));                   // the number of categories sizes the table
     const size_t nc = (size_t)a.n_cats;
-    const size_t startb = round256(sizeof(int64_t) * (nc + 1)), catb = round256(sizeof(double) * nc * k16_cat_stride(k) + 8),
-                 residb = round256(sizeof(double) * nc * k16_resid_stride(k, cluster) + 8);
-    const size_t gramb = round256(sizeof(double) * items * k16_gram_stride(k)), stateb = round256(sizeof(double) * G * k16_state_stride(k));
-    if ((rc = ensure_scratch(ctx, Work::AbsorbCats, startb + catb + residb, &wc))) return rc;
-    if ((rc = ensure_scratch(ctx, Work::AbsorbMoments, gramb + stateb, &wm))) return rc;
-    a.cat_start = static_cast<int64_t *>(wc);
-    a.cat = reinterpret_cast<double *>(static_cast<char *>(wc) + startb);
-    a.resid_part = reinterpret_cast<double *>(static_cast<char *>(wc) + startb + catb);
-    a.gram_part = static_cast<double *>(wm);
-    a.state = reinterpret_cast<double *>(static_cast<char *>(wm) + gramb);
+    Carve cats, moments;
+    cats.add(a.cat_start, sizeof(int64_t) * (nc + 1)); cats.add(a.cat, sizeof(double) * nc * k16_cat_stride(k) + 8);
+    cats.add(a.resid_part, sizeof(double) * nc * k16_resid_stride(k, cluster) + 8);
+    moments.add(a.gram_part, sizeof(double) * items * k16_gram_stride(k)); moments.add(a.state, sizeof(double) * G * k16_state_stride(k));
+    if ((rc = carve(ctx, Work::AbsorbCats, cats))) return rc;
+    if ((rc = carve(ctx, Work::AbsorbMoments, moments))) return rc;
     ExtraOut xo;
-    xo.add(ro->se, a.se, sizeof(double) * G * kc);
-    xo.add(ro->t_values, a.t_values, sizeof(double) * G * kc);
-    xo.add(ro->p_values, a.p_values, sizeof(double) * G * kc);
-    xo.add(ro->sigma2, a.sigma2, sizeof(double) * G);
-    xo.add(ro->r2_within, a.r2_within, sizeof(double) * G);
-    xo.add(ro->r2, a.r2, sizeof(double) * G);
+    const bool need_rows = absorb_stats_out(xo, a, ro, G, fc.kt);
     xo.add(ro->fe, a.fe, fc.sz * N);
-    xo.add(ro->n_obs, a.n_obs, sizeof(int64_t) * G);
-    xo.add(ro->n_categories, a.n_categories, sizeof(int64_t) * G);
+    xo.add(ro->n_obs, a.n_obs, sizeof(int64_t) * G); xo.add(ro->n_categories, a.n_categories, sizeof(int64_t) * G);
     if ((rc = xo.place(ctx, fc, Work::AbsorbOut))) return rc;
     ctx->last_kernel = a.order ? "k16_absorb_ordered" : "k16_absorb_sorted";
     if ((rc = k16_index_launch(ctx, a))) return rc;
@@ -566,30 +658,19 @@ void pols_absorb2_params_default(pols_absorb2_params *q) {
 // K17 (k17_absorb2.hip): K7c's order builder and K16's category launches on each id column, the stage launch (the rows in id-1 order,
 // perm2), the demean launch -- resident, global, or one of each over a group list when the frame has groups on both sides of the
 // resident capacity --, the moments of the demeaned columns, the per-group solve, the residual pass per id-1 category and the per-group
-// finish (only when a wanted output needs a residual), then the prediction pass.
+// finish (only when a wanted output needs a residual), then the prediction pass.  Three synchronisations: two order builds, one count copy.
 int pols_least_squares_absorb2(pols_ctx *ctx, const pols_batch *b, const pols_ols_params *p, const pols_absorb2_params *q, pols_out *o,
                                const pols_absorb2_out *ro) {
     FitCall fc;
     int rc = fit_check(ctx, b, p, q, o, "absorb2", K17_KMAX, &fc);
     if (rc) return rc;
-    if (p->alpha != 0.0 || p->positive || (p->has_l1_ratio && p->l1_ratio > 0.0))
-        return fail(POLS_ERR_INVALID, "absorb2: alpha / positive / l1_ratio do not apply (penalised absorbed fits are not built)");
-    if (b->n_features < 1) return fail(POLS_ERR_INVALID, "absorb2: no feature column");
-    if (!q->ids || !q->ids2) return fail(POLS_ERR_INVALID, "absorb2: ids / ids2 is NULL");
-    if (q->cov_type != POLS_COV_NONROBUST && q->cov_type != POLS_COV_CLUSTER)
-        return fail(POLS_ERR_INVALID, "absorb2: cov_type %d is not NONROBUST / CLUSTER", q->cov_type);
-    if (q->max_iter < 1) return fail(POLS_ERR_INVALID, "absorb2: max_iter %d < 1", q->max_iter);
-    if (!(q->tol > 0.0) || !std::isfinite(q->tol)) return fail(POLS_ERR_INVALID, "absorb2: tol %g is not positive and finite", q->tol);
-    if (b->n_rows >= ((int64_t)1 << 31)) return fail(POLS_ERR_UNSUPPORTED, "absorb2: %lld rows >= 2^31", (long long)b->n_rows);
-    if (b->n_groups == 0) return POLS_OK;
     ro = or_none(ro);
-    // (pred / resid / fe1 are written 16 bytes at a time; fe2 goes out row by row and is held to the same rule as its sibling)
-    if (!fc.host && !(aligned16(ro->fe1) && aligned16(ro->fe2) && aligned16(o->pred) && aligned16(o->resid)))
-        return fail(POLS_ERR_INVALID, "device columns must be 16-byte aligned");
-    const int k = b->n_features, kc = fc.kt;
+    const int64_t *ids[2] = {q->ids, q->ids2}, *d_ids[2] = {nullptr, nullptr};
+    if ((rc = absorb_check(b, p, o, fc, "absorb2", ids, 2, q->cov_type, q, ro->fe1, ro->fe2))) return rc;
+    if (b->n_groups == 0) return POLS_OK;
+    const int k = b->n_features;
     const size_t G = fc.G, N = (size_t)b->n_rows;
     const bool cluster = q->cov_type == POLS_COV_CLUSTER;
-    const bool need_rows = ro->se || ro->t_values || ro->p_values || ro->sigma2 || ro->r2_within || ro->r2;
     if ((rc = fit_stage(ctx, b, o, &fc))) return rc;
     Absorb2Args a = {};
     fit_frame(a, b, fc);
@@ -597,106 +678,25 @@ int pols_least_squares_absorb2(pols_ctx *ctx, const pols_batch *b, const pols_ol
     a.has_w = (fc.st.w || (fc.pol != POLS_NULL_IGNORE && fc.pol != POLS_NULL_ZERO)) ? 1 : 0;
     a.max_iter = q->max_iter; a.tol = q->tol;
     a.pred = fc.st.pred; a.resid = fc.st.resid;
-    const int64_t *d_ids[2] = {q->ids, q->ids2};
-    const size_t idb = round256(sizeof(int64_t) * N + 8);
-    if (fc.host) {
-        void *wi = nullptr;
-        if ((rc = ensure_scratch(ctx, Work::Absorb2Ids, 2 * idb, &wi))) return rc;
-        for (int w = 0; w < 2; ++w) {
-            char *dst = static_cast<char *>(wi) + idb * (size_t)w;
-            if (N > 0) POLS_HIP(hipMemcpyAsync(dst, w ? q->ids2 : q->ids, sizeof(int64_t) * N, hipMemcpyHostToDevice, ctx->stream));
-            d_ids[w] = reinterpret_cast<const int64_t *>(dst);
-        }
-    }
+    if ((rc = stage_ids(ctx, fc, Work::Absorb2Ids, ids, 2, N, d_ids))) return rc;
     SegTables sg;
     if ((rc = ensure_segments(ctx, b, fc.max_rows, 0, &sg))) return rc;
     fit_segments(a, sg);
     const size_t items = sg.n_seg > 0 ? (size_t)sg.n_seg : G;
     // which groups the resident store takes: by their rows alone (k17_resident_bytes lays the start tables out for C = n)
-    const int64_t cap = ctx->opt.absorb2_route == 1 ? -1 : k17_resident_rows(a.has_w != 0);
-    std::vector<int32_t> lists;                                    // the resident groups, then the others
-    int64_t n_res = 0, max_res = 0, max_glb = 0;
-    for (size_t g = 0; g < G; ++g) {
-        const int64_t rows = b->group_offsets[g + 1] - b->group_offsets[g];
-        if (rows <= cap) { ++n_res; max_res = std::max(max_res, rows); } else max_glb = std::max(max_glb, rows);
-    }
-    const bool mixed = n_res > 0 && (size_t)n_res < G;
-    if (mixed) {
-        lists.resize(G);
-        size_t ir = 0, ig = (size_t)n_res;
-        for (size_t g = 0; g < G; ++g)
-            lists[(b->group_offsets[g + 1] - b->group_offsets[g] <= cap) ? ir++ : ig++] = (int32_t)g;
-    }
-    // the orders: K7c's builder keeps one order at a time, so the first is copied before the builder runs again
-    const size_t ib = round256(sizeof(uint32_t) * N + 4), listb = mixed ? round256(sizeof(int32_t) * G) : 0;
-    void *wo = nullptr;
-    if ((rc = ensure_scratch(ctx, Work::Absorb2Order, 3 * ib + listb, &wo))) return rc;
-    uint32_t *ord1 = static_cast<uint32_t *>(wo);
-    a.pos1 = reinterpret_cast<uint32_t *>(static_cast<char *>(wo) + ib);
-    a.perm2 = reinterpret_cast<uint32_t *>(static_cast<char *>(wo) + 2 * ib);
-    int32_t *d_list = reinterpret_cast<int32_t *>(static_cast<char *>(wo) + 3 * ib);
-    if (mixed && (rc = upload_small(ctx, d_list, lists.data(), sizeof(int32_t) * G))) return rc;
-    if ((rc = k7c_order_launch(ctx, d_ids[0], fc.d_offs, b->n_groups, b->n_rows, &a.order1))) return rc;
-    if (a.order1) {
-        POLS_HIP(hipMemcpyAsync(ord1, a.order1, sizeof(uint32_t) * N, hipMemcpyDeviceToDevice, ctx->stream));
-        a.order1 = ord1;
-    }
-    if ((rc = k7c_order_launch(ctx, d_ids[1], fc.d_offs, b->n_groups, b->n_rows, &a.order2))) return rc;
+    const K17Split sp = k17_split_groups(b->group_offsets, G, ctx->opt.absorb2_route == 1 ? -1 : k17_resident_rows(a.has_w != 0));
+    const int32_t *d_list = nullptr;
+    if ((rc = absorb2_orders(ctx, b, fc, d_ids, sp, a, &d_list))) return rc;
     // the categories of each id column: K16's launches on an AbsorbArgs that names the column, its order and its tables
-    const size_t cntb = round256(sizeof(int32_t) * items), firstb = round256(sizeof(int64_t) * (items + 1)), idxb = round256(sizeof(int32_t) * N + 4);
-    void *wx = nullptr, *wc = nullptr, *wm = nullptr, *wl = nullptr;
-    if ((rc = ensure_scratch(ctx, Work::Absorb2Index, 2 * (cntb + firstb + idxb), &wx))) return rc;
     AbsorbArgs way[2] = {};
     for (int w = 0; w < 2; ++w) {
-        AbsorbArgs &c = way[w];
-        char *base = static_cast<char *>(wx) + (cntb + firstb + idxb) * (size_t)w;
-        c.offs = fc.d_offs; c.n_groups = b->n_groups; c.n_rows = b->n_rows;
-        fit_segments(c, sg);
-        c.ids = d_ids[w]; c.order = w ? a.order2 : a.order1;
-        c.item_cnt = reinterpret_cast<int32_t *>(base);
-        c.item_first = reinterpret_cast<int64_t *>(base + cntb);
-        c.catidx = reinterpret_cast<int32_t *>(base + cntb + firstb);
-        if ((rc = k16_count_launch(ctx, c))) return rc;
-        POLS_HIP(hipMemcpyAsync(&c.n_cats, c.item_first + items, sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
+        way[w].offs = fc.d_offs; way[w].n_groups = b->n_groups; way[w].n_rows = b->n_rows;
+        fit_segments(way[w], sg);
+        way[w].ids = d_ids[w]; way[w].order = w ? a.order2 : a.order1;
     }
+    if ((rc = categories(ctx, Work::Absorb2Index, way, 2, items, N))) return rc;
     POLS_HIP(hipStreamSynchronize(ctx->stream));                   // the numbers of categories size the tables
-    const size_t nc1 = (size_t)way[0].n_cats, nc2 = (size_t)way[1].n_cats, kz = (size_t)k + 1;
-    const size_t st1b = round256(sizeof(int64_t) * (nc1 + 1)), st2b = round256(sizeof(int64_t) * (nc2 + 1)),
-                 am1b = round256(sizeof(double) * kz * nc1 + 8), am2b = round256(sizeof(double) * kz * nc2 + 8),
-                 d1b = round256(sizeof(double) * nc1 + 8), d2b = round256(sizeof(double) * nc2 + 8),
-                 l1b = round256(sizeof(int32_t) * nc1 + 4), l2b = round256(sizeof(int32_t) * nc2 + 4),
-                 residb = round256(sizeof(double) * nc1 * k17_resid_stride(k, cluster) + 8);
-    if ((rc = ensure_scratch(ctx, Work::Absorb2Cats, st1b + st2b + 2 * (am1b + am2b) + 2 * d1b + 2 * d2b + l1b + l2b + residb, &wc))) return rc;
-    {
-        char *c = static_cast<char *>(wc);
-        way[0].cat_start = reinterpret_cast<int64_t *>(c); c += st1b;
-        way[1].cat_start = reinterpret_cast<int64_t *>(c); c += st2b;
-        a.am1 = reinterpret_cast<double *>(c); c += am1b;
-        a.am2 = reinterpret_cast<double *>(c); c += am2b;
-        a.aw1 = reinterpret_cast<double *>(c); c += am1b;
-        a.aw2 = reinterpret_cast<double *>(c); c += am2b;
-        a.wc1 = reinterpret_cast<double *>(c); c += d1b;
-        a.eff1 = reinterpret_cast<double *>(c); c += d1b;
-        a.wc2 = reinterpret_cast<double *>(c); c += d2b;
-        a.eff2 = reinterpret_cast<double *>(c); c += d2b;
-        a.lab1 = reinterpret_cast<int32_t *>(c); c += l1b;
-        a.lab2 = reinterpret_cast<int32_t *>(c); c += l2b;
-        a.resid_part = reinterpret_cast<double *>(c);
-    }
-    const size_t colsb = round256(sizeof(double) * kz * N + 8), wfb = round256(sizeof(double) * N + 8), labb = round256(sizeof(int32_t) * N + 4),
-                 fitbb = round256(N + 1);
-    if ((rc = ensure_scratch(ctx, Work::Absorb2Cols, colsb + wfb + labb + fitbb, &wl))) return rc;
-    a.cols = static_cast<double *>(wl);
-    a.wfit = reinterpret_cast<double *>(static_cast<char *>(wl) + colsb);
-    a.rowlab = reinterpret_cast<int32_t *>(static_cast<char *>(wl) + colsb + wfb);
-    a.fitb = reinterpret_cast<uint8_t *>(static_cast<char *>(wl) + colsb + wfb + labb);
-    const size_t gramb = round256(sizeof(double) * items * k17_gram_stride(k)), stateb = round256(sizeof(double) * G * k17_state_stride(k)),
-                 colstb = round256(sizeof(double) * G * kz * K17_COLSTAT), grpstb = round256(sizeof(double) * G * K17_GRPSTAT);
-    if ((rc = ensure_scratch(ctx, Work::Absorb2Moments, gramb + stateb + colstb + grpstb, &wm))) return rc;
-    a.gram_part = static_cast<double *>(wm);
-    a.state = reinterpret_cast<double *>(static_cast<char *>(wm) + gramb);
-    a.colstat = reinterpret_cast<double *>(static_cast<char *>(wm) + gramb + stateb);
-    a.grpstat = reinterpret_cast<double *>(static_cast<char *>(wm) + gramb + stateb + colstb);
+    if ((rc = absorb2_tables(ctx, a, way, items, G, N, k, cluster))) return rc;
     for (int w = 0; w < 2; ++w)
         if ((rc = k16_index_launch(ctx, way[w]))) return rc;
     a.first1 = way[0].item_first; a.first2 = way[1].item_first;
@@ -704,36 +704,14 @@ int pols_least_squares_absorb2(pols_ctx *ctx, const pols_batch *b, const pols_ol
     a.start1 = way[0].cat_start; a.start2 = way[1].cat_start;
     a.n_cats1 = way[0].n_cats; a.n_cats2 = way[1].n_cats;
     ExtraOut xo;
-    xo.add(ro->se, a.se, sizeof(double) * G * kc);
-    xo.add(ro->t_values, a.t_values, sizeof(double) * G * kc);
-    xo.add(ro->p_values, a.p_values, sizeof(double) * G * kc);
-    xo.add(ro->sigma2, a.sigma2, sizeof(double) * G);
-    xo.add(ro->r2_within, a.r2_within, sizeof(double) * G);
-    xo.add(ro->r2, a.r2, sizeof(double) * G);
-    xo.add(ro->fe1, a.fe1, fc.sz * N);
-    xo.add(ro->fe2, a.fe2, fc.sz * N);
-    xo.add(ro->n_obs, a.n_obs, sizeof(int64_t) * G);
-    xo.add(ro->n_categories, a.n_categories, sizeof(int64_t) * G);
-    xo.add(ro->n_categories2, a.n_categories2, sizeof(int64_t) * G);
-    xo.add(ro->n_components, a.n_components, sizeof(int64_t) * G);
+    const bool need_rows = absorb_stats_out(xo, a, ro, G, fc.kt);
+    xo.add(ro->fe1, a.fe1, fc.sz * N); xo.add(ro->fe2, a.fe2, fc.sz * N);
+    xo.add(ro->n_obs, a.n_obs, sizeof(int64_t) * G); xo.add(ro->n_categories, a.n_categories, sizeof(int64_t) * G);
+    xo.add(ro->n_categories2, a.n_categories2, sizeof(int64_t) * G); xo.add(ro->n_components, a.n_components, sizeof(int64_t) * G);
     xo.add(ro->n_iter, a.n_iter, sizeof(int32_t) * G);
     if ((rc = xo.place(ctx, fc, Work::Absorb2Out))) return rc;
-    ctx->last_kernel = mixed ? "k17_absorb2_mixed" : (n_res > 0 ? "k17_absorb2_resident" : "k17_absorb2_global");
-    if ((rc = k17_stage_launch(ctx, b->dtype, a))) return rc;
-    if (mixed) {
-        Absorb2Args part = a;
-        part.list = d_list; part.n_list = n_res;
-        if ((rc = k17_demean_launch(ctx, part, true, max_res))) return rc;
-        part.list = d_list + n_res; part.n_list = (int64_t)G - n_res;
-        if ((rc = k17_demean_launch(ctx, part, false, max_glb))) return rc;
-    } else if ((rc = k17_demean_launch(ctx, a, n_res > 0, n_res > 0 ? max_res : max_glb))) return rc;
-    if ((rc = k17_gram_launch(ctx, a))) return rc;
-    if ((rc = k17_solve_launch(ctx, a))) return rc;
-    if (need_rows) {
-        if ((rc = k17_resid_launch(ctx, a))) return rc;
-        if ((rc = k17_finish_launch(ctx, a))) return rc;
-    }
-    if ((rc = k17_predict_launch(ctx, b->dtype, a))) return rc;
+    ctx->last_kernel = sp.mixed() ? "k17_absorb2_mixed" : (sp.n_res > 0 ? "k17_absorb2_resident" : "k17_absorb2_global");
+    if ((rc = absorb2_launches(ctx, b->dtype, a, sp, d_list, need_rows))) return rc;
     return xo.home(ctx, b, o, fc);
 }
 
@@ -781,22 +759,6 @@ int pols_elastic_net_cv(pols_ctx *ctx, const pols_batch *b, const pols_ols_param
     const bool split = sg.n_seg > 0;
     const size_t items = split ? (size_t)sg.n_seg : G;
     const size_t per = (size_t)nf * k10_gram_stride(kt);
-    const size_t cntb = round256(sizeof(int64_t) * items), partb = round256(sizeof(double) * items * per),
-                 foldb = split ? round256(sizeof(double) * G * per) : 0;
-    const size_t alb = round256(sizeof(double) * (size_t)na + sizeof(int32_t) * (size_t)na), scb = round256(sizeof(double) * G * nf * (size_t)na),
-                 itb = round256(sizeof(int32_t) * G * (nf + 1) * (size_t)na), p64b = round256(sizeof(double) * G * (size_t)na * kt),
-                 grb = round256(sizeof(double) * G * (size_t)na), c64b = round256(sizeof(double) * G * kt);
-    void *wg = nullptr, *ws = nullptr;
-    if ((rc = ensure_scratch(ctx, Work::EnetCvGram, cntb + partb + foldb, &wg))) return rc;
-    if ((rc = ensure_scratch(ctx, Work::EnetCvWork, alb + scb + itb + p64b + grb + c64b, &ws))) return rc;
-    {   // the candidates and the order they are visited in: descending alpha, equal values in index order
-        std::vector<char> up(sizeof(double) * (size_t)na + sizeof(int32_t) * (size_t)na);
-        double *ua = reinterpret_cast<double *>(up.data());
-        int32_t *uo = reinterpret_cast<int32_t *>(up.data() + sizeof(double) * (size_t)na);
-        for (int j = 0; j < na; ++j) { ua[j] = automatic ? 0.0 : q->alphas[j]; uo[j] = j; }
-        if (!automatic) std::stable_sort(uo, uo + na, [&](int32_t x, int32_t y) { return ua[x] > ua[y]; });
-        if ((rc = upload_small(ctx, ws, up.data(), up.size()))) return rc;
-    }
     EnetCvArgs a = {};
     fit_frame(a, b, fc);
     fit_segments(a, sg);
@@ -804,17 +766,24 @@ int pols_elastic_net_cv(pols_ctx *ctx, const pols_batch *b, const pols_ols_param
     a.counted = (pol == POLS_NULL_DROP || pol == POLS_NULL_DROP_ZERO || pol == POLS_NULL_DROP_WINDOW || pol == POLS_NULL_DROP_Y_ZERO_X) ? 1 : 0;
     a.max_iter = q->max_iter; a.positive = q->positive ? 1 : 0;
     a.l1_ratio = q->l1_ratio; a.tol = q->tol; a.eps = q->eps;
-    char *cg = static_cast<char *>(wg), *cs = static_cast<char *>(ws);
-    a.item_count = reinterpret_cast<int64_t *>(cg);
-    a.fold_part = reinterpret_cast<double *>(cg + cntb);
-    a.fold_gram = split ? reinterpret_cast<double *>(cg + cntb + partb) : a.fold_part;
-    a.alphas = reinterpret_cast<const double *>(cs);
-    a.order = reinterpret_cast<const int32_t *>(cs + sizeof(double) * (size_t)na);
-    a.score_part = reinterpret_cast<double *>(cs + alb);
-    a.iters = reinterpret_cast<int32_t *>(cs + alb + scb);
-    a.path64 = reinterpret_cast<double *>(cs + alb + scb + itb);
-    a.grid = reinterpret_cast<double *>(cs + alb + scb + itb + p64b);
-    a.coef64 = reinterpret_cast<double *>(cs + alb + scb + itb + p64b + grb);
+    // the candidates and the order they are visited in share one region: n_alphas doubles, then n_alphas int32
+    std::vector<char> up(sizeof(double) * (size_t)na + sizeof(int32_t) * (size_t)na);
+    char *packed = nullptr;
+    Carve gram, work;
+    gram.add(a.item_count, sizeof(int64_t) * items); gram.add(a.fold_part, sizeof(double) * items * per);
+    gram.add(a.fold_gram, split ? sizeof(double) * G * per : 0, &a.fold_part);   // (nothing is split: the parts are the matrices)
+    work.add(packed, up.size()); work.add(a.score_part, sizeof(double) * G * nf * (size_t)na);
+    work.add(a.iters, sizeof(int32_t) * G * (nf + 1) * (size_t)na); work.add(a.path64, sizeof(double) * G * (size_t)na * kt);
+    work.add(a.grid, sizeof(double) * G * (size_t)na); work.add(a.coef64, sizeof(double) * G * kt);
+    if ((rc = carve(ctx, Work::EnetCvGram, gram))) return rc;
+    if ((rc = carve(ctx, Work::EnetCvWork, work))) return rc;
+    double *ua = reinterpret_cast<double *>(up.data());             // descending alpha, equal values in index order
+    int32_t *uo = reinterpret_cast<int32_t *>(up.data() + sizeof(double) * (size_t)na);
+    for (int j = 0; j < na; ++j) { ua[j] = automatic ? 0.0 : q->alphas[j]; uo[j] = j; }
+    if (!automatic) std::stable_sort(uo, uo + na, [&](int32_t x, int32_t y) { return ua[x] > ua[y]; });
+    if ((rc = upload_small(ctx, packed, up.data(), up.size()))) return rc;
+    a.alphas = reinterpret_cast<const double *>(packed);
+    a.order = reinterpret_cast<const int32_t *>(packed + sizeof(double) * (size_t)na);
     ExtraOut xo;
     xo.add(ro->alpha, a.alpha, sizeof(double) * G);
     xo.add(ro->score, a.score, sizeof(double) * G);

@@ -240,16 +240,7 @@ class Engine:
             res[key] = self._alloc(dev, f64, (b.n_groups, kt), like)
         so = L.StatsOut(**{k: self._ptr(res[k]) for k in ("r2", "mae", "mse", "std_err", "t_values", "p_values")})
         if ids is not None:
-            keep = []
-            for a in ids:
-                if a.shape[0] != b.n_rows:
-                    raise ValueError(f"clusters: {a.shape[0]} ids for {b.n_rows} rows")
-                if dev:
-                    keep.append(torch.as_tensor(a, device=like.device).to(torch.int64).contiguous())
-                elif _is_torch(a):
-                    keep.append(np.ascontiguousarray(a.cpu().numpy(), dtype=np.int64))
-                else:
-                    keep.append(np.ascontiguousarray(a, dtype=np.int64))
+            keep = [_id_column(a, dev, like, b.n_rows, lambda c: f"clusters: {c.shape[0]} ids for {b.n_rows} rows") for a in ids]
             res["n_clusters"] = self._alloc(dev, torch.int64 if dev else np.int64, (b.n_groups,) if len(ids) == 1 else (b.n_groups, 2), like)
             cl = _cluster_params(self._lib, len(ids), use_correction)
             for i, a in enumerate(keep):
@@ -437,14 +428,7 @@ class Engine:
         def bring_ids(b, like, dev):
             if ids is None:
                 raise ValueError("absorb: 'ids' is required")
-            if dev:
-                col = torch.as_tensor(ids, device=like.device).to(torch.int64).contiguous()
-            elif _is_torch(ids):
-                col = np.ascontiguousarray(ids.cpu().numpy(), dtype=np.int64)
-            else:
-                col = np.ascontiguousarray(ids, dtype=np.int64)
-            if tuple(col.shape) != (b.n_rows,):
-                raise ValueError(f"absorb: {tuple(col.shape)} ids for {b.n_rows} rows")
+            col = _id_column(ids, dev, like, b.n_rows, lambda c: f"absorb: {tuple(c.shape)} ids for {b.n_rows} rows")
             q.ids = self._ptr(col)
             return col
 
@@ -475,15 +459,7 @@ class Engine:
             for name, col in (("ids", ids), ("ids2", ids2)):
                 if col is None:
                     raise ValueError(f"absorb2: '{name}' is required")
-                if dev:
-                    col = torch.as_tensor(col, device=like.device).to(torch.int64).contiguous()
-                elif _is_torch(col):
-                    col = np.ascontiguousarray(col.cpu().numpy(), dtype=np.int64)
-                else:
-                    col = np.ascontiguousarray(col, dtype=np.int64)
-                if tuple(col.shape) != (b.n_rows,):
-                    raise ValueError(f"absorb2: {tuple(col.shape)} {name} for {b.n_rows} rows")
-                cols.append(col)
+                cols.append(_id_column(col, dev, like, b.n_rows, lambda c, name=name: f"absorb2: {tuple(c.shape)} {name} for {b.n_rows} rows"))
             q.ids, q.ids2 = self._ptr(cols[0]), self._ptr(cols[1])
             return cols
 
@@ -761,6 +737,20 @@ def _cov_params(lib, cov_type: str = "nonrobust", maxlags: Optional[int] = None)
     c.cov_type = L.COV_TYPES[cov_type]
     c.maxlags = int(maxlags) if maxlags is not None else 0
     return c
+
+
+def _id_column(col, dev: bool, like, n_rows: int, words):
+    """An id column as contiguous int64 where the batch lives (``like``: one of its columns), one value per row; ``words(column)``
+    is the text of the ValueError for any other shape (the callers word theirs differently)."""
+    if dev:
+        col = torch.as_tensor(col, device=like.device).to(torch.int64).contiguous()
+    elif _is_torch(col):
+        col = np.ascontiguousarray(col.cpu().numpy(), dtype=np.int64)
+    else:
+        col = np.ascontiguousarray(col, dtype=np.int64)
+    if tuple(col.shape) != (n_rows,):
+        raise ValueError(words(col))
+    return col
 
 
 def _cluster_columns(clusters) -> list:

@@ -626,27 +626,23 @@ def _apply_absorb(frame: Frame, over, eng: Optional[Engine], target: Expr, featu
     eng = eng or default_engine(y.device.index or 0 if _is_torch(y) else 0)
     grp = _Groups(eng, None if over is None else (frame[over] if isinstance(over, str) else over), y.shape[0])
     moved = grp.take([y, w] + list(xs) + ids)
-    if two_way is not None:
-        want = {"predictions": ("pred",), "residuals": ("resid",), "coefficients": ("coef",), "effects": ("fe1", "fe2"),
-                "statistics": ("coef", "status") + tuple(f for f in _lib.ABSORB2_FIELDS if f not in ("fe1", "fe2"))}[mode]
-        out = eng.absorb2(moved[0], moved[2:2 + len(xs)], moved[2 + len(xs)], moved[3 + len(xs)], grp.offsets, cov_type=cov_type,
-                          max_iter=two_way[0], tol=two_way[1], want=want, weights=moved[1], add_intercept=icpt, null_policy=null_policy)
-        if mode == "statistics":
-            return "statistics", AbsorbedOLS(names, out, grp.keys, cov_type)
-        if mode == "coefficients":
-            return "coefficients", Coefficients(names, out["coef"], grp.keys, grp.gid_frame(out["coef"]))
-        if mode == "effects":                                      # both effects, keyed by the absorbed columns (in their order)
-            keys = [c if isinstance(c, str) else f"effect_{j + 1}" for j, c in enumerate(absorb)]
-            return target.output_name, {keys[0]: grp.untake(out["fe1"]), keys[1]: grp.untake(out["fe2"])}
-        return target.output_name, grp.untake(out["pred" if mode == "predictions" else "resid"])
-    want = {"predictions": ("pred",), "residuals": ("resid",), "coefficients": ("coef",), "effects": ("fe",),
-            "statistics": ("coef", "status") + tuple(f for f in _lib.ABSORB_FIELDS if f != "fe")}[mode]
-    out = eng.absorb(moved[0], moved[2:2 + len(xs)], moved[2 + len(xs)], grp.offsets, cov_type=cov_type, want=want, weights=moved[1],
-                     add_intercept=icpt, null_policy=null_policy)
+    ys, ws, xss, idss = moved[0], moved[1], moved[2:2 + len(xs)], moved[2 + len(xs):]
+    effects = ("fe",) if two_way is None else ("fe1", "fe2")
+    own = _lib.ABSORB_FIELDS if two_way is None else _lib.ABSORB2_FIELDS
+    want = {"predictions": ("pred",), "residuals": ("resid",), "coefficients": ("coef",), "effects": effects,
+            "statistics": ("coef", "status") + tuple(f for f in own if f not in effects)}[mode]
+    common = dict(cov_type=cov_type, want=want, weights=ws, add_intercept=icpt, null_policy=null_policy)
+    if two_way is None:
+        out = eng.absorb(ys, xss, idss[0], grp.offsets, **common)
+    else:
+        out = eng.absorb2(ys, xss, idss[0], idss[1], grp.offsets, max_iter=two_way[0], tol=two_way[1], **common)
     if mode == "statistics":
         return "statistics", AbsorbedOLS(names, out, grp.keys, cov_type)
     if mode == "coefficients":
         return "coefficients", Coefficients(names, out["coef"], grp.keys, grp.gid_frame(out["coef"]))
+    if mode == "effects" and two_way is not None:                  # both effects, keyed by the absorbed columns (in their order)
+        keys = [c if isinstance(c, str) else f"effect_{j + 1}" for j, c in enumerate(absorb)]
+        return target.output_name, {key: grp.untake(out[f]) for key, f in zip(keys, effects)}
     return target.output_name, grp.untake(out[{"predictions": "pred", "residuals": "resid", "effects": "fe"}[mode]])
 
 
