@@ -345,39 +345,32 @@ int stage_inputs(pols_ctx *ctx, const pols_batch *b, int64_t coef_rows, int kt, 
         if (!ok) return fail(POLS_ERR_INVALID, "device columns must be 16-byte aligned");
         return POLS_OK;
     }
-    const int ncols = b->n_features + 1 + (b->weights ? 1 : 0);
-    void *in = nullptr, *out = nullptr;
-    int rc = ensure_scratch(ctx, Work::HostInputs, colb * ncols + round256((size_t)b->n_rows), &in);
+    // the weights take no room when there are none; the validity bytes keep theirs, so that a frame's buffer does not depend on its nulls
+    const void *xs = nullptr;
+    Carve in;
+    in.keep(st->y, colb);
+    in.keep(xs, colb * (size_t)b->n_features);
+    if (b->weights) in.keep(st->w, colb);
+    in.keep(st->valid, (size_t)b->n_rows, b->valid != nullptr);
+    int rc = carve(ctx, Work::HostInputs, in);
     if (rc) return rc;
-    char *p = static_cast<char *>(in);
-    auto put = [&](const void *src, size_t bytes, const void **dst) -> int {
-        POLS_HIP(hipMemcpyAsync(p, src, bytes, hipMemcpyHostToDevice, ctx->stream));
-        *dst = p;
-        p += round256(bytes);
+    auto put = [&](const void *dst, const void *src, size_t bytes) -> int {
+        POLS_HIP(hipMemcpyAsync(const_cast<void *>(dst), src, bytes, hipMemcpyHostToDevice, ctx->stream));
         return POLS_OK;
     };
-    if ((rc = put(b->y, sz * b->n_rows, &st->y))) return rc;
+    if ((rc = put(st->y, b->y, sz * b->n_rows))) return rc;
     for (int j = 0; j < b->n_features; ++j)
-        if ((rc = put(b->x_cols[j], sz * b->n_rows, &st->x[j]))) return rc;
-    if (b->weights && (rc = put(b->weights, sz * b->n_rows, &st->w))) return rc;
-    if (b->valid) {
-        const void *v = nullptr;
-        if ((rc = put(b->valid, (size_t)b->n_rows, &v))) return rc;
-        st->valid = static_cast<const uint8_t *>(v);
-    }
+        if ((rc = put(st->x[j] = column(xs, colb, (size_t)j), b->x_cols[j], sz * b->n_rows))) return rc;
+    if (b->weights && (rc = put(st->w, b->weights, sz * b->n_rows))) return rc;
+    if (b->valid && (rc = put(st->valid, b->valid, (size_t)b->n_rows))) return rc;
     if (o) {
-        const size_t coefb = round256(sz * (size_t)coef_rows * kt);
-        const size_t statb = round256(sizeof(int32_t) * (size_t)b->n_groups);
-        rc = ensure_scratch(ctx, Work::HostOutputs, coefb + 2 * colb + statb, &out);
-        if (rc) return rc;
-        char *q = static_cast<char *>(out);
-        if (o->coef) st->coef = q;
-        q += coefb;
-        if (o->pred) st->pred = q;
-        q += colb;
-        if (o->resid) st->resid = q;
-        q += colb;
-        if (o->status) st->status = reinterpret_cast<int32_t *>(q);
+        // a slot the caller does not want stays nullptr; its room stays, so that what is wanted does not move the others
+        Carve out;
+        out.keep(st->coef, sz * (size_t)coef_rows * kt, o->coef != nullptr);
+        out.keep(st->pred, colb, o->pred != nullptr);
+        out.keep(st->resid, colb, o->resid != nullptr);
+        out.keep(st->status, sizeof(int32_t) * (size_t)b->n_groups, o->status != nullptr);
+        if ((rc = carve(ctx, Work::HostOutputs, out))) return rc;
     }
     return POLS_OK;
 }
@@ -422,21 +415,29 @@ int compact_nulls(pols_ctx *ctx, const pols_batch *b, int policy, Compacted *c, 
     const size_t G = (size_t)b->n_groups, N = (size_t)b->n_rows;
     const size_t sz = dtype_size(b->dtype), colb = round256(sz * std::max<size_t>(N, 1));
     const size_t n_slabs = (N + 255) / 256;
-    const size_t vb = round256(std::max<size_t>(N, 1)), tabb = round256(sizeof(void *) * (size_t)ncols), offb = round256(sizeof(int64_t) * (G + 1));
-    const size_t cntb = round256(sizeof(uint32_t) * std::max<size_t>(n_slabs, 1)), baseb = round256(sizeof(int64_t) * (n_slabs + 1)),
-                 gfb = round256(sizeof(int64_t) * std::max<size_t>(n_slabs, 1));
-    void *d = nullptr;
     const bool stage_targets = n_targets > 0 && b->mem == POLS_MEM_HOST;      // host targets: uploaded behind the compacted columns
-    if ((rc = ensure_scratch(ctx, Work::DynPrep, cntb + baseb + gfb + vb + 2 * tabb + offb + colb * (size_t)(ncols + (stage_targets ? m : 0)), &d))) return rc;
-    char *base = static_cast<char *>(d);
-    char *q_valid = base + cntb + baseb + gfb, *q_tab = q_valid + vb, *q_offs = q_tab + 2 * tabb;
-    char *cols = q_offs + offb;
+    // slab-parallel (dyn_prep.hip, 256 rows per workgroup whatever the group sizes -- one long group used to be ONE workgroup's
+    // count and scatter): validity bytes, valid rows per slab + scan, the compacted offset of every group, a stable scatter
+    RowCompactArgs ra;
+    std::memset(&ra, 0, sizeof(ra));
+    char *cols = nullptr, *staged = nullptr;
+    Carve cv;
+    cv.add(ra.slab_cnt, sizeof(uint32_t) * std::max<size_t>(n_slabs, 1));
+    cv.add(ra.slab_base, sizeof(int64_t) * (n_slabs + 1));
+    cv.add(ra.slab_gfirst, sizeof(int64_t) * std::max<size_t>(n_slabs, 1));
+    cv.add(ra.valid_out, std::max<size_t>(N, 1));
+    cv.add(ra.in, sizeof(void *) * (size_t)ncols);
+    cv.add(ra.out, sizeof(void *) * (size_t)ncols);
+    cv.add(ra.c_offs, sizeof(int64_t) * (G + 1));
+    cv.add(cols, colb * (size_t)ncols);
+    cv.add(staged, stage_targets ? colb * (size_t)m : 0);
+    if ((rc = carve(ctx, Work::DynPrep, cv))) return rc;
     std::vector<const void *> inp((size_t)ncols);
     std::vector<void *> outp((size_t)ncols);
     for (int t = 0; t < m; ++t) {
         const void *src = n_targets > 0 ? targets[t] : st.y;
         if (stage_targets) {
-            char *dst = cols + colb * (size_t)(ncols + t);
+            char *dst = column(staged, colb, (size_t)t);
             POLS_HIP(hipMemcpyAsync(dst, targets[t], sz * N, hipMemcpyHostToDevice, ctx->stream));
             src = dst;
         }
@@ -444,28 +445,17 @@ int compact_nulls(pols_ctx *ctx, const pols_batch *b, int policy, Compacted *c, 
     }
     for (int j = 0; j < k; ++j) inp[(size_t)(m + j)] = st.x[(size_t)j];
     if (st.w) inp[(size_t)(m + k)] = st.w;
-    for (int j = 0; j < ncols; ++j) outp[(size_t)j] = cols + colb * (size_t)j;
-    if ((rc = upload_small(ctx, q_tab, inp.data(), sizeof(void *) * (size_t)ncols))) return rc;
-    if ((rc = upload_small(ctx, q_tab + tabb, outp.data(), sizeof(void *) * (size_t)ncols))) return rc;
-    // slab-parallel (dyn_prep.hip, 256 rows per workgroup whatever the group sizes -- one long group used to be ONE workgroup's
-    // count and scatter): validity bytes, valid rows per slab + scan, the compacted offset of every group, a stable scatter
-    RowCompactArgs ra;
-    std::memset(&ra, 0, sizeof(ra));
-    ra.in = reinterpret_cast<const void *const *>(q_tab);
-    ra.out = reinterpret_cast<void *const *>(q_tab + tabb);
+    for (int j = 0; j < ncols; ++j) outp[(size_t)j] = column(cols, colb, (size_t)j);
+    if ((rc = upload_small(ctx, const_cast<void **>(ra.in), inp.data(), sizeof(void *) * (size_t)ncols))) return rc;
+    if ((rc = upload_small(ctx, const_cast<void **>(ra.out), outp.data(), sizeof(void *) * (size_t)ncols))) return rc;
     ra.n_cols = ncols;
     ra.w_col = st.w ? m + k : -1;
     ra.drop = (policy == POLS_NULL_DROP || policy == POLS_NULL_DROP_ZERO || policy == POLS_NULL_DROP_WINDOW || policy == POLS_NULL_DROP_Y_ZERO_X) ? 1 : 0;
     ra.n_mask = policy == POLS_NULL_DROP_Y_ZERO_X ? m : m + k;                                 // ex.rs:209-220
     ra.zero_fill = (policy == POLS_NULL_ZERO || policy == POLS_NULL_DROP_Y_ZERO_X) ? 1 : 0;   // ex.rs:264-283
     ra.valid_in = st.valid;
-    ra.valid_out = reinterpret_cast<uint8_t *>(q_valid);
     ra.valid = ra.valid_out;
     ra.offs = d_offs; ra.n_rows = (int64_t)N; ra.n_groups = b->n_groups; ra.n_slabs = (int64_t)n_slabs;
-    ra.slab_cnt = reinterpret_cast<uint32_t *>(base);
-    ra.slab_base = reinterpret_cast<int64_t *>(base + cntb);
-    ra.slab_gfirst = reinterpret_cast<int64_t *>(base + cntb + baseb);
-    ra.c_offs = reinterpret_cast<int64_t *>(q_offs);
     c->offs.assign(G + 1, 0);
     if (N > 0) {
         if ((rc = row_compact_mask_launch(ctx, b->dtype, ra))) return rc;
@@ -474,12 +464,11 @@ int compact_nulls(pols_ctx *ctx, const pols_batch *b, int policy, Compacted *c, 
         POLS_HIP(hipStreamSynchronize(ctx->stream));       // the compacted offsets are a HOST array of the batch
         if ((rc = row_compact_scatter_launch(ctx, b->dtype, ra))) return rc;
     }
-    struct { uint8_t *vbytes; } ca{ra.valid_out};
     c->ra = ra;
     c->xcols.assign(outp.begin() + m, outp.begin() + m + k);
     c->ycols.assign(outp.begin(), outp.begin() + m);
     c->d_offs = d_offs;
-    c->vbytes = ca.vbytes;
+    c->vbytes = ra.valid_out;
     c->bb = *b;
     c->bb.mem = POLS_MEM_DEVICE;
     c->bb.n_rows = c->offs[G];
@@ -513,17 +502,13 @@ int ensure_segments(pols_ctx *ctx, const pols_batch *b, int64_t max_rows, size_t
     const bool same_frame = sc.valid && sc.offs_id == ctx->offs_id && sc.n_groups == b->n_groups && sc.n_rows == b->n_rows &&
                             sc.seg_target == seg_target && sc.class_key == class_key && sc.n_items == n_items;
     const bool hit = same_frame && sc.nz2 >= extra_per_seg;
-    auto lay = [&](char *sb, int64_t n_seg) {
-        const size_t b_so = round256(sizeof(int64_t) * (size_t)(ids ? 2 * n_seg : n_seg + 1)), b_sm = round256(sizeof(int32_t) * (size_t)n_seg),
-                     b_sf = round256(sizeof(int32_t) * (size_t)(n_items + 1));
-        t->offs = reinterpret_cast<const int64_t *>(sb);
-        t->map = reinterpret_cast<const int32_t *>(sb + b_so);
-        t->first = reinterpret_cast<const int32_t *>(sb + b_so + b_sm);
-        t->extra = sb + b_so + b_sm + b_sf;
-        t->n_seg = n_seg;
-        return b_so + b_sm + b_sf;
-    };
-    if (hit) { lay(static_cast<char *>(sc.buf.ptr), sc.n_seg); t->max_len = sc.max_len; t->max_seg = sc.max_seg; return POLS_OK; }
+    Carve cv;
+    if (hit) {
+        seg_tables_layout(cv, *t, sc.n_seg, n_items, ids != nullptr, sc.nz2);
+        cv.place(sc.buf.ptr);
+        t->max_len = sc.max_len; t->max_seg = sc.max_seg;
+        return POLS_OK;
+    }
     if (same_frame) extra_per_seg = std::max<size_t>(extra_per_seg, sc.nz2);
     sc.valid = false;
     std::vector<int64_t> so;
@@ -548,11 +533,8 @@ int ensure_segments(pols_ctx *ctx, const pols_batch *b, int64_t max_rows, size_t
     sf[(size_t)n_items] = (int32_t)sm.size();
     if (n_items > 0) max_seg = std::max<int64_t>(max_seg, (int64_t)sm.size() - sf[(size_t)n_items - 1]);
     const int64_t n_seg = (int64_t)sm.size();
-    const size_t tabs = round256(sizeof(int64_t) * so.size()) + round256(sizeof(int32_t) * sm.size()) + round256(sizeof(int32_t) * sf.size());
-    void *ds = nullptr;
-    if ((rc = grow(sc, tabs + round256(extra_per_seg * (size_t)n_seg), &ds))) return rc;
-    char *sb = static_cast<char *>(ds);
-    lay(sb, n_seg);
+    seg_tables_layout(cv, *t, n_seg, n_items, ids != nullptr, extra_per_seg);
+    if ((rc = carve(sc, cv))) return rc;
     if ((rc = upload_small(ctx, const_cast<int64_t *>(t->offs), so.data(), sizeof(int64_t) * so.size()))) return rc;
     if ((rc = upload_small(ctx, const_cast<int32_t *>(t->map), sm.data(), sizeof(int32_t) * sm.size()))) return rc;
     if ((rc = upload_small(ctx, const_cast<int32_t *>(t->first), sf.data(), sizeof(int32_t) * sf.size()))) return rc;
@@ -834,38 +816,36 @@ int pols_least_squares_sharded(pols_ctx *const *ctxs, pols_comm *const *comms, i
         // the collectives on this device's stream.  Every rank takes part in every collective, shard or no shard.
         int rc2 = check_ctx(ctx);
         if (rc2) return done(rc2);
-        const size_t colb = round256(sz * (size_t)std::max<int64_t>(nrows, 1)), vb = round256((size_t)std::max<int64_t>(nrows, 1));
-        const size_t coefb = round256(sz * (size_t)std::max<int64_t>(sb.n_groups, 1) * kt), allb = round256(sz * (size_t)std::max<int64_t>(b->n_groups, 1) * kt);
-        const size_t statb = round256(sizeof(int32_t) * (size_t)std::max<int64_t>(sb.n_groups, 1));
-        const int n_in = 1 + b->n_features + (b->weights ? 1 : 0);
-        void *base = nullptr;
-        if ((rc2 = ensure_scratch(ctx, Work::Collective, colb * (size_t)(n_in + 2) + vb + coefb + allb + statb, &base))) return done(rc2);
-        char *q = static_cast<char *>(base);
-        auto put = [&](const void *src, size_t bytes, size_t slot) -> const void * {
-            char *d = q; q += slot;
-            if (src && bytes && hipMemcpyAsync(d, src, bytes, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) rc2 = POLS_ERR_HIP;
-            return src ? d : nullptr;
-        };
+        const size_t rows1 = (size_t)std::max<int64_t>(nrows, 1), groups1 = (size_t)std::max<int64_t>(sb.n_groups, 1);
+        const size_t colb = round256(sz * rows1);
         pols_batch db = sb;
         db.mem = POLS_MEM_DEVICE;
-        db.y = put(sb.y, sz * (size_t)nrows, colb);
-        std::vector<const void *> dx((size_t)b->n_features);
-        for (int j = 0; j < b->n_features; ++j) dx[(size_t)j] = put(xs[(size_t)j], sz * (size_t)nrows, colb);
-        db.x_cols = dx.data();
-        if (b->weights) db.weights = put(sb.weights, sz * (size_t)nrows, colb);
-        db.valid = b->valid ? static_cast<const uint8_t *>(put(sb.valid, (size_t)nrows, vb)) : nullptr;
-        if (!b->valid) q += vb;
-        if (rc2) { set_error("staging copy failed on device %d", ctx->device); return done(rc2); }
         pols_out so;
         std::memset(&so, 0, sizeof(so));
-        if (o->pred) so.pred = q;
-        q += colb;
-        if (o->resid) so.resid = q;
-        q += colb;
-        if (o->coef) so.coef = q;
-        q += coefb;
-        void *all_coef = q; q += allb;
-        if (o->status) so.status = reinterpret_cast<int32_t *>(q);
+        const void *dxs = nullptr;
+        void *all_coef = nullptr;
+        // the validity bytes and every output keep their room, wanted or not: a rank's buffer depends on the shard's shape alone
+        Carve cv;
+        cv.keep(db.y, colb, sb.y != nullptr);
+        cv.add(dxs, colb * (size_t)b->n_features);
+        if (b->weights) cv.add(db.weights, colb);
+        cv.keep(db.valid, rows1, b->valid != nullptr);
+        cv.keep(so.pred, colb, o->pred != nullptr);
+        cv.keep(so.resid, colb, o->resid != nullptr);
+        cv.keep(so.coef, sz * groups1 * kt, o->coef != nullptr);
+        cv.add(all_coef, sz * (size_t)std::max<int64_t>(b->n_groups, 1) * kt);
+        cv.keep(so.status, sizeof(int32_t) * groups1, o->status != nullptr);
+        if ((rc2 = carve(ctx, Work::Collective, cv))) return done(rc2);
+        auto put = [&](const void *dst, const void *src, size_t bytes) {
+            if (src && bytes && hipMemcpyAsync(const_cast<void *>(dst), src, bytes, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) rc2 = POLS_ERR_HIP;
+        };
+        put(db.y, sb.y, sz * (size_t)nrows);
+        std::vector<const void *> dx((size_t)b->n_features);
+        for (int j = 0; j < b->n_features; ++j) put(dx[(size_t)j] = column(dxs, colb, (size_t)j), xs[(size_t)j], sz * (size_t)nrows);
+        db.x_cols = dx.data();
+        if (b->weights) put(db.weights, sb.weights, sz * (size_t)nrows);
+        if (b->valid) put(db.valid, sb.valid, (size_t)nrows);
+        if (rc2) { set_error("staging copy failed on device %d", ctx->device); return done(rc2); }
         if (sb.n_groups > 0 && (rc2 = pols_least_squares(ctx, &db, p, &so))) return done(rc2);
         met[(size_t)r] = 1;
         if (!rendezvous()) { rcs[(size_t)r] = POLS_OK; return; }    // another rank failed: nobody enters the collectives (its error is reported)

@@ -43,35 +43,34 @@ static int dynamic_prologue(pols_ctx *ctx, const pols_batch *b, int null_policy,
     const bool scan = st->valid == nullptr && !b->null_free;   // no validity bytes from the caller: a null is a NaN, the policy decides
     const bool has_w = st->w != nullptr, icpt = b->add_intercept != 0;
     bool some_invalid = !scan, some_null = false;
-    const size_t sz = dtype_size(b->dtype), colb = round256(sz * (size_t)b->n_rows), vb = round256((size_t)b->n_rows);
-    char *base = nullptr;
+    const size_t colb = round256(dtype_size(b->dtype) * (size_t)b->n_rows);
     DynPrepArgs &pa = ds->pa;
     // (a caller's validity bytes without weights / intercept: the columns may still hold NaNs on the masked rows -- they are
     //  zero-filled like everywhere else, so that no prefix sum ever meets a NaN; null_free says there is nothing to fill)
     if (scan || has_w || icpt || (st->valid != nullptr && !b->null_free)) {
-        // Work::DynPrep: [flags][validity bytes][feature pointers in][column pointers out][sqrt(w)][target][k columns]
-        void *d = nullptr;
-        const size_t tabb = round256(sizeof(void *) * (size_t)std::max(k, 1));
-        if ((rc = ensure_scratch(ctx, Work::DynPrep, 256 + vb + 2 * tabb + colb * (size_t)(k + 2), &d))) return rc;
-        base = static_cast<char *>(d);
-        char *cols = base + 256 + vb + 2 * tabb;
+        // (the flag words lead on a 256-byte line of their own; sqrt(w) keeps its room without weights: the columns do not move)
+        const size_t tabb = sizeof(void *) * (size_t)std::max(k, 1);
+        void *xs = nullptr;
+        Carve cv;
+        cv.add(pa.flags, 256);
+        cv.add(pa.valid_out, (size_t)b->n_rows);
+        cv.add(pa.xtab, tabb);
+        cv.add(pa.xout, tabb);
+        cv.keep(pa.sw_out, colb, has_w);
+        cv.add(pa.y_out, colb);
+        cv.add(xs, colb * (size_t)k);
+        if ((rc = carve(ctx, Work::DynPrep, cv))) return rc;
         std::vector<void *> outp((size_t)k);
-        for (int j = 0; j < k; ++j) outp[(size_t)j] = cols + colb * (size_t)(2 + j);
-        if ((rc = upload_small(ctx, base + 256 + vb, st->x.data(), sizeof(void *) * (size_t)b->n_features))) return rc;
-        if ((rc = upload_small(ctx, base + 256 + vb + tabb, outp.data(), sizeof(void *) * (size_t)k))) return rc;
+        for (int j = 0; j < k; ++j) outp[(size_t)j] = column(xs, colb, (size_t)j);
+        if ((rc = upload_small(ctx, const_cast<void **>(pa.xtab), st->x.data(), sizeof(void *) * (size_t)b->n_features))) return rc;
+        if ((rc = upload_small(ctx, const_cast<void **>(pa.xout), outp.data(), sizeof(void *) * (size_t)k))) return rc;
         pa.y = st->y; pa.w = st->w;
-        pa.xtab = reinterpret_cast<const void *const *>(base + 256 + vb);
         pa.k_user = b->n_features; pa.add_intercept = icpt ? 1 : 0; pa.null_policy = null_policy; pa.n_rows = b->n_rows;
-        pa.valid_out = reinterpret_cast<uint8_t *>(base + 256);
-        pa.flags = reinterpret_cast<int32_t *>(base);
-        pa.sw_out = has_w ? cols : nullptr;
-        pa.y_out = cols + colb;
-        pa.xout = reinterpret_cast<void *const *>(base + 256 + vb + tabb);
         if (scan) {
-            POLS_HIP(hipMemsetAsync(base, 0, 256, ctx->stream));
+            POLS_HIP(hipMemsetAsync(pa.flags, 0, 256, ctx->stream));
             if ((rc = dyn_scan_launch(ctx, b->dtype, pa))) return rc;
             int32_t flags[2] = {0, 0};
-            POLS_HIP(hipMemcpyAsync(flags, base, sizeof(flags), hipMemcpyDeviceToHost, ctx->stream));
+            POLS_HIP(hipMemcpyAsync(flags, pa.flags, sizeof(flags), hipMemcpyDeviceToHost, ctx->stream));
             POLS_HIP(hipStreamSynchronize(ctx->stream));   // the host decides which path runs (mask-free tables are cached)
             some_invalid = flags[0] > 0;
             some_null = flags[1] > 0;
@@ -114,20 +113,20 @@ static int dynamic_rewrite_deferred(pols_ctx *ctx, const pols_batch *b, Staged *
 // inversion: a few hundred long chunks instead of thousands of 64-row ones
 static int64_t hbm_state_chunk(int64_t n_rows) { return std::max<int64_t>(64, (n_rows + 383) / 384); }
 
-// Work::Tables of the dynamic entries: [128 doubles: RLS prior mean][column pointer table for more than 32 features]
-static int dynamic_tables(pols_ctx *ctx, void **base) {
-    return ensure_scratch(ctx, Work::Tables, sizeof(double) * K4Y_KMAX + sizeof(void *) * K4Y_KMAX, base);
+// Work::Tables of the dynamic entries: the RLS prior mean, then the column pointer table for more than 32 features
+static int dynamic_tables(pols_ctx *ctx, const double *&mean0, const void *const *&xtab) {
+    Carve cv;
+    cv.add(mean0, sizeof(double) * K4Y_KMAX);
+    cv.add(xtab, sizeof(void *) * K4Y_KMAX);
+    return carve(ctx, Work::Tables, cv);
 }
 static int upload_column_table(pols_ctx *ctx, const Staged &st, int k, K4Args *a) {
     for (int j = 0; j < std::min(k, (int)POLS_MAX_FEATURES); ++j) a->x[j] = st.x[j];
     if (k <= POLS_MAX_FEATURES) return POLS_OK;
-    void *d = nullptr;
-    int rc = dynamic_tables(ctx, &d);
+    const double *mean0 = nullptr;
+    int rc = dynamic_tables(ctx, mean0, a->xtab);
     if (rc) return rc;
-    char *tab = static_cast<char *>(d) + sizeof(double) * K4Y_KMAX;
-    if ((rc = upload_small(ctx, tab, st.x.data(), sizeof(void *) * (size_t)k))) return rc;
-    a->xtab = reinterpret_cast<const void *const *>(tab);
-    return POLS_OK;
+    return upload_small(ctx, const_cast<void **>(a->xtab), st.x.data(), sizeof(void *) * (size_t)k);
 }
 
 // Sequence-start bytes of the row-parallel dynamic kernels, cached per uploaded offsets.
@@ -265,27 +264,23 @@ static int walk_chunks(const pols_batch *b, const uint8_t *hv, int64_t mp, int64
 
 // Validity bytes that live on the device: cnt / vidx are built there and the uploaded groups -- which carry the null-free constants
 // mpv = min_periods, gate_n = min(rows, min_periods) -- are patched from the bytes (all_nan only depends on the group's length: n_valid
-// never exceeds min_periods).  `scratch`: slab counts, slab bases and compacted offsets of the pass, behind the tables.
-static int patch_tables_on_device(pols_ctx *ctx, const pols_batch *b, int64_t mp, void *groups, int32_t *cnt, int32_t *vidx, char *scratch) {
+// never exceeds min_periods).  The slab counts, slab bases and compacted offsets of the pass live behind the tables.
+static int patch_tables_on_device(pols_ctx *ctx, const pols_batch *b, int64_t mp, const ChunkTables &t) {
     const int64_t N = b->n_rows, n_slabs = (N + 255) / 256;
     int rc;
     RowCompactArgs ra;
     std::memset(&ra, 0, sizeof(ra));
     ra.valid = b->valid; ra.offs = static_cast<const int64_t *>(ctx->offsets.buf.ptr);
     ra.n_rows = N; ra.n_groups = b->n_groups; ra.n_slabs = n_slabs;
-    ra.slab_cnt = reinterpret_cast<uint32_t *>(scratch);
-    scratch += round256(sizeof(uint32_t) * (size_t)n_slabs);
-    ra.slab_base = reinterpret_cast<int64_t *>(scratch);
-    scratch += round256(sizeof(int64_t) * (size_t)(n_slabs + 1));
-    ra.c_offs = reinterpret_cast<int64_t *>(scratch);
+    ra.slab_cnt = t.slab_cnt; ra.slab_base = t.slab_base; ra.c_offs = t.c_offs;
     ra.slab_gfirst = nullptr;
     if ((rc = row_compact_offsets_launch(ctx, ra))) return rc;
     ValidTablesArgs va;
     std::memset(&va, 0, sizeof(va));
     va.valid = b->valid; va.offs = ra.offs; va.n_rows = N; va.n_groups = b->n_groups; va.n_slabs = n_slabs;
     va.slab_base = ra.slab_base; va.c_offs = ra.c_offs;
-    va.cnt = cnt; va.vidx = vidx;
-    va.groups = groups; va.min_periods = mp;
+    va.cnt = t.cnt; va.vidx = t.vidx;
+    va.groups = t.groups; va.min_periods = mp;
     return valid_tables_launch(ctx, va);
 }
 
@@ -314,56 +309,43 @@ static int build_chunk_tables(pols_ctx *ctx, const pols_batch *b, int64_t mp, in
     const int64_t chunk_len = std::min<int64_t>(std::max(max_chunk, min_chunk), std::max<int64_t>(min_chunk, N / 16384));
     auto &cc = ctx->chunk_cache;
     const bool cacheable = !hv && !dev_tables && uploaded;
-    if (cacheable && cc.valid && cc.offs_id == ctx->offs_id && cc.n_groups == b->n_groups &&
-        cc.n_rows == N && cc.mp == mp && cc.chunk_len == (int32_t)chunk_len) {      // same frame as the last call
-        void *tot = nullptr;
-        if ((rc = ensure_scratch(ctx, Work::Gram, sizeof(double) * (size_t)slots * std::max<size_t>(1, (size_t)cc.n_chunks), &tot))) return rc;
-        const char *tp = static_cast<const char *>(cc.buf.ptr);
-        a->groups = reinterpret_cast<const K4Group *>(tp);
-        a->chunks = reinterpret_cast<const K4Chunk *>(tp + cc.b_groups);
-        a->order = reinterpret_cast<const int32_t *>(tp + cc.b_groups + round256(sizeof(K4Chunk) * (size_t)cc.n_chunks));
-        a->cnt = nullptr; a->vidx = nullptr;
-        a->n_chunks = cc.n_chunks; a->n_groups = (int32_t)b->n_groups;
+    ChunkTables t;
+    Carve cv;
+    void *tot = nullptr;
+    auto hand_out = [&](int64_t n_chunks) {
+        a->groups = reinterpret_cast<const K4Group *>(t.groups);
+        a->chunks = reinterpret_cast<const K4Chunk *>(t.chunks);
+        a->order = t.order; a->cnt = t.cnt; a->vidx = t.vidx;
+        a->n_chunks = n_chunks; a->n_groups = (int32_t)b->n_groups;
         a->totals = static_cast<double *>(tot);
         a->chunk_len = (int32_t)chunk_len;
+    };
+    if (cacheable && cc.valid && cc.offs_id == ctx->offs_id && cc.n_groups == b->n_groups &&
+        cc.n_rows == N && cc.mp == mp && cc.chunk_len == (int32_t)chunk_len) {      // same frame as the last call
+        if ((rc = ensure_scratch(ctx, Work::Gram, sizeof(double) * (size_t)slots * std::max<size_t>(1, (size_t)cc.n_chunks), &tot))) return rc;
+        chunk_tables_layout(cv, t, sizeof(K4Group), sizeof(K4Chunk), b->n_groups, cc.n_chunks, N, false, false);
+        cv.place(cc.buf.ptr);
+        hand_out(cc.n_chunks);
         return POLS_OK;
     }
     ChunkWalk w;
     if ((rc = walk_chunks(b, hv, mp, chunk_len, &w))) return rc;
-    // the table: [groups][chunks][order][cnt][vidx][scratch of the device-validity pass]
-    const size_t b_groups = round256(sizeof(K4Group) * w.groups.size());
-    const size_t b_chunks = round256(sizeof(K4Chunk) * w.chunks.size());
-    const size_t b_order = round256(sizeof(int32_t) * w.order.size());
-    const size_t b_cnt = (hv || dev_tables) ? round256(sizeof(int32_t) * (size_t)N) : 0;
-    const int64_t n_slabs = (N + 255) / 256;
-    const size_t b_sc = dev_tables ? round256(sizeof(uint32_t) * (size_t)n_slabs) : 0, b_sb = dev_tables ? round256(sizeof(int64_t) * (size_t)(n_slabs + 1)) : 0,
-                 b_co = dev_tables ? round256(sizeof(int64_t) * (size_t)(b->n_groups + 1)) : 0;
-    void *tab = nullptr, *tot = nullptr;
+    chunk_tables_layout(cv, t, sizeof(K4Group), sizeof(K4Chunk), b->n_groups, (int64_t)w.chunks.size(), N, hv || dev_tables, dev_tables);
     cc.valid = false;                                  // the table is about to be rewritten
-    if ((rc = grow(cc, b_groups + b_chunks + b_order + 2 * b_cnt + b_sc + b_sb + b_co + 256, &tab))) return rc;
+    if ((rc = carve(cc, cv))) return rc;
     if ((rc = ensure_scratch(ctx, Work::Gram, sizeof(double) * (size_t)slots * std::max<size_t>(1, w.chunks.size()), &tot))) return rc;
-    char *t_groups = static_cast<char *>(tab), *t_chunks = t_groups + b_groups, *t_order = t_chunks + b_chunks, *t_cnt = t_order + b_order,
-         *t_vidx = t_cnt + b_cnt;
-    if ((rc = upload_small(ctx, t_groups, w.groups.data(), sizeof(K4Group) * w.groups.size()))) return rc;   // locals: through the pinned ring
-    if ((rc = upload_small(ctx, t_chunks, w.chunks.data(), sizeof(K4Chunk) * w.chunks.size()))) return rc;
-    if ((rc = upload_small(ctx, t_order, w.order.data(), sizeof(int32_t) * w.order.size()))) return rc;
+    if ((rc = upload_small(ctx, t.groups, w.groups.data(), sizeof(K4Group) * w.groups.size()))) return rc;   // locals: through the pinned ring
+    if ((rc = upload_small(ctx, t.chunks, w.chunks.data(), sizeof(K4Chunk) * w.chunks.size()))) return rc;
+    if ((rc = upload_small(ctx, t.order, w.order.data(), sizeof(int32_t) * w.order.size()))) return rc;
     if (hv) {
-        if ((rc = upload_small(ctx, t_cnt, w.cnt.data(), sizeof(int32_t) * (size_t)N))) return rc;
-        if ((rc = upload_small(ctx, t_vidx, w.vidx.data(), sizeof(int32_t) * (size_t)N))) return rc;
+        if ((rc = upload_small(ctx, t.cnt, w.cnt.data(), sizeof(int32_t) * (size_t)N))) return rc;
+        if ((rc = upload_small(ctx, t.vidx, w.vidx.data(), sizeof(int32_t) * (size_t)N))) return rc;
     }
-    if (dev_tables && (rc = patch_tables_on_device(ctx, b, mp, t_groups, reinterpret_cast<int32_t *>(t_cnt), reinterpret_cast<int32_t *>(t_vidx), t_vidx + b_cnt))) return rc;
-    a->groups = reinterpret_cast<const K4Group *>(t_groups);
-    a->chunks = reinterpret_cast<const K4Chunk *>(t_chunks);
-    a->order = reinterpret_cast<const int32_t *>(t_order);
-    a->cnt = (hv || dev_tables) ? reinterpret_cast<const int32_t *>(t_cnt) : nullptr;
-    a->vidx = (hv || dev_tables) ? reinterpret_cast<const int32_t *>(t_vidx) : nullptr;
-    a->n_chunks = (int64_t)w.chunks.size();
-    a->n_groups = (int32_t)b->n_groups;
-    a->totals = static_cast<double *>(tot);
-    a->chunk_len = (int32_t)chunk_len;
+    if (dev_tables && (rc = patch_tables_on_device(ctx, b, mp, t))) return rc;
+    hand_out((int64_t)w.chunks.size());
     if (cacheable) {
         cc.offs_id = ctx->offs_id; cc.n_groups = b->n_groups; cc.n_rows = N; cc.mp = mp; cc.n_chunks = a->n_chunks;
-        cc.chunk_len = (int32_t)chunk_len; cc.valid = true; cc.b_groups = b_groups;
+        cc.chunk_len = (int32_t)chunk_len; cc.valid = true;
     }
     return POLS_OK;
 }
@@ -434,16 +416,6 @@ static int chunk_kernel_args(DynCall &c, int64_t mp, const ChunkPlan &pl, K4Args
     return upload_column_table(c.ctx, c.st, c.k, a);
 }
 
-// a scratch area handed out piece by piece
-struct Carver {
-    char *p;
-    template <typename T> T *take(size_t bytes) {
-        T *q = reinterpret_cast<T *>(p);
-        p += bytes;
-        return q;
-    }
-};
-
 // ------------------------------------------------------------------ recursive least squares
 // Rows: the row-parallel, read-once kernel K3c (k3c_scan.hip) up to 10 features, whatever the sequence lengths; Scan: the chunk-parallel
 // kernels (K3s lane-per-chunk / K3sw, K3p wave-per-chunk from 9 features / K3x, K3y workgroup-per-chunk from 33); Seq: K3, the
@@ -478,12 +450,16 @@ static int rls_route_rows(RlsCall &c) {
     const int kf = c.k;
     const int64_t N = b->n_rows, tile_rows = k3c_tile_rows(kf), n_tiles = (N + tile_rows - 1) / tile_rows;
     const int64_t n_blocks = (n_tiles + 63) / 64;
-    const size_t b_rec = round256(sizeof(double) * K3C_NCP * (size_t)n_tiles), b_int = round256(sizeof(int32_t) * (size_t)n_tiles),
-                 b_brec = round256(sizeof(double) * K3C_NCP * (size_t)n_blocks), b_bint = round256(sizeof(int32_t) * (size_t)n_blocks);
-    void *d = nullptr;
-    if ((rc = ensure_scratch(ctx, Work::K3cRecords, 2 * b_rec + 2 * b_int + 2 * b_brec + b_bint, &d))) return rc;
+    const size_t b_rec = sizeof(double) * K3C_NCP * (size_t)n_tiles, b_int = sizeof(int32_t) * (size_t)n_tiles,
+                 b_brec = sizeof(double) * K3C_NCP * (size_t)n_blocks, b_bint = sizeof(int32_t) * (size_t)n_blocks;
     K3cArgs a;
     std::memset(&a, 0, sizeof(a));
+    Carve cv;
+    cv.add(a.rec, b_rec); cv.add(a.carry, b_rec);
+    cv.add(a.rec_closed, b_int); cv.add(a.carry_open, b_int);
+    cv.add(a.brec, b_brec); cv.add(a.bcarry, b_brec);
+    cv.add(a.brec_closed, b_bint);
+    if ((rc = carve(ctx, Work::K3cRecords, cv))) return rc;
     if ((rc = ensure_start_flags(ctx, c.d_offs, b->n_groups, N, &a.start))) return rc;
     // No sequence longer than a tile (less the three rows a tile may start before its first sequence): tiles are cut at sequence
     // starts -- whole sequences, first fit in frame order -- and need no carry-in, so ONE launch reads and writes the frame once.
@@ -494,11 +470,6 @@ static int rls_route_rows(RlsCall &c) {
     for (int j = 0; j < kf; ++j) a.x[j] = st.x[j];
     a.n_rows = N; a.coef = st.coef; a.pred = st.pred; a.mean0 = c.mean0;
     a.ff = c.ff; a.p0 = c.p0;
-    Carver area{static_cast<char *>(d)};
-    a.rec = area.take<double>(b_rec); a.carry = area.take<double>(b_rec);
-    a.rec_closed = area.take<int32_t>(b_int); a.carry_open = area.take<int32_t>(b_int);
-    a.brec = area.take<double>(b_brec); a.bcarry = area.take<double>(b_brec);
-    a.brec_closed = area.take<int32_t>(b_bint);
     a.n_tiles = n_packed ? n_packed : n_tiles; a.k = kf;
     a.all_closed = n_packed || c.max_rows <= tile_rows ? 1 : 0;   // (any tile_rows consecutive rows then hold a sequence start)
     // A finite half-life bounds how far back a row's state reaches: with ff^H <= 2^-36 for H = 256 .. 2 048 rows (half_life <= 56.9) a tile
@@ -711,35 +682,30 @@ static int rolling_route_compacted(RollingCall &c, const RollingFacts &f, bool *
     *declined = false;
     const int64_t N = b->n_rows, G = b->n_groups, n_slabs = (N + 255) / 256;
     const size_t sz = dtype_size(b->dtype), colb = round256(sz * (size_t)N);
-    const size_t b_cnt = round256(sizeof(uint32_t) * (size_t)n_slabs), b_base = round256(sizeof(int64_t) * (size_t)(n_slabs + 1)),
-                 b_offs = round256(sizeof(int64_t) * (size_t)(G + 1)), b_gf = round256(sizeof(int64_t) * (size_t)n_slabs),
-                 b_tab = round256(sizeof(void *) * (size_t)(k + 1));
     const bool on_tiles = compacted_fits_tiles(f);
     const bool gather = on_tiles && N < ((int64_t)1 << 31) && ctx->opt.rolling_engine != RollingEngine::Scatter;
-    void *d = nullptr;
-    if ((rc = ensure_scratch(ctx, Work::RowCompact, b_cnt + b_base + b_offs + b_gf + 2 * b_tab + (gather ? 0 : colb * (size_t)(k + 1)), &d))) return rc;
-    // Work::RowCompact: [slab counts][slab bases][compacted offsets][slab -> group's compacted offset][column pointers in][out][k + 1 compacted columns]
-    Carver area{static_cast<char *>(d)};
     RowCompactArgs ra;
     std::memset(&ra, 0, sizeof(ra));
-    ra.slab_cnt = area.take<uint32_t>(b_cnt);
-    ra.slab_base = area.take<int64_t>(b_base);
-    ra.c_offs = area.take<int64_t>(b_offs);
-    ra.slab_gfirst = area.take<int64_t>(b_gf);
-    void *tab_in = area.take<void>(b_tab), *tab_out = area.take<void>(b_tab);
-    char *cols = area.p;
+    char *cols = nullptr;                              // k + 1 compacted columns: none when the tile kernel gathers
+    Carve cv;
+    cv.add(ra.slab_cnt, sizeof(uint32_t) * (size_t)n_slabs);
+    cv.add(ra.slab_base, sizeof(int64_t) * (size_t)(n_slabs + 1));
+    cv.add(ra.c_offs, sizeof(int64_t) * (size_t)(G + 1));
+    cv.add(ra.slab_gfirst, sizeof(int64_t) * (size_t)n_slabs);
+    cv.add(ra.in, sizeof(void *) * (size_t)(k + 1));
+    cv.add(ra.out, sizeof(void *) * (size_t)(k + 1));
+    cv.add(cols, gather ? 0 : colb * (size_t)(k + 1));
+    if ((rc = carve(ctx, Work::RowCompact, cv))) return rc;
     std::vector<const void *> inp((size_t)k + 1);
     std::vector<void *> outp((size_t)k + 1);
     inp[0] = st.y;
     for (int j = 0; j < k; ++j) inp[(size_t)j + 1] = st.x[(size_t)j];
-    for (int j = 0; j <= k; ++j) outp[(size_t)j] = gather ? nullptr : cols + colb * (size_t)j;
-    if ((rc = upload_small(ctx, tab_in, inp.data(), sizeof(void *) * (size_t)(k + 1)))) return rc;
-    if ((rc = upload_small(ctx, tab_out, outp.data(), sizeof(void *) * (size_t)(k + 1)))) return rc;
+    for (int j = 0; j <= k; ++j) outp[(size_t)j] = gather ? nullptr : column(cols, colb, (size_t)j);
+    if ((rc = upload_small(ctx, const_cast<void **>(ra.in), inp.data(), sizeof(void *) * (size_t)(k + 1)))) return rc;
+    if ((rc = upload_small(ctx, const_cast<void **>(ra.out), outp.data(), sizeof(void *) * (size_t)(k + 1)))) return rc;
     ra.valid = st.valid;
     if ((rc = ensure_start_flags(ctx, c.d_offs, G, N, &ra.start))) return rc;
     ra.offs = c.d_offs; ra.n_rows = N; ra.n_groups = G; ra.n_slabs = n_slabs;
-    ra.in = static_cast<const void *const *>(tab_in);
-    ra.out = static_cast<void *const *>(tab_out);
     ra.n_cols = k + 1; ra.k = k;
     if ((rc = row_compact_offsets_launch(ctx, ra))) return rc;
     std::vector<int64_t> c_offs((size_t)G + 1);
@@ -806,26 +772,25 @@ static int rolling_route_masked(RollingCall &c, bool *declined) {
     int rc;
     *declined = false;
     const int64_t N = b->n_rows, G = b->n_groups, n_slabs = (N + 255) / 256, n_blk = (n_slabs + 1023) / 1024;
-    const size_t b_r2 = round256(sizeof(uint16_t) * (size_t)N), b_sol = round256((size_t)N + 4), b_sc = round256(sizeof(uint32_t) * (size_t)n_slabs),
-                 b_s8 = round256(sizeof(int64_t) * (size_t)(n_slabs + 1)), b_g8 = round256(sizeof(int64_t) * (size_t)(G + 1)),
-                 b_g4 = round256(sizeof(int32_t) * (size_t)G), b_blk = round256(sizeof(unsigned long long) * 2 * (size_t)n_blk);
-    void *d = nullptr;
-    if ((rc = ensure_scratch(ctx, Work::RowCompact, 256 + b_blk + 2 * b_r2 + b_sol + b_sc + 3 * b_s8 + 2 * b_g8 + b_g4, &d))) return rc;   // (Work::RowCompact: the compaction's, never live here)
-    Carver area{static_cast<char *>(d)};
+    const size_t b_blk = sizeof(unsigned long long) * (size_t)n_blk, b_r2 = sizeof(uint16_t) * (size_t)N,
+                 b_s8 = sizeof(int64_t) * (size_t)(n_slabs + 1), b_g8 = sizeof(int64_t) * (size_t)(G + 1);
     RollMaskArgs ma;
     std::memset(&ma, 0, sizeof(ma));
-    ma.flag = area.take<int32_t>(256);
-    ma.blk_cnt = area.take<unsigned long long>(b_blk); ma.blk_last = ma.blk_cnt + n_blk;
-    ma.incl = area.take<uint16_t>(b_r2);
-    ma.code = area.take<uint16_t>(b_r2);
-    ma.solved = area.take<uint8_t>(b_sol);
-    ma.slab_cnt = area.take<uint32_t>(b_sc);
-    ma.slab_base = area.take<int64_t>(b_s8);
-    ma.slab_last = area.take<int64_t>(b_s8);
-    ma.slab_carry = area.take<int64_t>(b_s8);
-    ma.c_offs = area.take<int64_t>(b_g8);
-    ma.g_mpv = area.take<int64_t>(b_g8);
-    ma.g_gate = area.take<int32_t>(b_g4);
+    Carve cv;
+    cv.add(ma.flag, 256);                              // the flag word on a line of its own
+    cv.add(ma.blk_cnt, 2 * b_blk);                     // ... and blk_last, its second half
+    cv.add(ma.incl, b_r2);
+    cv.add(ma.code, b_r2);
+    cv.add(ma.solved, (size_t)N + 4);
+    cv.add(ma.slab_cnt, sizeof(uint32_t) * (size_t)n_slabs);
+    cv.add(ma.slab_base, b_s8);
+    cv.add(ma.slab_last, b_s8);
+    cv.add(ma.slab_carry, b_s8);
+    cv.add(ma.c_offs, b_g8);
+    cv.add(ma.g_mpv, b_g8);
+    cv.add(ma.g_gate, sizeof(int32_t) * (size_t)G);
+    if ((rc = carve(ctx, Work::RowCompact, cv))) return rc;   // (Work::RowCompact: the compaction's, never live here)
+    ma.blk_last = column(ma.blk_cnt, b_blk, 1);
     ma.valid = st.valid; ma.offs = c.d_offs; ma.n_rows = N; ma.n_groups = G; ma.n_slabs = n_slabs;
     ma.window = c.window; ma.min_periods = c.min_periods;
     if ((rc = roll_mask_tables_launch(ctx, ma))) return rc;
@@ -890,10 +855,9 @@ int pols_recursive_least_squares(pols_ctx *ctx, const pols_batch *b, const pols_
     c.ff = p->has_half_life ? std::exp(std::log(0.5) / p->half_life) : 1.0;   // ls.rs:513-517
     c.p0 = p->initial_state_covariance;
     if (p->initial_state_mean) {
-        void *d = nullptr;
-        if ((rc = dynamic_tables(ctx, &d))) return rc;
-        if ((rc = upload_small(ctx, d, p->initial_state_mean, sizeof(double) * c.k))) return rc;   // the host array belongs to the caller (k values)
-        c.mean0 = static_cast<const double *>(d);
+        const void *const *xtab = nullptr;
+        if ((rc = dynamic_tables(ctx, c.mean0, xtab))) return rc;
+        if ((rc = upload_small(ctx, const_cast<double *>(c.mean0), p->initial_state_mean, sizeof(double) * c.k))) return rc;   // the host array belongs to the caller (k values)
     }
     switch (route) {
     case RlsRoute::Rows: return rls_route_rows(c);

@@ -18,7 +18,6 @@
 #include "k7c_cluster.hpp"
 #pragma GCC visibility push(hidden)     // host helpers of this file alone: nothing of them is exported
 #include "k17_split.hpp"
-#include "scratch_carve.hpp"
 #pragma GCC visibility pop
 
 using namespace pols;
@@ -80,14 +79,6 @@ template <typename A> void fit_frame(A &a, const pols_batch *b, const FitCall &f
 }
 template <typename A> void fit_segments(A &a, const SegTables &sg) {
     if (sg.n_seg > 0) { a.seg_offs = sg.offs; a.seg_map = sg.map; a.seg_first = sg.first; a.n_seg = sg.n_seg; }
-}
-
-// One work buffer for the regions declared on `cv`: the allocation of their total, then every slot points into it.
-int carve(pols_ctx *ctx, Work w, const Carve &cv) {
-    void *base = nullptr;
-    int rc = ensure_scratch(ctx, w, cv.total(), &base);
-    if (!rc) cv.place(base);
-    return rc;
 }
 
 // The entry's own outputs, each registered once: the caller's pointer, the slot of the argument struct, the bytes.  place(): the

@@ -18,12 +18,28 @@
 #include "common.hpp"
 #include "dyn_prep.hpp"
 #include "k8_wide.hpp"
+#include "table_layout.hpp"
 
 namespace pols {
 
 int check_ctx(pols_ctx *ctx);
 int check_batch(const pols_batch *b, const pols_out *o, int max_features = POLS_MAX_FEATURES);
 inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+// One work buffer for the regions declared on `cv` (scratch_carve.hpp): ONE allocation of their total, then every slot points into it.
+// The buffer is a Work member of the context, or one that grow() keeps across calls (a cached table, the K3c granules).
+static inline int carve(pols_ctx *ctx, Work w, const Carve &cv) {
+    void *base = nullptr;
+    const int rc = ensure_scratch(ctx, w, cv.total(), &base);
+    if (!rc) cv.place(base);
+    return rc;
+}
+static inline int carve(CachedTable &t, const Carve &cv) {
+    void *base = nullptr;
+    const int rc = grow(t, cv.total(), &base);
+    if (!rc) cv.place(base);
+    return rc;
+}
 
 // Host-resident batch: stage every column into device scratch (PCIe-inclusive path).
 struct Staged {
@@ -121,13 +137,7 @@ int wide_static(pols_ctx *ctx, const pols_batch *b, const pols_ols_params *p, po
 // kernels, so ONE regression over a 10M-row frame used to be one CU's work.  Groups longer than two segments are cut into pieces
 // of about N / (8 x CUs) rows (256-row multiples), the others are one segment each; tables in ctx->seg_cache -- segment offsets,
 // segment -> group, group -> first segment -- followed by `extra_per_seg` bytes per segment for the caller's partial results.
-// n_seg = 0: nothing is longer than two segments (or POLS_NO_SPLIT).  Cached per frame.
-struct SegTables {
-    const int64_t *offs = nullptr;
-    const int32_t *map = nullptr, *first = nullptr;
-    int64_t n_seg = 0, max_len = 0, max_seg = 0;      // rows of the longest segment; most segments of one group
-    char *extra = nullptr;
-};
+// n_seg = 0: nothing is longer than two segments (or POLS_NO_SPLIT).  Cached per frame.  (SegTables and its layout: table_layout.hpp)
 // ids (size classes): the tables cover only the listed groups (ascending), `offs` holds (start, end) PAIRS per segment, `map` gives the segment's
 // position in the list and `first` is indexed by list position; class_key tells such tables apart in the cache (0 = the whole frame).
 int ensure_segments(pols_ctx *ctx, const pols_batch *b, int64_t max_rows, size_t extra_per_seg, SegTables *t,

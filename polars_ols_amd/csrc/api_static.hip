@@ -441,11 +441,7 @@ static int run_stream(StaticCall &c, const std::vector<int32_t> *ids, const int3
     int rc;
     const int64_t ng = ids ? (int64_t)ids->size() : b->n_groups;
     const int64_t mr = ids ? cls_max_rows : c.max_rows;
-    void *scr = nullptr;
     const size_t nz = (size_t)kt + 1;
-    const size_t gram_bytes = round256(sizeof(double) * nz * nz * (size_t)ng);
-    const size_t c64_bytes = round256(sizeof(double) * (size_t)kt * (size_t)ng);
-    const size_t nv_bytes = nulls ? round256(sizeof(double) * (size_t)b->n_groups) : 0;
     // Few long groups (ONE regression over a whole frame is the reference's first README example): a group is one workgroup in
     // the Gram and the prediction pass, so a 10M-row group used to be one CU's work -- 94 ms.  Long groups are cut into segments
     // (segment offsets, one workgroup each; the segments' Gram matrices are summed per group in segment order), sized so that the
@@ -455,9 +451,13 @@ static int run_stream(StaticCall &c, const std::vector<int32_t> *ids, const int3
     const bool split = sg.n_seg > 0;
     // few groups of hundreds of segments: the segment sums go through 16 slices per group (gram_reduce_launch)
     const int n_slices = (split && sg.max_seg >= 256 && ng <= 256) ? 16 : 1;
-    const size_t slice_bytes = n_slices > 1 ? round256(sizeof(double) * nz * nz * (size_t)n_slices * (size_t)ng) : 0;
-    if ((rc = ensure_scratch(ctx, Work::Gram, gram_bytes + c64_bytes + nv_bytes + slice_bytes, &scr))) return rc;
-    double *nvalid = nulls ? reinterpret_cast<double *>(static_cast<char *>(scr) + gram_bytes + c64_bytes) : nullptr;
+    double *gram = nullptr, *coef64 = nullptr, *nvalid = nullptr, *slices = nullptr;
+    Carve cv;
+    cv.keep(gram, sizeof(double) * nz * nz * (size_t)ng);
+    cv.keep(coef64, sizeof(double) * (size_t)kt * (size_t)ng);
+    cv.add(nvalid, nulls ? sizeof(double) * (size_t)b->n_groups : 0);
+    cv.add(slices, n_slices > 1 ? sizeof(double) * nz * nz * (size_t)n_slices * (size_t)ng : 0);
+    if ((rc = carve(ctx, Work::Gram, cv))) return rc;
     const int64_t *seg_offs = split ? sg.offs : c.d_offs;
     const int64_t n_seg = split ? sg.n_seg : ng;
     double *gram_part = reinterpret_cast<double *>(sg.extra);
@@ -465,7 +465,7 @@ static int run_stream(StaticCall &c, const std::vector<int32_t> *ids, const int3
     GramArgs ga;
     fill_columns(ga, c);
     ga.offs = seg_offs; ga.n_groups = n_seg; ga.n_rows = b->n_rows; ga.offs_pairs = ids ? 1 : 0;
-    ga.gram = split ? gram_part : static_cast<double *>(scr);
+    ga.gram = split ? gram_part : gram;
     ga.kt = kt;
     ga.valid = st.valid; ga.null_policy = c.pol; ga.nvalid = split ? nv_part : nvalid;
     if ((rc = gram_stream_launch(ctx, b->dtype, ga))) return rc;
@@ -473,17 +473,17 @@ static int run_stream(StaticCall &c, const std::vector<int32_t> *ids, const int3
         GramReduceArgs ra;
         std::memset(&ra, 0, sizeof(ra));
         ra.part = gram_part; ra.nv_part = nv_part; ra.first = sg.first;
-        ra.gram = static_cast<double *>(scr); ra.nvalid = nvalid; ra.n_groups = ng; ra.nz2 = (int32_t)(nz * nz);
+        ra.gram = gram; ra.nvalid = nvalid; ra.n_groups = ng; ra.nz2 = (int32_t)(nz * nz);
         ra.max_segments = (int32_t)std::min<int64_t>(1 << 30, sg.max_seg);
-        if (n_slices > 1) { ra.slices = reinterpret_cast<double *>(static_cast<char *>(scr) + gram_bytes + c64_bytes + nv_bytes); ra.n_slices = n_slices; }
+        if (n_slices > 1) { ra.slices = slices; ra.n_slices = n_slices; }
         if ((rc = gram_reduce_launch(ctx, ra))) return rc;
-        ga.gram = static_cast<double *>(scr);
+        ga.gram = gram;
         ctx->last_kernel += "_split";
     }
     CdArgs ca;
     std::memset(&ca, 0, sizeof(ca));
     ca.gram = ga.gram; ca.offs = c.d_offs; ca.n_groups = ng; ca.glist = d_ids;
-    ca.coef = st.coef; ca.coef64 = reinterpret_cast<double *>(static_cast<char *>(scr) + gram_bytes);
+    ca.coef = st.coef; ca.coef64 = coef64;
     ca.status = st.status;
     ca.alpha = p->alpha; ca.l1_ratio = c.plan.enet_l1; ca.tol = p->tol; ca.max_iter = p->max_iter;
     ca.positive = p->positive ? 1 : 0; ca.active_set = (p->solve_method == POLS_SOLVE_CD_ACTIVE_SET) ? 1 : 0; ca.kt = kt;
@@ -696,14 +696,17 @@ int wide_static(pols_ctx *ctx, const pols_batch *b, const pols_ols_params *p, po
         yptr.assign(y_cols, y_cols + m);
         if (pred_cols) pptr.assign(pred_cols, pred_cols + m);
         if (host) {
-            void *mt = nullptr;
-            if ((rc = ensure_scratch(ctx, Work::HostStaged, colb_mt * (size_t)m * (pred_cols ? 2 : 1), &mt))) return rc;
-            char *q = static_cast<char *>(mt);
+            char *ys = nullptr, *ps = nullptr;
+            Carve mt;
+            mt.keep(ys, colb_mt * (size_t)m);
+            if (pred_cols) mt.keep(ps, colb_mt * (size_t)m);
+            if ((rc = carve(ctx, Work::HostStaged, mt))) return rc;
             for (int t = 0; t < m; ++t) {
-                POLS_HIP(hipMemcpyAsync(q, y_cols[t], dtype_size(b->dtype) * (size_t)b->n_rows, hipMemcpyHostToDevice, ctx->stream));
-                yptr[t] = q; q += colb_mt;
+                char *yt = column(ys, colb_mt, (size_t)t);
+                POLS_HIP(hipMemcpyAsync(yt, y_cols[t], dtype_size(b->dtype) * (size_t)b->n_rows, hipMemcpyHostToDevice, ctx->stream));
+                yptr[t] = yt;
+                if (pred_cols) pptr[t] = column(ps, colb_mt, (size_t)t);
             }
-            for (int t = 0; pred_cols && t < m; ++t) { pptr[t] = q; q += colb_mt; }
         }
     }
     const size_t mat = sizeof(double) * (size_t)NZ * NZ;
@@ -715,16 +718,24 @@ int wide_static(pols_ctx *ctx, const pols_batch *b, const pols_ols_params *p, po
     rps = (rps + 63) / 64 * 64;
     splits = (std::max<int64_t>(1, max_rows) + rps - 1) / rps;
 
-    void *tab = nullptr, *scr = nullptr;
+    void *tab = nullptr;
     std::vector<const void *> table(st.x.begin(), st.x.end());         // [features][targets][predictions]
     table.insert(table.end(), yptr.begin(), yptr.end());
     table.insert(table.end(), pptr.begin(), pptr.end());
     if ((rc = ensure_scratch(ctx, Work::Tables, sizeof(void *) * table.size(), &tab))) return rc;
     if ((rc = upload_small(ctx, tab, table.data(), sizeof(void *) * table.size()))) return rc;   // `table` is a local: pinned ring
-    const size_t gram_b = round256(mat * G), part_b = round256(mat * G * (size_t)splits), c64_b = round256(sizeof(double) * G * kt * m);
     const bool nulls = p->null_policy != POLS_NULL_IGNORE;
-    const size_t mask_b = nulls ? round256((size_t)b->n_rows) + round256(sizeof(double) * G) : 0;
-    if ((rc = ensure_scratch(ctx, Work::Gram, gram_b + part_b + c64_b + mask_b, &scr))) return rc;
+    WideArgs a;
+    std::memset(&a, 0, sizeof(a));
+    Carve cv;
+    cv.keep(a.gram, mat * G);
+    cv.keep(a.partial, mat * G * (size_t)splits);
+    cv.keep(a.coef64, sizeof(double) * G * kt * m);
+    if (nulls) {
+        cv.keep(a.rowmask, (size_t)b->n_rows);
+        cv.keep(a.nfit, sizeof(double) * G);
+    }
+    if ((rc = carve(ctx, Work::Gram, cv))) return rc;
     if (!st.status) {
         void *sp = nullptr;
         if ((rc = ensure_scratch(ctx, Work::Status, sizeof(int32_t) * G, &sp))) return rc;
@@ -732,8 +743,6 @@ int wide_static(pols_ctx *ctx, const pols_batch *b, const pols_ols_params *p, po
     }
     if ((rc = ensure_fallback_epoch(ctx))) return rc;
 
-    WideArgs a;
-    std::memset(&a, 0, sizeof(a));
     a.cols = static_cast<const void *const *>(tab);
     if (m > 1) {
         a.n_targets = m;
@@ -742,9 +751,6 @@ int wide_static(pols_ctx *ctx, const pols_batch *b, const pols_ols_params *p, po
     }
     a.y = st.y; a.w = st.w; a.offs = d_offs; a.n_groups = b->n_groups; a.n_rows = b->n_rows;
     a.k_user = b->n_features; a.kt = kt;
-    a.gram = static_cast<double *>(scr);
-    a.partial = reinterpret_cast<double *>(static_cast<char *>(scr) + gram_b);
-    a.coef64 = reinterpret_cast<double *>(static_cast<char *>(scr) + gram_b + part_b);
     a.splits = (int32_t)splits; a.rows_per_split = rps;
     a.alpha = enet ? p->alpha : plan.ridge_alpha; a.l1_ratio = plan.enet_l1; a.tol = p->tol; a.max_iter = p->max_iter;
     a.positive = p->positive ? 1 : 0; a.active_set = (p->solve_method == POLS_SOLVE_CD_ACTIVE_SET) ? 1 : 0;
@@ -755,8 +761,6 @@ int wide_static(pols_ctx *ctx, const pols_batch *b, const pols_ols_params *p, po
     a.null_policy = p->null_policy;
     if (nulls) {
         a.valid = st.valid;
-        a.rowmask = reinterpret_cast<uint8_t *>(static_cast<char *>(scr) + gram_b + part_b + c64_b);
-        a.nfit = reinterpret_cast<double *>(static_cast<char *>(scr) + gram_b + part_b + c64_b + round256((size_t)b->n_rows));
         if ((rc = wide_rowmask_launch(ctx, b->dtype, a))) return rc;
     }
     if ((rc = wide_gram_launch(ctx, b->dtype, a))) return rc;
@@ -843,14 +847,21 @@ int pols_multi_target_least_squares(pols_ctx *ctx, const pols_batch *b, const vo
         if ((rc = compact_nulls(ctx, &bb, policy, &c, y_cols, n_targets))) return rc;
         const bool host = b->mem == POLS_MEM_HOST;
         const size_t G = (size_t)b->n_groups, N = (size_t)b->n_rows, sz = dtype_size(b->dtype);
-        const size_t coefb = round256(sz * G * n_targets * kt), statb = round256(sizeof(int32_t) * G), colb = round256(sz * std::max<size_t>(N, 1));
-        const size_t tabb = round256(sizeof(void *) * (size_t)std::max(b->n_features, n_targets));
-        void *d = nullptr;
-        if ((rc = ensure_scratch(ctx, Work::CompactOut, coefb + statb + 2 * tabb + (host && pred_cols ? colb * (size_t)n_targets : 0), &d))) return rc;
-        char *q = static_cast<char *>(d);
-        void *dcoef = (!host && coef) ? coef : static_cast<void *>(q);
-        int32_t *dstat = (!host && status) ? status : reinterpret_cast<int32_t *>(q + coefb);
-        char *tabs = q + coefb + statb, *preds = tabs + 2 * tabb;
+        const size_t colb = round256(sz * std::max<size_t>(N, 1)), tabb = sizeof(void *) * (size_t)std::max(b->n_features, n_targets);
+        void *dcoef = nullptr;
+        int32_t *dstat = nullptr;
+        char *preds = nullptr;
+        MtPredictArgs ma;
+        std::memset(&ma, 0, sizeof(ma));
+        Carve cv;
+        cv.keep(dcoef, sz * G * n_targets * kt);
+        cv.keep(dstat, sizeof(int32_t) * G);
+        cv.add(ma.xtab, tabb);
+        cv.add(ma.ptab, tabb);
+        cv.add(preds, host && pred_cols ? colb * (size_t)n_targets : 0);
+        if ((rc = carve(ctx, Work::CompactOut, cv))) return rc;
+        if (!host && coef) dcoef = coef;
+        if (!host && status) dstat = status;
         pols_ols_params pp = *p;
         pp.null_policy = POLS_NULL_IGNORE;
         if ((rc = pols_multi_target_least_squares(ctx, &c.bb, c.ycols.data(), n_targets, &pp, nullptr, dcoef, dstat))) return rc;
@@ -860,13 +871,9 @@ int pols_multi_target_least_squares(pols_ctx *ctx, const pols_batch *b, const vo
             int64_t mr = 0;
             if ((rc = upload_offsets(ctx, b->group_offsets, b->n_groups, &d_offs, &mr, b->offsets_generation))) return rc;
             std::vector<void *> pt((size_t)n_targets);
-            for (int t = 0; t < n_targets; ++t) pt[(size_t)t] = host ? static_cast<void *>(preds + colb * (size_t)t) : pred_cols[t];
-            if ((rc = upload_small(ctx, tabs, c.st.x.data(), sizeof(void *) * (size_t)b->n_features))) return rc;
-            if ((rc = upload_small(ctx, tabs + tabb, pt.data(), sizeof(void *) * (size_t)n_targets))) return rc;
-            MtPredictArgs ma;
-            std::memset(&ma, 0, sizeof(ma));
-            ma.xtab = reinterpret_cast<const void *const *>(tabs);
-            ma.ptab = reinterpret_cast<void *const *>(tabs + tabb);
+            for (int t = 0; t < n_targets; ++t) pt[(size_t)t] = host ? static_cast<void *>(column(preds, colb, (size_t)t)) : pred_cols[t];
+            if ((rc = upload_small(ctx, const_cast<void **>(ma.xtab), c.st.x.data(), sizeof(void *) * (size_t)b->n_features))) return rc;
+            if ((rc = upload_small(ctx, const_cast<void **>(ma.ptab), pt.data(), sizeof(void *) * (size_t)n_targets))) return rc;
             ma.w = c.st.w; ma.coef = dcoef; ma.vbytes = c.vbytes; ma.offs = d_offs; ma.n_groups = b->n_groups;
             ma.k_user = b->n_features; ma.kt = kt; ma.m = n_targets;
             ma.mask_drop = p->null_policy == POLS_NULL_DROP ? 1 : 0;                   // ex.rs:575-583

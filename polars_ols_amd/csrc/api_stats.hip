@@ -34,28 +34,31 @@ static int cluster_ways(const pols_cluster_params *cl) { return cl->cov_type == 
 
 // ------------------------------------------------------------------ the six statistic arrays
 // r2 / mae / mse (one double per group) and std_err / t_values / p_values (kt per group), in pols_stats_out's order: where the caller wants
-// them, where the kernels write them, and the copy home.  Staged in `area` (host batches) every slot advances whether or not it is wanted --
-// the layout inside Work::CompactOut, Work::HostStaged and Work::Tables; area == nullptr: the kernels write the caller's device arrays.
+// them, where the kernels write them, and the copy home.  As constructed the kernels write the caller's device arrays; stage() adds the
+// six to the buffer the caller is carving (Work::CompactOut, Work::HostStaged, Work::Tables).  Every one keeps its room whether or not it
+// is wanted: the buffer of a frame does not depend on what was asked for.  (The carve holds the addresses of dev[]: stage the object
+// where it stays.)
 struct SixOut {
     double *user[6] = {}, *dev[6] = {};
     size_t G = 0;
     int kt = 0;
-    static size_t slot(int i, size_t G, int kt) { return round256(sizeof(double) * G * (size_t)(i < 3 ? 1 : kt)); }
-    static size_t bytes(size_t G, int kt) { return 3 * slot(0, G, kt) + 3 * slot(3, G, kt); }
+    size_t bytes(int i) const { return sizeof(double) * G * (size_t)(i < 3 ? 1 : kt); }
     SixOut() = default;
-    SixOut(const pols_stats_out *s, size_t G_, int kt_, void *area) : G(G_), kt(kt_) {
+    SixOut(const pols_stats_out *s, size_t G_, int kt_) : G(G_), kt(kt_) {
         double *const u[6] = {s->r2, s->mae, s->mse, s->std_err, s->t_values, s->p_values};
-        char *q = static_cast<char *>(area);
+        for (int i = 0; i < 6; ++i) user[i] = dev[i] = u[i];
+    }
+    // staged (host batches): the wanted ones are written into the buffer; else only their room is kept
+    void stage(Carve &cv, bool staged) {
         for (int i = 0; i < 6; ++i) {
-            user[i] = u[i];
-            dev[i] = !u[i] ? nullptr : (area ? reinterpret_cast<double *>(q) : u[i]);
-            if (area) q += slot(i, G, kt);
+            if (staged) cv.keep(dev[i], bytes(i), user[i] != nullptr);
+            else cv.gap(bytes(i));
         }
     }
     pols_stats_out on_device() const { pols_stats_out d; d.r2 = dev[0]; d.mae = dev[1]; d.mse = dev[2]; d.std_err = dev[3]; d.t_values = dev[4]; d.p_values = dev[5]; return d; }
     int copy_home(pols_ctx *ctx) const {           // (staged arrays only: asynchronous, the caller synchronises)
         for (int i = 0; i < 6; ++i)
-            if (user[i]) POLS_HIP(hipMemcpyAsync(user[i], dev[i], sizeof(double) * G * (size_t)(i < 3 ? 1 : kt), hipMemcpyDeviceToHost, ctx->stream));
+            if (user[i]) POLS_HIP(hipMemcpyAsync(user[i], dev[i], bytes(i), hipMemcpyDeviceToHost, ctx->stream));
         return POLS_OK;
     }
 };
@@ -103,13 +106,15 @@ static int cluster_device_ids(pols_ctx *ctx, const pols_batch *b, const pols_clu
         return POLS_OK;
     }
     const size_t colb = round256(sizeof(int64_t) * (size_t)std::max<int64_t>(b->n_rows, 1));
-    void *d = nullptr;
-    int rc = ensure_scratch(ctx, Work::ClusterIds, colb * (size_t)ways, &d);
+    int64_t *ids = nullptr;
+    Carve cv;
+    cv.add(ids, colb * (size_t)ways);
+    int rc = carve(ctx, Work::ClusterIds, cv);
     if (rc) return rc;
     for (int w = 0; w < ways; ++w) {
-        char *dst = static_cast<char *>(d) + colb * (size_t)w;
+        int64_t *dst = column(ids, colb, (size_t)w);
         if (b->n_rows) POLS_HIP(hipMemcpyAsync(dst, cl->ids[w], sizeof(int64_t) * (size_t)b->n_rows, hipMemcpyHostToDevice, ctx->stream));
-        dev[w] = reinterpret_cast<const int64_t *>(dst);
+        dev[w] = dst;
     }
     return POLS_OK;
 }
@@ -133,14 +138,14 @@ static int influence_rows(pols_ctx *ctx, const pols_batch *b, const Staged &st, 
     a.valid = valid; a.zero_fill = zero_fill;
     a.k_user = b->n_features; a.kt = b->n_features + (b->add_intercept ? 1 : 0);
     a.prep = f.infl_prep; a.grp = f.infl_grp;
-    void *rows = nullptr;
-    if (host && n_out && (rc = ensure_scratch(ctx, Work::InflRows, colb * (size_t)n_out, &rows))) return rc;
-    char *q = static_cast<char *>(rows);
-    for (int i = 0; i < K7I_NOUT; ++i) {
+    void *rows = nullptr;                             // one column per wanted output of a host batch: what is not wanted takes no room
+    Carve cv;
+    cv.add(rows, host ? colb * (size_t)n_out : 0);
+    if (host && n_out && (rc = carve(ctx, Work::InflRows, cv))) return rc;
+    for (int i = 0, at = 0; i < K7I_NOUT; ++i) {
         if (!user[i]) continue;
         if (!host && !aligned16(user[i])) return fail(POLS_ERR_INVALID, "device columns must be 16-byte aligned");
-        a.out[i] = host ? static_cast<void *>(q) : user[i];
-        q += host ? colb : 0;
+        a.out[i] = host ? column(rows, colb, (size_t)at++) : user[i];
     }
     if ((rc = k7i_rows_launch(ctx, b->dtype, a))) return rc;
     if (host && N)
@@ -161,13 +166,16 @@ static int stats_wide(pols_ctx *ctx, const pols_batch *b, const pols_ols_params 
     int rc;
     SolvePlan plan;
     if ((rc = resolve_solve_plan(p, b->dtype, kt, 1, &plan))) return rc;
-    void *staged = nullptr;
-    if (host && (rc = ensure_scratch(ctx, Work::HostStaged, SixOut::bytes(G, kt), &staged))) return rc;
+    f->six = SixOut(s, G, kt);
+    if (host) {
+        Carve cv;
+        f->six.stage(cv, true);
+        if ((rc = carve(ctx, Work::HostStaged, cv))) return rc;
+    }
     f->coef.ask(o, host, nullptr);                  // (a device batch without coefficients: wide_static keeps its own)
     WideInfo wi;
     if ((rc = wide_static(ctx, b, p, &f->coef.oo, kt, plan, nullptr, 1, nullptr, &wi))) return rc;
     f->st = std::move(wi.st);
-    f->six = SixOut(s, G, kt, staged);
     WideStatsOut so;
     so.r2 = f->six.dev[0]; so.mae = f->six.dev[1]; so.mse = f->six.dev[2]; so.se = f->six.dev[3]; so.tv = f->six.dev[4]; so.pv = f->six.dev[5];
     so.lambda = p->alpha;
@@ -329,21 +337,24 @@ static int influence_group_stage(pols_ctx *ctx, const pols_batch *b, const pols_
 
 // The level that never sees a null: solve, Gram matrices, K7 and what the kind adds, everything left on the device (fit_home copies a host
 // batch's outputs back).  An influence call's row pass is the caller's: it owns the rows the diagnostics are for.
-// Work::Tables: [coefficients when the caller did not ask for them (device batches)] [the six arrays of a host batch]
+// Work::Tables: the coefficients' room serves a device batch whose caller did not ask for them, the six arrays' a host batch
 static int statistics_fit(pols_ctx *ctx, const pols_batch *b, const pols_ols_params *p, const StatsCall &call, const pols_out *o,
                           const pols_stats_out *s, Fit *f) {
     const int kt = b->n_features + (b->add_intercept ? 1 : 0);
     if (kt > K7_KMAX) return stats_wide(ctx, b, p, o, s, kt, f);
     const bool host = b->mem == POLS_MEM_HOST;
-    const size_t G = (size_t)b->n_groups, coefb = round256(dtype_size(b->dtype) * G * kt);
+    const size_t G = (size_t)b->n_groups;
     int rc;
-    void *scr = nullptr;
-    if ((rc = ensure_scratch(ctx, Work::Tables, coefb + SixOut::bytes(G, kt), &scr))) return rc;
-    f->coef.ask(o, host, scr);
+    void *spare = nullptr;
+    f->six = SixOut(s, G, kt);
+    Carve cv;
+    cv.keep(spare, dtype_size(b->dtype) * G * kt);
+    f->six.stage(cv, host);
+    if ((rc = carve(ctx, Work::Tables, cv))) return rc;
+    f->coef.ask(o, host, spare);
     LsInfo info;
     if ((rc = ls_core(ctx, b, p, &f->coef.oo, &info))) return rc;
     f->st = std::move(info.st); f->d_offs = info.d_offs;
-    f->six = SixOut(s, G, kt, host ? static_cast<char *>(scr) + coefb : nullptr);
     double *gram = nullptr;
     if ((rc = stats_gram(ctx, b, kt, *f, info.gram, &gram))) return rc;
     StatsArgs sa;
@@ -377,14 +388,17 @@ static int compacted_cluster_ids(pols_ctx *ctx, const pols_batch *b, const pols_
     const int64_t *src[2] = {nullptr, nullptr};
     if ((rc = cluster_device_ids(ctx, b, cl, ways, src))) return rc;
     const int64_t nv = c.offs[G];
-    const size_t mapb = round256(sizeof(int32_t) * (size_t)std::max<int64_t>(nv, 1)), colb = round256(sizeof(int64_t) * (size_t)std::max<int64_t>(nv, 1));
-    void *d = nullptr;
-    if ((rc = ensure_scratch(ctx, Work::ClusterCompact, mapb + colb * (size_t)ways, &d))) return rc;
-    int64_t *dst[2] = {nullptr, nullptr};
-    for (int w = 0; w < ways; ++w) dst[w] = reinterpret_cast<int64_t *>(static_cast<char *>(d) + mapb + colb * (size_t)w);
+    const size_t colb = round256(sizeof(int64_t) * (size_t)std::max<int64_t>(nv, 1));
+    int32_t *map = nullptr;
+    int64_t *ids = nullptr, *dst[2] = {nullptr, nullptr};
+    Carve cv;
+    cv.add(map, sizeof(int32_t) * (size_t)std::max<int64_t>(nv, 1));
+    cv.add(ids, colb * (size_t)ways);
+    if ((rc = carve(ctx, Work::ClusterCompact, cv))) return rc;
+    for (int w = 0; w < ways; ++w) dst[w] = column(ids, colb, (size_t)w);
     if (nv > 0) {
         RowCompactArgs ra = c.ra;
-        ra.src = static_cast<int32_t *>(d);
+        ra.src = map;
         if ((rc = row_compact_srcmap_launch(ctx, ra))) return rc;
         if ((rc = k7c_gather_ids_launch(ctx, ra.src, nv, src, dst, ways))) return rc;
     }
@@ -413,7 +427,7 @@ static int influence_rows_of_frame(pols_ctx *ctx, const pols_batch *b, const Com
 // The statistics are those of the rows handle_nulls leaves (src/expressions.rs:469-471): filter / zero-fill on the device, then the fit level
 // on the filtered batch -- a device batch without nulls (compact_nulls: null_free = 1, valid = nullptr), so the fit level is entered exactly
 // once and with null_policy = ignore.  Outputs are per group: a device batch's land where the caller wants them, a host batch's are staged
-// in Work::CompactOut -- [coefficients] [status] [the six arrays] -- and copied home here.  (The compacted batch passes check_batch by
+// in Work::CompactOut and copied home here.  (The compacted batch passes check_batch by
 // construction: the caller's batch did, and its offsets start at 0 and end at its row count.)
 static int statistics_filtered(pols_ctx *ctx, const pols_batch *b, const pols_ols_params *p, const StatsCall &call, const pols_out *o,
                                const pols_stats_out *s) {
@@ -432,16 +446,14 @@ static int statistics_filtered(pols_ctx *ctx, const pols_batch *b, const pols_ol
         cc.params = &ccl;
     }
     pols_out od = *o;
-    SixOut six(s, G, kt, nullptr);
+    SixOut six(s, G, kt);
     if (host) {
-        const size_t coefb = round256(sz * G * kt), statb = round256(sizeof(int32_t) * G);
-        void *d = nullptr;
-        if ((rc = ensure_scratch(ctx, Work::CompactOut, coefb + statb + SixOut::bytes(G, kt), &d))) return rc;
-        char *q = static_cast<char *>(d);
         std::memset(&od, 0, sizeof(od));
-        if (o->coef) od.coef = q;
-        if (o->status) od.status = reinterpret_cast<int32_t *>(q + coefb);
-        six = SixOut(s, G, kt, q + coefb + statb);
+        Carve cv;
+        cv.keep(od.coef, sz * G * kt, o->coef != nullptr);
+        cv.keep(od.status, sizeof(int32_t) * G, o->status != nullptr);
+        six.stage(cv, true);
+        if ((rc = carve(ctx, Work::CompactOut, cv))) return rc;
     }
     const pols_stats_out sd = six.on_device();
     Fit f;      // (of a device batch: nothing of it is to be copied home)

@@ -220,8 +220,7 @@ struct pols_ctx {
     // The caches below each own their device table (pols::CachedTable): a hit needs the table's `valid` flag and a matching key.
     // chunk tables of the dynamic kernels for mask-free batches of the uploaded offsets: rebuilt only when the offsets,
     // min_periods or the chunk length change
-    struct : pols::CachedTable { uint64_t offs_id = 0; int64_t n_groups = -1, n_rows = -1, mp = -1, n_chunks = 0; int32_t chunk_len = 0;
-                                 size_t b_groups = 0; } chunk_cache;
+    struct : pols::CachedTable { uint64_t offs_id = 0; int64_t n_groups = -1, n_rows = -1, mp = -1, n_chunks = 0; int32_t chunk_len = 0; } chunk_cache;
     // K3c (k3c_scan.hip): first row of every PACKED tile (tiles cut at sequence starts, single-pass mode); n_tiles 0 =
     // this frame does not pack (a sequence longer than a tile, or tiles too empty)
     struct : pols::CachedTable { uint64_t offs_id = 0; int64_t n_groups = -1, n_rows = -1, tile_rows = 0, n_tiles = 0; } k3c;

@@ -1,7 +1,8 @@
-// carve_check.cpp -- csrc/scratch_carve.hpp and csrc/k17_split.hpp on the CPU (no HIP): test_scratch_carve_cpu.py compiles this with
+// carve_check.cpp -- csrc/scratch_carve.hpp, csrc/table_layout.hpp and csrc/k17_split.hpp on the CPU (no HIP): test_scratch_carve_cpu.py compiles this with
 // -fsanitize=address,undefined, runs it and compares every printed line with formulas written out by hand.  Each scenario carves a heap
 // buffer of exactly total() bytes and writes every region end to end, so a region that reaches past the total is a sanitizer report.
-// Output: "<scenario> <offset of every slot, -1 for nullptr> ... <total>"; "split <n_res> <max_res> <max_glb> : <list>".
+// Output: "<scenario> <offset of every slot, -1 for nullptr> ... <total>"; "split <n_res> <max_res> <max_glb> : <list>".  The two cached
+// tables print the slots of the build view, then those of the view a cache hit takes over the same buffer.
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -9,6 +10,7 @@
 
 #include "k17_split.hpp"
 #include "scratch_carve.hpp"
+#include "table_layout.hpp"
 
 using pols::Carve;
 
@@ -35,6 +37,49 @@ static void enet_gram(const char *name, size_t items, size_t G, size_t per, bool
     fill(count, 8 * items); fill(part, 8 * items * per);
     if (split) fill(gram, 8 * G * per);
     std::printf("%s %ld %ld %ld %zu\n", name, off(count), off(part), off(gram), cv.total());
+}
+
+// a region that keeps its room: the staged outputs of a host batch (coef, pred, resid, status), `wanted` one bit each
+static void kept(const char *name, unsigned wanted) {
+    char *coef = nullptr, *pred = nullptr, *resid = nullptr;
+    int32_t *status = nullptr;
+    const size_t cb = 4 * 5 * 7, rb = 4 * 415, sb = 4 * 5;
+    Carve cv;
+    cv.keep(coef, cb, wanted & 1); cv.keep(pred, rb, wanted & 2); cv.keep(resid, rb, wanted & 4); cv.keep(status, sb, wanted & 8);
+    place(cv);
+    fill(coef, cb); fill(pred, rb); fill(resid, rb); fill(status, sb);
+    std::printf("%s %ld %ld %ld %ld %zu\n", name, off(coef), off(pred), off(resid), off(status), cv.total());
+}
+
+// build_chunk_tables' table: the build carves it, a later view (the cache hit) places the same list over the kept buffer
+static void chunk_tables(const char *name, int64_t G, int64_t chunks, int64_t N, bool prefix, bool on_device) {
+    pols::ChunkTables t, hit;
+    Carve cv, again;
+    pols::chunk_tables_layout(cv, t, 40, 24, G, chunks, N, prefix, on_device);
+    place(cv);
+    const int64_t slabs = (N + 255) / 256;
+    fill(t.groups, 40 * G); fill(t.chunks, 24 * chunks); fill(t.order, 4 * chunks); fill(t.cnt, 4 * N); fill(t.vidx, 4 * N);
+    fill(t.slab_cnt, 4 * slabs); fill(t.slab_base, 8 * (slabs + 1)); fill(t.c_offs, 8 * (G + 1));
+    pols::chunk_tables_layout(again, hit, 40, 24, G, chunks, N, prefix, on_device);
+    again.place(g_base);
+    std::printf("%s %ld %ld %ld %ld %ld %ld %ld %ld %zu", name, off(t.groups), off(t.chunks), off(t.order), off(t.cnt), off(t.vidx), off(t.slab_cnt),
+                off(t.slab_base), off(t.c_offs), cv.total());
+    std::printf(" %ld %ld %ld %ld %ld %ld %ld %ld %zu\n", off(hit.groups), off(hit.chunks), off(hit.order), off(hit.cnt), off(hit.vidx),
+                off(hit.slab_cnt), off(hit.slab_base), off(hit.c_offs), again.total());
+}
+
+// ensure_segments' tables, the same way
+static void seg_tables(const char *name, int64_t n_seg, int64_t n_items, bool pairs, size_t extra) {
+    SegTables t, hit;
+    Carve cv, again;
+    pols::seg_tables_layout(cv, t, n_seg, n_items, pairs, extra);
+    place(cv);
+    fill(const_cast<int64_t *>(t.offs), 8 * (pairs ? 2 * n_seg : n_seg + 1)); fill(const_cast<int32_t *>(t.map), 4 * n_seg);
+    fill(const_cast<int32_t *>(t.first), 4 * (n_items + 1)); fill(t.extra, extra * n_seg);
+    pols::seg_tables_layout(again, hit, n_seg, n_items, pairs, extra);
+    again.place(g_base);
+    std::printf("%s %ld %ld %ld %ld %zu %ld %ld %ld %ld %zu\n", name, off(t.offs), off(t.map), off(t.first), off(t.extra), cv.total(), off(hit.offs),
+                off(hit.map), off(hit.first), off(hit.extra), again.total());
 }
 
 int main() {
@@ -77,6 +122,31 @@ int main() {
         fill(packed, 1200); fill(exact, 512);
         std::printf("raw %ld %ld %ld %zu\n", off(packed), off(exact), off(ro), cv.total());
     }
+    kept("kept_all", 15); kept("kept_mid", 1 | 4 | 8); kept("kept_end", 1 | 2); kept("kept_none", 0);
+    {   // a fixed pad in front of and behind a region: flag words on a line of their own, the pad that ends a table
+        double *mid = nullptr;
+        Carve cv;
+        cv.gap(256); cv.add(mid, 8 * 33); cv.gap(256);
+        place(cv);
+        fill(mid, 8 * 33);
+        std::printf("gap %ld %zu\n", off(mid), cv.total());
+    }
+    {   // a run of equal columns is one region (5 columns of 415 floats, each on its own 256-byte line); an empty frame's column still has an address
+        char *cols = nullptr, *none = nullptr;
+        const size_t stride = Carve::round(4 * 415);
+        Carve cv;
+        cv.add(cols, stride * 5); cv.keep(none, 0);
+        place(cv);
+        for (size_t j = 0; j < 5; ++j) fill(pols::column(cols, stride, j), 4 * 415);
+        const float *ro = reinterpret_cast<const float *>(cols);
+        std::printf("columns %ld %ld %ld %ld %ld %zu\n", off(pols::column(cols, stride, 0)), off(pols::column(cols, stride, 3)),
+                    off(pols::column(cols, stride, 4)), off(pols::column(ro, stride, 2)), off(none), cv.total());
+    }
+    chunk_tables("chunks_plain", 5, 37, 9000, false, false);
+    chunk_tables("chunks_host_valid", 5, 37, 9000, true, false);
+    chunk_tables("chunks_device_valid", 5, 37, 9000, true, true);
+    seg_tables("seg_frame", 40, 4, false, 8 * 17);
+    seg_tables("seg_classes", 40, 3, true, 8 * 17);
     std::free(g_base);
     // the groups K17 keeps resident: all, none, mixed with an empty group, cap = -1 (the global route for every group, the empty one too)
     const int64_t offs[] = {0, 60, 260, 260, 7860, 7980}, full[] = {0, 60, 260, 7860};

@@ -1,4 +1,5 @@
-"""The scratch carver (csrc/scratch_carve.hpp) and K17's resident / global split of the groups (csrc/k17_split.hpp) on the CPU: a
+"""The scratch carver (csrc/scratch_carve.hpp), the layouts of the two cached tables (csrc/table_layout.hpp: the build view and the view a
+cache hit takes must agree) and K17's resident / global split of the groups (csrc/k17_split.hpp) on the CPU: a
 stand-alone program (tests/carve_check.cpp, plain C++, no HIP) is compiled with the address and undefined-behaviour sanitizers and run;
 what it prints is compared with offsets and totals written out by hand below.  The program writes every region it carved end to end
 into a buffer of exactly the total, so a region that reaches past the allocation is a sanitizer report and a failed run."""
@@ -57,6 +58,57 @@ def test_a_repeat_lays_the_same_tables_out_once_per_column(printed):
     named, _ = printed
     one = r(4 * 7) + r(8 * 8) + r(4 * 415 + 4)                    # counts, firsts, row index
     assert named["repeat"] == [0, r(4 * 7), r(4 * 7) + r(8 * 8), one, one + r(4 * 7), one + r(4 * 7) + r(8 * 8), 2 * one]
+
+
+def test_a_kept_region_keeps_its_room_when_it_is_not_wanted(printed):
+    named, _ = printed
+    # the staged outputs of a host batch as api.hip laid them out before the carver: q += coefb; q += colb; q += colb; total
+    # coefb + 2 * colb + statb whatever is wanted (5 groups, 7 columns, 415 rows, f32)
+    coefb, colb, statb = r(4 * 5 * 7), r(4 * 415), r(4 * 5)
+    total = coefb + 2 * colb + statb
+    assert named["kept_all"] == [0, coefb, coefb + colb, coefb + 2 * colb, total]
+    assert named["kept_mid"] == [0, -1, coefb + colb, coefb + 2 * colb, total]          # pred unwanted: resid and status do not move
+    assert named["kept_end"] == [0, coefb, -1, -1, total]                               # unwanted at the end: the total stays
+    assert named["kept_none"] == [-1, -1, -1, -1, total]
+
+
+def test_a_gap_is_room_without_a_slot(printed):
+    named, _ = printed
+    assert named["gap"] == [256, 256 + r(8 * 33) + 256]
+
+
+def test_a_run_of_columns_is_one_region(printed):
+    named, _ = printed
+    colb = r(4 * 415)                                                                   # cols + colb * j
+    assert named["columns"] == [0, 3 * colb, 4 * colb, 2 * colb, 5 * colb, 5 * colb]    # ... and a wanted region of 0 bytes has an address
+
+
+def test_chunk_tables_as_built_and_as_found_again(printed):
+    named, _ = printed
+    # api_dynamic.hip before the carver, 5 groups (40-byte records), 37 chunks (24-byte records), 9 000 rows:
+    # b_groups + b_chunks + b_order + 2 * b_cnt + b_sc + b_sb + b_co + 256; a hit read groups at 0, chunks at b_groups, order behind them
+    b_groups, b_chunks, b_order, b_cnt = r(40 * 5), r(24 * 37), r(4 * 37), r(4 * 9000)
+    slabs = (9000 + 255) // 256
+    b_sc, b_sb, b_co = r(4 * slabs), r(8 * (slabs + 1)), r(8 * (5 + 1))
+    head = [0, b_groups, b_groups + b_chunks]
+    t_cnt = b_groups + b_chunks + b_order
+    plain = head + [-1] * 5 + [t_cnt + 256]
+    host = head + [t_cnt, t_cnt + b_cnt, -1, -1, -1, t_cnt + 2 * b_cnt + 256]
+    scr = t_cnt + 2 * b_cnt
+    dev = head + [t_cnt, t_cnt + b_cnt, scr, scr + b_sc, scr + b_sc + b_sb, scr + b_sc + b_sb + b_co + 256]
+    assert named["chunks_plain"] == plain + plain
+    assert named["chunks_host_valid"] == host + host
+    assert named["chunks_device_valid"] == dev + dev
+
+
+def test_segment_tables_as_built_and_as_found_again(printed):
+    named, _ = printed
+    # api.hip before the carver, 40 segments with 136 bytes of partial results each: the whole frame (4 groups) keeps n_seg + 1 offsets,
+    # a size-class list (3 groups) a (start, end) pair per segment; map, first, then the extra area
+    for name, b_so, items in (("seg_frame", r(8 * 41), 4), ("seg_classes", r(8 * 80), 3)):
+        b_sm, b_sf = r(4 * 40), r(4 * (items + 1))
+        view = [0, b_so, b_so + b_sm, b_so + b_sm + b_sf, b_so + b_sm + b_sf + r(136 * 40)]
+        assert named[name] == view + view
 
 
 def test_every_offset_is_a_multiple_of_256(printed):
