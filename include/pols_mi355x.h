@@ -689,6 +689,67 @@ typedef struct pols_iv_out {
 int pols_iv2sls(pols_ctx *ctx, const pols_batch *b, const pols_ols_params *p, const pols_iv_params *q, pols_out *out,
                 const pols_iv_out *r);
 
+/* AR(1) feasible generalised least squares per group: Cochrane-Orcutt / Prais-Winsten (no reference counterpart; statsmodels' GLSAR,
+ * Stata's prais / prais, corc and R's prais / orcutt for every group of the frame in one call).  Everything below is per group g.
+ * Rows and columns.  The rows in frame order are t = 1..n: this is TIME order, and the caller sorts.  z_t = (x_t1 .. x_tk, 1 if
+ * add_intercept, y_t), kt = n_features + intercept, T = kt + 1.  All arithmetic is f64 on the inputs' values, for f32 batches too.
+ * Null policies.  "ignore": the values as they are.  "zero": nulls are filled exactly as pols_least_squares does, and every row is
+ * fitted.  A drop-family policy on a batch that is not null_free, or with a validity mask, is POLS_ERR_UNSUPPORTED (the lag partner
+ * across a gap is not built); a null_free batch under any policy runs as "ignore".  b->weights != NULL is POLS_ERR_UNSUPPORTED.
+ * Transformed model at rho.  For t = 2..n the transformed row is z*_t = z_t - rho z_{t-1}; POLS_AR1_PRAIS_WINSTEN adds
+ * z*_1 = sqrt(1 - rho^2) z_1.  n* = n - 1 (Cochrane-Orcutt) or n (Prais-Winsten) transformed rows.  The ones column is transformed
+ * like any other, so the intercept stays on the original scale.  With S = sum_{1..n} z z', C = sum_{t=2..n} z_t z_{t-1}',
+ * S_1 = S - z_1 z_1' and S_n = S - z_n z_n':  A(rho) = S_1 - rho (C + C') + rho^2 S_n, plus (1 - rho^2) z_1 z_1' for Prais-Winsten.
+ * b(rho) solves the X-block of A(rho) against its y-column by the static entries' f64 Cholesky (a pivot fails when
+ * d^2 <= 16 kt eps A_jj).
+ * Iteration.  rho^0 = 0, so b^0 is OLS.  Update i -> i + 1 with v = (-b^i, 1): rho^{i+1} = v'C v / v'S_n v -- the regression of e_t on
+ * e_{t-1} over t = 2..n, e = y - X b^i on the ORIGINAL rows (Stata's default rhotype(regress)).  Converged when
+ * |rho^{i+1} - rho^i| <= tol.  It stops on convergence, or after max_iter updates with POLS_GROUP_NOT_CONVERGED and the results still
+ * returned.  n_iter is the number of updates made.  The reported coefficients are b(rho*) at the last rho (one more solve).
+ * max_iter = 1 is the classical two-step estimator.
+ * Reported values.  e_t = y_t - x_t'b (original scale); u_t = e_t - rho* e_{t-1} for t >= 2, u_1 = sqrt(1 - rho*^2) e_1 for
+ * Prais-Winsten.  RSS* = sum u^2, summed over the rows and not taken from the moments; df = n* - kt, sigma2 = RSS* / df;
+ * V = sigma2 A_xx(rho*)^-1, se_j = sqrt(V_jj), t_j = b_j / se_j, p the two-sided Student-t(df) p-value.
+ * dw = sum (u_t - u_{t-1})^2 / sum u_t^2 over consecutive transformed rows; dw_ols = sum_{t>=2} (e0_t - e0_{t-1})^2 / sum_{t>=1} e0_t^2
+ * with e0 = y - X b^0.  out->pred = x_t'b and out->resid = y - pred, both on the original scale.  rho = rho*.
+ * out->status per group: POLS_GROUP_EMPTY for n = 0 (zero coefficients, everything else NaN, n_iter 0); POLS_GROUP_BAD_DOF for
+ * n* <= kt (everything NaN); POLS_GROUP_FALLBACK with everything NaN when a pivot fails in any solve, a moment is not finite,
+ * v'S_n v is not positive and finite, or |rho^{i+1}| >= 1 (n_iter: the updates made until then); POLS_GROUP_NOT_CONVERGED;
+ * otherwise POLS_GROUP_OK.  n_obs = n in every case.
+ * coef / pred / resid are in the batch dtype, everything else is f64.  No floating-point atomics, every sum in a fixed order: two
+ * runs are bit-identical, HOST and DEVICE batches agree bit for bit.  Groups may have any length.  When none of se / t_values /
+ * p_values / cov / sigma2 / dw / dw_ols is asked for, the columns are read once (and once more for pred / resid).
+ * From pols_ols_params only null_policy is read.  POLS_ERR_INVALID: alpha != 0, positive, or has_l1_ratio with l1_ratio > 0; an
+ * unknown method, max_iter < 1, tol not positive and finite; an unknown null policy; a validity mask without a drop-family policy.
+ * POLS_ERR_UNSUPPORTED: more than 31 columns incl. the intercept, and the two cases above.  There is no Arrow twin and no sharded
+ * entry. */
+enum { POLS_AR1_COCHRANE_ORCUTT = 0, POLS_AR1_PRAIS_WINSTEN = 1 };
+
+typedef struct pols_glsar_params {
+    int32_t method;             /* POLS_AR1_*                                    */
+    int32_t max_iter;           /* updates of rho at the most, >= 1              */
+    double  tol;                /* on |rho^{i+1} - rho^i|, positive and finite   */
+} pols_glsar_params;
+
+/* method = POLS_AR1_PRAIS_WINSTEN, max_iter = 100, tol = 1e-6 (Stata's prais) */
+void pols_glsar_params_default(pols_glsar_params *q);
+
+typedef struct pols_glsar_out {
+    double  *se;                /* n_groups x kt                                 */
+    double  *t_values;          /* n_groups x kt                                 */
+    double  *p_values;          /* n_groups x kt                                 */
+    double  *cov;               /* n_groups x kt x kt, row-major: V              */
+    double  *sigma2;            /* n_groups: RSS* / df                           */
+    double  *rho;               /* n_groups: rho*                                */
+    double  *dw;                /* n_groups: Durbin-Watson of the transformed residuals */
+    double  *dw_ols;            /* n_groups: Durbin-Watson of the OLS residuals  */
+    int32_t *n_iter;            /* n_groups: rho updates made                    */
+    int64_t *n_obs;             /* n_groups: n                                   */
+} pols_glsar_out;               /* all live where b->mem says; any may be NULL */
+
+int pols_glsar(pols_ctx *ctx, const pols_batch *b, const pols_ols_params *p, const pols_glsar_params *q, pols_out *out,
+               const pols_glsar_out *r);
+
 /* Regression that absorbs one categorical effect inside every group -- the "within" estimator (no reference counterpart; Stata's
  * areg / xtreg, fe and linearmodels' PanelOLS(entity_effects=True) for every group of the frame in one call, without a dummy column
  * per category).  Everything below is per group g.

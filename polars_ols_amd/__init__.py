@@ -15,6 +15,7 @@ from .least_squares import (  # noqa: F401
     compute_rlm, RLM,
     compute_glm, GLM,
     compute_iv2sls, IV2SLS,
+    compute_glsar, GLSAR,
     compute_absorbed_least_squares, AbsorbedOLS,
     compute_elastic_net_cv, ElasticNetCV,
 )

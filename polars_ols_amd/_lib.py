@@ -202,6 +202,20 @@ class Absorb2Out(C.Structure):        # pols_absorb2_out
     _fields_ = [(n, C.c_void_p) for n in ABSORB2_FIELDS]
 
 
+class GlsarParams(C.Structure):       # pols_glsar_params
+    _fields_ = [("method", C.c_int32), ("max_iter", C.c_int32), ("tol", C.c_double)]
+
+
+# pols_glsar_out, in the struct's order; the methods (POLS_AR1_*)
+GLSAR_FIELDS = ("se", "t_values", "p_values", "cov", "sigma2", "rho", "dw", "dw_ols", "n_iter", "n_obs")
+GLSAR_METHODS = {"cochrane_orcutt": 0, "prais_winsten": 1}
+GLSAR_MAX_COLUMNS = 31
+
+
+class GlsarOut(C.Structure):          # pols_glsar_out
+    _fields_ = [(n, C.c_void_p) for n in GLSAR_FIELDS]
+
+
 EXPORTS = [
     "pols_device_count", "pols_version", "pols_last_error", "pols_create", "pols_destroy", "pols_set_stream",
     "pols_use_private_stream",
@@ -226,6 +240,7 @@ EXPORTS = [
     "pols_iv_params_default", "pols_iv2sls",
     "pols_absorb_params_default", "pols_least_squares_absorb",
     "pols_absorb2_params_default", "pols_least_squares_absorb2",
+    "pols_glsar_params_default", "pols_glsar",
 ]
 # measurement aids (include/pols_mi355x_debug.h): not part of the reference interface
 DEBUG_EXPORTS = ["pols_timing_enable", "pols_timing_collect", "pols_last_kernel_name", "pols_stream_probe", "pols_stream_probe_ex",
@@ -309,6 +324,8 @@ def lib() -> C.CDLL:
         L.pols_absorb2_params_default.argtypes, L.pols_absorb2_params_default.restype = [C.POINTER(Absorb2Params)], None
         L.pols_least_squares_absorb2.argtypes = [C.c_void_p, C.POINTER(Batch), C.POINTER(OlsParams), C.POINTER(Absorb2Params), C.POINTER(Out),
                                                  C.POINTER(Absorb2Out)]
+        L.pols_glsar_params_default.argtypes, L.pols_glsar_params_default.restype = [C.POINTER(GlsarParams)], None
+        L.pols_glsar.argtypes = [C.c_void_p, C.POINTER(Batch), C.POINTER(OlsParams), C.POINTER(GlsarParams), C.POINTER(Out), C.POINTER(GlsarOut)]
         L.pols_enet_cv_params_default.argtypes, L.pols_enet_cv_params_default.restype = [C.POINTER(EnetCvParams)], None
         L.pols_elastic_net_cv.argtypes = [C.c_void_p, C.POINTER(Batch), C.POINTER(OlsParams), C.POINTER(EnetCvParams), C.POINTER(Out),
                                           C.POINTER(EnetCvOut)]

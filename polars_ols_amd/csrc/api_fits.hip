@@ -1,5 +1,5 @@
 // api_fits.hip -- the per-group fit entries of the C-ABI: pols_ridge_cv (K10), pols_rlm (K11), pols_elastic_net_cv (K12), pols_glm
-// (K13), pols_iv2sls (K14), pols_least_squares_absorb (K16), pols_least_squares_absorb2 (K17).  Host code only.  What they share is written once, up front: the opening checks and the staging
+// (K13), pols_iv2sls (K14), pols_least_squares_absorb (K16), pols_least_squares_absorb2 (K17), pols_glsar (K18).  Host code only.  What they share is written once, up front: the opening checks and the staging
 // (FitCall), the common fields of the kernel argument structs (fit_frame, fit_segments), the work buffers (Carve, carve), the entry's own
 // outputs (ExtraOut), K10's prediction pass (fit_predict), extra input columns (stage_extra_columns), the tile count rlm and glm route by
 // (group_tiles) and the stages of the absorb pair.  DESIGN.md, "Adding a per-group fit entry".
@@ -15,6 +15,7 @@
 #include "k14_iv.hpp"
 #include "k16_absorb.hpp"
 #include "k17_absorb2.hpp"
+#include "k18_glsar.hpp"
 #include "k7c_cluster.hpp"
 #pragma GCC visibility push(hidden)     // host helpers of this file alone: nothing of them is exported
 #include "k17_split.hpp"
@@ -576,6 +577,71 @@ int pols_iv2sls(pols_ctx *ctx, const pols_batch *b, const pols_ols_params *p, co
     }
     // the prediction pass: the regressors alone, or -- "drop" -- the whole list with zero coefficients for the instruments, whose nulls mask rows
     if ((rc = fit_predict(ctx, b, fc, &sg, a.x, pred_all ? nf + m : nf, pred_all ? T : kx, a.coefp))) return rc;
+    return xo.home(ctx, b, o, fc);
+}
+
+void pols_glsar_params_default(pols_glsar_params *q) {
+    if (!q) return;
+    q->method = POLS_AR1_PRAIS_WINSTEN;
+    q->max_iter = 100;
+    q->tol = 1e-6;
+}
+
+// K18 (k18_glsar.hip): the lag-Gram launch (S, the lag-one cross-moments C and the row count per item: the columns are read once),
+// the per-group solve with the whole iteration, the row pass and the per-group finish (only when a wanted output needs a residual),
+// then K10's prediction pass with the f64 coefficients.
+int pols_glsar(pols_ctx *ctx, const pols_batch *b, const pols_ols_params *p, const pols_glsar_params *q, pols_out *o, const pols_glsar_out *ro) {
+    FitCall fc;
+    int rc = fit_check(ctx, b, p, q, o, "glsar", K18_KMAX, &fc);
+    if (rc) return rc;
+    if (p->alpha != 0.0 || p->positive || (p->has_l1_ratio && p->l1_ratio > 0.0))
+        return fail(POLS_ERR_INVALID, "glsar: alpha / positive / l1_ratio do not apply");
+    if (q->method != POLS_AR1_COCHRANE_ORCUTT && q->method != POLS_AR1_PRAIS_WINSTEN) return fail(POLS_ERR_INVALID, "glsar: unknown method %d", q->method);
+    if (q->max_iter < 1) return fail(POLS_ERR_INVALID, "glsar: max_iter %d < 1", q->max_iter);
+    if (!(q->tol > 0.0) || !std::isfinite(q->tol)) return fail(POLS_ERR_INVALID, "glsar: tol %g is not positive and finite", q->tol);
+    if (fc.kt < 1) return fail(POLS_ERR_INVALID, "glsar: no column");
+    // the lag partner of a row is the row before it: a policy that takes rows out of the fit needs an in-tile scan, weights a second scaling
+    if (fc.pol != POLS_NULL_IGNORE && fc.pol != POLS_NULL_ZERO)
+        return fail(POLS_ERR_UNSUPPORTED, "glsar: drop-family null policies are not built (pass null_free data, \"ignore\" or \"zero\")");
+    if (b->weights) return fail(POLS_ERR_UNSUPPORTED, "glsar: weights are not built");
+    if (b->n_groups == 0) return POLS_OK;
+    ro = or_none(ro);
+    const bool need_rows = ro->se || ro->t_values || ro->p_values || ro->cov || ro->sigma2 || ro->dw || ro->dw_ols;
+    const int kt = fc.kt;
+    const size_t G = fc.G;
+    if ((rc = fit_stage(ctx, b, o, &fc))) return rc;
+    SegTables sg;
+    if ((rc = ensure_segments(ctx, b, fc.max_rows, 0, &sg))) return rc;
+    const size_t items = sg.n_seg > 0 ? (size_t)sg.n_seg : G;
+    GlsarArgs a = {};
+    fit_frame(a, b, fc);
+    fit_segments(a, sg);
+    a.method = q->method; a.max_iter = q->max_iter; a.tol = q->tol;
+    Carve moments, state;
+    moments.add(a.gram_part, sizeof(double) * items * k18_gram_stride(kt)); moments.add(a.rows_part, sizeof(double) * items * K18_ROWS_STRIDE);
+    state.add(a.state, sizeof(double) * G * k18_state_stride(kt)); state.add(a.coefp, sizeof(double) * G * (size_t)kt);
+    if ((rc = carve(ctx, Work::GlsarMoments, moments))) return rc;
+    if ((rc = carve(ctx, Work::GlsarState, state))) return rc;
+    ExtraOut xo;
+    xo.add(ro->se, a.se, sizeof(double) * G * kt);
+    xo.add(ro->t_values, a.t_values, sizeof(double) * G * kt);
+    xo.add(ro->p_values, a.p_values, sizeof(double) * G * kt);
+    xo.add(ro->cov, a.cov, sizeof(double) * G * kt * kt);
+    xo.add(ro->sigma2, a.sigma2, sizeof(double) * G);
+    xo.add(ro->rho, a.rho, sizeof(double) * G);
+    xo.add(ro->dw, a.dw, sizeof(double) * G);
+    xo.add(ro->dw_ols, a.dw_ols, sizeof(double) * G);
+    xo.add(ro->n_iter, a.n_iter, sizeof(int32_t) * G);
+    xo.add(ro->n_obs, a.n_obs, sizeof(int64_t) * G);
+    if ((rc = xo.place(ctx, fc, Work::GlsarOut))) return rc;
+    ctx->last_kernel = sg.n_seg > 0 ? "k18_glsar_split" : "k18_glsar";
+    if ((rc = k18_gram_launch(ctx, b->dtype, a))) return rc;
+    if ((rc = k18_solve_launch(ctx, b->dtype, a))) return rc;
+    if (need_rows) {
+        if ((rc = k18_rows_launch(ctx, b->dtype, a))) return rc;
+        if ((rc = k18_finish_launch(ctx, a))) return rc;
+    }
+    if ((rc = fit_predict(ctx, b, fc, &sg, a.x, a.k_user, kt, a.coefp))) return rc;
     return xo.home(ctx, b, o, fc);
 }
 

@@ -106,6 +106,9 @@ enum class Work : int {
     Absorb2Cols,    // two absorbed effects (K17): the column scratch (k + 1) x n_rows in id-1 order (f64), the rows' weights, labels and fit bytes
     Absorb2Moments, // two absorbed effects (K17): Gram partials per segment / group, the groups' state, the per-column and per-group records of the demean launch
     Absorb2Out,     // two absorbed effects (K17): the pols_absorb2_out fields of a HOST batch before they go home
+    GlsarMoments,   // AR(1) FGLS (K18): S, the lag-one cross-moments C and the row count per segment / group, then the partials of the rows launch
+    GlsarState,     // AR(1) FGLS (K18): n, usable, rho*, sqrt(1 - rho*^2), b, b0 and A_xx(rho*)^-1 per group (f64), then the coefficients for the prediction pass
+    GlsarOut,       // AR(1) FGLS (K18): the pols_glsar_out fields of a HOST batch before they go home
     Count
 };
 

@@ -290,7 +290,7 @@ class Engine:
         return res
 
     def _fit_entry(self, name, fn, fields, out_cls, q, shapes, want, y, x_cols, offsets, plan_kw, extra=None, keep=()):
-        """What ridge_cv / rlm / glm / iv2sls / elastic_net_cv share: the ``want`` check, the plan of the frame, the entry's own
+        """What ridge_cv / rlm / glm / iv2sls / glsar / elastic_net_cv share: the ``want`` check, the plan of the frame, the entry's own
         outputs and the call of the C entry named ``fn`` with (ctx, batch, params, q, out, out_cls(...)); returns the results.
         ``plan_kw["out"]`` may carry pre-allocated ``coef`` / ``pred`` / ``resid`` / ``status`` buffers, as in ``least_squares``.
         ``shapes(G, N, kt)`` gives {field: (shape, "f64" | "i32" | "i64" | "batch")} for ``fields``.  ``extra(b, like, dev)`` is
@@ -410,6 +410,28 @@ class Engine:
                                                  "n_obs": ((G,), "i64")},
                                want, y, x_cols, offsets, dict(weights=weights, valid=valid, add_intercept=add_intercept, null_policy=null_policy, out=out),
                                extra=bring_instruments)
+
+    def glsar(self, y, x_cols: Sequence, offsets, *, method: str = "prais_winsten", max_iter: int = 100, tol: float = 1e-6,
+              want: Sequence[str] = ("coef", "status", "rho", "se", "dw"), weights=None, valid=None, add_intercept: bool = False,
+              null_policy: str = "ignore", null_free: bool = False, out: Optional[Dict] = None) -> Dict:
+        """AR(1) feasible GLS -- Cochrane-Orcutt / Prais-Winsten, statsmodels' ``GLSAR``, Stata's ``prais`` -- for every group in one
+        call, the whole iteration on the device (pols_glsar; the definitions and edge rules are in include/pols_mi355x.h).  The rows
+        of a group are its time series in order.  ``method``: "prais_winsten" or "cochrane_orcutt"; ``max_iter`` / ``tol``: the
+        updates of rho at the most and the stop rule on its change (status 3 = stopped at ``max_iter``, the result is still
+        returned; ``max_iter=1`` is the two-step estimator).  ``null_policy``: "ignore" or "zero" (a drop-family policy only with
+        ``null_free=True``); ``weights`` and ``valid`` are not built and raise.  ``want``: any of ``coef pred resid status`` (status
+        4 = no degrees of freedom), ``se t_values p_values`` [n_groups, k, f64], ``cov`` [n_groups, k, k, f64], ``sigma2 rho dw
+        dw_ols`` [n_groups, f64], ``n_iter`` [n_groups, int32] and ``n_obs`` [n_groups, int64].  Arrays are numpy or torch and live
+        where the inputs live.  Without any of ``se t_values p_values cov sigma2 dw dw_ols`` the columns are read once."""
+        if weights is not None or valid is not None:
+            raise ValueError("glsar: sample weights and validity masks are not built")
+        q = _glsar_params(self._lib, method, max_iter, tol)
+        return self._fit_entry("glsar", "pols_glsar", L.GLSAR_FIELDS, L.GlsarOut, q,
+                               lambda G, N, kt: {"se": ((G, kt), "f64"), "t_values": ((G, kt), "f64"), "p_values": ((G, kt), "f64"),
+                                                 "cov": ((G, kt, kt), "f64"), "sigma2": ((G,), "f64"), "rho": ((G,), "f64"),
+                                                 "dw": ((G,), "f64"), "dw_ols": ((G,), "f64"), "n_iter": ((G,), "i32"),
+                                                 "n_obs": ((G,), "i64")},
+                               want, y, x_cols, offsets, dict(add_intercept=add_intercept, null_policy=null_policy, null_free=null_free, out=out))
 
     def absorb(self, y, x_cols: Sequence, ids, offsets, *, cov_type: str = "nonrobust",
                want: Sequence[str] = ("coef", "status", "se", "n_obs", "n_categories"), weights=None, valid=None,
@@ -834,6 +856,21 @@ def _absorb2_params(lib, n_features, cov_type, add_intercept, max_iter, tol) -> 
     if lib is not None:
         lib.pols_absorb2_params_default(C.byref(q))
     q.ids, q.ids2, q.cov_type, q.max_iter, q.tol = None, None, L.COV_TYPES[cov_type], int(max_iter), float(tol)
+    return q
+
+
+def _glsar_params(lib, method, max_iter, tol) -> "L.GlsarParams":
+    """the argument checks of Engine.glsar / compute_glsar (``lib`` None: check only, no device needed)"""
+    if method not in L.GLSAR_METHODS:
+        raise ValueError(f"glsar: 'method' must be one of {sorted(L.GLSAR_METHODS)}, got {method!r}")
+    if isinstance(max_iter, bool) or int(max_iter) != max_iter or max_iter < 1:
+        raise ValueError(f"glsar: 'max_iter' must be an integer >= 1 (got {max_iter!r})")
+    if not (isinstance(tol, (int, float)) and not isinstance(tol, bool) and 0.0 < float(tol) < float("inf")):
+        raise ValueError(f"glsar: 'tol' must be positive and finite (got {tol!r})")
+    q = L.GlsarParams()
+    if lib is not None:
+        lib.pols_glsar_params_default(C.byref(q))
+    q.method, q.max_iter, q.tol = L.GLSAR_METHODS[method], int(max_iter), float(tol)
     return q
 
 

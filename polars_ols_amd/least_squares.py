@@ -26,7 +26,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import PolsPanic
-from .engine import Engine, Layout, _absorb_params, _absorb2_params, _enet_cv_params, _is_torch, _glm_params, _iv_params, _ridge_cv_grid, _rlm_params, default_engine
+from .engine import Engine, Layout, _absorb_params, _absorb2_params, _enet_cv_params, _is_torch, _glm_params, _glsar_params, _iv_params, _ridge_cv_grid, _rlm_params, default_engine
 
 try:
     import torch
@@ -45,6 +45,7 @@ __all__ = [
     "compute_rlm", "RLM",
     "compute_glm", "GLM",
     "compute_iv2sls", "IV2SLS",
+    "compute_glsar", "GLSAR",
     "compute_absorbed_least_squares", "AbsorbedOLS",
 ]
 
@@ -597,6 +598,42 @@ def _apply_iv2sls(frame: Frame, over, eng: Optional[Engine], target: Expr, exog:
     return target.output_name, grp.untake(out["pred"] if mode == "predictions" else out["resid"])
 
 
+class GLSAR(dict):
+    """mode="statistics" of an AR(1) feasible GLS fit (pols_glsar; the definitions are in include/pols_mi355x.h): per group
+    ``coefficients standard_errors t_values p_values`` [G, k] (``feature_names``), ``cov`` [G, k, k], ``sigma2 rho dw dw_ols n_iter
+    n_obs status`` [G] (``rho``: the AR(1) coefficient of the errors, ``dw`` / ``dw_ols``: Durbin-Watson of the transformed and of the
+    OLS residuals, status 3 = stopped at max_iter); ``keys`` holds the group keys of an ``.over`` (None for a whole-frame fit,
+    where G == 1)."""
+
+    def __init__(self, names, out, keys, method):
+        super().__init__(feature_names=list(names), keys=keys, coefficients=out["coef"], standard_errors=out["se"],
+                         t_values=out["t_values"], p_values=out["p_values"], cov=out["cov"], sigma2=out["sigma2"], rho=out["rho"],
+                         dw=out["dw"], dw_ols=out["dw_ols"], n_iter=out["n_iter"], n_obs=out["n_obs"], status=out["status"],
+                         method=method)
+        self.keys_ = keys
+
+
+_VALID_GLSAR_MODES = ("predictions", "residuals", "coefficients", "statistics")
+
+
+def _apply_glsar(frame: Frame, over, eng: Optional[Engine], target: Expr, features: Sequence[Expr], add_intercept: bool, mode: str,
+                 method: str, max_iter: int, tol: float, null_policy: str):
+    """compute_glsar body: the group layout of _apply_static around Engine.glsar (the rows of a group keep their frame order)."""
+    y, xs, names, icpt, _ = _pre_process_data(frame, target, features, None, add_intercept)
+    eng = eng or default_engine(y.device.index or 0 if _is_torch(y) else 0)
+    grp = _Groups(eng, None if over is None else (frame[over] if isinstance(over, str) else over), y.shape[0])
+    moved = grp.take([y] + list(xs))
+    want = {"predictions": ("pred",), "residuals": ("resid",), "coefficients": ("coef",),
+            "statistics": ("coef", "status") + _lib.GLSAR_FIELDS}[mode]
+    out = eng.glsar(moved[0], moved[1:], grp.offsets, method=method, max_iter=max_iter, tol=tol, want=want, add_intercept=icpt,
+                    null_policy=null_policy)
+    if mode == "statistics":
+        return "statistics", GLSAR(names, out, grp.keys, method)
+    if mode == "coefficients":
+        return "coefficients", Coefficients(names, out["coef"], grp.keys, grp.gid_frame(out["coef"]))
+    return target.output_name, grp.untake(out["pred"] if mode == "predictions" else out["resid"])
+
+
 class AbsorbedOLS(dict):
     """mode="statistics" of an absorbed-effect fit (pols_least_squares_absorb; the definitions are in include/pols_mi355x.h): per
     group ``coefficients standard_errors t_values p_values`` [G, k] (``feature_names``; with an intercept the last coefficient is the
@@ -838,6 +875,24 @@ def compute_iv2sls(target, *exog, endog, instruments, cov_type: str = "nonrobust
     _iv_params(None, len(ex) + len(en), len(zs), len(en), cov_type, small_sample, icpt)
     return Expr(t._name, fn=lambda frame, over, eng: _apply_iv2sls(frame, over, eng, t, ex, en, zs, sample_weights, add_intercept, mode,
                                                                    cov_type, small_sample, null_policy))
+
+
+def compute_glsar(target, *features, method: str = "prais_winsten", max_iter: int = 100, tol: float = 1e-6, add_intercept: bool = False,
+                  mode: str = "predictions", null_policy: str = "ignore") -> Expr:
+    """Regression with AR(1) errors per group by feasible GLS (statsmodels' GLSAR, Stata's prais / prais, corc for every group of the
+    frame in one call): the rows of a group are its time series in frame order.  ``method``: "prais_winsten" or "cochrane_orcutt";
+    ``max_iter`` / ``tol``: the updates of rho at the most and the stop rule (``max_iter=1``: the two-step estimator).  Modes
+    "predictions" (x'b on the original scale), "residuals" and "coefficients"; mode="statistics" returns a ``GLSAR`` with rho, standard
+    errors, t and p values, the covariance matrix and the Durbin-Watson statistics before and after.  ``null_policy``: "ignore" or
+    "zero"."""
+    if mode not in _VALID_GLSAR_MODES:
+        raise ValueError(f"'mode' must be one of {_VALID_GLSAR_MODES}, got {mode!r}")
+    if null_policy not in ("ignore", "zero"):
+        raise ValueError(f"glsar: 'null_policy' must be 'ignore' or 'zero' (the drop family is not built), got {null_policy!r}")
+    _glsar_params(None, method, max_iter, tol)
+    t, fs = parse_into_expr(target), [parse_into_expr(f) for f in features]
+    return Expr(t._name, fn=lambda frame, over, eng: _apply_glsar(frame, over, eng, t, fs, add_intercept, mode, method, max_iter, tol,
+                                                                  null_policy))
 
 
 def compute_absorbed_least_squares(target, *features, absorb, cov_type: str = "nonrobust", sample_weights=None,
@@ -1137,6 +1192,11 @@ class LeastSquares:
             raise ValueError("lasso_cv: l1_ratio is fixed at 1; use elastic_net_cv")
         kwargs["l1_ratio"] = 1.0
         return self.elastic_net_cv(*features, **kwargs)
+
+    def glsar(self, *features, method: str = "prais_winsten", max_iter: int = 100, tol: float = 1e-6, add_intercept: bool = False,
+              mode: str = "predictions", null_policy: str = "ignore") -> Expr:
+        return compute_glsar(self._expr, *features, method=method, max_iter=max_iter, tol=tol, add_intercept=add_intercept, mode=mode,
+                             null_policy=null_policy)
 
     def rlm(self, *features, norm: str = "huber", c: Optional[float] = None, max_iter: int = 50, tol: float = 1e-8,
             sample_weights=None, add_intercept: bool = False, mode: str = "predictions", null_policy: str = "ignore") -> Expr:
