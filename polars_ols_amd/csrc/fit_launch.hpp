@@ -1,4 +1,5 @@
-// fit_launch.hpp -- the host side of a launch of the per-group fit kernels K10 .. K14 and K16 (the device side: fit_tile.inl, fit_solve.inl).
+// fit_launch.hpp -- the host side of a launch of the per-group fit kernels K10 .. K14 and K16 .. K18 (the device side: fit_tile.inl,
+// fit_solve.inl, fit_group.inl).
 #pragma once
 #include "common.hpp"
 
@@ -26,6 +27,15 @@ int fit_launch(pols_ctx *ctx, K kernel, OncePerDevice &once, const int64_t grid,
                const A &...args) {
     const int rc = fit_raise_lds(ctx, kernel, once, budget);
     if (rc) return rc;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(block), lds, ctx->stream, args...);
+    POLS_HIP(hipGetLastError());
+    return POLS_OK;
+}
+
+// the plain launch of a kernel whose LDS stays under the default limit (the one-wave-per-group kernels): nothing for an empty grid
+template <typename K, typename... A>
+static inline int fit_launch_plain(pols_ctx *ctx, K kernel, const int64_t grid, const int block, const size_t lds, const A &...args) {
+    if (grid == 0) return POLS_OK;
     hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(block), lds, ctx->stream, args...);
     POLS_HIP(hipGetLastError());
     return POLS_OK;

@@ -1,6 +1,7 @@
-// fit_solve.inl -- the one-wave Cholesky solve of K11 (k11_rlm.hip), K13 (k13_glm.hip) and K14 (k14_iv.hip): a packed Gram matrix in
-// LDS goes to the coefficients by a right-looking factorisation (the trailing update spread over the lanes) and the two
-// substitutions; K14 also takes the factorisation alone, and K16 (k16_absorb.hip) takes it with pivots held against another diagonal.
+// fit_solve.inl -- the one-wave Cholesky solve of K11 (k11_rlm.hip), K13 (k13_glm.hip), K14 (k14_iv.hip) and K18 (k18_glsar.hip): a
+// packed Gram matrix in LDS goes to the coefficients by a right-looking factorisation (the trailing update spread over the lanes) and
+// the two substitutions; K14 also takes the factorisation alone, and K16 / K17 (k16_solve_core, k16_absorb.inl) take it with pivots held
+// against another diagonal.  What the one-wave-per-group kernels share around the solve is in fit_group.inl.
 #pragma once
 #include "fit_tile.inl"
 

@@ -30,29 +30,10 @@
 #include "k14_iv.hpp"
 #include "k10_ridge_path.hpp"
 #include "fit_launch.hpp"
-#include "fit_solve.inl"
-#include "k7_stats.hpp"
+#include "fit_group.inl"
+#include "fit_lds.hpp"
 
 namespace pols {
-
-// offsets (doubles) of the solve launch's LDS areas
-struct K14Lds { int Gs, A, d0, B, Gm2, A2, rhs2, d02, Ri, tmp, total; };
-__host__ __device__ inline K14Lds k14_lds(int kx, int L, int T) {
-    K14Lds o;
-    int at = 0;
-    o.Gs = at;   at += (T + 1) * (T + 2) / 2 + 1;      // the summed moments (packed upper triangle), then n
-    o.A = at;    at += L * (L + 1);                    // Z~'Z~, then its factor R in the lower triangle
-    o.d0 = at;   at += L;
-    o.B = at;    at += L * (kx + 1);                   // [C | Z~'y~] -> [Q | r] -> Pi in the first kx columns
-    o.Gm2 = at;  at += (kx + 1) * (kx + 2) / 2;        // packed [M, Q'r; ., r'r]
-    o.A2 = at;   at += kx * (kx + 1);                  // M, then its factor
-    o.rhs2 = at; at += kx;                             // Q'r -> b
-    o.d02 = at;  at += kx;
-    o.Ri = at;   at += kx * kx;                        // the inverse of M's factor
-    o.tmp = at;  at += L;                              // the Sargan terms
-    o.total = at;
-    return o;
-}
 
 size_t k14_solve_lds(int kx, int L, int T) { return sizeof(double) * (size_t)k14_lds(kx, L, T).total; }
 
@@ -61,21 +42,17 @@ __global__ void __launch_bounds__(64) k14_solve_kernel(const IvArgs a) {
     extern __shared__ __attribute__((aligned(16))) double dyn[];
     const int lane = threadIdx.x, T = a.kt, nz = T + 1, ne = nz * (nz + 1) / 2;
     const int nf = a.n_feat, icpt = a.icpt, kx = nf + icpt, k1 = nf - a.n_endog, m = a.n_inst, L = kx - a.n_endog + m;
-    const int LD = L + 1, LDB = kx + 1, LD2 = kx + 1;
+    const int LD = L + 1, LDB = kx + 1;
     const K14Lds o = k14_lds(kx, L, T);
     double *Gs = dyn + o.Gs, *A = dyn + o.A, *d0 = dyn + o.d0, *B = dyn + o.B, *Gm2 = dyn + o.Gm2, *A2 = dyn + o.A2, *rhs2 = dyn + o.rhs2,
            *d02 = dyn + o.d02, *Ri = dyn + o.Ri, *tmp = dyn + o.tmp;
     const int64_t g = blockIdx.x;
+    // (fit_group_items, written out: through the call the compiler fetches the two seg_first words with one 8-byte scalar load and lays
+    // the head of the kernel out differently, and the long-group lines of scripts/bench_iv.py -- one wave summing every segment's
+    // partials -- came out up to 0.3 % over the range of the kernel before; this form compiles to that kernel's instructions up to
+    // the inverse.  profiles/fit_group_stages_bench.txt has both runs; the second does not prove the helper was the cause)
     const int64_t v0 = a.seg_offs ? a.seg_first[g] : g, v1 = a.seg_offs ? a.seg_first[g + 1] : g + 1;
-    const size_t gs = k10_gram_stride(T);
-    bool fin = true;
-    for (int en = lane; en <= ne; en += 64) {
-        double v = 0.0;
-        for (int64_t it = v0; it < v1; ++it) v += a.gram_part[(size_t)it * gs + en];
-        Gs[en] = v;
-        fin = fin && fabs(v) <= FIT_DBL_MAX;
-    }
-    const bool finite = __ballot(!fin) == 0;
+    const bool finite = fit_sum_parts(a.gram_part, k10_gram_stride(T), v0, v1, ne + 1, Gs, lane);   // the triangle, then n
     fit_wave_sync();
     const double n = Gs[ne];
     // where column i of X and column l of Z (factorisation order [X1 | 1 | Z2]) sit in the staged list [X1 | X2 | Z2 | 1]
@@ -136,24 +113,11 @@ __global__ void __launch_bounds__(64) k14_solve_kernel(const IvArgs a) {
             fsf = (dl / (double)m) / (rssu / (n - (double)L));
             pr2 = dl / (dl + rssu);
         }
-        if (lane < kx) {                                           // column `lane` of the inverse of M's factor
-            for (int j = 0; j < kx; ++j) {
-                double s = j == lane ? 1.0 : 0.0;
-                for (int i = lane; i < j; ++i) s = fma(-A2[j * LD2 + i], Ri[i * kx + lane], s);
-                Ri[j * kx + lane] = j < lane ? 0.0 : s / A2[j * LD2 + j];
-            }
-        }
-        fit_wave_sync();
+        fit_chol_inverse(A2, Ri, st + 4 + kx, kx, lane);           // M^-1 (its fit_wave_sync() publishes tmp as well)
         if (lane == 0) {
             double v = 0.0;
             for (int l = 0; l < L; ++l) v += tmp[l];
             st[2] = v;
-        }
-        for (int p = lane; p < kx * kx; p += 64) {                 // M^-1
-            const int i = p / kx, j = p - i * kx;
-            double v = 0.0;
-            for (int l = i > j ? i : j; l < kx; ++l) v = fma(Ri[l * kx + i], Ri[l * kx + j], v);
-            st[4 + kx + p] = v;
         }
         if (lane < kx) {                                           // R'Pi = Q in place, rows stored in the tile's order [X1 | Z2 | 1]
             double *Pi = st + 4 + kx + kx * kx;
@@ -179,7 +143,7 @@ __global__ void __launch_bounds__(64) k14_solve_kernel(const IvArgs a) {
     if (lane < kx) {
         const double bv = ok ? rhs2[lane] : fillv;
         st[4 + lane] = bv;
-        if (a.coef) { if (a.f32) static_cast<float *>(a.coef)[(size_t)g * kx + lane] = (float)bv; else static_cast<double *>(a.coef)[(size_t)g * kx + lane] = bv; }
+        fit_store_coef(a, g, kx, lane, bv);
     }
     if (a.pred_all) {                                              // [b_X1 b_X2 | 0 (Z2) | b_1]
         if (lane < T) a.coefp[(size_t)g * T + lane] = lane < nf ? (ok ? rhs2[lane] : fillv) : (lane < nf + m ? 0.0 : (ok ? rhs2[nf] : fillv));
@@ -193,11 +157,8 @@ __global__ void __launch_bounds__(64) k14_solve_kernel(const IvArgs a) {
 }
 
 int k14_solve_launch(pols_ctx *ctx, const IvArgs &a) {
-    if (a.n_groups == 0) return POLS_OK;
     const int kx = a.n_feat + a.icpt, L = kx - a.n_endog + a.n_inst;
-    hipLaunchKernelGGL(k14_solve_kernel, dim3((unsigned)a.n_groups), dim3(64), k14_solve_lds(kx, L, a.kt), ctx->stream, a);
-    POLS_HIP(hipGetLastError());
-    return POLS_OK;
+    return fit_launch_plain(ctx, k14_solve_kernel, a.n_groups, 64, k14_solve_lds(kx, L, a.kt), a);
 }
 
 // ---------------------------------------------------------------- rows
@@ -275,18 +236,15 @@ __global__ void __launch_bounds__(64) k14_finish_kernel(const IvArgs a) {
     const int lane = threadIdx.x, kx = a.n_feat + a.icpt, L = kx - a.n_endog + a.n_inst, dof = a.n_inst - a.n_endog;
     const bool robust = a.cov_type != POLS_COV_NONROBUST;
     const int64_t g = blockIdx.x;
-    const int64_t v0 = a.seg_offs ? a.seg_first[g] : g, v1 = a.seg_offs ? a.seg_first[g + 1] : g + 1;
+    int64_t v0, v1;
+    fit_group_items(a, g, v0, v1);
     const double *st = a.state + (size_t)g * k14_state_stride(kx, L);
     const double n = st[0];
     const bool ok = st[1] != 0.0;                                  // (wave-uniform)
     double *cov = a.cov ? a.cov + (size_t)g * kx * kx : nullptr;
     if (!ok) {
         const double q = fit_nan();
-        if (lane < kx) {
-            if (a.se) a.se[(size_t)g * kx + lane] = q;
-            if (a.t_values) a.t_values[(size_t)g * kx + lane] = q;
-            if (a.p_values) a.p_values[(size_t)g * kx + lane] = q;
-        }
+        if (lane < kx) fit_store_stats(a, g, kx, lane, q, q, q);
         if (cov) for (int p = lane; p < kx * kx; p += 64) cov[p] = q;
         if (lane == 0) {
             if (a.sigma2) a.sigma2[g] = q;
@@ -330,10 +288,10 @@ __global__ void __launch_bounds__(64) k14_finish_kernel(const IvArgs a) {
     __syncthreads();
     if (cov) for (int p = lane; p < kx * kx; p += 64) cov[p] = Me[p];
     if (lane < kx) {
+        // (not fit_se_t_p: on a NaN t it stores the canonical NaN, k7_betai its argument's -- one form for both would change bytes)
         const double se = sqrt(Me[lane * kx + lane]), tv = st[4 + lane] / se;
-        if (a.se) a.se[(size_t)g * kx + lane] = se;
-        if (a.t_values) a.t_values[(size_t)g * kx + lane] = tv;
-        if (a.p_values) a.p_values[(size_t)g * kx + lane] = a.small_sample ? k7_betai(0.5 * df, 0.5, df / (df + tv * tv)) : erfc(fabs(tv) * 0.70710678118654752440);
+        const double pv = !a.p_values ? 0.0 : (a.small_sample ? k7_betai(0.5 * df, 0.5, df / (df + tv * tv)) : erfc(fabs(tv) * 0.70710678118654752440));
+        fit_store_stats(a, g, kx, lane, se, tv, pv);
     }
     if (lane == 0) {
         if (a.sigma2) a.sigma2[g] = sigma2;
@@ -343,11 +301,6 @@ __global__ void __launch_bounds__(64) k14_finish_kernel(const IvArgs a) {
     }
 }
 
-int k14_finish_launch(pols_ctx *ctx, const IvArgs &a) {
-    if (a.n_groups == 0) return POLS_OK;
-    hipLaunchKernelGGL(k14_finish_kernel, dim3((unsigned)a.n_groups), dim3(64), 0, ctx->stream, a);
-    POLS_HIP(hipGetLastError());
-    return POLS_OK;
-}
+int k14_finish_launch(pols_ctx *ctx, const IvArgs &a) { return fit_launch_plain(ctx, k14_finish_kernel, a.n_groups, 64, 0, a); }
 
 }  // namespace pols

@@ -122,13 +122,7 @@ int k16_count_launch(pols_ctx *ctx, const AbsorbArgs &a) {
     return POLS_OK;
 }
 
-int k16_index_launch(pols_ctx *ctx, const AbsorbArgs &a) {
-    const int64_t items = fit_items(a);
-    if (items == 0) return POLS_OK;
-    hipLaunchKernelGGL(k16_index_kernel, dim3((unsigned)items), dim3(256), 0, ctx->stream, a);
-    POLS_HIP(hipGetLastError());
-    return POLS_OK;
-}
+int k16_index_launch(pols_ctx *ctx, const AbsorbArgs &a) { return fit_launch_plain(ctx, k16_index_kernel, fit_items(a), 256, 0, a); }
 
 // ---------------------------------------------------------------- means
 template <typename T>
@@ -164,11 +158,8 @@ __global__ void __launch_bounds__(64) k16_means_kernel(const AbsorbArgs a) {
 }
 
 int k16_means_launch(pols_ctx *ctx, int dtype, const AbsorbArgs &a) {
-    if (a.n_cats == 0) return POLS_OK;
-    if (dtype == POLS_F32) hipLaunchKernelGGL(k16_means_kernel<float>, dim3((unsigned)a.n_cats), dim3(64), 0, ctx->stream, a);
-    else hipLaunchKernelGGL(k16_means_kernel<double>, dim3((unsigned)a.n_cats), dim3(64), 0, ctx->stream, a);
-    POLS_HIP(hipGetLastError());
-    return POLS_OK;
+    return dtype == POLS_F32 ? fit_launch_plain(ctx, k16_means_kernel<float>, a.n_cats, 64, 0, a)
+                             : fit_launch_plain(ctx, k16_means_kernel<double>, a.n_cats, 64, 0, a);
 }
 
 // ---------------------------------------------------------------- gram
@@ -241,19 +232,14 @@ int k16_gram_launch(pols_ctx *ctx, int dtype, const AbsorbArgs &a) {
 // ---------------------------------------------------------------- solve
 __global__ void __launch_bounds__(64) k16_solve_kernel(const AbsorbArgs a) {
     extern __shared__ __attribute__((aligned(16))) double dyn[];
-    const int lane = threadIdx.x, k = a.k_user, nz = k + 1, ne = nz * (nz + 1) / 2, LD = k + 1, kc = k + a.icpt;
-    double *Gs = dyn, *A = Gs + ne + k + 1, *d0 = A + k * LD, *rhs = d0 + k, *Ri = rhs + k;
+    const int lane = threadIdx.x, k = a.k_user, nz = k + 1, ne = nz * (nz + 1) / 2, kc = k + a.icpt;
+    const AbsorbLds o = k16_lds(k);
+    double *Gs = dyn + o.Gs, *rhs = dyn + o.rhs;
     const int64_t g = blockIdx.x;
-    const int64_t v0 = a.seg_offs ? a.seg_first[g] : g, v1 = a.seg_offs ? a.seg_first[g + 1] : g + 1;
-    const size_t gs = k16_gram_stride(k), cs = k16_cat_stride(k);
-    bool fin = true;
-    for (int en = lane; en < ne + k + 1; en += 64) {
-        double v = 0.0;
-        for (int64_t it = v0; it < v1; ++it) v += a.gram_part[(size_t)it * gs + en];
-        Gs[en] = v;
-        fin = fin && fabs(v) <= FIT_DBL_MAX;
-    }
-    const bool finite = __ballot(!fin) == 0;
+    int64_t v0, v1;
+    fit_group_items(a, g, v0, v1);
+    const size_t cs = k16_cat_stride(k);
+    const bool finite = fit_sum_parts(a.gram_part, k16_gram_stride(k), v0, v1, ne + k + 1, Gs, lane);   // the triangle, T_jj, n
     fit_wave_sync();
     const double n = Gs[ne + k];
     // the group's categories: those with a fitted row count; the weighted mean of y and the between sum of squares from the table
@@ -273,7 +259,7 @@ __global__ void __launch_bounds__(64) k16_solve_kernel(const AbsorbArgs a) {
     const double df = n - (double)k - C;
     bool ok = finite && n > 0.0 && df > 0.0;
     double *st = a.state + (size_t)g * k16_state_stride(k);
-    ok = k16_solve_core(ok, Gs, Gs + ne, A, d0, rhs, Ri, st + 8 + k, k, lane);
+    ok = k16_solve_core(ok, dyn, o, st + 8 + k, k, lane);
     // the effects a_c = ybar_c - xbar_c'b into the table (NaN for a category without a fitted row, and for a group without a fit)
     double lA = 0.0;
     for (int64_t c = c0i + lane; c < c1i; c += 64) {
@@ -296,21 +282,11 @@ __global__ void __launch_bounds__(64) k16_solve_kernel(const AbsorbArgs a) {
     }
     const double fillv = n > 0.0 ? fit_nan() : 0.0;                // no rows: zeros, as the existing entries
     if (lane < k) st[8 + lane] = ok ? rhs[lane] : fit_nan();
-    if (lane < kc) {
-        const double bv = ok ? (lane < k ? rhs[lane] : c0) : fillv;
-        if (a.coef) { if (a.f32) static_cast<float *>(a.coef)[(size_t)g * kc + lane] = (float)bv; else static_cast<double *>(a.coef)[(size_t)g * kc + lane] = bv; }
-    }
-}
-
-static size_t k16_solve_lds(int k) {
-    return sizeof(double) * ((size_t)(k + 1) * (k + 2) / 2 + k + 1 + (size_t)k * (k + 1) + 2 * (size_t)k + (size_t)k * k);
+    if (lane < kc) fit_store_coef(a, g, kc, lane, ok ? (lane < k ? rhs[lane] : c0) : fillv);
 }
 
 int k16_solve_launch(pols_ctx *ctx, const AbsorbArgs &a) {
-    if (a.n_groups == 0) return POLS_OK;
-    hipLaunchKernelGGL(k16_solve_kernel, dim3((unsigned)a.n_groups), dim3(64), k16_solve_lds(a.k_user), ctx->stream, a);
-    POLS_HIP(hipGetLastError());
-    return POLS_OK;
+    return fit_launch_plain(ctx, k16_solve_kernel, a.n_groups, 64, sizeof(double) * (size_t)k16_lds(a.k_user).total, a);
 }
 
 // ---------------------------------------------------------------- resid
@@ -325,15 +301,9 @@ __global__ void __launch_bounds__(64) k16_resid_kernel(const AbsorbArgs a) {
     const double *st = a.state + (size_t)g * k16_state_stride(k);
     const double *m = a.cat + (size_t)c * k16_cat_stride(k);
     double *out = a.resid_part + (size_t)c * k16_resid_stride(k, cluster);
-    if (st[1] == 0.0) {                                            // no fit (wave-uniform): the finish writes NaN
-        if (lane == 0) out[0] = 0.0;
-        if (cluster && lane < k) out[1 + lane] = 0.0;
-        return;
-    }
+    if (!absorb_resid_head(st, 8, 8 + k, out, cluster, k, lane, bs, Ai)) return;
     k16_columns(a, xp, lane);
-    if (lane < k) { bs[lane] = st[8 + lane]; ms[lane] = m[3 + lane]; }
-    if (cluster)
-        for (int q = lane; q < k * k; q += 64) Ai[q] = st[8 + k + q];
+    if (lane < k) ms[lane] = m[3 + lane];
     __syncthreads();
     const T *yp = static_cast<const T *>(a.y), *wp = static_cast<const T *>(a.w);
     const double ybar = m[2];
@@ -359,82 +329,26 @@ __global__ void __launch_bounds__(64) k16_resid_kernel(const AbsorbArgs a) {
             }
         }
     }
-    const double tot = k16_wave_sum(rss);
-    if (lane == 0) out[0] = tot;
-    if (cluster) {
-        if (lane < k) ss[lane] = sacc;
-        __syncthreads();
-        if (lane < k) {
-            double z = 0.0;
-            for (int q = 0; q < k; ++q) z = fma(Ai[lane * k + q], ss[q], z);
-            out[1 + lane] = z * z;
-        }
-    }
+    absorb_resid_tail(rss, sacc, ss, Ai, out, cluster, k, lane);
 }
 
 int k16_resid_launch(pols_ctx *ctx, int dtype, const AbsorbArgs &a) {
-    if (a.n_cats == 0) return POLS_OK;
-    if (dtype == POLS_F32) hipLaunchKernelGGL(k16_resid_kernel<float>, dim3((unsigned)a.n_cats), dim3(64), 0, ctx->stream, a);
-    else hipLaunchKernelGGL(k16_resid_kernel<double>, dim3((unsigned)a.n_cats), dim3(64), 0, ctx->stream, a);
-    POLS_HIP(hipGetLastError());
-    return POLS_OK;
+    return dtype == POLS_F32 ? fit_launch_plain(ctx, k16_resid_kernel<float>, a.n_cats, 64, 0, a)
+                             : fit_launch_plain(ctx, k16_resid_kernel<double>, a.n_cats, 64, 0, a);
 }
 
 // ---------------------------------------------------------------- finish
 __global__ void __launch_bounds__(64) k16_finish_kernel(const AbsorbArgs a) {
-    const int lane = threadIdx.x, k = a.k_user, kc = k + a.icpt;
-    const bool cluster = a.cluster != 0;
+    const int k = a.k_user;
     const int64_t g = blockIdx.x;
-    const int64_t v0 = a.seg_offs ? a.seg_first[g] : g, v1 = a.seg_offs ? a.seg_first[g + 1] : g + 1;
-    const int64_t c0i = a.item_first[v0], c1i = a.item_first[v1];
+    int64_t v0, v1;
+    fit_group_items(a, g, v0, v1);
     const double *st = a.state + (size_t)g * k16_state_stride(k);
-    const double n = st[0], C = st[2], df = st[3];
-    const bool ok = st[1] != 0.0;                                  // (wave-uniform)
-    const double q = fit_nan();
-    double se = q, tv = q, pv = q, sigma2 = q, r2w = q, r2 = q;
-    if (ok) {
-        const size_t rs = k16_resid_stride(k, cluster);
-        double l = 0.0;
-        for (int64_t c = c0i + lane; c < c1i; c += 64) l += a.resid_part[(size_t)c * rs];
-        const double rss = k16_wave_sum(l);
-        sigma2 = rss / df;
-        r2w = 1.0 - rss / st[5];
-        r2 = 1.0 - rss / st[6];
-        double v = q, dfp = df;
-        if (cluster) {
-            double mine = 0.0;
-            for (int j = 0; j < k; ++j) {
-                double lz = 0.0;
-                for (int64_t c = c0i + lane; c < c1i; c += 64) lz += a.resid_part[(size_t)c * rs + 1 + j];
-                const double t = k16_wave_sum(lz);
-                if (lane == j) mine = t;
-            }
-            const double d1 = n - (double)k - 1.0;
-            dfp = C - 1.0;
-            if (C >= 2.0 && d1 > 0.0) v = C / (C - 1.0) * (n - 1.0) / d1 * mine;
-        } else if (lane < k) {
-            v = sigma2 * st[8 + k + lane * k + lane];
-        }
-        if (lane < k) k16_se_t_p(v, st[8 + lane], dfp, se, tv, pv);
-    }
-    if (lane < kc) {                                               // (the intercept's entries stay NaN)
-        if (a.se) a.se[(size_t)g * kc + lane] = se;
-        if (a.t_values) a.t_values[(size_t)g * kc + lane] = tv;
-        if (a.p_values) a.p_values[(size_t)g * kc + lane] = pv;
-    }
-    if (lane == 0) {
-        if (a.sigma2) a.sigma2[g] = sigma2;
-        if (a.r2_within) a.r2_within[g] = r2w;
-        if (a.r2) a.r2[g] = r2;
-    }
+    const double n = st[0], C = st[2];
+    absorb_finish(a, g, st, a.item_first[v0], a.item_first[v1], k16_resid_stride(k, a.cluster != 0), C, n - (double)k - 1.0, 8, 8 + k);
 }
 
-int k16_finish_launch(pols_ctx *ctx, const AbsorbArgs &a) {
-    if (a.n_groups == 0) return POLS_OK;
-    hipLaunchKernelGGL(k16_finish_kernel, dim3((unsigned)a.n_groups), dim3(64), 0, ctx->stream, a);
-    POLS_HIP(hipGetLastError());
-    return POLS_OK;
-}
+int k16_finish_launch(pols_ctx *ctx, const AbsorbArgs &a) { return fit_launch_plain(ctx, k16_finish_kernel, a.n_groups, 64, 0, a); }
 
 // ---------------------------------------------------------------- predict
 template <typename T>
@@ -459,11 +373,8 @@ __global__ void __launch_bounds__(256) k16_predict_kernel(const AbsorbArgs a) {
 
 int k16_predict_launch(pols_ctx *ctx, int dtype, const AbsorbArgs &a) {
     if (a.n_groups == 0 || a.n_rows == 0 || (!a.pred && !a.resid && !a.fe)) return POLS_OK;
-    const int64_t n_items = fit_items(a);
-    if (dtype == POLS_F32) hipLaunchKernelGGL(k16_predict_kernel<float>, dim3((unsigned)n_items), dim3(256), 0, ctx->stream, a);
-    else hipLaunchKernelGGL(k16_predict_kernel<double>, dim3((unsigned)n_items), dim3(256), 0, ctx->stream, a);
-    POLS_HIP(hipGetLastError());
-    return POLS_OK;
+    return dtype == POLS_F32 ? fit_launch_plain(ctx, k16_predict_kernel<float>, fit_items(a), 256, 0, a)
+                             : fit_launch_plain(ctx, k16_predict_kernel<double>, fit_items(a), 256, 0, a);
 }
 
 }  // namespace pols

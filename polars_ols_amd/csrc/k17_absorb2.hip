@@ -23,7 +23,7 @@
 //   solve    one wave per group: partials in segment order, df = n - k - (C1 + C2 - M), k16_solve_core against the T_jj of the demean
 //            launch, the effects a1_c / a2_d from the accumulated means, their weighted means, c0, status, counts.
 //   resid    one wave per id-1 category: e~ from the demeaned columns, RSS_c, (cluster) z = A^-1 s_c.
-//   finish   one wave per group: RSS, sigma2, se / t / p (k16_se_t_p), r2_within, r2.
+//   finish   one wave per group: RSS, sigma2, se / t / p, r2_within, r2 (absorb_finish, K16's).
 //   predict  per item, fit_predict_rows: pred = x'b + a1 + a2 where the row's two categories lie in one component.
 #include "k17_absorb2.hpp"
 #include "k16_absorb.inl"
@@ -36,7 +36,8 @@ constexpr int K17_NOLABEL = 0x7fffffff;
 
 // the first and one-past-last category of group g in a table of k16_count_launch
 __device__ __forceinline__ void k17_cats(const Absorb2Args &a, const int64_t *first, const int64_t g, int64_t &c0, int64_t &c1) {
-    const int64_t v0 = a.seg_offs ? a.seg_first[g] : g, v1 = a.seg_offs ? a.seg_first[g + 1] : g + 1;
+    int64_t v0, v1;
+    fit_group_items(a, g, v0, v1);
     c0 = first[v0];
     c1 = first[v1];
 }
@@ -354,12 +355,8 @@ int k17_demean_launch(pols_ctx *ctx, const Absorb2Args &a, bool resident, int64_
     if (groups == 0) return POLS_OK;
     const int64_t grid = groups * (a.k_user + 2);
     const bool hw = a.has_w != 0;
-    if (!resident) {
-        if (hw) hipLaunchKernelGGL((k17_demean_kernel<false, true>), dim3((unsigned)grid), dim3(256), 0, ctx->stream, a);
-        else hipLaunchKernelGGL((k17_demean_kernel<false, false>), dim3((unsigned)grid), dim3(256), 0, ctx->stream, a);
-        POLS_HIP(hipGetLastError());
-        return POLS_OK;
-    }
+    if (!resident)
+        return hw ? fit_launch_plain(ctx, k17_demean_kernel<false, true>, grid, 256, 0, a) : fit_launch_plain(ctx, k17_demean_kernel<false, false>, grid, 256, 0, a);
     if (max_rows > k17_resident_rows(hw)) return fail(POLS_ERR_INVALID, "absorb2: %lld rows do not fit the resident store", (long long)max_rows);
     const size_t lds = (k17_resident_bytes(max_rows, hw) + 15) & ~(size_t)15;
     static OncePerDevice once_w, once_u;
@@ -402,20 +399,15 @@ int k17_gram_launch(pols_ctx *ctx, const Absorb2Args &a) {
 // ---------------------------------------------------------------- solve
 __global__ void __launch_bounds__(64) k17_solve_kernel(const Absorb2Args a) {
     extern __shared__ __attribute__((aligned(16))) double dyn[];
-    const int lane = threadIdx.x, k = a.k_user, nz = k + 1, ne = nz * (nz + 1) / 2, LD = k + 1, kc = k + a.icpt;
-    double *Gs = dyn, *Tl = Gs + ne, *A = Tl + k, *d0 = A + k * LD, *rhs = d0 + k, *Ri = rhs + k;
+    const int lane = threadIdx.x, k = a.k_user, nz = k + 1, ne = nz * (nz + 1) / 2, kc = k + a.icpt;
+    const AbsorbLds o = k17_lds(k);
+    double *Gs = dyn + o.Gs, *Tl = dyn + o.T, *rhs = dyn + o.rhs;
     const int64_t g = blockIdx.x;
-    const int64_t v0 = a.seg_offs ? a.seg_first[g] : g, v1 = a.seg_offs ? a.seg_first[g + 1] : g + 1;
-    const size_t gs = k17_gram_stride(k);
+    int64_t v0, v1;
+    fit_group_items(a, g, v0, v1);
     const double *gr = a.grpstat + (size_t)g * K17_GRPSTAT, *cr = a.colstat + (size_t)g * (k + 1) * K17_COLSTAT;
     const double n = gr[0], W = gr[1], C1 = gr[2], C2 = gr[3], M = gr[4];
-    bool fin = true;
-    for (int en = lane; en < ne; en += 64) {
-        double v = 0.0;
-        for (int64_t it = v0; it < v1; ++it) v += a.gram_part[(size_t)it * gs + en];
-        Gs[en] = v;
-        fin = fin && fabs(v) <= FIT_DBL_MAX;
-    }
+    bool fin = fit_sum_parts(a.gram_part, k17_gram_stride(k), v0, v1, ne, Gs, lane);
     int sweeps = 0;
     bool fired = true;
     if (lane <= k) {
@@ -432,7 +424,7 @@ __global__ void __launch_bounds__(64) k17_solve_kernel(const Absorb2Args a) {
     const double df = n - (double)k - (C1 + C2 - M);
     bool ok = finite && n > 0.0 && df > 0.0;
     double *st = a.state + (size_t)g * k17_state_stride(k);
-    ok = k16_solve_core(ok, Gs, Tl, A, d0, rhs, Ri, st + 16 + k, k, lane);
+    ok = k16_solve_core(ok, dyn, o, st + 16 + k, k, lane);
     // the effects a1_c = a1_c(y) - sum_j b_j a1_c(x_j) into the tables (NaN for a category without a fitted row, and for a group without
     // a fit), and their weighted means over the fitted rows
     double mean[2];
@@ -470,19 +462,11 @@ __global__ void __launch_bounds__(64) k17_solve_kernel(const Absorb2Args a) {
     }
     const double fillv = n > 0.0 ? fit_nan() : 0.0;                // no rows: zeros, as the existing entries
     if (lane < k) st[16 + lane] = ok ? rhs[lane] : fit_nan();
-    if (lane < kc) {
-        const double bv = ok ? (lane < k ? rhs[lane] : c0) : fillv;
-        if (a.coef) { if (a.f32) static_cast<float *>(a.coef)[(size_t)g * kc + lane] = (float)bv; else static_cast<double *>(a.coef)[(size_t)g * kc + lane] = bv; }
-    }
+    if (lane < kc) fit_store_coef(a, g, kc, lane, ok ? (lane < k ? rhs[lane] : c0) : fillv);
 }
 
 int k17_solve_launch(pols_ctx *ctx, const Absorb2Args &a) {
-    if (a.n_groups == 0) return POLS_OK;
-    const int k = a.k_user;
-    const size_t lds = sizeof(double) * ((size_t)(k + 1) * (k + 2) / 2 + k + (size_t)k * (k + 1) + 2 * (size_t)k + (size_t)k * k);
-    hipLaunchKernelGGL(k17_solve_kernel, dim3((unsigned)a.n_groups), dim3(64), lds, ctx->stream, a);
-    POLS_HIP(hipGetLastError());
-    return POLS_OK;
+    return fit_launch_plain(ctx, k17_solve_kernel, a.n_groups, 64, sizeof(double) * (size_t)k17_lds(a.k_user).total, a);
 }
 
 // ---------------------------------------------------------------- resid
@@ -494,14 +478,7 @@ __global__ void __launch_bounds__(64) k17_resid_kernel(const Absorb2Args a) {
     const int64_t g = k16_group_of(a.offs, a.n_groups, p0);
     const double *st = a.state + (size_t)g * k17_state_stride(k);
     double *out = a.resid_part + (size_t)c * k17_resid_stride(k, cluster);
-    if (st[1] == 0.0) {                                            // no fit (wave-uniform): the finish writes NaN
-        if (lane == 0) out[0] = 0.0;
-        if (cluster && lane < k) out[1 + lane] = 0.0;
-        return;
-    }
-    if (lane < k) bs[lane] = st[16 + lane];
-    if (cluster)
-        for (int q = lane; q < k * k; q += 64) Ai[q] = st[16 + k + q];
+    if (!absorb_resid_head(st, 16, 16 + k, out, cluster, k, lane, bs, Ai)) return;
     __syncthreads();
     double rss = 0.0, sacc = 0.0;                                  // sacc, lane j < k: s_cj
     for (int64_t pb = p0; pb < p1; pb += 64) {
@@ -523,81 +500,24 @@ __global__ void __launch_bounds__(64) k17_resid_kernel(const Absorb2Args a) {
             }
         }
     }
-    const double tot = k16_wave_sum(rss);
-    if (lane == 0) out[0] = tot;
-    if (cluster) {
-        if (lane < k) ss[lane] = sacc;
-        __syncthreads();
-        if (lane < k) {
-            double z = 0.0;
-            for (int q = 0; q < k; ++q) z = fma(Ai[lane * k + q], ss[q], z);
-            out[1 + lane] = z * z;
-        }
-    }
+    absorb_resid_tail(rss, sacc, ss, Ai, out, cluster, k, lane);
 }
 
-int k17_resid_launch(pols_ctx *ctx, const Absorb2Args &a) {
-    if (a.n_cats1 == 0) return POLS_OK;
-    hipLaunchKernelGGL(k17_resid_kernel, dim3((unsigned)a.n_cats1), dim3(64), 0, ctx->stream, a);
-    POLS_HIP(hipGetLastError());
-    return POLS_OK;
-}
+int k17_resid_launch(pols_ctx *ctx, const Absorb2Args &a) { return fit_launch_plain(ctx, k17_resid_kernel, a.n_cats1, 64, 0, a); }
 
 // ---------------------------------------------------------------- finish
 __global__ void __launch_bounds__(64) k17_finish_kernel(const Absorb2Args a) {
-    const int lane = threadIdx.x, k = a.k_user, kc = k + a.icpt;
-    const bool cluster = a.cluster != 0;
+    const int k = a.k_user;
     const int64_t g = blockIdx.x;
     const double *st = a.state + (size_t)g * k17_state_stride(k);
-    const double n = st[0], C1 = st[2], df = st[3], C2 = st[8], M = st[9];
+    const double n = st[0], C1 = st[2], C2 = st[8], M = st[9];
     int64_t c0i, c1i;
     k17_cats(a, a.first1, g, c0i, c1i);
-    const bool ok = st[1] != 0.0;                                  // (wave-uniform)
-    const double q = fit_nan();
-    double se = q, tv = q, pv = q, sigma2 = q, r2w = q, r2 = q;
-    if (ok) {
-        const size_t rs = k17_resid_stride(k, cluster);
-        double l = 0.0;
-        for (int64_t c = c0i + lane; c < c1i; c += 64) l += a.resid_part[(size_t)c * rs];
-        const double rss = k16_wave_sum(l);
-        sigma2 = rss / df;
-        r2w = 1.0 - rss / st[5];
-        r2 = 1.0 - rss / st[6];
-        double v = q, dfp = df;
-        if (cluster) {
-            double mine = 0.0;
-            for (int j = 0; j < k; ++j) {
-                double lz = 0.0;
-                for (int64_t c = c0i + lane; c < c1i; c += 64) lz += a.resid_part[(size_t)c * rs + 1 + j];
-                const double t = k16_wave_sum(lz);
-                if (lane == j) mine = t;
-            }
-            const double d1 = n - (double)k - 1.0 - (C2 - M);      // the second effect is charged like regressors
-            dfp = C1 - 1.0;
-            if (C1 >= 2.0 && d1 > 0.0) v = C1 / (C1 - 1.0) * (n - 1.0) / d1 * mine;
-        } else if (lane < k) {
-            v = sigma2 * st[16 + k + lane * k + lane];
-        }
-        if (lane < k) k16_se_t_p(v, st[16 + lane], dfp, se, tv, pv);
-    }
-    if (lane < kc) {                                               // (the intercept's entries stay NaN)
-        if (a.se) a.se[(size_t)g * kc + lane] = se;
-        if (a.t_values) a.t_values[(size_t)g * kc + lane] = tv;
-        if (a.p_values) a.p_values[(size_t)g * kc + lane] = pv;
-    }
-    if (lane == 0) {
-        if (a.sigma2) a.sigma2[g] = sigma2;
-        if (a.r2_within) a.r2_within[g] = r2w;
-        if (a.r2) a.r2[g] = r2;
-    }
+    const double d1 = n - (double)k - 1.0 - (C2 - M);              // the second effect is charged like regressors
+    absorb_finish(a, g, st, c0i, c1i, k17_resid_stride(k, a.cluster != 0), C1, d1, 16, 16 + k);
 }
 
-int k17_finish_launch(pols_ctx *ctx, const Absorb2Args &a) {
-    if (a.n_groups == 0) return POLS_OK;
-    hipLaunchKernelGGL(k17_finish_kernel, dim3((unsigned)a.n_groups), dim3(64), 0, ctx->stream, a);
-    POLS_HIP(hipGetLastError());
-    return POLS_OK;
-}
+int k17_finish_launch(pols_ctx *ctx, const Absorb2Args &a) { return fit_launch_plain(ctx, k17_finish_kernel, a.n_groups, 64, 0, a); }
 
 // ---------------------------------------------------------------- predict
 template <typename T>
@@ -631,11 +551,8 @@ __global__ void __launch_bounds__(256) k17_predict_kernel(const Absorb2Args a) {
 
 int k17_predict_launch(pols_ctx *ctx, int dtype, const Absorb2Args &a) {
     if (a.n_groups == 0 || a.n_rows == 0 || (!a.pred && !a.resid && !a.fe1 && !a.fe2)) return POLS_OK;
-    const int64_t n_items = fit_items(a);
-    if (dtype == POLS_F32) hipLaunchKernelGGL(k17_predict_kernel<float>, dim3((unsigned)n_items), dim3(256), 0, ctx->stream, a);
-    else hipLaunchKernelGGL(k17_predict_kernel<double>, dim3((unsigned)n_items), dim3(256), 0, ctx->stream, a);
-    POLS_HIP(hipGetLastError());
-    return POLS_OK;
+    return dtype == POLS_F32 ? fit_launch_plain(ctx, k17_predict_kernel<float>, fit_items(a), 256, 0, a)
+                             : fit_launch_plain(ctx, k17_predict_kernel<double>, fit_items(a), 256, 0, a);
 }
 
 }  // namespace pols

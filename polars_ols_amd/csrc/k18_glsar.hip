@@ -31,8 +31,8 @@
 //   predict   K10's prediction launch from the f64 coefficients (api_fits.hip).
 #include "k18_glsar.hpp"
 #include "fit_launch.hpp"
-#include "fit_solve.inl"
-#include "k7_stats.hpp"
+#include "fit_group.inl"
+#include "fit_lds.hpp"
 
 namespace pols {
 
@@ -134,58 +134,28 @@ int k18_gram_launch(pols_ctx *ctx, int dtype, const GlsarArgs &a) {
 }
 
 // ---------------------------------------------------------------- solve
-// offsets (doubles) of the solve launch's LDS areas
-struct K18Lds { int Ss, Cs, z1, zn, Gm, A, rhs, d0, b0, vv, tn, td, Ri, ij, total; };
-__host__ __device__ inline K18Lds k18_lds(int kt) {
-    const int TT = kt + 1, ne = TT * (TT + 1) / 2;
-    K18Lds o;
-    int at = 0;
-    o.Ss = at;  at += ne;                 // the summed S (packed upper triangle)
-    o.Cs = at;  at += TT * TT;            // the summed C
-    o.z1 = at;  at += TT;
-    o.zn = at;  at += TT;
-    o.Gm = at;  at += ne;                 // A(rho), packed as fit_chol_solve reads it
-    o.A = at;   at += kt * (kt + 1);      // its X-block, then the factor
-    o.rhs = at; at += kt;                 // the y-column -> b
-    o.d0 = at;  at += kt;
-    o.b0 = at;  at += kt;                 // b at rho = 0
-    o.vv = at;  at += TT;                 // v = (-b, 1)
-    o.tn = at;  at += TT;                 // lane i's term of v'C v ...
-    o.td = at;  at += TT;                 // ... and of v'S_n v
-    o.Ri = at;  at += kt * kt;            // the inverse of the last factor
-    o.ij = at;  at += (ne + 1) / 2;       // (i, j) of every packed entry, as int32
-    o.total = at;
-    return o;
-}
-
 size_t k18_solve_lds(int kt) { return sizeof(double) * (size_t)k18_lds(kt).total; }
 
 template <typename T>
 __global__ void __launch_bounds__(64) k18_solve_kernel(const GlsarArgs a) {
     extern __shared__ __attribute__((aligned(16))) double dyn[];
-    const int lane = threadIdx.x, kt = a.kt, TT = kt + 1, ne = TT * (TT + 1) / 2, nc = TT * TT, LD = kt + 1;
+    const int lane = threadIdx.x, kt = a.kt, TT = kt + 1, ne = TT * (TT + 1) / 2, nc = TT * TT;
     const K18Lds o = k18_lds(kt);
     double *Ss = dyn + o.Ss, *Cs = dyn + o.Cs, *z1 = dyn + o.z1, *zn = dyn + o.zn, *Gm = dyn + o.Gm, *A = dyn + o.A, *rhs = dyn + o.rhs,
            *d0 = dyn + o.d0, *b0 = dyn + o.b0, *vv = dyn + o.vv, *tn = dyn + o.tn, *td = dyn + o.td, *Ri = dyn + o.Ri;
     int32_t *ij = reinterpret_cast<int32_t *>(dyn + o.ij);
     const int64_t g = blockIdx.x;
-    const int64_t v0 = a.seg_offs ? a.seg_first[g] : g, v1 = a.seg_offs ? a.seg_first[g + 1] : g + 1;
+    int64_t v0, v1;
+    fit_group_items(a, g, v0, v1);
     const int64_t r0 = a.offs[g], r1 = a.offs[g + 1];
-    const size_t gs = k18_gram_stride(kt);
     const bool pw = a.method == POLS_AR1_PRAIS_WINSTEN;
-    bool fin = true;
-    for (int en = lane; en <= ne + nc; en += 64) {
-        double v = 0.0;
-        for (int64_t it = v0; it < v1; ++it) v += a.gram_part[(size_t)it * gs + en];
-        if (en < ne) {
-            Ss[en] = v;
-            int i, j;
-            tri_unpack(en, TT, i, j);
-            ij[en] = i << 8 | j;
-        } else if (en < ne + nc) Cs[en - ne] = v;
-        fin = fin && fabs(v) <= FIT_DBL_MAX;
+    // S and, right behind it in the partials as in LDS, C (the row count that follows them is not read: every row is a fitted row)
+    const bool finite = fit_sum_parts(a.gram_part, k18_gram_stride(kt), v0, v1, ne + nc, Ss, lane);
+    for (int en = lane; en < ne; en += 64) {
+        int i, j;
+        tri_unpack(en, TT, i, j);
+        ij[en] = i << 8 | j;
     }
-    const bool finite = __ballot(!fin) == 0;
     const double n = (double)(r1 - r0);                            // (every row is a fitted row)
     if (lane < TT) {
         z1[lane] = r1 > r0 ? k18_value<T>(a, lane, r0) : 0.0;
@@ -235,22 +205,7 @@ __global__ void __launch_bounds__(64) k18_solve_kernel(const GlsarArgs a) {
         rho = next;
     }
     double *st = a.state + (size_t)g * k18_state_stride(kt);
-    if (ok) {
-        if (lane < kt) {                                           // column `lane` of the inverse of the factor
-            for (int j = 0; j < kt; ++j) {
-                double s = j == lane ? 1.0 : 0.0;
-                for (int i = lane; i < j; ++i) s = fma(-A[j * LD + i], Ri[i * kt + lane], s);
-                Ri[j * kt + lane] = j < lane ? 0.0 : s / A[j * LD + j];
-            }
-        }
-        fit_wave_sync();
-        for (int p = lane; p < kt * kt; p += 64) {                 // A_xx(rho*)^-1
-            const int i = p / kt, j = p - i * kt;
-            double v = 0.0;
-            for (int l = i > j ? i : j; l < kt; ++l) v = fma(Ri[l * kt + i], Ri[l * kt + j], v);
-            st[4 + 2 * kt + p] = v;
-        }
-    }
+    if (ok) fit_chol_inverse(A, Ri, st + 4 + 2 * kt, kt, lane);    // A_xx(rho*)^-1
     if (lane == 0) {
         st[0] = n;
         st[1] = ok ? 1.0 : 0.0;
@@ -268,17 +223,14 @@ __global__ void __launch_bounds__(64) k18_solve_kernel(const GlsarArgs a) {
         st[4 + lane] = bv;
         st[4 + kt + lane] = ok ? b0[lane] : fillv;
         a.coefp[(size_t)g * kt + lane] = bv;
-        if (a.coef) { if (a.f32) static_cast<float *>(a.coef)[(size_t)g * kt + lane] = (float)bv; else static_cast<double *>(a.coef)[(size_t)g * kt + lane] = bv; }
+        fit_store_coef(a, g, kt, lane, bv);
     }
 }
 
 int k18_solve_launch(pols_ctx *ctx, int dtype, const GlsarArgs &a) {
-    if (a.n_groups == 0) return POLS_OK;
     const size_t lds = k18_solve_lds(a.kt);
-    if (dtype == POLS_F32) hipLaunchKernelGGL(k18_solve_kernel<float>, dim3((unsigned)a.n_groups), dim3(64), lds, ctx->stream, a);
-    else hipLaunchKernelGGL(k18_solve_kernel<double>, dim3((unsigned)a.n_groups), dim3(64), lds, ctx->stream, a);
-    POLS_HIP(hipGetLastError());
-    return POLS_OK;
+    return dtype == POLS_F32 ? fit_launch_plain(ctx, k18_solve_kernel<float>, a.n_groups, 64, lds, a)
+                             : fit_launch_plain(ctx, k18_solve_kernel<double>, a.n_groups, 64, lds, a);
 }
 
 // ---------------------------------------------------------------- rows
@@ -387,7 +339,8 @@ int k18_rows_launch(pols_ctx *ctx, int dtype, const GlsarArgs &a) {
 __global__ void __launch_bounds__(64) k18_finish_kernel(const GlsarArgs a) {
     const int lane = threadIdx.x, kt = a.kt;
     const int64_t g = blockIdx.x;
-    const int64_t v0 = a.seg_offs ? a.seg_first[g] : g, v1 = a.seg_offs ? a.seg_first[g + 1] : g + 1;
+    int64_t v0, v1;
+    fit_group_items(a, g, v0, v1);
     const double *st = a.state + (size_t)g * k18_state_stride(kt);
     const double n = st[0];
     const bool ok = st[1] != 0.0;                                  // (wave-uniform)
@@ -403,10 +356,9 @@ __global__ void __launch_bounds__(64) k18_finish_kernel(const GlsarArgs a) {
     const double *Ai = st + 4 + 2 * kt;
     if (cov) for (int p = lane; p < kt * kt; p += 64) cov[p] = ok ? sigma2 * Ai[p] : q;
     if (lane < kt) {
+        // (not fit_se_t_p: on a NaN t it stores the canonical NaN, k7_betai its argument's -- one form for both would change bytes)
         const double se = ok ? sqrt(sigma2 * Ai[lane * kt + lane]) : q, tv = ok ? st[4 + lane] / se : q;
-        if (a.se) a.se[(size_t)g * kt + lane] = se;
-        if (a.t_values) a.t_values[(size_t)g * kt + lane] = tv;
-        if (a.p_values) a.p_values[(size_t)g * kt + lane] = ok ? k7_betai(0.5 * df, 0.5, df / (df + tv * tv)) : q;
+        fit_store_stats(a, g, kt, lane, se, tv, (ok && a.p_values) ? k7_betai(0.5 * df, 0.5, df / (df + tv * tv)) : q);
     }
     if (lane == 0) {
         if (a.sigma2) a.sigma2[g] = sigma2;
@@ -415,11 +367,6 @@ __global__ void __launch_bounds__(64) k18_finish_kernel(const GlsarArgs a) {
     }
 }
 
-int k18_finish_launch(pols_ctx *ctx, const GlsarArgs &a) {
-    if (a.n_groups == 0) return POLS_OK;
-    hipLaunchKernelGGL(k18_finish_kernel, dim3((unsigned)a.n_groups), dim3(64), 0, ctx->stream, a);
-    POLS_HIP(hipGetLastError());
-    return POLS_OK;
-}
+int k18_finish_launch(pols_ctx *ctx, const GlsarArgs &a) { return fit_launch_plain(ctx, k18_finish_kernel, a.n_groups, 64, 0, a); }
 
 }  // namespace pols

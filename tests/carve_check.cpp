@@ -1,4 +1,4 @@
-// carve_check.cpp -- csrc/scratch_carve.hpp, csrc/table_layout.hpp and csrc/k17_split.hpp on the CPU (no HIP): test_scratch_carve_cpu.py compiles this with
+// carve_check.cpp -- csrc/scratch_carve.hpp, csrc/table_layout.hpp, csrc/k17_split.hpp and csrc/fit_lds.hpp on the CPU (no HIP): test_scratch_carve_cpu.py compiles this with
 // -fsanitize=address,undefined, runs it and compares every printed line with formulas written out by hand.  Each scenario carves a heap
 // buffer of exactly total() bytes and writes every region end to end, so a region that reaches past the total is a sanitizer report.
 // Output: "<scenario> <offset of every slot, -1 for nullptr> ... <total>"; "split <n_res> <max_res> <max_glb> : <list>".  The two cached
@@ -8,6 +8,7 @@
 #include <cstdlib>
 #include <cstring>
 
+#include "fit_lds.hpp"
 #include "k17_split.hpp"
 #include "scratch_carve.hpp"
 #include "table_layout.hpp"
@@ -82,7 +83,37 @@ static void seg_tables(const char *name, int64_t n_seg, int64_t n_items, bool pa
                 off(hit.map), off(hit.first), off(hit.extra), again.total());
 }
 
+// the LDS layout of a one-wave solve kernel (fit_lds.hpp): "lds <name> : <offset of every area, in the struct's order> <total>", in doubles
+template <int N>
+static void lds_line(const char *name, const int (&offs)[N]) {
+    std::printf("lds %s :", name);
+    for (int v : offs) std::printf(" %d", v);
+    std::printf("\n");
+}
+static void lds_layouts() {
+    char name[64];
+    for (int k = 1; k <= 31; ++k) {
+        const pols::AbsorbLds a = pols::k16_lds(k), b = pols::k17_lds(k);
+        std::snprintf(name, sizeof name, "k16_%d", k);
+        lds_line(name, {a.Gs, a.T, a.A, a.d0, a.rhs, a.Ri, a.total});
+        std::snprintf(name, sizeof name, "k17_%d", k);
+        lds_line(name, {b.Gs, b.T, b.A, b.d0, b.rhs, b.Ri, b.total});
+        const pols::K18Lds c = pols::k18_lds(k);
+        std::snprintf(name, sizeof name, "k18_%d", k);
+        lds_line(name, {c.Ss, c.Cs, c.z1, c.zn, c.Gm, c.A, c.rhs, c.d0, c.b0, c.vv, c.tn, c.td, c.Ri, c.ij, c.total});
+    }
+    // K14: (kx, L, T) -- every kx with one endogenous column and one instrument, then wider instrument lists up to the cap T = 31
+    auto k14 = [&](int kx, int L, int T) {
+        const pols::K14Lds d = pols::k14_lds(kx, L, T);
+        std::snprintf(name, sizeof name, "k14_%d_%d_%d", kx, L, T);
+        lds_line(name, {d.Gs, d.A, d.d0, d.B, d.Gm2, d.A2, d.rhs2, d.d02, d.Ri, d.tmp, d.total});
+    };
+    for (int kx = 1; kx <= 30; ++kx) k14(kx, kx, kx + 1);
+    k14(6, 8, 10); k14(2, 29, 30); k14(30, 31, 31); k14(15, 16, 31);
+}
+
 int main() {
+    lds_layouts();
     enet_gram("enet_split", 37, 5, 45, true);
     enet_gram("enet_whole", 5, 5, 45, false);
     {   // an absent region without a stand-in (K17's group list of a frame that is not mixed), between two present ones

@@ -1,10 +1,11 @@
-"""The recorded results of the per-group fit entries (ridge_cv, rlm, elastic_net_cv, glm, iv2sls, absorb, absorb2) and the frames they were
-recorded on.
+"""The recorded results of the per-group fit entries (ridge_cv, rlm, elastic_net_cv, glm, iv2sls, absorb, absorb2, glsar) and the frames
+they were recorded on.
 
 CASES describes every case -- entry, columns, group sizes, the null pattern and policy, the entry's parameters, library options, host or
 device batch, the fields wanted -- and frame() rebuilds its frame from a seed derived from the case id.  tests/fits_record.json holds, per
-case and dtype, what the library produced BEFORE the entries of csrc/api_fits.hip were rewritten on the scratch carver and the absorb pair
-was cut into stages (the commit is named in the file): the ``last_kernel`` string, a sha256 of the input frame and a sha256 of the raw bytes
+case and dtype, what the library produced on the commit named in the file -- the parent of the latest change that has to leave the
+entries' outputs bit for bit as they were (last: the one-wave solve / resid / finish kernels put on csrc/fit_group.inl; every case that was
+in the file before came out with the digests it had) --: the ``last_kernel`` string, a sha256 of the input frame and a sha256 of the raw bytes
 of every returned array (the first 16 hex digits of each, one line per case: the file stays as long as the case list) -- or, for the calls the library refuses, the exception type, the error code and the message.  It is a measurement
 of that parent, never of the code under test: scripts/record_fits.py wrote it, test_fits_record_gpu.py holds the library to it.
 
@@ -20,10 +21,10 @@ import statistics_record as SR
 from statistics_record import BASE, DRIFTED, DTYPES, SEG, SEG_OPT  # noqa: F401  (shared with the statistics recording)
 
 PATH = Path(__file__).resolve().parent / "fits_record.json"
-ENTRIES = ("ridge_cv", "rlm", "elastic_net_cv", "glm", "iv2sls", "absorb", "absorb2")
+ENTRIES = ("ridge_cv", "rlm", "elastic_net_cv", "glm", "iv2sls", "absorb", "absorb2", "glsar")
 COMMON = ("coef", "pred", "resid", "status")
 FN = {"ridge_cv": "pols_ridge_cv", "rlm": "pols_rlm", "elastic_net_cv": "pols_elastic_net_cv", "glm": "pols_glm", "iv2sls": "pols_iv2sls",
-      "absorb": "pols_least_squares_absorb", "absorb2": "pols_least_squares_absorb2"}
+      "absorb": "pols_least_squares_absorb", "absorb2": "pols_least_squares_absorb2", "glsar": "pols_glsar"}
 RIDGE_GRID = [0.0, 0.1, 1.0, 10.0]
 ENET_GRID = [0.5, 0.05, 0.5, 0.2, 0.01]          # a repeated value: the visiting order is descending and stable
 ENET_KW = {"n_folds": 3, "max_iter": 200}
@@ -31,11 +32,16 @@ ENET_KW = {"n_folds": 3, "max_iter": 200}
 RLM_BOTH = [300, 4000, 0, 3000]
 # absorb2 keeps a group of up to 7 435 weighted / 11 684 unweighted rows resident
 ABSORB2_MIXED = [7600, 60, 0, 200]
+# the groups that end in the failure branches: three rows at k = 4 (no degrees of freedom), none, one, and two ordinary groups -- the
+# first of which has its second feature overwritten with a copy of its first (`edge`: a Cholesky pivot fails)
+EDGE = [60, 3, 0, 1, 40]
+EDGE_SEG = [1500, 3, 0, 700]
+SEGMENTED = ("ridge_cv", "elastic_net_cv", "iv2sls", "absorb", "absorb2", "glsar")
 
 
 def _case(id, entry, k=4, sizes=BASE, **more):
     """kw: the entry's parameters; opts: library options; host / weights / icpt; nulls + policy; want: "all" or the fields; ids:
-    "sorted" (inside every group) or "shuffled"; offset (glm); poke: [(struct, field, value)] applied between the front end and the C
+    "sorted" (inside every group) or "shuffled"; offset (glm); edge: group 0's second feature becomes a copy of its first; poke: [(struct, field, value)] applied between the front end and the C
     entry; reject: the library is expected to refuse the call"""
     assert entry in ENTRIES, entry
     return dict(id=id, entry=entry, k=k, sizes=sizes, **more)
@@ -55,7 +61,8 @@ OWN = {"ridge_cv": ("alpha", "alpha_index", "score", "cv_scores", "coef_path"), 
        "iv2sls": ("se", "t_values", "p_values", "cov", "sigma2", "first_stage_f", "partial_r2", "sargan", "sargan_p", "n_obs"),
        "absorb": ("se", "t_values", "p_values", "sigma2", "r2_within", "r2", "fe", "n_obs", "n_categories"),
        "absorb2": ("se", "t_values", "p_values", "sigma2", "r2_within", "r2", "fe1", "fe2", "n_obs", "n_categories", "n_categories2",
-                   "n_components", "n_iter")}
+                   "n_components", "n_iter"),
+       "glsar": ("se", "t_values", "p_values", "cov", "sigma2", "rho", "dw", "dw_ols", "n_iter", "n_obs")}
 
 CASES = []
 for _e in ENTRIES:
@@ -63,12 +70,16 @@ for _e in ENTRIES:
     CASES += _both(f"{_e}-all", _e, kw=_kw(_e))
     for _f in OWN[_e]:
         CASES += _both(f"{_e}-only-{_f}", _e, kw=_kw(_e), want=(_f,))
-    # 2. weights + intercept; 10 % of the rows hold a NaN under "drop"
-    CASES += _both(f"{_e}-wi", _e, kw=_kw(_e), weights=True, icpt=True)
-    CASES += _both(f"{_e}-drop", _e, kw=_kw(_e), nulls=0.1, policy="drop")
+    # 2. weights + intercept; 10 % of the rows hold a NaN under "drop".  glsar refuses both: the intercept alone, the NaNs under "zero"
+    if _e == "glsar":
+        CASES += _both("glsar-icpt", _e, icpt=True)
+        CASES += _both("glsar-zero", _e, nulls=0.1, policy="zero")
+    else:
+        CASES += _both(f"{_e}-wi", _e, kw=_kw(_e), weights=True, icpt=True)
+        CASES += _both(f"{_e}-drop", _e, kw=_kw(_e), nulls=0.1, policy="drop")
     CASES += [_case(f"{_e}-empty-host", _e, kw=_kw(_e), sizes=[], host=True)]          # n_groups == 0: nothing runs, nothing is refused
 # 3. long groups cut into segments
-for _e in ("ridge_cv", "elastic_net_cv", "iv2sls", "absorb", "absorb2"):
+for _e in SEGMENTED:
     CASES += _both(f"{_e}-seg", _e, kw=_kw(_e), k=3, sizes=SEG, opts=SEG_OPT)
 CASES += _both("glm-seg", "glm", k=3, sizes=SEG, opts=SEG_OPT)                         # (stays resident: the segments are not asked for)
 CASES += _both("glm-seg-split", "glm", k=3, sizes=SEG, opts=dict(SEG_OPT, GLM_ENGINE="split"))
@@ -92,6 +103,13 @@ CASES += _both("absorb2-mixed", "absorb2", sizes=ABSORB2_MIXED, weights=True)
 CASES += _both("absorb2-mixed_frame_unweighted", "absorb2", sizes=ABSORB2_MIXED)
 CASES += _both("absorb2-cluster", "absorb2", kw={"cov_type": "cluster"})
 CASES += [_case("absorb2-no_resid-dev", "absorb2", want=("coef", "status", "fe1", "fe2", "n_iter"))]
+CASES += _both("glsar-cochrane_orcutt", "glsar", kw={"method": "cochrane_orcutt"})
+CASES += _both("glsar-two_step", "glsar", kw={"max_iter": 1})
+# 4b. the groups without a fit: every field wanted
+for _e in ENTRIES:
+    CASES += _both(f"{_e}-edge", _e, kw=_kw(_e), sizes=EDGE, edge=True)
+for _e in SEGMENTED:
+    CASES += _both(f"{_e}-edge-seg", _e, kw=_kw(_e), sizes=EDGE_SEG, edge=True, opts=SEG_OPT)
 # 5. rejections: (exception type, code, message).  MISALIGN: a one-element offset view of a larger device tensor
 NAN, INF, MISALIGN, TWO31 = float("nan"), float("inf"), "misalign", 1 << 31
 
@@ -137,7 +155,10 @@ CASES += [_rej("grid_empty", "ridge_cv", [("q", "n_alphas", 0)]),
           _rej("linpred_misaligned", "glm", [("ro", "linpred", MISALIGN)]),
           _rej("alpha", "iv2sls", [("p", "alpha", 1.0)]), _rej("n_endog", "iv2sls", [("q", "n_endog", 0)]),
           _rej("instruments", "iv2sls", [("q", "n_instruments", 0)]), _rej("z_null", "iv2sls", [("q", "z_cols", None)]),
-          _rej("cov_type", "iv2sls", [("q", "cov_type", 6)])]
+          _rej("cov_type", "iv2sls", [("q", "cov_type", 6)]),
+          _rej("weights", "glsar", [("b", "weights", MISALIGN)]), _rej("null_policy_drop", "glsar", [("p", "null_policy", 2)]),
+          _rej("method", "glsar", [("q", "method", 9)]), _rej("max_iter", "glsar", [("q", "max_iter", 0)]),
+          _rej("tol_zero", "glsar", [("q", "tol", 0.0)]), _rej("tol_nan", "glsar", [("q", "tol", NAN)])]
 for _c in CASES:
     _c["seed"] = zlib.crc32(_c["id"].encode())
     assert _c.get("want", "all") == "all" or set(_c["want"]) <= set(COMMON + OWN[_c["entry"]]), _c["id"]
@@ -219,6 +240,8 @@ def frame(case, dtype):
             into = [y] + cols + z + ([w] if w is not None else [])
             for r, j in zip(rows, rng.integers(0, len(into), size=len(rows))):
                 into[j][r] = np.nan
+    if case.get("edge"):                       # (behind every draw: no other case's frame moves)
+        cols[1][offs[0]:offs[1]] = cols[0][offs[0]:offs[1]]
     return dict(y=y, cols=cols, offs=offs, valid=valid, w=w, offset=offset, z=z, ids=ids)
 
 
@@ -290,6 +313,8 @@ def run(eng, case, dtype):
             out = eng.absorb(y, cols, put(f["ids"][0]), f["offs"], **kw)
         elif entry == "absorb2":
             out = eng.absorb2(y, cols, put(f["ids"][0]), put(f["ids"][1]), f["offs"], **kw)
+        elif entry == "glsar":
+            out = eng.glsar(y, cols, f["offs"], **kw)
         else:
             out = eng.rlm(y, cols, f["offs"], **kw)
         eng.synchronize()

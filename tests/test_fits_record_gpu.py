@@ -48,7 +48,7 @@ def test_the_field_tables_are_the_front_end_s():
     from polars_ols_amd import _lib as L
 
     assert FR.OWN == {"ridge_cv": L.RIDGE_CV_FIELDS, "rlm": L.RLM_FIELDS, "elastic_net_cv": L.ENET_CV_FIELDS, "glm": L.GLM_FIELDS,
-                      "iv2sls": L.IV_FIELDS, "absorb": L.ABSORB_FIELDS, "absorb2": L.ABSORB2_FIELDS}
+                      "iv2sls": L.IV_FIELDS, "absorb": L.ABSORB_FIELDS, "absorb2": L.ABSORB2_FIELDS, "glsar": L.GLSAR_FIELDS}
 
 
 def test_the_recorded_commit_reproduced_itself():

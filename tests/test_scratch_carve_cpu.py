@@ -1,8 +1,10 @@
 """The scratch carver (csrc/scratch_carve.hpp), the layouts of the two cached tables (csrc/table_layout.hpp: the build view and the view a
-cache hit takes must agree) and K17's resident / global split of the groups (csrc/k17_split.hpp) on the CPU: a
+cache hit takes must agree), K17's resident / global split of the groups (csrc/k17_split.hpp) and the LDS layouts of the one-wave solve
+kernels (csrc/fit_lds.hpp: the kernel's offsets and the launcher's total come from one function) on the CPU: a
 stand-alone program (tests/carve_check.cpp, plain C++, no HIP) is compiled with the address and undefined-behaviour sanitizers and run;
 what it prints is compared with offsets and totals written out by hand below.  The program writes every region it carved end to end
 into a buffer of exactly the total, so a region that reaches past the allocation is a sanitizer report and a failed run."""
+import itertools
 import shutil
 import subprocess
 from pathlib import Path
@@ -18,16 +20,26 @@ def r(b):
 
 
 @pytest.fixture(scope="module")
-def printed(tmp_path_factory):
+def lines(tmp_path_factory):
     gxx = shutil.which("g++")
     assert gxx, "g++ is part of the image"
     exe = tmp_path_factory.mktemp("carve") / "carve_check"
     subprocess.run([gxx, "-std=c++17", "-Wall", "-Wextra", "-Werror", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
                     f"-I{ROOT / 'polars_ols_amd' / 'csrc'}", str(ROOT / "tests" / "carve_check.cpp"), "-o", str(exe)], check=True)
     out = subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout
-    lines = [ln.split() for ln in out.splitlines()]
-    named = {ln[0]: [int(v) for v in ln[1:]] for ln in lines if ln[0] != "split"}
+    return [ln.split() for ln in out.splitlines()]
+
+
+@pytest.fixture(scope="module")
+def printed(lines):
+    named = {ln[0]: [int(v) for v in ln[1:]] for ln in lines if ln[0] not in ("split", "lds")}
     return named, [ln[1:] for ln in lines if ln[0] == "split"]
+
+
+@pytest.fixture(scope="module")
+def lds(lines):
+    """the LDS layouts of the one-wave solve kernels (csrc/fit_lds.hpp): name -> the offsets of the areas in order, then the total (doubles)"""
+    return {ln[1]: [int(v) for v in ln[3:]] for ln in lines if ln[0] == "lds"}
 
 
 def test_offsets_and_totals(printed):
@@ -124,3 +136,45 @@ def test_k17_split_of_the_groups(printed):
     assert splits[1] == ["0", "0", "7600", ":"]                                   # 60, 200, 7600 rows under cap 10: none
     assert splits[2] == ["4", "200", "7600", ":", "0", "1", "2", "4", "3"]        # cap 200: the empty group counts as resident
     assert splits[3] == ["0", "0", "7600", ":"]                                   # cap -1: not even the empty group
+
+
+def _tri(n):
+    return n * (n + 1) // 2
+
+
+def _laid_out(got, sizes):
+    """the areas follow each other in the struct's order, none empty, none over the next: offsets = running sums of the sizes the kernel
+    uses, and the total ends the last one"""
+    assert all(s > 0 for s in sizes)
+    assert got == list(itertools.accumulate([0] + sizes)), (got, sizes)
+    assert all(a < b for a, b in zip(got, got[1:]))
+
+
+def test_lds_layouts_of_the_absorb_solves(lds):
+    for k in range(1, 32):
+        # Gs, T_jj (K16: then n), A, d0, rhs, Ri
+        _laid_out(lds[f"k16_{k}"], [_tri(k + 1), k + 1, k * (k + 1), k, k, k * k])
+        _laid_out(lds[f"k17_{k}"], [_tri(k + 1), k, k * (k + 1), k, k, k * k])
+        # the launchers' own sums before there was a layout function (k16_solve_lds; k17_solve_launch)
+        assert lds[f"k16_{k}"][-1] == (k + 1) * (k + 2) // 2 + k + 1 + k * (k + 1) + 2 * k + k * k
+        assert lds[f"k17_{k}"][-1] == (k + 1) * (k + 2) // 2 + k + k * (k + 1) + 2 * k + k * k
+
+
+def test_lds_layout_of_the_glsar_solve(lds):
+    for kt in range(1, 32):
+        T = kt + 1
+        ne = _tri(T)
+        # Ss, Cs, z1, zn, Gm, A, rhs, d0, b0, vv, tn, td, Ri, ij (two int32 per double)
+        _laid_out(lds[f"k18_{kt}"], [ne, T * T, T, T, ne, kt * (kt + 1), kt, kt, kt, T, T, T, kt * kt, (ne + 1) // 2])
+        assert lds[f"k18_{kt}"][1] == ne                                             # C right behind S: the kernel sums both as one run
+        assert lds[f"k18_{kt}"][-1] == 2 * ne + T * T + 5 * T + kt * (kt + 1) + 3 * kt + kt * kt + (ne + 1) // 2
+
+
+def test_lds_layout_of_the_iv_solve(lds):
+    triples = [(kx, kx, kx + 1) for kx in range(1, 31)] + [(6, 8, 10), (2, 29, 30), (30, 31, 31), (15, 16, 31)]
+    for kx, L, T in triples:
+        # Gs (+ n), A, d0, B, Gm2, A2, rhs2, d02, Ri, tmp
+        got = lds[f"k14_{kx}_{L}_{T}"]
+        _laid_out(got, [_tri(T + 1) + 1, L * (L + 1), L, L * (kx + 1), _tri(kx + 1), kx * (kx + 1), kx, kx, kx * kx, L])
+        assert got[-1] == _tri(T + 1) + 1 + L * (L + 1) + 2 * L + L * (kx + 1) + _tri(kx + 1) + kx * (kx + 1) + 2 * kx + kx * kx
+    assert 8 * lds["k14_6_8_10"][-1] == 2632 and 8 * lds["k14_30_31_31"][-1] == 39440     # the figures in k14_iv.hip's header
