@@ -886,6 +886,78 @@ typedef struct pols_absorb2_out {
 int pols_least_squares_absorb2(pols_ctx *ctx, const pols_batch *b, const pols_ols_params *p, const pols_absorb2_params *q,
                                pols_out *out, const pols_absorb2_out *r);
 
+/* Random-effects panel regression with the Hausman test inside every group (no reference counterpart; Stata's xtreg, re followed by
+ * hausman, linearmodels' RandomEffects and BetweenOLS, for every group of the frame in one call).  Everything below is per group g.
+ * Fitted rows, ids and categories.  Exactly as pols_least_squares_absorb: the same null policies, validity-mask rule and id rules.  n is
+ * the number of fitted rows, C the number of categories, T_c the fitted rows of category c, k = n_features, kc = kt = k + 1 with
+ * add_intercept (the intercept is the last coefficient).  Weights are not built: a batch with weights is refused.
+ * 1. Within.  The fit of pols_least_squares_absorb unchanged: b_w, A_w = X~'X~, X~'y~ and RSS_w, summed over the rows;
+ * df_w = n - k - C, sigma2_e = RSS_w / df_w.
+ * 2. Between.  zbar_c = (xbar_c, 1) with the intercept, xbar_c without; the regression is unweighted over the categories:
+ * B = sum_c zbar_c zbar_c', b_b = B^-1 sum_c zbar_c ybar_c by Cholesky, pivot j fails when d_j <= 16 kc eps sum_c zbar_cj^2;
+ * RSS_b = sum_c (ybar_c - zbar_c'b_b)^2, summed over the table of category means and not taken from the moments; df_b = C - kc.
+ * 3. Variance components (Swamy-Arora, Stata's default for unbalanced panels).  Tbar = C / sum_c (1 / T_c),
+ * sigma2_u = max(0, RSS_b / df_b - sigma2_e / Tbar), rho = sigma2_u / (sigma2_u + sigma2_e),
+ * theta_c = 1 - sqrt(sigma2_e / (sigma2_e + T_c sigma2_u)).
+ * 4. GLS.  q_c = T_c (1 - theta_c)^2; M = embed(A_w) + sum_c q_c zbar_c zbar_c', v = embed(X~'y~) + sum_c q_c zbar_c ybar_c,
+ * b = M^-1 v by Cholesky, pivot j fails when d_j <= 16 kc eps T_jj with T_jj the raw second moment sum x_ij^2 (n for the intercept).
+ * "embed" puts the k x k within block into the leading corner and zeros into the intercept's row and column.  With
+ * x*_i = x_i - theta_c xbar_c = x~_i + (1 - theta_c) xbar_c the cross terms vanish inside a category, so M = X*'X* and v = X*'y*: the
+ * quasi-demeaned columns are never formed.
+ * 5. Residual sum.  RSS = sum_i (y~_i - x~_i'b_1..k)^2 + sum_c q_c (ybar_c - zbar_c'b)^2, the first term from the rows and the second
+ * from the table; df = n - kc, sigma2 = RSS / df.
+ * 6. Inference.  V = sigma2 M^-1, se_j = sqrt(V_jj), t_j = b_j / se_j, p two-sided Student-t(df), the intercept included.
+ * 7. Hausman.  d = b_w - b_1..k, D = sigma2_e (A_w^-1 - (M^-1)_1..k,1..k) -- sigma2_e on both sides, which makes D positive
+ * semi-definite by construction --, H = d'D^-1 d by Cholesky of D, hausman_p = Q(k / 2, H / 2), the upper tail of chi2(k).  Both are NaN
+ * when a pivot of D is not positive; the group's status is unaffected.
+ * 8. Effects.  u_c = T_c sigma2_u / (T_c sigma2_u + sigma2_e) (ybar_c - zbar_c'b).
+ * 9. Row outputs.  out->pred = z_i'b with no effect added, out->resid = y - pred, every row predicted or masked exactly as
+ * pols_least_squares does for the policy.  effects and theta hold u_c(i) and theta_c(i) per row in the batch dtype; NaN for a row whose
+ * id has no fitted row in its group.  out->coef is b.
+ * out->status: POLS_GROUP_EMPTY for n = 0 (zero coefficients, everything else NaN); POLS_GROUP_BAD_DOF for df_w <= 0 or df_b <= 0
+ * (everything NaN); POLS_GROUP_FALLBACK with everything NaN when any of the three pivots fails or a sum is not finite; otherwise
+ * POLS_GROUP_OK.  n_obs and n_categories are written in every case.
+ * All arithmetic is f64 on the inputs' values, for f32 batches too.  No floating-point atomics; every sum runs in a fixed order.  The
+ * within sums are those of pols_least_squares_absorb.  A sum over the table of a group runs over its categories by ascending id: an
+ * entry of B or M (packed triangles of kc + 1 columns, ybar the last, E = (kc + 1)(kc + 2) / 2 entries) in P = 256 / E interleaved
+ * partitions (P = 1 beyond 256 entries), partition p over categories p, p + P, .., the partitions added in order and the within moment
+ * last; a scalar (RSS_b, sum 1 / T_c, the table's part of RSS) in 256 interleaved partitions that meet in a fixed tree.  The row term of
+ * RSS is summed as RSS_w is.  Results are bit-identical run to run, between HOST and DEVICE batches, and between the two routes of the
+ * table kernel: a group whose rows of the table fit a workgroup's LDS is held there, any other is read from global memory
+ * (POLS_RANDOM_EFFECTS_ROUTE=global sends every group there).  The call synchronises the stream twice (the order probe, the category
+ * counts).  When none of se / t_values / p_values is asked for, the second residual pass is skipped.
+ * From pols_ols_params only null_policy is read.  POLS_ERR_INVALID: NULL ids; n_features < 1; alpha != 0, positive, or has_l1_ratio
+ * with l1_ratio > 0; a validity mask without a drop-family policy; on the device, a pred / resid / effects / theta that is not 16-byte
+ * aligned.  POLS_ERR_UNSUPPORTED: weights; kt > 31 or n_rows >= 2^31.  There is no Arrow twin and no sharded entry.
+ * Not built: weights; time effects or two-way random effects; robust or clustered covariance; other variance-component estimators;
+ * the Mundlak / robust Hausman form; Stata's three R2. */
+typedef struct pols_random_effects_params {
+    const int64_t *ids;         /* one entity id per row, in the batch's row order, where b->mem says */
+} pols_random_effects_params;
+
+/* ids = NULL */
+void pols_random_effects_params_default(pols_random_effects_params *q);
+
+typedef struct pols_random_effects_out {
+    double  *se;                /* n_groups x kt                                 */
+    double  *t_values;          /* n_groups x kt                                 */
+    double  *p_values;          /* n_groups x kt                                 */
+    double  *coef_between;      /* n_groups x kt: b_b                            */
+    double  *coef_within;       /* n_groups x n_features: b_w                    */
+    double  *sigma2_e;          /* n_groups                                      */
+    double  *sigma2_u;          /* n_groups                                      */
+    double  *rho;               /* n_groups                                      */
+    double  *hausman;           /* n_groups: H                                   */
+    double  *hausman_p;         /* n_groups                                      */
+    void    *effects;           /* n_rows, batch dtype: the row's u_c            */
+    void    *theta;             /* n_rows, batch dtype: the row's theta_c        */
+    int64_t *n_obs;             /* n_groups: fitted rows                         */
+    int64_t *n_categories;      /* n_groups: C                                   */
+} pols_random_effects_out;      /* all live where b->mem says; any may be NULL */
+
+int pols_random_effects(pols_ctx *ctx, const pols_batch *b, const pols_ols_params *p, const pols_random_effects_params *q,
+                        pols_out *out, const pols_random_effects_out *r);
+
 /* ---- group-key ingestion: `.over(key)` / `group_by(key)` ------------------------------------------------------------
  * The reference's plugin functions never see a key column: Polars partitions the frame on the host and calls them once per
  * group (README.md:19, README.md:57 and :91 `.over("group")`, tests/test_ols.py:110, :384, :860).  The batched entries

@@ -17,6 +17,7 @@ from .least_squares import (  # noqa: F401
     compute_iv2sls, IV2SLS,
     compute_glsar, GLSAR,
     compute_absorbed_least_squares, AbsorbedOLS,
+    compute_random_effects, RandomEffects,
     compute_elastic_net_cv, ElasticNetCV,
 )
 

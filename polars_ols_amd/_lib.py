@@ -202,6 +202,20 @@ class Absorb2Out(C.Structure):        # pols_absorb2_out
     _fields_ = [(n, C.c_void_p) for n in ABSORB2_FIELDS]
 
 
+class RandomEffectsParams(C.Structure):   # pols_random_effects_params
+    _fields_ = [("ids", C.c_void_p)]
+
+
+# pols_random_effects_out, in the struct's order
+RANDOM_EFFECTS_FIELDS = ("se", "t_values", "p_values", "coef_between", "coef_within", "sigma2_e", "sigma2_u", "rho", "hausman", "hausman_p",
+                         "effects", "theta", "n_obs", "n_categories")
+RANDOM_EFFECTS_MAX_COLUMNS = 31
+
+
+class RandomEffectsOut(C.Structure):      # pols_random_effects_out
+    _fields_ = [(n, C.c_void_p) for n in RANDOM_EFFECTS_FIELDS]
+
+
 class GlsarParams(C.Structure):       # pols_glsar_params
     _fields_ = [("method", C.c_int32), ("max_iter", C.c_int32), ("tol", C.c_double)]
 
@@ -241,6 +255,7 @@ EXPORTS = [
     "pols_absorb_params_default", "pols_least_squares_absorb",
     "pols_absorb2_params_default", "pols_least_squares_absorb2",
     "pols_glsar_params_default", "pols_glsar",
+    "pols_random_effects_params_default", "pols_random_effects",
 ]
 # measurement aids (include/pols_mi355x_debug.h): not part of the reference interface
 DEBUG_EXPORTS = ["pols_timing_enable", "pols_timing_collect", "pols_last_kernel_name", "pols_stream_probe", "pols_stream_probe_ex",
@@ -326,6 +341,9 @@ def lib() -> C.CDLL:
                                                  C.POINTER(Absorb2Out)]
         L.pols_glsar_params_default.argtypes, L.pols_glsar_params_default.restype = [C.POINTER(GlsarParams)], None
         L.pols_glsar.argtypes = [C.c_void_p, C.POINTER(Batch), C.POINTER(OlsParams), C.POINTER(GlsarParams), C.POINTER(Out), C.POINTER(GlsarOut)]
+        L.pols_random_effects_params_default.argtypes, L.pols_random_effects_params_default.restype = [C.POINTER(RandomEffectsParams)], None
+        L.pols_random_effects.argtypes = [C.c_void_p, C.POINTER(Batch), C.POINTER(OlsParams), C.POINTER(RandomEffectsParams), C.POINTER(Out),
+                                          C.POINTER(RandomEffectsOut)]
         L.pols_enet_cv_params_default.argtypes, L.pols_enet_cv_params_default.restype = [C.POINTER(EnetCvParams)], None
         L.pols_elastic_net_cv.argtypes = [C.c_void_p, C.POINTER(Batch), C.POINTER(OlsParams), C.POINTER(EnetCvParams), C.POINTER(Out),
                                           C.POINTER(EnetCvOut)]

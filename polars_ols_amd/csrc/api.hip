@@ -228,6 +228,7 @@ bool options_set(Options &o, const char *key, const char *v) {
     else if (ieq(key, "RLM_ENGINE")) o.rlm_engine = !on ? 0 : ieq(v, "stream") ? 1 : 0;
     else if (ieq(key, "GLM_ENGINE")) o.glm_engine = !on ? 0 : ieq(v, "split") ? 1 : 0;
     else if (ieq(key, "ABSORB2_ROUTE")) o.absorb2_route = !on ? 0 : ieq(v, "global") ? 1 : 0;
+    else if (ieq(key, "RANDOM_EFFECTS_ROUTE")) o.random_effects_route = !on ? 0 : ieq(v, "global") ? 1 : 0;
     else if (ieq(key, "RLS_SPINS")) o.rls_spin_limit = on ? std::atoi(v) : d.rls_spin_limit;
     else if (ieq(key, "RLS_EARLY")) o.rls_early = on ? std::atoi(v) : d.rls_early;
     else if (ieq(key, "ROLLING_ENGINE")) {
@@ -243,7 +244,7 @@ bool options_set(Options &o, const char *key, const char *v) {
 void options_from_env(Options &o) {
     static const char *const keys[] = {"TIMELINE", "K1_NOOCC4", "K1_NOFAST", "K1_NOTINY", "K1_NORC1", "K1_SHAPE", "K1_F64_TEAM",
                                        "KG_NOYV", "K2_NOPREFETCH", "K1_PASSES", "K1_WG", "RLS_SPINS", "RLS_EARLY", "K1T_RC4", "K1_NT_LOADS", "STATIC_ENGINE",
-                                       "RLS_ENGINE", "RLM_ENGINE", "GLM_ENGINE", "ABSORB2_ROUTE", "ROLLING_ENGINE", "K1_ENGINE", "K9_TAKE", "K1_PERSIST", "K1_PERSIST_SUB", "K1T_SUB32", "K1_NOEDGE", "K1T_SUB8",
+                                       "RLS_ENGINE", "RLM_ENGINE", "GLM_ENGINE", "ABSORB2_ROUTE", "RANDOM_EFFECTS_ROUTE", "ROLLING_ENGINE", "K1_ENGINE", "K9_TAKE", "K1_PERSIST", "K1_PERSIST_SUB", "K1T_SUB32", "K1_NOEDGE", "K1T_SUB8",
                                        "K1_XCD", "NO_SPLIT", "DEBUG_SKIP_FIXUP", "K4P_LPS", "SEG_TARGET", "K1_RC2_WIDE", "KG_SINGLE_BUFFER", "PREDICT_LOOP", "NO_CLASSES"};
     char name[64];
     for (const char *k : keys) {

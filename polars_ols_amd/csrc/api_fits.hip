@@ -1,5 +1,5 @@
 // api_fits.hip -- the per-group fit entries of the C-ABI: pols_ridge_cv (K10), pols_rlm (K11), pols_elastic_net_cv (K12), pols_glm
-// (K13), pols_iv2sls (K14), pols_least_squares_absorb (K16), pols_least_squares_absorb2 (K17), pols_glsar (K18).  Host code only.  What they share is written once, up front: the opening checks and the staging
+// (K13), pols_iv2sls (K14), pols_least_squares_absorb (K16), pols_least_squares_absorb2 (K17), pols_glsar (K18), pols_random_effects (K19).  Host code only.  What they share is written once, up front: the opening checks and the staging
 // (FitCall), the common fields of the kernel argument structs (fit_frame, fit_segments), the work buffers (Carve, carve), the entry's own
 // outputs (ExtraOut), K10's prediction pass (fit_predict), extra input columns (stage_extra_columns), the tile count rlm and glm route by
 // (group_tiles) and the stages of the absorb pair.  DESIGN.md, "Adding a per-group fit entry".
@@ -16,9 +16,11 @@
 #include "k16_absorb.hpp"
 #include "k17_absorb2.hpp"
 #include "k18_glsar.hpp"
+#include "k19_random_effects.hpp"
 #include "k7c_cluster.hpp"
 #pragma GCC visibility push(hidden)     // host helpers of this file alone: nothing of them is exported
 #include "k17_split.hpp"
+#include "k19_split.hpp"
 #pragma GCC visibility pop
 
 using namespace pols;
@@ -700,6 +702,103 @@ int pols_least_squares_absorb(pols_ctx *ctx, const pols_batch *b, const pols_ols
         if ((rc = k16_finish_launch(ctx, a))) return rc;
     }
     if ((rc = k16_predict_launch(ctx, b->dtype, a))) return rc;
+    return xo.home(ctx, b, o, fc);
+}
+
+void pols_random_effects_params_default(pols_random_effects_params *q) {
+    if (!q) return;
+    q->ids = nullptr;
+}
+
+// K19 (k19_random_effects.hip): K16's launches as they are on an AbsorbArgs -- order, categories, index, means, moments, solve, the
+// residual pass and the finish for sigma2_e --, then the table kernel (resident, global, or one of each over a group list when the
+// frame has groups on both sides of the resident capacity), K16's residual pass again with b and the finish (only when se / t / p are
+// wanted), then the prediction pass.  Two synchronisations: the order probe, the category counts.
+int pols_random_effects(pols_ctx *ctx, const pols_batch *b, const pols_ols_params *p, const pols_random_effects_params *q, pols_out *o,
+                        const pols_random_effects_out *ro) {
+    FitCall fc;
+    int rc = fit_check(ctx, b, p, q, o, "random_effects", K19_KMAX, &fc);
+    if (rc) return rc;
+    ro = or_none(ro);
+    if ((rc = absorb_check(b, p, o, fc, "random_effects", &q->ids, 1, POLS_COV_NONROBUST, nullptr, ro->effects, ro->theta))) return rc;
+    if (b->weights) return fail(POLS_ERR_UNSUPPORTED, "random_effects: weights are not built");
+    if (b->n_groups == 0) return POLS_OK;
+    const int k = b->n_features, kc = fc.kt;
+    const size_t G = fc.G, N = (size_t)b->n_rows;
+    if ((rc = fit_stage(ctx, b, o, &fc))) return rc;
+    AbsorbArgs a = {};                                             // the within fit: no coefficient, status or row output of its own
+    fit_frame(a, b, fc);
+    a.kt = k + 1; a.coef = nullptr; a.status = nullptr;
+    if ((rc = stage_ids(ctx, fc, Work::RandomEffectsIds, &q->ids, 1, N, &a.ids))) return rc;
+    SegTables sg;
+    if ((rc = ensure_segments(ctx, b, fc.max_rows, 0, &sg))) return rc;
+    fit_segments(a, sg);
+    const size_t items = sg.n_seg > 0 ? (size_t)sg.n_seg : G;
+    RandomEffectsArgs r = {};
+    fit_frame(r, b, fc);
+    fit_segments(r, sg);
+    int32_t *list = nullptr;
+    Carve moments;
+    moments.add(a.gram_part, sizeof(double) * items * k16_gram_stride(k)); moments.add(a.state, sizeof(double) * G * k16_state_stride(k));
+    moments.add(a.sigma2, sizeof(double) * G); moments.add(r.state, sizeof(double) * G * k19_state_stride(kc));
+    moments.add(r.rstate, sizeof(double) * G * k16_state_stride(k)); moments.add(r.table_rows, sizeof(int64_t) * G);
+    moments.add(list, sizeof(int32_t) * G);
+    if ((rc = carve(ctx, Work::RandomEffectsMoments, moments))) return rc;
+    if ((rc = k7c_order_launch(ctx, a.ids, fc.d_offs, b->n_groups, b->n_rows, &a.order))) return rc;
+    if ((rc = categories(ctx, Work::RandomEffectsIndex, &a, 1, items, N))) return rc;
+    r.item_first = a.item_first; r.catidx = a.catidx;
+    if ((rc = k19_rows_launch(ctx, r))) return rc;
+    std::vector<int64_t> table_rows(G);
+    POLS_HIP(hipMemcpyAsync(table_rows.data(), r.table_rows, sizeof(int64_t) * G, hipMemcpyDeviceToHost, ctx->stream));
+    POLS_HIP(hipStreamSynchronize(ctx->stream));                   // the number of categories sizes the table, their counts per group pick the route
+    const size_t nc = (size_t)a.n_cats;
+    // which groups the resident table kernel takes: by the rows of the table they span
+    const K19Split sp = k19_split_groups(table_rows.data(), G, ctx->opt.random_effects_route == 1 ? -1 : k19_resident_rows(k, kc, (long long)FIT_LDS_BUDGET));
+    if (sp.mixed() && (rc = upload_small(ctx, list, sp.list.data(), sizeof(int32_t) * G))) return rc;
+    double *rss_rows = nullptr;
+    Carve cats;
+    cats.add(a.cat_start, sizeof(int64_t) * (nc + 1)); cats.add(a.cat, sizeof(double) * nc * k16_cat_stride(k) + 8);
+    cats.add(a.resid_part, sizeof(double) * nc + 8); cats.add(rss_rows, sizeof(double) * nc + 8);
+    cats.add(r.theta_c, sizeof(double) * nc + 8); cats.add(r.u_c, sizeof(double) * nc + 8); cats.add(r.q_c, sizeof(double) * nc + 8);
+    if ((rc = carve(ctx, Work::RandomEffectsCats, cats))) return rc;
+    ExtraOut xo;
+    xo.add(ro->se, r.se, sizeof(double) * G * kc); xo.add(ro->t_values, r.t_values, sizeof(double) * G * kc);
+    xo.add(ro->p_values, r.p_values, sizeof(double) * G * kc);
+    xo.add(ro->coef_between, r.coef_between, sizeof(double) * G * kc); xo.add(ro->coef_within, r.coef_within, sizeof(double) * G * k);
+    xo.add(ro->sigma2_e, r.sigma2_e_out, sizeof(double) * G); xo.add(ro->sigma2_u, r.sigma2_u, sizeof(double) * G);
+    xo.add(ro->rho, r.rho, sizeof(double) * G); xo.add(ro->hausman, r.hausman, sizeof(double) * G);
+    xo.add(ro->hausman_p, r.hausman_p, sizeof(double) * G);
+    xo.add(ro->effects, r.effects, fc.sz * N); xo.add(ro->theta, r.theta, fc.sz * N);
+    xo.add(ro->n_obs, a.n_obs, sizeof(int64_t) * G); xo.add(ro->n_categories, a.n_categories, sizeof(int64_t) * G);
+    if ((rc = xo.place(ctx, fc, Work::RandomEffectsOut))) return rc;
+    const bool need_rows = ro->se || ro->t_values || ro->p_values;
+    ctx->last_kernel = sp.mixed() ? "k19_random_effects_mixed" : (sp.n_res > 0 ? "k19_random_effects_resident" : "k19_random_effects_global");
+    // 1. within: K16 unchanged; its residual pass and finish give sigma2_e
+    if ((rc = k16_index_launch(ctx, a))) return rc;
+    if ((rc = k16_means_launch(ctx, b->dtype, a))) return rc;
+    if ((rc = k16_gram_launch(ctx, b->dtype, a))) return rc;
+    if ((rc = k16_solve_launch(ctx, a))) return rc;
+    if ((rc = k16_resid_launch(ctx, b->dtype, a))) return rc;
+    if ((rc = k16_finish_launch(ctx, a))) return rc;
+    // 2. - 8. the table kernel
+    r.cat = a.cat; r.gram_part = a.gram_part; r.wstate = a.state; r.sigma2_e = a.sigma2;
+    r.res_rows = (int32_t)sp.max_res;
+    if (sp.mixed()) {
+        RandomEffectsArgs part = r;
+        part.list = list;
+        if ((rc = k19_table_launch(ctx, part, true, sp.n_res))) return rc;
+        part.list = list + sp.n_res;
+        if ((rc = k19_table_launch(ctx, part, false, sp.n_glb))) return rc;
+    } else if ((rc = k19_table_launch(ctx, r, sp.n_res > 0, (int64_t)G))) return rc;
+    if (need_rows) {                                               // the row term of RSS: K16's residual pass on the state row that holds b
+        AbsorbArgs rows = a;
+        rows.state = r.rstate; rows.resid_part = rss_rows;
+        if ((rc = k16_resid_launch(ctx, b->dtype, rows))) return rc;
+        r.resid_part = rss_rows;
+        if ((rc = k19_finish_launch(ctx, r))) return rc;
+    }
+    r.pred = fc.st.pred; r.resid = fc.st.resid;
+    if ((rc = k19_predict_launch(ctx, b->dtype, r))) return rc;
     return xo.home(ctx, b, o, fc);
 }
 

@@ -109,6 +109,11 @@ enum class Work : int {
     GlsarMoments,   // AR(1) FGLS (K18): S, the lag-one cross-moments C and the row count per segment / group, then the partials of the rows launch
     GlsarState,     // AR(1) FGLS (K18): n, usable, rho*, sqrt(1 - rho*^2), b, b0 and A_xx(rho*)^-1 per group (f64), then the coefficients for the prediction pass
     GlsarOut,       // AR(1) FGLS (K18): the pols_glsar_out fields of a HOST batch before they go home
+    RandomEffectsIds,     // random effects (K19): the id column of a HOST batch
+    RandomEffectsIndex,   // random effects (K19): K16's run starts / prefix / category index of every row
+    RandomEffectsCats,    // random effects (K19): K16's first positions and table, RSS_w and the row term of RSS per category, theta_c, u_c, q_c
+    RandomEffectsMoments, // random effects (K19): K16's Gram partials and state, sigma2_e, K19's state, b where K16's resid launch reads it, the table rows per group, the group list of a mixed frame
+    RandomEffectsOut,     // random effects (K19): the pols_random_effects_out fields of a HOST batch before they go home
     Count
 };
 
@@ -173,6 +178,7 @@ struct Options {
     int rlm_engine = 0;           // POLS_RLM_ENGINE     0 auto (groups that fit the LDS stay resident), 1 "stream" (K11's streamed form for every group)
     int glm_engine = 0;           // POLS_GLM_ENGINE     0 auto (groups that fit the LDS stay resident), 1 "split" (K13's split form for every group)
     int absorb2_route = 0;        // POLS_ABSORB2_ROUTE  0 auto / "resident" (groups that fit the LDS store stay resident), 1 "global" (K17's scratch form for every group)
+    int random_effects_route = 0; // POLS_RANDOM_EFFECTS_ROUTE  0 auto / "resident" (groups whose category table fits the LDS stay resident), 1 "global" (K19's table kernel reads the table in global memory for every group)
     int k1_xcd = 0;               // POLS_K1_XCD      resident K1 kernels: 1 = XCD-contiguous workgroup -> group map (each XCD walks one eighth of the frame)
 };
 void options_from_env(Options &o);

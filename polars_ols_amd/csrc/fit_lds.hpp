@@ -1,4 +1,4 @@
-// fit_lds.hpp -- the dynamic-LDS layouts of the one-wave solve kernels of K14, K16, K17 and K18: offsets in doubles and their total.  Each
+// fit_lds.hpp -- the dynamic-LDS layouts of the one-wave solve kernels of K14, K16, K17 and K18 and of K19's table kernel: offsets in doubles and their total.  Each
 // is ONE function, called by the kernel (its offsets) and by the launcher (its total), so the two cannot drift apart.  Plain C++ when
 // compiled without HIP: tests/carve_check.cpp checks order, disjointness and the totals on the CPU.
 #pragma once
@@ -71,6 +71,39 @@ FIT_HD static inline K18Lds k18_lds(int kt) {
     o.ij = at;  at += (ne + 1) / 2;       // (i, j) of every packed entry, as int32
     o.total = at;
     return o;
+}
+
+// K19 (k19_random_effects.hip), the table kernel: k features, kc = k + intercept columns, `rows` rows of K16's category table held
+// resident (0: the global route reads the table where it lies).  nz = kc + 1 counts the ybar column of the packed triangles.
+struct K19Lds { int tab, q, part, Gw, Gs, T, A, d0, rhs, Ri, Minv, bb, D, dz, dv, red, sc, total; };
+FIT_HD static inline K19Lds k19_lds(int k, int kc, int rows) {
+    const int nz = kc + 1, ne = nz * (nz + 1) / 2, nw = (k + 1) * (k + 2) / 2;
+    K19Lds o;
+    int at = 0;
+    o.tab = at;  at += rows * (k + 3);        // the group's rows of the category table, as K16 lays them out
+    o.q = at;    at += rows;                  // q_c = T_c (1 - theta_c)^2
+    o.part = at; at += ne > 256 ? ne : 256;   // the partitions of a table sum before they meet
+    o.Gw = at;   at += nw + k + 1;            // the within moments summed over the items: the triangle, T_jj, n
+    o.Gs = at;   at += ne;                    // packed [B g; g' .], later [M v; v' .]
+    o.T = at;    at += kc;                    // what the pivots of M are held against
+    o.A = at;    at += kc * (kc + 1);         // the matrix, then its factor
+    o.d0 = at;   at += kc;
+    o.rhs = at;  at += kc;                    // the right-hand side -> the coefficients
+    o.Ri = at;   at += kc * kc;               // the inverse of the factor
+    o.Minv = at; at += kc * kc;               // M^-1
+    o.bb = at;   at += kc;                    // the between coefficients
+    o.D = at;    at += k * (k + 1);           // Hausman's D, then its factor
+    o.dz = at;   at += k;                     // zeros: its pivots are held against 0
+    o.dv = at;   at += k;                     // b_w - b -> L^-1 (b_w - b)
+    o.red = at;  at += 4;                     // fit_block_sum
+    o.sc = at;   at += 4;                     // flags of wave 0 for the others
+    o.total = at;
+    return o;
+}
+// the rows of the table a resident workgroup can hold under `budget` bytes of LDS (<= 0: none)
+FIT_HD static inline long long k19_resident_rows(int k, int kc, long long budget) {
+    const long long fixed = k19_lds(k, kc, 0).total;
+    return (budget / 8 - fixed) / (k + 4);
 }
 
 }  // namespace pols

@@ -174,11 +174,11 @@ __device__ __forceinline__ bool fit_stage(const Args &a, const int64_t s, const 
 // loads, all issued before the first use), sums  lin = icpt + sum_j fill(x_j) cg[j] [+ fill(add)]  in f64 (features and the additive
 // column `add`, nullptr for none, zero-filled under every policy but "ignore") and hands every row to
 //   row(lin, y, r, in, fit, o)   in: r is a row of the item; fit: false for a row that "drop" kept out of the fit (ex.rs:409-417);
-// which fills o[k], the value of out[k] (any may be nullptr) at row r.  Whole chunks inside the item go out as 16-byte streaming
+// which fills o[k], the value of out[k] (NO of them, any may be nullptr) at row r.  Whole chunks inside the item go out as 16-byte streaming
 // stores, the others row by row.  Args: y, x, n_rows, valid, null_policy, k_user.
-template <typename T, typename Args, typename Row>
+template <typename T, int NO, typename Args, typename Row>
 __device__ __forceinline__ void fit_predict_rows(const Args &a, const int64_t s, const int64_t e, const int64_t base, const double *cg,
-                                                 const double icpt, const T *add, T *const (&out)[3], Row &&row) {
+                                                 const double icpt, const T *add, T *const (&out)[NO], Row &&row) {
     using V = typename Vec16<T>::type;
     constexpr int VEC = Vec16<T>::N;
     const int tid = threadIdx.x, ku = a.k_user, pol = a.null_policy;
@@ -215,20 +215,20 @@ __device__ __forceinline__ void fit_predict_rows(const Args &a, const int64_t s,
                 }
             }
         }
-        T ov[3][VEC];
+        T ov[NO][VEC];
 #pragma unroll
         for (int v = 0; v < VEC; ++v) {
             const int64_t r = row0 + v;
             const bool in = r >= s && r < e;
             const T yv = in ? yp[r] : T(0);
             const bool fit = pol != POLS_NULL_DROP || (!(a.valid && in && !a.valid[r]) && yv == yv && !nullx[v]);
-            double o[3] = {0.0, 0.0, 0.0};
+            double o[NO] = {};
             row(p[v], (double)yv, r, in, fit, o);
 #pragma unroll
-            for (int k = 0; k < 3; ++k) ov[k][v] = (T)o[k];
+            for (int k = 0; k < NO; ++k) ov[k][v] = (T)o[k];
         }
 #pragma unroll
-        for (int k = 0; k < 3; ++k) {
+        for (int k = 0; k < NO; ++k) {
             if (!out[k]) continue;
             if (full) {
                 if constexpr (VEC == 4) store_stream(reinterpret_cast<V *>(out[k] + row0), V{ov[k][0], ov[k][1], ov[k][2], ov[k][3]});

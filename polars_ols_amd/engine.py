@@ -494,6 +494,38 @@ class Engine:
                                want, y, x_cols, offsets, dict(weights=weights, valid=valid, add_intercept=add_intercept, null_policy=null_policy, out=out),
                                extra=bring_ids)
 
+    def random_effects(self, y, x_cols: Sequence, ids, offsets, *,
+                       want: Sequence[str] = ("coef", "status", "se", "sigma2_e", "sigma2_u", "hausman", "hausman_p", "n_obs", "n_categories"),
+                       weights=None, valid=None, add_intercept: bool = False, null_policy: str = "ignore", out: Optional[Dict] = None) -> Dict:
+        """Random-effects panel regression with the Hausman test inside every group -- ``xtreg, re`` and ``hausman``, linearmodels'
+        ``RandomEffects`` / ``BetweenOLS`` -- for every group in one call (pols_random_effects; the definitions and edge rules are in
+        include/pols_mi355x.h).  ``ids``: one integer entity id per row, in the rows' order.  ``weights`` are not built and raise.
+        ``want``: any of ``coef`` (the GLS coefficients, the intercept last with ``add_intercept``) ``pred resid status`` (status 4 =
+        no degrees of freedom within or between), ``se t_values p_values coef_between`` [n_groups, k, f64], ``coef_within``
+        [n_groups, n_features, f64], ``sigma2_e sigma2_u rho hausman hausman_p`` [n_groups, f64], ``effects theta`` [n_rows, batch
+        dtype: the row's u_c and theta_c], ``n_obs n_categories`` [n_groups, int64].  Arrays are numpy or torch and live where the
+        inputs live.  Without any of ``se t_values p_values`` the second residual pass is skipped."""
+        x_cols = list(x_cols)
+        q = _random_effects_params(self._lib, len(x_cols), add_intercept, weights)
+
+        def bring_ids(b, like, dev):
+            if ids is None:
+                raise ValueError("random_effects: 'ids' is required")
+            col = _id_column(ids, dev, like, b.n_rows, lambda c: f"random_effects: {tuple(c.shape)} ids for {b.n_rows} rows")
+            q.ids = self._ptr(col)
+            return col
+
+        nf = len(x_cols)
+        return self._fit_entry("random_effects", "pols_random_effects", L.RANDOM_EFFECTS_FIELDS, L.RandomEffectsOut, q,
+                               lambda G, N, kt: {"se": ((G, kt), "f64"), "t_values": ((G, kt), "f64"), "p_values": ((G, kt), "f64"),
+                                                 "coef_between": ((G, kt), "f64"), "coef_within": ((G, nf), "f64"),
+                                                 "sigma2_e": ((G,), "f64"), "sigma2_u": ((G,), "f64"), "rho": ((G,), "f64"),
+                                                 "hausman": ((G,), "f64"), "hausman_p": ((G,), "f64"),
+                                                 "effects": ((N,), "batch"), "theta": ((N,), "batch"),
+                                                 "n_obs": ((G,), "i64"), "n_categories": ((G,), "i64")},
+                               want, y, x_cols, offsets, dict(valid=valid, add_intercept=add_intercept, null_policy=null_policy, out=out),
+                               extra=bring_ids)
+
     def elastic_net_cv(self, y, x_cols: Sequence, offsets, alphas=None, *, n_alphas: int = 100, eps: float = 1e-3, l1_ratio: float = 0.5,
                        n_folds: int = 5, max_iter: int = 1000, tol: float = 1e-5, positive: bool = False,
                        want: Sequence[str] = ("coef", "status", "alpha", "alpha_index", "score"), weights=None, valid=None,
@@ -856,6 +888,22 @@ def _absorb2_params(lib, n_features, cov_type, add_intercept, max_iter, tol) -> 
     if lib is not None:
         lib.pols_absorb2_params_default(C.byref(q))
     q.ids, q.ids2, q.cov_type, q.max_iter, q.tol = None, None, L.COV_TYPES[cov_type], int(max_iter), float(tol)
+    return q
+
+
+def _random_effects_params(lib, n_features, add_intercept, weights=None) -> "L.RandomEffectsParams":
+    """the argument checks of Engine.random_effects / compute_random_effects (``lib`` None: check only, no device needed)"""
+    if weights is not None:
+        raise ValueError("random_effects: sample weights are not built")
+    if n_features < 1:
+        raise ValueError("random_effects: at least one feature is required")
+    total = n_features + int(bool(add_intercept))
+    if total > L.RANDOM_EFFECTS_MAX_COLUMNS:
+        raise ValueError(f"random_effects: {total} features (incl. intercept) > {L.RANDOM_EFFECTS_MAX_COLUMNS}")
+    q = L.RandomEffectsParams()
+    if lib is not None:
+        lib.pols_random_effects_params_default(C.byref(q))
+    q.ids = None
     return q
 
 

@@ -26,7 +26,8 @@ import numpy as np
 
 from . import _lib
 from ._lib import PolsPanic
-from .engine import Engine, Layout, _absorb_params, _absorb2_params, _enet_cv_params, _is_torch, _glm_params, _glsar_params, _iv_params, _ridge_cv_grid, _rlm_params, default_engine
+from .engine import (Engine, Layout, _absorb_params, _absorb2_params, _enet_cv_params, _is_torch, _glm_params, _glsar_params, _iv_params,
+                     _random_effects_params, _ridge_cv_grid, _rlm_params, default_engine)
 
 try:
     import torch
@@ -47,6 +48,7 @@ __all__ = [
     "compute_iv2sls", "IV2SLS",
     "compute_glsar", "GLSAR",
     "compute_absorbed_least_squares", "AbsorbedOLS",
+    "compute_random_effects", "RandomEffects",
 ]
 
 # ---- polars_ols/least_squares.py:47-63 --------------------------------------------------------------------------
@@ -683,6 +685,44 @@ def _apply_absorb(frame: Frame, over, eng: Optional[Engine], target: Expr, featu
     return target.output_name, grp.untake(out[{"predictions": "pred", "residuals": "resid", "effects": "fe"}[mode]])
 
 
+class RandomEffects(dict):
+    """mode="statistics" of a random-effects fit (pols_random_effects; the definitions are in include/pols_mi355x.h): per group
+    ``coefficients standard_errors t_values p_values coefficients_between`` [G, k] (``feature_names``), ``coefficients_within``
+    [G, n_features], ``sigma2_e sigma2_u rho hausman hausman_p n_obs n_categories status`` [G]; ``keys`` holds the group keys of an
+    ``.over`` (None for a whole-frame fit, where G == 1)."""
+
+    def __init__(self, names, out, keys):
+        super().__init__(feature_names=list(names), keys=keys, coefficients=out["coef"], standard_errors=out["se"],
+                         t_values=out["t_values"], p_values=out["p_values"], coefficients_between=out["coef_between"],
+                         coefficients_within=out["coef_within"], sigma2_e=out["sigma2_e"], sigma2_u=out["sigma2_u"], rho=out["rho"],
+                         hausman=out["hausman"], hausman_p=out["hausman_p"], n_obs=out["n_obs"], n_categories=out["n_categories"],
+                         status=out["status"])
+        self.keys_ = keys
+
+
+_VALID_RANDOM_EFFECTS_MODES = ("predictions", "residuals", "coefficients", "statistics", "effects", "theta")
+
+
+def _apply_random_effects(frame: Frame, over, eng: Optional[Engine], target: Expr, features: Sequence[Expr], entity, add_intercept: bool,
+                          mode: str, null_policy: str):
+    """compute_random_effects body: the group layout of _apply_static around Engine.random_effects; the id column moves with its rows."""
+    y, xs, names, icpt, _ = _pre_process_data(frame, target, features, None, add_intercept)
+    ids = _cluster_ids(frame, [entity], y)
+    eng = eng or default_engine(y.device.index or 0 if _is_torch(y) else 0)
+    grp = _Groups(eng, None if over is None else (frame[over] if isinstance(over, str) else over), y.shape[0])
+    moved = grp.take([y] + list(xs) + ids)
+    ys, xss, idss = moved[0], moved[1:1 + len(xs)], moved[1 + len(xs):]
+    rows = {"predictions": "pred", "residuals": "resid", "effects": "effects", "theta": "theta"}
+    want = {"coefficients": ("coef",),
+            "statistics": ("coef", "status") + tuple(f for f in _lib.RANDOM_EFFECTS_FIELDS if f not in ("effects", "theta"))}.get(mode) or (rows[mode],)
+    out = eng.random_effects(ys, xss, idss[0], grp.offsets, want=want, add_intercept=icpt, null_policy=null_policy)
+    if mode == "statistics":
+        return "statistics", RandomEffects(names, out, grp.keys)
+    if mode == "coefficients":
+        return "coefficients", Coefficients(names, out["coef"], grp.keys, grp.gid_frame(out["coef"]))
+    return target.output_name, grp.untake(out[rows[mode]])
+
+
 def _apply_dynamic(frame: Frame, over, eng: Optional[Engine], target: Expr, features: Sequence[Expr], sample_weights,
                    add_intercept: bool, mode: str, kind: str, kw):
     """compute_recursive_least_squares / compute_rolling_least_squares bodies (ls.py:332-409 around
@@ -932,6 +972,26 @@ def compute_absorbed_least_squares(target, *features, absorb, cov_type: str = "n
         _absorb2_params(None, len(fs), cov_type, icpt, *two_way)
     return Expr(t._name, fn=lambda frame, over, eng: _apply_absorb(frame, over, eng, t, fs, absorb, sample_weights, add_intercept, mode,
                                                                    cov_type, null_policy, two_way))
+
+
+def compute_random_effects(target, *features, entity, sample_weights=None, add_intercept: bool = False, mode: str = "predictions",
+                           null_policy: str = "ignore") -> Expr:
+    """Random-effects panel regression per group (Stata's ``xtreg, re`` followed by ``hausman``, linearmodels' ``RandomEffects``):
+    feasible GLS with Swamy-Arora variance components, closed form.  ``entity``: the id column of the panel's entities (a name, an
+    expression or an array; under ``.over(key)`` it moves with its rows).  Modes "predictions" (z'b, no effect added), "residuals",
+    "coefficients", "effects" (the row's predicted effect u_c) and "theta" (the row's quasi-demeaning factor); mode="statistics"
+    returns a ``RandomEffects`` with standard errors, t and p values, the between and within coefficients, sigma2_e, sigma2_u, rho,
+    the Hausman statistic with its p-value and the counts.  ``sample_weights`` are not built and raise."""
+    if mode not in _VALID_RANDOM_EFFECTS_MODES:
+        raise ValueError(f"'mode' must be one of {_VALID_RANDOM_EFFECTS_MODES}, got {mode!r}")
+    if null_policy not in _VALID_NULL_POLICIES:
+        raise ValueError(f"'null_policy' must be one of {sorted(_VALID_NULL_POLICIES)}, got {null_policy!r}")
+    if entity is None:
+        raise ValueError("'entity' names the id column of the panel's entities")
+    t, fs = parse_into_expr(target), [parse_into_expr(f) for f in features]
+    icpt = add_intercept and not any(f.output_name == "const" for f in fs)
+    _random_effects_params(None, len(fs), icpt, sample_weights)
+    return Expr(t._name, fn=lambda frame, over, eng: _apply_random_effects(frame, over, eng, t, fs, entity, add_intercept, mode, null_policy))
 
 
 def compute_multi_target_least_squares(targets, *features, sample_weights=None, add_intercept: bool = False,
@@ -1218,6 +1278,11 @@ class LeastSquares:
                tol: Optional[float] = None) -> Expr:
         return compute_absorbed_least_squares(self._expr, *features, absorb=absorb, cov_type=cov_type, sample_weights=sample_weights,
                                               add_intercept=add_intercept, mode=mode, null_policy=null_policy, max_iter=max_iter, tol=tol)
+
+    def random_effects(self, *features, entity=None, sample_weights=None, add_intercept: bool = False, mode: str = "predictions",
+                       null_policy: str = "ignore") -> Expr:
+        return compute_random_effects(self._expr, *features, entity=entity, sample_weights=sample_weights, add_intercept=add_intercept,
+                                      mode=mode, null_policy=null_policy)
 
     def lasso(self, *features, alpha: float, **kwargs) -> Expr:
         return self.least_squares(*features, alpha=alpha, l1_ratio=1.0, **kwargs)
